@@ -2,6 +2,7 @@
 """bench.py - throughput of the IRaytracer hot path on MI355X, in BASELINE.json's metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg4crop|cfg5base|cfg5]
+                    [--dump-outputs DIR] [--full]
 
 A step = one frame: every primary ray of the workload through hit-test -> shade -> reflection loop, scene and
 rays resident in HBM before the timed region (rays are regenerated in-kernel from (W,H,z); the framebuffer is
@@ -10,8 +11,17 @@ written to HBM; for N > 1 the step includes the RCCL gather of row-tiles to rank
 Default workload, for every N = BASELINE.json configs[3], the configuration the metric ("... at 4096x4096,
 1/2/4/8 GPU") and the north_star target are quoted on: synthetic 100k spheres + 32 lights, 4096x4096,
 shade_and_reflect, depth 3 - it fits one GPU (32 MB of scene) and is the same frame at every N, so the per-N
-values are comparable (strong scaling). At N = 1 the line also carries `extra.cfg3`: BASELINE configs[2]
-(simpleScene 4096x4096 depth 3, the HBM-bound small-scene kernel) with its own HBM roofline.
+values are comparable (strong scaling).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line. `--full` adds
+the measurements that take runs of their own (at N = 1): `extra.cfg3` (BASELINE configs[2], simpleScene 4096x4096
+depth 3, the HBM-bound small-scene kernel, with its own HBM roofline, plain and under RT_FLAG_FAST_PHONG),
+`roofline.brute_force`, `cpu_baseline` / `cpu_backend` and `render_wall_ms_incl_d2h`; `--no-extra` and
+`--no-cpu-baseline` leave parts of that out again.
+
+`--dump-outputs DIR` writes the frame of the last timed step (what Render() hands its caller, float32 RGBA per pixel)
+to DIR/frame.npy; a frame of more than DUMP_MAX_PIXELS pixels is written as a fixed sample of that many (see
+dump_outputs). Every input is deterministic, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0). `value` is Mrays/s over the rays this backend really TRACED for the frame (primary +
 shadow + reflection after its exact eliminations = R_act, SURVEY.md 8d's primary figure); the rays the reference
@@ -40,6 +50,7 @@ from opencl_raytracer_amd import camera, scene_loader, sharding, synthetic, tess
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_PEAK_LANE_OPS = 256 * 4 * 32 * 2.4e9  # 256 CUs x 4 SIMD-32 x 2.4 GHz = 7.86e13 fp32 lane-instructions/s (157.3 TFLOP/s FMA)
 SPHERE_TEST_LANE_OPS = 35  # minimal exact ray-sphere rejection test: 19 fma + 12 mul + 4 add
+DUMP_MAX_PIXELS = 1 << 21  # --dump-outputs: 2 Mi pixels x 16 B = 32 MB at most
 
 WORKLOADS = {
     # name: (description, scene, W, H, kernel, depth)
@@ -268,6 +279,27 @@ def measure_cfg3(device_index, fast_phong=False):
     return res
 
 
+def dump_sample_index(n, limit=DUMP_MAX_PIXELS, seed=0):
+    """Pixels --dump-outputs writes: all of them up to `limit`, else one pixel drawn (fixed seed) from each of `limit`
+    equal runs of the frame - ascending, distinct, spread over every row band, the same in every run."""
+    if n <= limit:
+        return None
+    run = n // limit
+    return np.arange(limit, dtype=np.int64) * run + np.random.default_rng(seed).integers(0, run, size=limit)
+
+
+def dump_outputs(out_dir, frame):
+    """The last timed step's frame (float32, one row per pixel) -> out_dir/frame.npy, sampled by dump_sample_index."""
+    import torch
+    idx = dump_sample_index(int(frame.shape[0]))
+    if torch.is_tensor(frame):
+        frame = (frame if idx is None else frame[torch.from_numpy(idx).to(frame.device)]).cpu().numpy()
+    else:
+        frame = np.asarray(frame) if idx is None else np.asarray(frame)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame, dtype=np.float32))
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -326,7 +358,13 @@ def main():
     ap.add_argument("--ray-buffer", action="store_true", help="read primary rays from an uploaded buffer instead of in-kernel generation")
     ap.add_argument("--fast-phong", action="store_true", help="RT_FLAG_FAST_PHONG: colour-only normalisations / specular power on the fast hardware paths (opt-in)")
     ap.add_argument("--no-grid", action="store_true", help="large scenes: test every object for every ray (brute-force traversal, the VALU-roofline kernel)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements: extra.cfg3, roofline.brute_force, the CPU baselines, render_wall_ms_incl_d2h")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame to DIR/frame.npy (float32; sampled above 2 Mi pixels)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -446,9 +484,11 @@ def main():
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
     kernel_ms_sum, launches = rt.rt.timing_summary()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame)
 
     extra = {}
-    if world == 1 and args.workload == "cfg4" and not args.no_extra:
+    if args.full and world == 1 and args.workload == "cfg4" and not args.no_extra:
         extra["cfg3"] = measure_cfg3(local_rank)
         extra["cfg3_fast_phong"] = measure_cfg3(local_rank, fast_phong=True)
         extra["cfg3_fast_phong"]["flag"] = ("RT_FLAG_FAST_PHONG (opt-in): shading normal / view vector / reflected light vector by v_rsq + "
@@ -467,7 +507,7 @@ def main():
     share_ms = [float(x) for x in share.tolist()]
     # what the boundary's synchronous Render() costs a caller: kernels + blocking read-back into pinned host memory
     # (OpenCLRaytracer.cpp:94), and the one-time set-up that sits outside every timer (its constructor's work, :13-74)
-    render_wall_ms = rt.rt.render_host_ms(3) if world == 1 else None
+    render_wall_ms = rt.rt.render_host_ms(3) if (args.full and world == 1) else None
     setup_ms = rt.rt.setup_times()
 
     if rank == 0:
@@ -485,7 +525,7 @@ def main():
         traffic = prof["hbm_bytes_per_launch"] if prof else None
         out = {
             "metric": "Mrays/s (primary+reflect+shadow) at 4096x4096, 1/2/4/8 GPU; max RGB diff vs ref",
-            "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup,
+            "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": steps, "warmup": warmup, "full": bool(args.full),
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": desc, "width": frame_w, "height": frame_h, "objects": int(len(objs)),
@@ -557,9 +597,9 @@ def main():
                     "SURVEY 8d's definition (35 lane-instructions x executed tests) the frame sits at a small fraction of the VALU "
                     "roofline; what the kernels are really limited by is in valu_issue (issue slots, lanes per instruction) and in "
                     "hbm / per_kernel (bytes the L2s pulled through the fabric vs the compulsory bytes). The brute-force traversal "
-                    "kernels the grid replaces - which ARE bound by those tests - are measured in brute_force") % (
+                    "kernels the grid replaces - which ARE bound by those tests - are measured in brute_force (--full)") % (
                         tests / max(rays_act, 1), len(objs))
-                if world == 1 and not args.no_extra:
+                if args.full and world == 1 and not args.no_extra:
                     out["roofline"]["brute_force"] = measure_brute_force_window(local_rank, 4096, default_frame=frame if torch.is_tensor(frame) else None)
         elif args.workload == "cfg5":
             hbm["kernel"] = "rt::wf_trace_grid_persistent<closest|any, triangles> + rt::wf_trace_primary_tiles (+ wf_resume)"
@@ -572,7 +612,7 @@ def main():
             out["roofline"] = hbm
         if extra:
             out["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if crop is not None or args.workload in ("cfg4", "cfg5"):
                 e = 16 if args.workload == "cfg5" else 64   # the CPU statement tests every object for every ray
                 cx, cy, cw, ch = (W // 2 - e // 2, H // 2 - e // 2, e, e)

@@ -19,6 +19,7 @@ Outputs are the kernel's output buffer as the reference host would see it: pixel
 only RGB (or t) is stored.
 
 Usage:  python tests/golden/make_golden.py        (rewrites every fixture; deterministic)
+        python tests/golden/make_golden.py --reference-runs   (only tests/golden/ref_runs/, see reference_runs())
 """
 from __future__ import annotations
 
@@ -262,10 +263,47 @@ def round2():
                 save(f"degenerate_{kind}_{where}_{kernel}", kernel, R.objects_array(recs), l, 2, cam=(48, 32, 60.0))
 
 
+REF_RUNS = HERE / "ref_runs"
+
+
+def reference_runs():
+    """tests/golden/ref_runs/: the reference kernels' outputs that the CPU tests hold the restatement and the known answer
+    against where oracle/_ref cannot be built (test_oracle_vs_ref.py), and sha-256 digests of the shim-variant builds'
+    outputs on tests/golden_alt/shim_variants.npz's fixtures (test_shim_variants.py)."""
+    import hashlib
+    from helpers import load_fixture, ref_run_scene
+    REF_RUNS.mkdir(exist_ok=True)
+    runs = {}
+    for seed in (101, 102, 103):
+        objs, lights, rays = ref_run_scene(seed)
+        for kernel in KID:
+            for flavour, fused in (("fused", True), ("unfused", False)):
+                runs[f"random_{seed}_{kernel}_{flavour}"] = oracle.Reference(kernel, fused).render(objs, lights, rays, 3)["out"]
+    objs, lights = scene_loader.load_scene(str(SCENES / "simpleSphere.txt"))
+    rays = camera.primary_rays(256, 256)
+    for kernel in ("shade", "shade_and_reflect"):
+        for flavour, fused in (("fused", True), ("unfused", False)):
+            runs[f"simpleSphere_256_{kernel}_{flavour}"] = oracle.Reference(kernel, fused).render(objs, lights, rays, 3)["out"]
+    np.savez_compressed(REF_RUNS / "oracle_vs_ref.npz", **runs)
+    store = np.load(HERE.parent / "golden_alt" / "shim_variants.npz")
+    digests = {}
+    for name in store.files:
+        fx = load_fixture(name)
+        kernel = {1: "shade", 2: "shade_and_reflect"}[fx["kernel"]]
+        digests[name] = np.array([hashlib.sha256(np.ascontiguousarray(
+            oracle.Reference(kernel, True, v).render(fx["objs"], fx["lights"], fx["rays"], fx["max_bounces"])["out"][:, :3]
+        ).view(np.uint32).tobytes()).hexdigest() for v in range(1, 7)])
+    np.savez_compressed(REF_RUNS / "shim_variant_digests.npz", **digests)
+    for p in sorted(REF_RUNS.iterdir()):
+        print(f"{p.name:32s} {p.stat().st_size / 1024:7.1f} KiB")
+
+
 if __name__ == "__main__":
     if not oracle.reference_available():
         sys.exit("oracle/_ref is not built (needs /root/reference): run `make -C oracle` in the build container")
-    if "--round2" in sys.argv:
+    if "--reference-runs" in sys.argv:
+        reference_runs()
+    elif "--round2" in sys.argv:
         round2()   # only the fixtures added in round 2 (the others are unchanged)
     else:
         main()

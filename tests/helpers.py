@@ -76,6 +76,13 @@ def random_scene(n_spheres, n_boxes, n_lights, seed, absorption=None, directiona
     return R.objects_array(objs), R.lights_array(lights)
 
 
+def ref_run_scene(seed):
+    """Seeded scene and 40x30 pinhole rays of tests/test_oracle_vs_ref.py (make_golden.py --reference-runs stores the
+    reference kernels' output on them)."""
+    objs, lights = random_scene(10 + seed % 7, 8, 1 + seed % 4, seed=seed, directional_lights=seed % 2)
+    return objs, lights, camera.primary_rays(40, 30)
+
+
 def rgb_bits(a):
     return np.ascontiguousarray(a[:, :3]).view(np.uint32)
 
