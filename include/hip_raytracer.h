@@ -49,7 +49,9 @@ extern "C" {
  *   3  rt_get_stats_multi / rt_count_rays_multi (the counters of every shard, summed); rt_render_multi places every device's
  *      tiles straight in the pinned host frame (no hop through devices[0]); rt_create / rt_set_camera switch a frame whose
  *      primary directions leave the default path's domain (|d|^2 == 0, < 1e-30, > 1e30) to RT_FLAG_LITERAL by themselves.
- *      Additions only: a caller built against version 2 keeps working. */
+ *      Additions only: a caller built against version 2 keeps working.
+ *      Later addition, same version: RT_FLAG_DEVICE_OPENCL (0x80). A library without it refuses the bit with "unknown flag bits",
+ *      which is how a caller detects support. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -97,6 +99,15 @@ typedef enum rt_kernel {
                                     shadow and reflection rays, the reference-equivalent ray count - stays bit-exact; colours
                                     stay within the 1e-5 the reference comparison allows (north_star), not bit-identical to
                                     the default arithmetic.                                                              */
+
+#define RT_FLAG_DEVICE_OPENCL 0x80u /* opt-in: the arithmetic of the reference's kernels as AMD's OpenCL toolchain builds them for gfx950,
+                                    instead of the x86 oracle's: `/` as v_frexp + v_rcp_f32 + v_ldexp (2.5 ulp), sqrt as a scaled
+                                    v_sqrt_f32, normalize as the OpenCL library's scaled v_rsq_f32 (a zero vector stays zero), dot as an
+                                    fma chain, contraction as the default. Someone who renders with the reference's OpenCLRaytracer on
+                                    an AMD GPU gets that picture. Refused (RT_ERR_INVALID_ARGUMENT) together with RT_FLAG_UNFUSED or
+                                    RT_FLAG_FAST_PHONG, and for scenes with triangles (type 2). The default organisation renders it
+                                    (RT_FRAME_KERNEL / RT_STEP_ROUNDS do not apply); a scene with a light inside an object's bounding
+                                    sphere, or a directional light of direction 0, is rendered with RT_FLAG_LITERAL set by rt_create. */
 
 typedef struct rt_stats_t {
     uint64_t rays_traced;     /* rays this backend actually issued in the last counted render (R_act)          */

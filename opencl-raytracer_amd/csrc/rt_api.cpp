@@ -661,8 +661,9 @@ int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count) {
     const uint32_t slot = c->ev_count % kTimingSlots;
     RT_HIP(c, hipEventRecord(c->ev_begin[slot], stream));
     hipError_t e;
-    if (c->last_wavefront) e = rt::launch_wavefront(p, c->kernel, !(c->flags & RT_FLAG_UNFUSED), count, c->wf, stream, &c->last_rounds);
-    else e = rt::launch_render(p, c->kernel, !(c->flags & RT_FLAG_UNFUSED), count, stream);
+    const int arith = (c->flags & RT_FLAG_DEVICE_OPENCL) ? rt::kDeviceCL : ((c->flags & RT_FLAG_UNFUSED) ? rt::kUnfused : rt::kFused);
+    if (c->last_wavefront) e = rt::launch_wavefront(p, c->kernel, arith, count, c->wf, stream, &c->last_rounds);
+    else e = rt::launch_render(p, c->kernel, arith, count, stream);
     if (e != hipSuccess) return fail_hip(c, e, "kernel launch");
     RT_HIP(c, hipEventRecord(c->ev_end[slot], stream));
     c->ev_count += 1;
@@ -1706,8 +1707,17 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     if (kernel < 0 || kernel > 2) return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "kernel must be 0, 1 or 2");
     if ((n_objs && !objs) || (n_lights && !lights))
         return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "objs/lights is NULL with a non-zero count");
-    if (flags & ~(RT_FLAG_UNFUSED | RT_FLAG_LITERAL | RT_FLAG_NO_RAYGEN | RT_FLAG_WAVEFRONT | RT_FLAG_MONOLITHIC | RT_FLAG_NO_GRID | RT_FLAG_FAST_PHONG))
+    if (flags & ~(RT_FLAG_UNFUSED | RT_FLAG_LITERAL | RT_FLAG_NO_RAYGEN | RT_FLAG_WAVEFRONT | RT_FLAG_MONOLITHIC | RT_FLAG_NO_GRID |
+                  RT_FLAG_FAST_PHONG | RT_FLAG_DEVICE_OPENCL))
         return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    if ((flags & RT_FLAG_DEVICE_OPENCL) && (flags & RT_FLAG_UNFUSED))
+        return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "RT_FLAG_DEVICE_OPENCL and RT_FLAG_UNFUSED are exclusive (the device build contracts)");
+    if ((flags & RT_FLAG_DEVICE_OPENCL) && (flags & RT_FLAG_FAST_PHONG))
+        return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "RT_FLAG_DEVICE_OPENCL and RT_FLAG_FAST_PHONG are exclusive");
+    if (flags & RT_FLAG_DEVICE_OPENCL)
+        for (uint32_t i = 0; i < n_objs; ++i)
+            if (static_cast<const rt_object_data*>(objs)[i].type == 2u)
+                return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "RT_FLAG_DEVICE_OPENCL: triangles (type 2) have no reference arithmetic to match");
     if (n_lights >= (1u << 22))  // the large-scene path keeps a pixel's light index in 22 bits of its phase word
         return fail(nullptr, RT_ERR_INVALID_ARGUMENT, "more than 4 194 303 lights");
     if ((flags & RT_FLAG_WAVEFRONT) && (flags & RT_FLAG_MONOLITHIC))
@@ -1849,6 +1859,30 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             }
         });
         if (degenerate.load()) { c->flags |= RT_FLAG_LITERAL; c->forced_literal = true; }
+    }
+    // RT_FLAG_DEVICE_OPENCL: the device normalize(0) is 0, so the shadow ray of a light AT the hit point (or of a directional
+    // light of direction 0) has a finite start and direction 0. Every sphere of the reference's loop then accepts it with a NaN
+    // time and every box that contains the start with MAX_FLOAT: the outcome depends on the order of the loop, which only the
+    // literal loops follow. Such a ray needs a light on a surface, i.e. inside an object's bounding sphere.
+    if ((flags & RT_FLAG_DEVICE_OPENCL) && !(c->flags & RT_FLAG_LITERAL) && n_lights) {
+        const rt_light* L = static_cast<const rt_light*>(lights);
+        bool ordered = false;
+        for (uint32_t l = 0; l < n_lights && !ordered; ++l)
+            if (L[l].position[3] == 0.f && L[l].position[0] == 0.f && L[l].position[1] == 0.f && L[l].position[2] == 0.f) ordered = true;
+        std::atomic<bool> near{ordered};
+        parallel_for(n_objs, 8192, [&](size_t i0, size_t i1) {
+            for (size_t i = i0; i < i1 && !near.load(std::memory_order_relaxed); ++i) {
+                const Bound b = object_bound(static_cast<const rt_object_data*>(objs)[i]);
+                if (!(b.r >= 0.0)) continue;  // never hit
+                const double reach = b.r * (1.0 + 1e-4) + 1e-4 * (std::fabs(b.x) + std::fabs(b.y) + std::fabs(b.z) + b.r);
+                for (uint32_t l = 0; l < n_lights; ++l) {
+                    if (L[l].position[3] == 0.f) continue;
+                    const double dx = (double)L[l].position[0] - b.x, dy = (double)L[l].position[1] - b.y, dz = (double)L[l].position[2] - b.z;
+                    if (!(dx * dx + dy * dy + dz * dz > reach * reach)) { near.store(true, std::memory_order_relaxed); break; }
+                }
+            }
+        });
+        if (near.load()) { c->flags |= RT_FLAG_LITERAL; c->forced_literal = true; }
     }
     lap("instance checks");
     c->base_flags = c->flags;

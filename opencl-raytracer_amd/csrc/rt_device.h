@@ -16,10 +16,12 @@
 //
 // Floating point contract (re-derived from the reference kernels' LLVM IR): this file is
 // compiled with -ffp-contract=off and -fhip-fp32-correctly-rounded-divide-sqrt; the places where the OpenCL
-// front-end forms llvm.fmuladd are written fma_<FUSED>(). FUSED=true is a single-rounding v_fma_f32,
-// FUSED=false a v_mul_f32 followed by v_add_f32. In a sum of products the first product is fused onto the
-// second: t = b*y; t = fma(a,x,t); t = fma(c,z,t); t = fma(d,w,t). dot()/normalize() are the unfused
-// left-to-right forms the oracle defines for the OpenCL builtins (oracle/ref_shim.cl).
+// front-end forms llvm.fmuladd are written fma_<AM>(), AM being the arithmetic mode (kUnfused, kFused, kDeviceCL below).
+// kFused is a single-rounding v_fma_f32, kUnfused a v_mul_f32 followed by v_add_f32. In a sum of products the first
+// product is fused onto the second: t = b*y; t = fma(a,x,t); t = fma(c,z,t); t = fma(d,w,t). In kUnfused and kFused,
+// `/`, sqrt(), dot() and normalize() are the IEEE / unfused left-to-right forms the oracle defines for the OpenCL builtins
+// (oracle/ref_shim.cl). kDeviceCL (RT_FLAG_DEVICE_OPENCL) contracts like kFused and computes those four operations as AMD's
+// OpenCL build of the reference does on gfx950 (cl_div, cl_sqrt, cl_dot3, cl_normalize3).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -100,9 +102,14 @@ struct Counters {
 };
 
 // ---- arithmetic primitives -----------------------------------------------------------------------------
-template <bool FUSED>
+// Arithmetic mode, the template parameter AM of everything below: what an OpenCL device without contraction computes
+// (RT_FLAG_UNFUSED), with contraction (default), and what the reference's kernels compute when AMD's OpenCL toolchain
+// builds them for gfx950 (RT_FLAG_DEVICE_OPENCL: contraction as kFused, and the builtins below).
+enum : int { kUnfused = 0, kFused = 1, kDeviceCL = 2 };
+
+template <int AM>
 __device__ __forceinline__ float fma_(float a, float b, float c) {
-    if constexpr (FUSED) return __builtin_fmaf(a, b, c);
+    if constexpr (AM != kUnfused) return __builtin_fmaf(a, b, c);
     else return a * b + c;  // -ffp-contract=off: two roundings
 }
 
@@ -123,12 +130,91 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
     z = z / len;
 }
 
+// ---- kDeviceCL: the operations the reference leaves to the OpenCL implementation, as ROCm's OpenCL compiler lowers them for
+// gfx950 without -cl-fp32-correctly-rounded-divide-sqrt (the instruction sequences of the reference's gfx950 code objects). Written with
+// explicit builtins, so that the TU's own -fhip-fp32-correctly-rounded-divide-sqrt cannot change them; tools/proof/cl_arith.hip
+// compares each one with the compiler's own lowering over every input.
+// a / b: both operands split by v_frexp_mant / v_frexp_exp, one v_rcp_f32 (1 ulp) of the denominator's mantissa, one product,
+// one v_ldexp_f32 - 2.5 ulp, no v_div_scale / v_div_fixup.
+__device__ __forceinline__ float cl_div(float a, float b) {
+    const float rcp = __builtin_amdgcn_rcpf(__builtin_amdgcn_frexp_mantf(b));
+    const int e = __builtin_amdgcn_frexp_expf(a) - __builtin_amdgcn_frexp_expf(b);
+    return __builtin_ldexpf(__builtin_amdgcn_frexp_mantf(a) * rcp, e);
+}
+// sqrt(x): v_sqrt_f32, an input below the smallest normal scaled by 2^32 first and the result by 2^-16
+__device__ __forceinline__ float cl_sqrt(float x) {
+    const bool scale = x < 0x1.0p-126f;
+    const float r = __builtin_amdgcn_sqrtf(__builtin_ldexpf(x, scale ? 32 : 0));
+    return __builtin_ldexpf(r, scale ? -16 : 0);
+}
+// OCML's rsqrt with denormals on: v_rsq_f32 (1 ulp), an input below the smallest normal scaled by 2^24, the result by 2^12
+__device__ __forceinline__ float cl_rsq(float x) {
+    const bool scale = x < 0x1.0p-126f;
+    const float r = __builtin_amdgcn_rsqf(scale ? x * 0x1.0p+24f : x);
+    return scale ? r * 4096.0f : r;
+}
+// dot(float3, float3) of the OpenCL library: fmuladd(a.z, b.z, fmuladd(a.y, b.y, a.x * b.x)), contracted
+__device__ __forceinline__ float cl_dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    float s = ax * bx;
+    s = __builtin_fmaf(ay, by, s);
+    s = __builtin_fmaf(az, bz, s);
+    return s;
+}
+// normalize(float3) of the OpenCL library (restated in oracle/ref_shim.cl, SHIM_VARIANT 4): a zero vector comes back
+// unchanged (no NaN); a dot below 2^-126 rescales the vector by 2^86, an infinite one by 2^-66 (then, if still infinite,
+// +-1 for the infinite components and +-0 for the others); then v * rsqrt(dot(v, v)).
+__device__ __forceinline__ void cl_normalize3(float& x, float& y, float& z) {
+    if (x == 0.f && y == 0.f && z == 0.f) return;
+    float l2 = cl_dot3(x, y, z, x, y, z);
+    if (l2 < 0x1.0p-126f) {
+        x = x * 0x1.0p+86f; y = y * 0x1.0p+86f; z = z * 0x1.0p+86f;
+        l2 = cl_dot3(x, y, z, x, y, z);
+    } else if (l2 == __builtin_inff()) {
+        x = x * 0x1.0p-66f; y = y * 0x1.0p-66f; z = z * 0x1.0p-66f;
+        l2 = cl_dot3(x, y, z, x, y, z);
+        if (l2 == __builtin_inff()) {
+            x = __builtin_copysignf(__builtin_fabsf(x) == __builtin_inff() ? 1.f : 0.f, x);
+            y = __builtin_copysignf(__builtin_fabsf(y) == __builtin_inff() ? 1.f : 0.f, y);
+            z = __builtin_copysignf(__builtin_fabsf(z) == __builtin_inff() ? 1.f : 0.f, z);
+            l2 = cl_dot3(x, y, z, x, y, z);
+        }
+    }
+    const float r = cl_rsq(l2);
+    x = x * r;
+    y = y * r;
+    z = z * r;
+}
+
+// the reference's `/`, sqrt(), dot() and normalize() in arithmetic mode AM
+template <int AM>
+__device__ __forceinline__ float div_(float a, float b) {
+    if constexpr (AM == kDeviceCL) return cl_div(a, b);
+    else return a / b;
+}
+template <int AM>
+__device__ __forceinline__ float sqrt_(float x) {
+    if constexpr (AM == kDeviceCL) return cl_sqrt(x);
+    else return __builtin_sqrtf(x);
+}
+template <int AM>
+__device__ __forceinline__ float dot3_(float ax, float ay, float az, float bx, float by, float bz) {
+    if constexpr (AM == kDeviceCL) return cl_dot3(ax, ay, az, bx, by, bz);
+    else return dot3(ax, ay, az, bx, by, bz);
+}
+template <int AM>
+__device__ __forceinline__ void normalize3_(float& x, float& y, float& z) {
+    if constexpr (AM == kDeviceCL) cl_normalize3(x, y, z);
+    else normalize3(x, y, z);
+}
+
 // RT_FLAG_FAST_PHONG (opt-in): normalisation of a vector that feeds COLOUR only - the shading normal, the view vector, the
 // reflected light vector of the Phong term; never a vector a ray is built from. dot() as the reference's, then the
 // hardware reciprocal square root (1 ulp) with one Newton step and three multiplies instead of an IEEE square root and
 // three IEEE divisions (~8 instead of ~40 instructions); relative error ~1e-7, far inside the 1e-5 colour tolerance.
+// (kDeviceCL: never fast - rt_create refuses the combination)
+template <int AM>
 __device__ __forceinline__ void normalize3_shading(bool fast, float& x, float& y, float& z) {
-    if (!fast) { normalize3(x, y, z); return; }
+    if (AM == kDeviceCL || !fast) { normalize3_<AM>(x, y, z); return; }
     float s = x * x;
     s = s + y * y;
     s = s + z * z;
@@ -140,46 +226,46 @@ __device__ __forceinline__ void normalize3_shading(bool fast, float& x, float& y
 }
 
 // one row of transform(): m0*x + m1*y + m2*z + m3*w in the reference's association
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ float row4(float m0, float m1, float m2, float m3, float x, float y, float z, float w) {
     float t = m1 * y;
-    t = fma_<FUSED>(m0, x, t);
-    t = fma_<FUSED>(m2, z, t);
-    t = fma_<FUSED>(m3, w, t);
+    t = fma_<AM>(m0, x, t);
+    t = fma_<AM>(m2, z, t);
+    t = fma_<AM>(m3, w, t);
     return t;
 }
 // the same row for a vector whose w is exactly 0 (shadow / reflection / pinhole directions): the dropped
 // fma(m3, 0, t) can only change the sign of a zero, which no later operation observes
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ float row3(float m0, float m1, float m2, float x, float y, float z) {
     float t = m1 * y;
-    t = fma_<FUSED>(m0, x, t);
-    t = fma_<FUSED>(m2, z, t);
+    t = fma_<AM>(m0, x, t);
+    t = fma_<AM>(m2, z, t);
     return t;
 }
 
 // ---- primitive tests in object space ---------------------------------------------------------------------
 // unit sphere (shade_and_reflect_kernel.cl:82-106): true if the candidate passes the reference's
 // `radical < 0` and `tMin < 0` rejections; t = the reference's tMin
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool sphere_candidate(float sx, float sy, float sz, float dx, float dy, float dz, float& t) {
     float A = dy * dy;
-    A = fma_<FUSED>(dx, dx, A);
-    A = fma_<FUSED>(dz, dz, A);
+    A = fma_<AM>(dx, dx, A);
+    A = fma_<AM>(dz, dz, A);
     float B = sy * dy;
-    B = fma_<FUSED>(dx, sx, B);
-    B = fma_<FUSED>(dz, sz, B);
+    B = fma_<AM>(dx, sx, B);
+    B = fma_<AM>(dz, sz, B);
     B = B * 2.0f;
     float C = sy * sy;
-    C = fma_<FUSED>(sx, sx, C);
-    C = fma_<FUSED>(sz, sz, C);
+    C = fma_<AM>(sx, sx, C);
+    C = fma_<AM>(sz, sz, C);
     C = C + -1.0f;
-    const float radical = fma_<FUSED>(B, B, (A * 4.0f) * (-C));
+    const float radical = fma_<AM>(B, B, (A * 4.0f) * (-C));
     if (radical < 0) return false;
-    const float root = __builtin_sqrtf(radical);
+    const float root = sqrt_<AM>(radical);
     const float den = A * 2.0f;
-    const float t1 = (-B - root) / den;
-    const float t2 = (root - B) / den;
+    const float t1 = div_<AM>(-B - root, den);
+    const float t2 = div_<AM>(root - B, den);
     const float tMin = (t1 >= 0 && t2 >= 0) ? __builtin_fminf(t1, t2) : __builtin_fmaxf(t1, t2);
     if (tMin < 0) return false;
     t = tMin;
@@ -187,6 +273,7 @@ __device__ __forceinline__ bool sphere_candidate(float sx, float sy, float sz, f
 }
 
 // one slab of the unit box (shade_and_reflect_kernel.cl:33-58)
+template <int AM>
 __device__ __forceinline__ bool box_slab(float& tmin, float& tmax, float start, float dir) {
     float t1 = -0.5f - start;
     float t2 = 0.5f - start;
@@ -196,8 +283,8 @@ __device__ __forceinline__ bool box_slab(float& tmin, float& tmax, float start, 
         tmax = kMaxFloat;
         return true;
     }
-    t1 = t1 / dir;
-    t2 = t2 / dir;
+    t1 = div_<AM>(t1, dir);
+    t2 = div_<AM>(t2, dir);
     if (dir < 0) {
         tmin = __builtin_fminf(t1, t2);
         tmax = __builtin_fmaxf(t1, t2);
@@ -256,12 +343,13 @@ __device__ __forceinline__ bool triangle_candidate(float v0x, float v0y, float v
 }
 
 // unit box [-0.5,0.5]^3 (shade_and_reflect_kernel.cl:123-144)
+template <int AM>
 __device__ __forceinline__ bool box_candidate(float sx, float sy, float sz, float dx, float dy, float dz, float& t) {
     if (box_line_misses(sx, sy, sz, dx, dy, dz)) return false;
     float txMin, txMax, tyMin, tyMax, tzMin, tzMax;
-    if (!box_slab(txMin, txMax, sx, dx)) return false;
-    if (!box_slab(tyMin, tyMax, sy, dy)) return false;
-    if (!box_slab(tzMin, tzMax, sz, dz)) return false;
+    if (!box_slab<AM>(txMin, txMax, sx, dx)) return false;
+    if (!box_slab<AM>(tyMin, tyMax, sy, dy)) return false;
+    if (!box_slab<AM>(tzMin, tzMax, sz, dz)) return false;
     const float tMin = __builtin_fmaxf(__builtin_fmaxf(txMin, tyMin), tzMin);
     const float tMax = __builtin_fminf(__builtin_fminf(txMax, tyMax), tzMax);
     if (tMax < tMin) return false;
@@ -304,68 +392,68 @@ __device__ __forceinline__ RaySplat splat(const Ray& r) {
     return q;
 }
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ f2 fma2_(f2 a, f2 b, f2 c) {
-    if constexpr (FUSED) return __builtin_elementwise_fma(a, b, c);
+    if constexpr (AM != kUnfused) return __builtin_elementwise_fma(a, b, c);
     else return a * b + c;
 }
 
 // both objects of a pair: ray -> object space (rows x,y,z), the reference's association (row4 / row3)
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void pair_object_space(const HotPair& h, const RaySplat& r, f2& sx, f2& sy, f2& sz, f2& dx,
                                                   f2& dy, f2& dz) {
-    sx = h.m[1] * r.sy; sx = fma2_<FUSED>(h.m[0], r.sx, sx); sx = fma2_<FUSED>(h.m[2], r.sz, sx); sx = fma2_<FUSED>(h.m[3], r.sw, sx);
-    sy = h.m[5] * r.sy; sy = fma2_<FUSED>(h.m[4], r.sx, sy); sy = fma2_<FUSED>(h.m[6], r.sz, sy); sy = fma2_<FUSED>(h.m[7], r.sw, sy);
-    sz = h.m[9] * r.sy; sz = fma2_<FUSED>(h.m[8], r.sx, sz); sz = fma2_<FUSED>(h.m[10], r.sz, sz); sz = fma2_<FUSED>(h.m[11], r.sw, sz);
-    dx = h.m[1] * r.dy; dx = fma2_<FUSED>(h.m[0], r.dx, dx); dx = fma2_<FUSED>(h.m[2], r.dz, dx);
-    dy = h.m[5] * r.dy; dy = fma2_<FUSED>(h.m[4], r.dx, dy); dy = fma2_<FUSED>(h.m[6], r.dz, dy);
-    dz = h.m[9] * r.dy; dz = fma2_<FUSED>(h.m[8], r.dx, dz); dz = fma2_<FUSED>(h.m[10], r.dz, dz);
+    sx = h.m[1] * r.sy; sx = fma2_<AM>(h.m[0], r.sx, sx); sx = fma2_<AM>(h.m[2], r.sz, sx); sx = fma2_<AM>(h.m[3], r.sw, sx);
+    sy = h.m[5] * r.sy; sy = fma2_<AM>(h.m[4], r.sx, sy); sy = fma2_<AM>(h.m[6], r.sz, sy); sy = fma2_<AM>(h.m[7], r.sw, sy);
+    sz = h.m[9] * r.sy; sz = fma2_<AM>(h.m[8], r.sx, sz); sz = fma2_<AM>(h.m[10], r.sz, sz); sz = fma2_<AM>(h.m[11], r.sw, sz);
+    dx = h.m[1] * r.dy; dx = fma2_<AM>(h.m[0], r.dx, dx); dx = fma2_<AM>(h.m[2], r.dz, dx);
+    dy = h.m[5] * r.dy; dy = fma2_<AM>(h.m[4], r.dx, dy); dy = fma2_<AM>(h.m[6], r.dz, dy);
+    dz = h.m[9] * r.dy; dz = fma2_<AM>(h.m[8], r.dx, dz); dz = fma2_<AM>(h.m[10], r.dz, dz);
     if constexpr (!DW0) {
-        dx = fma2_<FUSED>(h.m[3], r.dw, dx);
-        dy = fma2_<FUSED>(h.m[7], r.dw, dy);
-        dz = fma2_<FUSED>(h.m[11], r.dw, dz);
+        dx = fma2_<AM>(h.m[3], r.dw, dx);
+        dy = fma2_<AM>(h.m[7], r.dw, dy);
+        dz = fma2_<AM>(h.m[11], r.dw, dz);
     }
 }
 
 // the reference's `radical` (shade_and_reflect_kernel.cl:85-94) for both spheres of a pair
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ f2 pair_radical(f2 sx, f2 sy, f2 sz, f2 dx, f2 dy, f2 dz) {
-    f2 A = dy * dy; A = fma2_<FUSED>(dx, dx, A); A = fma2_<FUSED>(dz, dz, A);
-    f2 B = sy * dy; B = fma2_<FUSED>(dx, sx, B); B = fma2_<FUSED>(dz, sz, B); B = B * 2.0f;
-    f2 C = sy * sy; C = fma2_<FUSED>(sx, sx, C); C = fma2_<FUSED>(sz, sz, C); C = C + -1.0f;
-    return fma2_<FUSED>(B, B, (A * 4.0f) * (-C));
+    f2 A = dy * dy; A = fma2_<AM>(dx, dx, A); A = fma2_<AM>(dz, dz, A);
+    f2 B = sy * dy; B = fma2_<AM>(dx, sx, B); B = fma2_<AM>(dz, sz, B); B = B * 2.0f;
+    f2 C = sy * sy; C = fma2_<AM>(sx, sx, C); C = fma2_<AM>(sz, sz, C); C = C + -1.0f;
+    return fma2_<AM>(B, B, (A * 4.0f) * (-C));
 }
 
 // one object of a pair, generic type, on an object-space ray: closest-hit update with the reference's tie rules
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void closest_update(uint32_t type, float sx, float sy, float sz, float dx, float dy, float dz,
                                                int k, float& T, int& index) {
     float t;
     if (type == 0u) {
-        if (sphere_candidate<FUSED>(sx, sy, sz, dx, dy, dz, t)) {
+        if (sphere_candidate<AM>(sx, sy, sz, dx, dy, dz, t)) {
             if (!(T < t)) { T = t; index = k; }   // ties: the later sphere wins (Q3)
         }
     } else if (type == 1u) {
-        if (box_candidate(sx, sy, sz, dx, dy, dz, t)) {
+        if (box_candidate<AM>(sx, sy, sz, dx, dy, dz, t)) {
             if (!(T <= t)) { T = t; index = k; }  // ties: the earlier object wins (Q3)
         }
     }
 }
 
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void closest_pair(const HotPair& h, int p, const RaySplat& r, float& T, int& index) {
     f2 sx, sy, sz, dx, dy, dz;
-    pair_object_space<FUSED, DW0>(h, r, sx, sy, sz, dx, dy, dz);
+    pair_object_space<AM, DW0>(h, r, sx, sy, sz, dx, dy, dz);
     if ((h.type_a | h.type_b) == 0u) {  // two spheres: packed discriminant filter
-        const f2 rad = pair_radical<FUSED>(sx, sy, sz, dx, dy, dz);
+        const f2 rad = pair_radical<AM>(sx, sy, sz, dx, dy, dz);
         const bool ca = !(rad.x < 0), cb = !(rad.y < 0);
         if (ca || cb) {
-            if (ca) closest_update<FUSED>(0u, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x, 2 * p, T, index);
-            if (cb) closest_update<FUSED>(0u, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y, 2 * p + 1, T, index);
+            if (ca) closest_update<AM>(0u, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x, 2 * p, T, index);
+            if (cb) closest_update<AM>(0u, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y, 2 * p + 1, T, index);
         }
     } else {
-        closest_update<FUSED>(h.type_a, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x, 2 * p, T, index);
-        closest_update<FUSED>(h.type_b, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y, 2 * p + 1, T, index);
+        closest_update<AM>(h.type_a, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x, 2 * p, T, index);
+        closest_update<AM>(h.type_b, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y, 2 * p + 1, T, index);
     }
 }
 
@@ -395,7 +483,7 @@ __device__ __forceinline__ void l2_warm_finish(Warm& w) {
 
 // Closest hit over all objects in ascending index order (the reference's raycast(), :72-177, keeping only
 // (t, index)). Two pair records are kept in flight: the next one is requested before the current one is used.
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void closest_hit(const HotPair* __restrict__ pairs, uint32_t n_pairs, const Ray& ray, float& T,
                                             int& index) {
     if (n_pairs == 0) return;
@@ -406,41 +494,41 @@ __device__ __forceinline__ void closest_hit(const HotPair* __restrict__ pairs, u
     for (; p + 1 < n_pairs; p += 2) {
         if ((p & (kWarmPeriod - 1u)) == 0u) l2_warm(pairs, n_pairs, p, warm);
         const HotPair b = pairs[p + 1];
-        closest_pair<FUSED, DW0>(a, (int)p, r, T, index);
+        closest_pair<AM, DW0>(a, (int)p, r, T, index);
         a = pairs[(p + 2 < n_pairs) ? p + 2 : p + 1];
-        closest_pair<FUSED, DW0>(b, (int)p + 1, r, T, index);
+        closest_pair<AM, DW0>(b, (int)p + 1, r, T, index);
     }
-    if (p < n_pairs) closest_pair<FUSED, DW0>(a, (int)p, r, T, index);
+    if (p < n_pairs) closest_pair<AM, DW0>(a, (int)p, r, T, index);
     l2_warm_finish(warm);
 }
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool occludes(uint32_t type, float sx, float sy, float sz, float dx, float dy, float dz) {
     float t;
     bool cand = false;
-    if (type == 0u) cand = sphere_candidate<FUSED>(sx, sy, sz, dx, dy, dz, t);
-    else if (type == 1u) cand = box_candidate(sx, sy, sz, dx, dy, dz, t);
+    if (type == 0u) cand = sphere_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
+    else if (type == 1u) cand = box_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
     // `!(t >= 1)`, not `t < 1`: a NaN time (a shadow ray with a NaN in it - a light exactly at the hit point, a zero
     // directional light) is accepted by every sphere / box of the reference's loop, the final time is NaN, and its
     // `time >= 1 || time < 0` (:229) then reports the light as blocked
     return cand && !(t >= 1.f);
 }
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool any_hit_pair(const HotPair& h, const RaySplat& r) {
     f2 sx, sy, sz, dx, dy, dz;
-    pair_object_space<FUSED, true>(h, r, sx, sy, sz, dx, dy, dz);
+    pair_object_space<AM, true>(h, r, sx, sy, sz, dx, dy, dz);
     bool occ = false;
     if ((h.type_a | h.type_b) == 0u) {
-        const f2 rad = pair_radical<FUSED>(sx, sy, sz, dx, dy, dz);
+        const f2 rad = pair_radical<AM>(sx, sy, sz, dx, dy, dz);
         const bool ca = !(rad.x < 0), cb = !(rad.y < 0);
         if (ca || cb) {
-            if (ca) occ = occludes<FUSED>(0u, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x);
-            if (cb && !occ) occ = occludes<FUSED>(0u, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y);
+            if (ca) occ = occludes<AM>(0u, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x);
+            if (cb && !occ) occ = occludes<AM>(0u, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y);
         }
     } else {
-        occ = occludes<FUSED>(h.type_a, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x);
-        if (!occ) occ = occludes<FUSED>(h.type_b, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y);
+        occ = occludes<AM>(h.type_a, sx.x, sy.x, sz.x, dx.x, dy.x, dz.x);
+        if (!occ) occ = occludes<AM>(h.type_b, sx.y, sy.y, sz.y, dx.y, dy.y, dz.y);
     }
     return occ;
 }
@@ -449,7 +537,7 @@ __device__ __forceinline__ bool any_hit_pair(const HotPair& h, const RaySplat& r
 // means an occluder between the point and the light, shade_and_reflect_kernel.cl:201-209,229). The loop stays
 // wave-uniform (no per-lane break: lanes that already found their occluder just ride along) and the wave
 // leaves as soon as every active lane has one.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool any_hit_before_one(const HotPair* __restrict__ pairs, uint32_t n_pairs, const Ray& ray,
                                                    uint32_t* pairs_visited = nullptr) {
     if (pairs_visited) *pairs_visited = 0;
@@ -462,13 +550,13 @@ __device__ __forceinline__ bool any_hit_before_one(const HotPair* __restrict__ p
     for (; p + 1 < n_pairs; p += 2) {
         if ((p & (kWarmPeriod - 1u)) == 0u) l2_warm(pairs, n_pairs, p, warm);
         const HotPair b = pairs[p + 1];
-        occluded |= any_hit_pair<FUSED>(a, r);
+        occluded |= any_hit_pair<AM>(a, r);
         a = pairs[(p + 2 < n_pairs) ? p + 2 : p + 1];
-        occluded |= any_hit_pair<FUSED>(b, r);
+        occluded |= any_hit_pair<AM>(b, r);
         if (__ballot(!occluded) == 0ull) { done = true; p += 2; break; }  // wave-uniform exit
     }
     if (!done && p < n_pairs) {  // odd pair count: one record left
-        if (__ballot(!occluded) != 0ull) { occluded |= any_hit_pair<FUSED>(a, r); p = n_pairs; }
+        if (__ballot(!occluded) != 0ull) { occluded |= any_hit_pair<AM>(a, r); p = n_pairs; }
     }
     if (pairs_visited) *pairs_visited = p;
     l2_warm_finish(warm);
@@ -480,25 +568,25 @@ __device__ __forceinline__ bool any_hit_before_one(const HotPair* __restrict__ p
 // loops cost registers there). The monolithic kernel therefore walks HotObject records one by one; `mask`
 // (wave-uniform, bit k = object k may be hit by some ray of this wave) skips objects that the per-tile bounding
 // test (rt_kernels.hip) has ruled out for the whole wave. Object order stays ascending, so the tie rules hold.
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void object_space_one(const RT_CONST HotObjectC* o, const Ray& ray, float& sx, float& sy,
                                                  float& sz, float& dx, float& dy, float& dz) {
     const f4 r0 = o->row0, r1 = o->row1, r2 = o->row2;
-    sx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    sy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    sz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
     if constexpr (DW0) {
-        dx = row3<FUSED>(r0.x, r0.y, r0.z, ray.dx, ray.dy, ray.dz);
-        dy = row3<FUSED>(r1.x, r1.y, r1.z, ray.dx, ray.dy, ray.dz);
-        dz = row3<FUSED>(r2.x, r2.y, r2.z, ray.dx, ray.dy, ray.dz);
+        dx = row3<AM>(r0.x, r0.y, r0.z, ray.dx, ray.dy, ray.dz);
+        dy = row3<AM>(r1.x, r1.y, r1.z, ray.dx, ray.dy, ray.dz);
+        dz = row3<AM>(r2.x, r2.y, r2.z, ray.dx, ray.dy, ray.dz);
     } else {
-        dx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
     }
 }
 
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void closest_hit_small(const HotObject* __restrict__ hot_, uint32_t n, bool use_mask, uint64_t mask,
                                                   const Ray& ray, float& T, int& index) {
     const RT_CONST HotObjectC* hot = (const RT_CONST HotObjectC*)(hot_);
@@ -507,26 +595,26 @@ __device__ __forceinline__ void closest_hit_small(const HotObject* __restrict__ 
             const int k = __builtin_ctzll(mask);
             mask &= mask - 1ull;
             float sx, sy, sz, dx, dy, dz;
-            object_space_one<FUSED, DW0>(hot + k, ray, sx, sy, sz, dx, dy, dz);
-            closest_update<FUSED>(hot[k].type, sx, sy, sz, dx, dy, dz, k, T, index);
+            object_space_one<AM, DW0>(hot + k, ray, sx, sy, sz, dx, dy, dz);
+            closest_update<AM>(hot[k].type, sx, sy, sz, dx, dy, dz, k, T, index);
         }
     } else {
         for (uint32_t k = 0; k < n; ++k) {
             float sx, sy, sz, dx, dy, dz;
-            object_space_one<FUSED, DW0>(hot + k, ray, sx, sy, sz, dx, dy, dz);
-            closest_update<FUSED>(hot[k].type, sx, sy, sz, dx, dy, dz, (int)k, T, index);
+            object_space_one<AM, DW0>(hot + k, ray, sx, sy, sz, dx, dy, dz);
+            closest_update<AM>(hot[k].type, sx, sy, sz, dx, dy, dz, (int)k, T, index);
         }
     }
 }
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool any_hit_small(const HotObject* __restrict__ hot_, uint32_t n, const Ray& ray) {
     const RT_CONST HotObjectC* hot = (const RT_CONST HotObjectC*)(hot_);
     bool occluded = false;
     for (uint32_t k = 0; k < n; ++k) {
         float sx, sy, sz, dx, dy, dz;
-        object_space_one<FUSED, true>(hot + k, ray, sx, sy, sz, dx, dy, dz);
-        occluded |= occludes<FUSED>(hot[k].type, sx, sy, sz, dx, dy, dz);
+        object_space_one<AM, true>(hot + k, ray, sx, sy, sz, dx, dy, dz);
+        occluded |= occludes<AM>(hot[k].type, sx, sy, sz, dx, dy, dz);
         if (__ballot(!occluded) == 0ull) break;
     }
     return occluded;
@@ -543,7 +631,7 @@ struct ObjRows {
     uint32_t type, pad0;
 };
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ objrec, const ColdObject* __restrict__ cold,
                                             int index, float t, const Ray& ray, HitRec& h, bool affine = false, ObjRows* rows = nullptr,
                                             float* absorption = nullptr) {
@@ -554,29 +642,29 @@ __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ obj
     if (absorption) *absorption = o->absorption;
     if (type == 2u) {  // triangle (extension): view-space point on the ray, normal = normalize(e1 x e2)
         const float4 e1 = o->inv_row[1], e2 = o->inv_row[2];
-        h.px = fma_<FUSED>(t, ray.dx, ray.sx);
-        h.py = fma_<FUSED>(t, ray.dy, ray.sy);
-        h.pz = fma_<FUSED>(t, ray.dz, ray.sz);
-        h.pw = fma_<FUSED>(t, ray.dw, ray.sw);
+        h.px = fma_<AM>(t, ray.dx, ray.sx);
+        h.py = fma_<AM>(t, ray.dy, ray.sy);
+        h.pz = fma_<AM>(t, ray.dz, ray.sz);
+        h.pw = fma_<AM>(t, ray.dw, ray.sw);
         float nx = e1.y * e2.z - e1.z * e2.y;
         float ny = e1.z * e2.x - e1.x * e2.z;
         float nz = e1.x * e2.y - e1.y * e2.x;
         normalize3(nx, ny, nz);
         h.nx = nx; h.ny = ny; h.nz = nz;
         const float k2 = dot3(ray.dx, ray.dy, ray.dz, nx, ny, nz) * -2.0f;
-        h.rx = fma_<FUSED>(k2, nx, ray.dx);
-        h.ry = fma_<FUSED>(k2, ny, ray.dy);
-        h.rz = fma_<FUSED>(k2, nz, ray.dz);
+        h.rx = fma_<AM>(k2, nx, ray.dx);
+        h.ry = fma_<AM>(k2, ny, ray.dy);
+        h.rz = fma_<AM>(k2, nz, ray.dz);
         h.index = index;
         return;
     }
     const float4 r0 = o->inv_row[0], r1 = o->inv_row[1], r2 = o->inv_row[2];
-    const float sx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    const float sy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    const float sz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    const float dx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
-    const float dy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
-    const float dz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
+    const float sx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float dx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
+    const float dy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
+    const float dz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
     // Row w of the transforms. With bottom rows (0,0,0,1) - every instance of an `affine` scene, checked at upload - the
     // reference's own expression 0*y + 0*x + 0*z + 1*w returns w for finite x, y, z (the zeros can only change the sign of a
     // zero): the two 16-byte rows are not fetched and the identity is used instead.
@@ -586,13 +674,13 @@ __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ obj
         dw = ray.dw;
     } else {
         const float4 r3 = c->inv_row3;
-        sw = row4<FUSED>(r3.x, r3.y, r3.z, r3.w, ray.sx, ray.sy, ray.sz, ray.sw);
-        dw = row4<FUSED>(r3.x, r3.y, r3.z, r3.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        sw = row4<AM>(r3.x, r3.y, r3.z, r3.w, ray.sx, ray.sy, ray.sz, ray.sw);
+        dw = row4<AM>(r3.x, r3.y, r3.z, r3.w, ray.dx, ray.dy, ray.dz, ray.dw);
     }
-    const float px = fma_<FUSED>(t, dx, sx);
-    const float py = fma_<FUSED>(t, dy, sy);
-    const float pz = fma_<FUSED>(t, dz, sz);
-    const float pw = fma_<FUSED>(t, dw, sw);
+    const float px = fma_<AM>(t, dx, sx);
+    const float py = fma_<AM>(t, dy, sy);
+    const float pz = fma_<AM>(t, dz, sz);
+    const float pw = fma_<AM>(t, dw, sw);
     float ox, oy, oz;  // object-space normal
     if (type == 0u) {
         ox = px; oy = py; oz = pz;
@@ -603,24 +691,24 @@ __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ obj
         if (pz > 0.4998f) oz += 1.f; else if (pz < -0.4998f) oz -= 1.f;
     }
     const float4 m0 = o->mv_row[0], m1 = o->mv_row[1], m2 = o->mv_row[2];
-    h.px = row4<FUSED>(m0.x, m0.y, m0.z, m0.w, px, py, pz, pw);
-    h.py = row4<FUSED>(m1.x, m1.y, m1.z, m1.w, px, py, pz, pw);
-    h.pz = row4<FUSED>(m2.x, m2.y, m2.z, m2.w, px, py, pz, pw);
+    h.px = row4<AM>(m0.x, m0.y, m0.z, m0.w, px, py, pz, pw);
+    h.py = row4<AM>(m1.x, m1.y, m1.z, m1.w, px, py, pz, pw);
+    h.pz = row4<AM>(m2.x, m2.y, m2.z, m2.w, px, py, pz, pw);
     if (affine) {
         h.pw = pw;
     } else {
         const float4 m3 = c->mv_row[3];
-        h.pw = row4<FUSED>(m3.x, m3.y, m3.z, m3.w, px, py, pz, pw);
+        h.pw = row4<AM>(m3.x, m3.y, m3.z, m3.w, px, py, pz, pw);
     }
-    float nx = row4<FUSED>(m0.x, m0.y, m0.z, m0.w, ox, oy, oz, 0.f);
-    float ny = row4<FUSED>(m1.x, m1.y, m1.z, m1.w, ox, oy, oz, 0.f);
-    float nz = row4<FUSED>(m2.x, m2.y, m2.z, m2.w, ox, oy, oz, 0.f);
-    normalize3(nx, ny, nz);
+    float nx = row4<AM>(m0.x, m0.y, m0.z, m0.w, ox, oy, oz, 0.f);
+    float ny = row4<AM>(m1.x, m1.y, m1.z, m1.w, ox, oy, oz, 0.f);
+    float nz = row4<AM>(m2.x, m2.y, m2.z, m2.w, ox, oy, oz, 0.f);
+    normalize3_<AM>(nx, ny, nz);
     h.nx = nx; h.ny = ny; h.nz = nz;
-    const float k2 = dot3(ray.dx, ray.dy, ray.dz, nx, ny, nz) * -2.0f;
-    h.rx = fma_<FUSED>(k2, nx, ray.dx);
-    h.ry = fma_<FUSED>(k2, ny, ray.dy);
-    h.rz = fma_<FUSED>(k2, nz, ray.dz);
+    const float k2 = dot3_<AM>(ray.dx, ray.dy, ray.dz, nx, ny, nz) * -2.0f;
+    h.rx = fma_<AM>(k2, nx, ray.dx);
+    h.ry = fma_<AM>(k2, ny, ray.dy);
+    h.rz = fma_<AM>(k2, nz, ray.dz);
     h.index = index;
 }
 
@@ -672,15 +760,15 @@ struct Scene {
 
 // secondary rays (shadow / reflection; direction.w == 0): pair stream in the wavefront kernels, one object at a
 // time in the monolithic kernel (SMALL)
-template <bool FUSED, bool SMALL>
+template <int AM, bool SMALL>
 __device__ __forceinline__ void closest_secondary(const Scene& S, const Ray& ray, float& T, int& idx) {
-    if constexpr (SMALL) closest_hit_small<FUSED, true>(S.hot, S.n_objs, false, 0ull, ray, T, idx);
-    else closest_hit<FUSED, true>(S.pairs, S.n_pairs, ray, T, idx);
+    if constexpr (SMALL) closest_hit_small<AM, true>(S.hot, S.n_objs, false, 0ull, ray, T, idx);
+    else closest_hit<AM, true>(S.pairs, S.n_pairs, ray, T, idx);
 }
-template <bool FUSED, bool SMALL>
+template <int AM, bool SMALL>
 __device__ __forceinline__ bool any_secondary(const Scene& S, const Ray& ray) {
-    if constexpr (SMALL) return any_hit_small<FUSED>(S.hot, S.n_objs, ray);
-    else return any_hit_before_one<FUSED>(S.pairs, S.n_pairs, ray);
+    if constexpr (SMALL) return any_hit_small<AM>(S.hot, S.n_objs, ray);
+    else return any_hit_before_one<AM>(S.pairs, S.n_pairs, ray);
 }
 
 struct LightGeom {
@@ -705,39 +793,39 @@ __device__ __forceinline__ float specular_power(float rDotV, float shininess, bo
 // the shadow ray of light L from the point (px, py, pz), and the normalised light vector (shade_and_reflect_kernel.cl:195-205).
 // One function for everybody who needs that ray: the light loop, and the trace kernels that REBUILD it from the stored
 // hit point instead of reading a stored copy (rt_wavefront.hip) - same statements, same bits.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void shadow_ray_to(const LightRec& L, float px, float py, float pz, Ray& shadow, float& nlx, float& nly, float& nlz) {
     float lx, ly, lz;
     if (L.position.w != 0) { lx = L.position.x - px; ly = L.position.y - py; lz = L.position.z - pz; }
     else { lx = -L.position.x; ly = -L.position.y; lz = -L.position.z; }
     nlx = lx; nly = ly; nlz = lz;
-    normalize3(nlx, nly, nlz);
-    shadow.sx = fma_<FUSED>(nlx, 0.01f, px);
-    shadow.sy = fma_<FUSED>(nly, 0.01f, py);
-    shadow.sz = fma_<FUSED>(nlz, 0.01f, pz);
-    shadow.sw = fma_<FUSED>(0.0f, 0.01f, 1.0f);
+    normalize3_<AM>(nlx, nly, nlz);
+    shadow.sx = fma_<AM>(nlx, 0.01f, px);
+    shadow.sy = fma_<AM>(nly, 0.01f, py);
+    shadow.sz = fma_<AM>(nlz, 0.01f, pz);
+    shadow.sw = fma_<AM>(0.0f, 0.01f, 1.0f);
     shadow.dx = lx; shadow.dy = ly; shadow.dz = lz; shadow.dw = 0.0f;
 }
 
 // everything of one light-loop iteration that does not depend on the shadow test
 // (shade_and_reflect_kernel.cl:194-224)
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void light_geometry(const LightRec& L, const HitRec& h, float nvx, float nvy, float nvz,
                                                float vvx, float vvy, float vvz, LightGeom& g, bool fast = false) {
     float nlx, nly, nlz;
-    shadow_ray_to<FUSED>(L, h.px, h.py, h.pz, g.shadow, nlx, nly, nlz);
+    shadow_ray_to<AM>(L, h.px, h.py, h.pz, g.shadow, nlx, nly, nlz);
     g.nlx = nlx; g.nly = nly; g.nlz = nlz;
-    g.nDotL = dot3(nvx, nvy, nvz, nlx, nly, nlz);
-    const float kk = dot3(-nlx, -nly, -nlz, nvx, nvy, nvz) * -2.0f;
-    float rx = fma_<FUSED>(kk, nvx, -nlx);
-    float ry = fma_<FUSED>(kk, nvy, -nly);
-    float rz = fma_<FUSED>(kk, nvz, -nlz);
-    normalize3_shading(fast, rx, ry, rz);
-    g.rDotV = __builtin_fmaxf(dot3(rx, ry, rz, vvx, vvy, vvz), 0.0f);
+    g.nDotL = dot3_<AM>(nvx, nvy, nvz, nlx, nly, nlz);
+    const float kk = dot3_<AM>(-nlx, -nly, -nlz, nvx, nvy, nvz) * -2.0f;
+    float rx = fma_<AM>(kk, nvx, -nlx);
+    float ry = fma_<AM>(kk, nvy, -nly);
+    float rz = fma_<AM>(kk, nvz, -nlz);
+    normalize3_shading<AM>(fast, rx, ry, rz);
+    g.rDotV = __builtin_fmaxf(dot3_<AM>(rx, ry, rz, vvx, vvy, vvz), 0.0f);
 }
 
 // lit iff the reference's `shadowcastHit.time >= 1.f || shadowcastHit.time < 0` (:229)
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ bool light_visible(const Scene& S, const Ray& shadow, Counters& ctr) {
     if constexpr (COUNT) ctr.traced += 1;
     if (!S.literal) {  // the any-hit test is order-free: a NaN shadow ray's outcome is not (`time >= 1 || time < 0`, :229)
@@ -747,32 +835,32 @@ __device__ __forceinline__ bool light_visible(const Scene& S, const Ray& shadow,
     if (S.literal) {
         float T = kMaxFloat;
         int idx = -1;
-        closest_secondary<FUSED, true>(S, shadow, T, idx);
+        closest_secondary<AM, true>(S, shadow, T, idx);
         return (T >= 1.f || T < 0);
     }
-    return !any_secondary<FUSED, true>(S, shadow);
+    return !any_secondary<AM, true>(S, shadow);
 }
 
 // The light loop in the reference's order. ACCUMULATE: shade_kernel.cl:252 (sum over lights);
 // otherwise shade_and_reflect_kernel.cl:238 (assignment - the last light's terms survive). Both carry the
 // stale specular: it is re-assigned only when lit with nDotL > 0 and zeroed when shadowed (:229-237).
-template <bool FUSED, bool ACCUMULATE, bool COUNT>
+template <int AM, bool ACCUMULATE, bool COUNT>
 __device__ __forceinline__ void shade_forward(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
                                               Counters& ctr) {
     const ColdObject* c = S.cold + h.index;
     const float4 amb = c->amb_absorb, dif = c->dif_shine, spec = c->spec_type;
     float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-    normalize3_shading(S.fast_phong != 0u, nvx, nvy, nvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, nvx, nvy, nvz);
     float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-    normalize3_shading(S.fast_phong != 0u, vvx, vvy, vvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, vvx, vvy, vvz);
     cr = 0.f; cg = 0.f; cb = 0.f;
     float sr = 0.f, sg = 0.f, sb = 0.f;  // specular carried across iterations
     if constexpr (COUNT) ctr.reference += S.n_lights;
     for (uint32_t li = 0; li < S.n_lights; ++li) {
         const LightRec L = S.lights[li];
         LightGeom g;
-        light_geometry<FUSED>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
-        const bool lit = light_visible<FUSED, COUNT>(S, g.shadow, ctr);
+        light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
+        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr);
         const float ar = amb.x * L.ambient.x, ag = amb.y * L.ambient.y, ab = amb.z * L.ambient.z;
         float dr, dg, db;
         if (lit) {
@@ -797,7 +885,7 @@ __device__ __forceinline__ void shade_forward(const Scene& S, const HitRec& h, f
 // shade_and_reflect's colour without tracing the shadow rays whose result cannot reach it: ambient and
 // diffuse come from the last light only; the specular from the last light j that was either shadowed
 // (-> 0) or lit with nDotL > 0. Scan backwards from the last light and stop at j.
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
                                                       Counters& ctr) {
     cr = 0.f; cg = 0.f; cb = 0.f;
@@ -806,9 +894,9 @@ __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitR
     const ColdObject* c = S.cold + h.index;
     const float4 amb = c->amb_absorb, dif = c->dif_shine, spec = c->spec_type;
     float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-    normalize3_shading(S.fast_phong != 0u, nvx, nvy, nvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, nvx, nvy, nvz);
     float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-    normalize3_shading(S.fast_phong != 0u, vvx, vvy, vvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, vvx, vvy, vvz);
     float sr = 0.f, sg = 0.f, sb = 0.f;
     float dr = 0.f, dg = 0.f, db = 0.f;
     float ar = 0.f, ag = 0.f, ab = 0.f;
@@ -816,8 +904,8 @@ __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitR
     for (uint32_t li = S.n_lights; li-- > 0 && need_specular;) {
         const LightRec L = S.lights[li];
         LightGeom g;
-        light_geometry<FUSED>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
-        const bool lit = light_visible<FUSED, COUNT>(S, g.shadow, ctr);
+        light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
+        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr);
         if (li == S.n_lights - 1) {
             ar = amb.x * L.ambient.x; ag = amb.y * L.ambient.y; ab = amb.z * L.ambient.z;
             if (lit) {
@@ -837,32 +925,32 @@ __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitR
     cr = (ar + dr) + sr; cg = (ag + dg) + sg; cb = (ab + db) + sb;
 }
 
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ void shade_assign(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
                                              Counters& ctr) {
-    if (S.literal) shade_forward<FUSED, false, COUNT>(S, h, cr, cg, cb, ctr);
-    else shade_last_light_wins<FUSED, COUNT>(S, h, cr, cg, cb, ctr);
+    if (S.literal) shade_forward<AM, false, COUNT>(S, h, cr, cg, cb, ctr);
+    else shade_last_light_wins<AM, COUNT>(S, h, cr, cg, cb, ctr);
 }
 
 // next ray of the reflection chain: start = intersection + 0.001 * normalize(reflection), direction = reflection
 // (shade_and_reflect_kernel.cl:260-263, 275-277)
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void reflection_ray(const HitRec& h, Ray& r) {
     float nx = h.rx, ny = h.ry, nz = h.rz;
-    normalize3(nx, ny, nz);
-    r.sx = fma_<FUSED>(nx, 0.001f, h.px);
-    r.sy = fma_<FUSED>(ny, 0.001f, h.py);
-    r.sz = fma_<FUSED>(nz, 0.001f, h.pz);
-    r.sw = fma_<FUSED>(0.0f, 0.001f, h.pw);
+    normalize3_<AM>(nx, ny, nz);
+    r.sx = fma_<AM>(nx, 0.001f, h.px);
+    r.sy = fma_<AM>(ny, 0.001f, h.py);
+    r.sz = fma_<AM>(nz, 0.001f, h.pz);
+    r.sw = fma_<AM>(0.0f, 0.001f, h.pw);
     r.dx = h.rx; r.dy = h.ry; r.dz = h.rz; r.dw = 0.0f;
 }
 
 // __kernel shade_and_reflect for one work-item whose primary ray hit (shade_and_reflect_kernel.cl:253-284)
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ void shade_and_reflect_pixel(const Scene& S, uint32_t max_bounces, const HitRec& hit,
                                                         float& outr, float& outg, float& outb, Counters& ctr) {
     float cr, cg, cb;
-    shade_assign<FUSED, COUNT>(S, hit, cr, cg, cb, ctr);
+    shade_assign<AM, COUNT>(S, hit, cr, cg, cb, ctr);
     float ap = S.cold[hit.index].amb_absorb.w;
     float abr = cr * ap, abg = cg * ap, abb = cb * ap;
     float rr = 0.f, rg = 0.f, rb = 0.f;  // reflectColor
@@ -878,23 +966,23 @@ __device__ __forceinline__ void shade_and_reflect_pixel(const Scene& S, uint32_t
         if (!absorbing && !S.literal) break;  // the reference still casts this ray but never reads the result
         if constexpr (COUNT) ctr.traced += 1;
         Ray ray;
-        reflection_ray<FUSED>(from, ray);
+        reflection_ray<AM>(from, ray);
         float T = kMaxFloat;
         int idx = -1;
-        closest_secondary<FUSED, true>(S, ray, T, idx);
+        closest_secondary<AM, true>(S, ray, T, idx);
         if (T == kMaxFloat) break;  // raycast() returned false (:173)
         if (!absorbing) break;
         HitRec rh;
-        materialise<FUSED>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u);
-        shade_assign<FUSED, COUNT>(S, rh, rr, rg, rb, ctr);
+        materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u);
+        shade_assign<AM, COUNT>(S, rh, rr, rg, rb, ctr);
         const float ra = (1.f - ap) * S.cold[rh.index].amb_absorb.w;
-        abr = fma_<FUSED>(ra, rr, abr); abg = fma_<FUSED>(ra, rg, abg); abb = fma_<FUSED>(ra, rb, abb);
+        abr = fma_<AM>(ra, rr, abr); abg = fma_<AM>(ra, rg, abg); abb = fma_<AM>(ra, rb, abb);
         ap = ap + ra;
         from = rh;
     }
     if (bounces == 0u && ap < 1.f) {  // (:281-282)
         const float w = 1.f - ap;
-        abr = fma_<FUSED>(w, rr, abr); abg = fma_<FUSED>(w, rg, abg); abb = fma_<FUSED>(w, rb, abb);
+        abr = fma_<AM>(w, rr, abr); abg = fma_<AM>(w, rg, abg); abb = fma_<AM>(w, rb, abb);
     }
     outr = abr; outg = abg; outb = abb;
 }

@@ -207,13 +207,13 @@ __device__ __forceinline__ void closest_take(float t, int k, bool sphere, float&
     if (take) { T = t; index = k; cur_sphere = sphere; }
 }
 
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void closest_update_unordered(uint32_t type, float sx, float sy, float sz, float dx, float dy,
                                                          float dz, int k, float& T, int& index, bool& cur_sphere) {
     float t;
     bool cand = false;
-    if (type == 0u) cand = sphere_candidate<FUSED>(sx, sy, sz, dx, dy, dz, t);
-    else if (type == 1u) cand = box_candidate(sx, sy, sz, dx, dy, dz, t);
+    if (type == 0u) cand = sphere_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
+    else if (type == 1u) cand = box_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
     if (cand) closest_take(t, k, type == 0u, T, index, cur_sphere);
 }
 
@@ -257,27 +257,27 @@ __device__ __forceinline__ bool entered_inside(const float4 s, const Ray& ray, f
 }
 
 // per-lane object test: the HotObject arrives through ordinary (divergent) vector loads
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void lane_object_space(const HotObject* __restrict__ o, const Ray& ray, float& sx, float& sy,
                                                   float& sz, float& dx, float& dy, float& dz, uint32_t& type) {
     const float4 r0 = o->row0, r1 = o->row1, r2 = o->row2;
     type = o->type;
-    sx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    sy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    sz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    sz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
     if constexpr (DW0) {
-        dx = row3<FUSED>(r0.x, r0.y, r0.z, ray.dx, ray.dy, ray.dz);
-        dy = row3<FUSED>(r1.x, r1.y, r1.z, ray.dx, ray.dy, ray.dz);
-        dz = row3<FUSED>(r2.x, r2.y, r2.z, ray.dx, ray.dy, ray.dz);
+        dx = row3<AM>(r0.x, r0.y, r0.z, ray.dx, ray.dy, ray.dz);
+        dy = row3<AM>(r1.x, r1.y, r1.z, ray.dx, ray.dy, ray.dz);
+        dz = row3<AM>(r2.x, r2.y, r2.z, ray.dx, ray.dy, ray.dz);
     } else {
-        dx = row4<FUSED>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dy = row4<FUSED>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dz = row4<FUSED>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
     }
 }
 
 // the reference's exact test of one object (any type) for one lane: candidate or not, and its t
-template <bool FUSED, bool DW0, bool TRI = true>
+template <int AM, bool DW0, bool TRI = true>
 __device__ __forceinline__ bool lane_candidate(const HotObject* __restrict__ o, const Ray& ray, float& t, bool& sphere) {
     const uint32_t type = o->type;
     sphere = (type == 0u);
@@ -288,34 +288,34 @@ __device__ __forceinline__ bool lane_candidate(const HotObject* __restrict__ o, 
     }
     float sx, sy, sz, dx, dy, dz;
     uint32_t ty;
-    lane_object_space<FUSED, DW0>(o, ray, sx, sy, sz, dx, dy, dz, ty);
-    if (type == 0u) return sphere_candidate<FUSED>(sx, sy, sz, dx, dy, dz, t);
-    if (type == 1u) return box_candidate(sx, sy, sz, dx, dy, dz, t);
+    lane_object_space<AM, DW0>(o, ray, sx, sy, sz, dx, dy, dz, ty);
+    if (type == 0u) return sphere_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
+    if (type == 1u) return box_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
     return false;
 }
 
 // ... of an object whose record is in registers already (materialise: ObjRows)
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ bool rows_candidate(const ObjRows& o, const Ray& ray, float& t, bool& sphere) {
     sphere = (o.type == 0u);
     if (o.type == 2u)
         return triangle_candidate(o.r0.x, o.r0.y, o.r0.z, o.r1.x, o.r1.y, o.r1.z, o.r2.x, o.r2.y, o.r2.z, o.r0.w, o.r1.w, o.r2.w,
                                   __uint_as_float(o.pad0), ray, t);
-    const float sx = row4<FUSED>(o.r0.x, o.r0.y, o.r0.z, o.r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    const float sy = row4<FUSED>(o.r1.x, o.r1.y, o.r1.z, o.r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
-    const float sz = row4<FUSED>(o.r2.x, o.r2.y, o.r2.z, o.r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sx = row4<AM>(o.r0.x, o.r0.y, o.r0.z, o.r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sy = row4<AM>(o.r1.x, o.r1.y, o.r1.z, o.r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sz = row4<AM>(o.r2.x, o.r2.y, o.r2.z, o.r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
     float dx, dy, dz;
     if constexpr (DW0) {
-        dx = row3<FUSED>(o.r0.x, o.r0.y, o.r0.z, ray.dx, ray.dy, ray.dz);
-        dy = row3<FUSED>(o.r1.x, o.r1.y, o.r1.z, ray.dx, ray.dy, ray.dz);
-        dz = row3<FUSED>(o.r2.x, o.r2.y, o.r2.z, ray.dx, ray.dy, ray.dz);
+        dx = row3<AM>(o.r0.x, o.r0.y, o.r0.z, ray.dx, ray.dy, ray.dz);
+        dy = row3<AM>(o.r1.x, o.r1.y, o.r1.z, ray.dx, ray.dy, ray.dz);
+        dz = row3<AM>(o.r2.x, o.r2.y, o.r2.z, ray.dx, ray.dy, ray.dz);
     } else {
-        dx = row4<FUSED>(o.r0.x, o.r0.y, o.r0.z, o.r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dy = row4<FUSED>(o.r1.x, o.r1.y, o.r1.z, o.r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
-        dz = row4<FUSED>(o.r2.x, o.r2.y, o.r2.z, o.r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dx = row4<AM>(o.r0.x, o.r0.y, o.r0.z, o.r0.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dy = row4<AM>(o.r1.x, o.r1.y, o.r1.z, o.r1.w, ray.dx, ray.dy, ray.dz, ray.dw);
+        dz = row4<AM>(o.r2.x, o.r2.y, o.r2.z, o.r2.w, ray.dx, ray.dy, ray.dz, ray.dw);
     }
-    if (o.type == 0u) return sphere_candidate<FUSED>(sx, sy, sz, dx, dy, dz, t);
-    if (o.type == 1u) return box_candidate(sx, sy, sz, dx, dy, dz, t);
+    if (o.type == 0u) return sphere_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
+    if (o.type == 1u) return box_candidate<AM>(sx, sy, sz, dx, dy, dz, t);
     return false;
 }
 
@@ -464,7 +464,7 @@ __device__ __forceinline__ bool lean_next(const GridDesc& g, LeanWalk& k) {
 }
 
 // Closest hit through the grid. Same (T, index) as closest_hit() over all objects.
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __device__ __forceinline__ void closest_hit_grid(const GridDesc& g, const HotObject* __restrict__ hot, const Ray& ray, float& T,
                                                  int& index, uint32_t& tested) {
     bool cur_sphere = false;
@@ -473,7 +473,7 @@ __device__ __forceinline__ void closest_hit_grid(const GridDesc& g, const HotObj
         const int k = (int)g.always[a];
         float t;
         bool sphere;
-        if (lane_candidate<FUSED, DW0>(hot + k, ray, t, sphere)) closest_take(t, k, sphere, T, index, cur_sphere);
+        if (lane_candidate<AM, DW0>(hot + k, ray, t, sphere)) closest_take(t, k, sphere, T, index, cur_sphere);
     }
     Walk w = walk_begin(g, ray, 3.0e38f);
     if (!w.alive) return;
@@ -492,7 +492,7 @@ __device__ __forceinline__ void closest_hit_grid(const GridDesc& g, const HotObj
             float t;
             bool sphere;
             ++tested;
-            if (lane_candidate<FUSED, DW0>(hot + k, ray, t, sphere)) closest_take(t, k, sphere, T, index, cur_sphere);
+            if (lane_candidate<AM, DW0>(hot + k, ray, t, sphere)) closest_take(t, k, sphere, T, index, cur_sphere);
         }
         // an empty cell's offset word says how many FURTHER steps are sure to land in empty cells (build_grid): those cells are
         // stepped through without fetching them
@@ -506,14 +506,14 @@ __device__ __forceinline__ void closest_hit_grid(const GridDesc& g, const HotObj
 
 // Any hit with t < 1 through the grid, one thread per ray (the tail of a frame: wf_finish). Same answer as the
 // brute-force any-hit loops: every candidate that can occlude is registered in a cell the walk visits.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool any_hit_grid(const GridDesc& g, const Scene& S, const Ray& ray, uint32_t& tested) {
     const HotObject* __restrict__ hot = S.hot;
     for (uint32_t a = 0; a < g.n_always; ++a) {
         float t;
         bool sphere;
         ++tested;
-        if (lane_candidate<FUSED, true>(hot + (int)g.always[a], ray, t, sphere) && !(t >= 1.f)) return true;
+        if (lane_candidate<AM, true>(hot + (int)g.always[a], ray, t, sphere) && !(t >= 1.f)) return true;
     }
     const float dd = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
     const float len = __builtin_sqrtf(dd);
@@ -528,7 +528,7 @@ __device__ __forceinline__ bool any_hit_grid(const GridDesc& g, const Scene& S, 
             float t;
             bool sphere;
             ++tested;
-            if (lane_candidate<FUSED, true>(hot + (int)g.entries[e], ray, t, sphere) && !(t >= 1.f)) return true;
+            if (lane_candidate<AM, true>(hot + (int)g.entries[e], ray, t, sphere) && !(t >= 1.f)) return true;
         }
         uint32_t steps = range.y ? 1u : 1u + range.x;  // (as in closest_hit_grid)
         bool stop = false;

@@ -32,7 +32,7 @@ struct RenderParams {
     Counters* counters;               // used by counted launches only
 };
 
-hipError_t launch_render(const RenderParams& p, int kernel, bool fused, bool count, hipStream_t stream);
+hipError_t launch_render(const RenderParams& p, int kernel, int arith, bool count, hipStream_t stream);
 
 // large-N path (rt_wavefront.hip): traversal and shading as separate kernels, pixel state in HBM
 struct WavefrontBuffers {
@@ -56,7 +56,7 @@ size_t wavefront_queue_bytes(uint64_t n_local);
 size_t wavefront_counter_bytes();
 // Runs a whole frame; the rounds are enqueued without host round trips (device-side round state), `stream` is
 // synchronised once per batch of rounds - once per frame in the normal case.
-hipError_t launch_wavefront(const RenderParams& p, int kernel, bool fused, bool count, WavefrontBuffers& buf,
+hipError_t launch_wavefront(const RenderParams& p, int kernel, int arith, bool count, WavefrontBuffers& buf,
                             hipStream_t stream, uint32_t* rounds_out);
 
 }  // namespace rt

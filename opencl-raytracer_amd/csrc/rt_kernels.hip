@@ -1,6 +1,6 @@
 // rt_kernels.hip - gfx950 kernels of the IRaytracer hot path and their launcher.
 //
-// render_pixels<KERNEL, FUSED, COUNT>: one work-item per ray, 256-thread workgroups (4 wave64). Replaces the
+// render_pixels<KERNEL, AM, COUNT>: one work-item per ray, 256-thread workgroups (4 wave64). Replaces the
 // reference's three NDRange kernels (hittest_kernel.cl:54, shade_kernel.cl:180,
 // shade_and_reflect_kernel.cl:244; launched 1-D with local size 32 at OpenCLRaytracer.cpp:89-91).
 // The whole bounce loop of a pixel stays in registers; object records arrive through scalar loads
@@ -39,7 +39,7 @@ __device__ __forceinline__ uint64_t bundle_candidates(const float4* __restrict__
 // shadow ray, reflection), so the distribution is left to the hardware workgroup dispatcher: measured here, a
 // persistent grid with static striding loses 25 % to imbalance, and one drawing bundles from an atomic counter
 // saturates that counter at ~88 tickets/us (3 ms for a 4096^2 frame).
-template <int KERNEL, bool FUSED, bool COUNT>
+template <int KERNEL, int AM, bool COUNT>
 __global__ __launch_bounds__(256) void render_pixels(const RenderParams p) {
     Counters ctr = {};
     const uint32_t lane = threadIdx.x & 63u;
@@ -112,8 +112,8 @@ __global__ __launch_bounds__(256) void render_pixels(const RenderParams p) {
                 ray.dx = d.x; ray.dy = d.y; ray.dz = d.z; ray.dw = d.w;
             }
 
-            if (p.dir_w_zero) closest_hit_small<FUSED, true>(S.hot, S.n_objs, use_mask, mask, ray, T, idx);
-            else closest_hit_small<FUSED, false>(S.hot, S.n_objs, use_mask, mask, ray, T, idx);
+            if (p.dir_w_zero) closest_hit_small<AM, true>(S.hot, S.n_objs, use_mask, mask, ray, T, idx);
+            else closest_hit_small<AM, false>(S.hot, S.n_objs, use_mask, mask, ray, T, idx);
 
             // raycast()'s return value: shade_and_reflect_kernel.cl:173 vs shade_kernel.cl:167 / hittest_kernel.cl:149
             hit = (KERNEL == 2) ? !(T == kMaxFloat) : (T < kMaxFloat);
@@ -121,9 +121,9 @@ __global__ __launch_bounds__(256) void render_pixels(const RenderParams p) {
             if constexpr (KERNEL != 0) {
                 if (hit) {
                     HitRec h;
-                    materialise<FUSED>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u);
-                    if constexpr (KERNEL == 1) shade_forward<FUSED, true, COUNT>(S, h, outr, outg, outb, ctr);
-                    else shade_and_reflect_pixel<FUSED, COUNT>(S, p.max_bounces, h, outr, outg, outb, ctr);
+                    materialise<AM>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u);
+                    if constexpr (KERNEL == 1) shade_forward<AM, true, COUNT>(S, h, outr, outg, outb, ctr);
+                    else shade_and_reflect_pixel<AM, COUNT>(S, p.max_bounces, h, outr, outg, outb, ctr);
                 }
             }
         }
@@ -153,23 +153,33 @@ __global__ __launch_bounds__(256) void render_pixels(const RenderParams p) {
     }
 }
 
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 static hipError_t launch2(const RenderParams& p, bool count, hipStream_t stream) {
     if (p.n_bundles == 0) return hipSuccess;
     uint32_t blocks;
     if (p.tile2d) blocks = ((p.bundles_x + 1u) / 2u) * ((((p.local_rows + 7u) / 8u) + 1u) / 2u);  // 2x2 bundles each
     else blocks = (p.n_bundles + 3u) / 4u;
     const dim3 grid(blocks), block(256);
-    if (count) hipLaunchKernelGGL((render_pixels<KERNEL, FUSED, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((render_pixels<KERNEL, FUSED, false>), grid, block, 0, stream, p);
+    if (count) hipLaunchKernelGGL((render_pixels<KERNEL, AM, true>), grid, block, 0, stream, p);
+    else hipLaunchKernelGGL((render_pixels<KERNEL, AM, false>), grid, block, 0, stream, p);
     return hipGetLastError();
 }
 
-hipError_t launch_render(const RenderParams& p, int kernel, bool fused, bool count, hipStream_t stream) {
+template <int KERNEL>
+static hipError_t launch_arith(const RenderParams& p, int arith, bool count, hipStream_t stream) {
+    switch (arith) {
+        case kUnfused: return launch2<KERNEL, kUnfused>(p, count, stream);
+        case kFused: return launch2<KERNEL, kFused>(p, count, stream);
+        case kDeviceCL: return launch2<KERNEL, kDeviceCL>(p, count, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_render(const RenderParams& p, int kernel, int arith, bool count, hipStream_t stream) {
     switch (kernel) {
-        case 0: return fused ? launch2<0, true>(p, count, stream) : launch2<0, false>(p, count, stream);
-        case 1: return fused ? launch2<1, true>(p, count, stream) : launch2<1, false>(p, count, stream);
-        case 2: return fused ? launch2<2, true>(p, count, stream) : launch2<2, false>(p, count, stream);
+        case 0: return launch_arith<0>(p, arith, count, stream);
+        case 1: return launch_arith<1>(p, arith, count, stream);
+        case 2: return launch_arith<2>(p, arith, count, stream);
         default: return hipErrorInvalidValue;
     }
 }

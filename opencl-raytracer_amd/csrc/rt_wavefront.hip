@@ -175,13 +175,13 @@ __device__ __forceinline__ void load_closest_result(const WfParams& w, uint64_t 
 __device__ __forceinline__ bool shadow_rays_rebuilt(const WfParams& w) {
     return w.grid.enabled && !w.rp.scene.literal && !w.grid.has_triangles;
 }
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ Ray shadow_of_pixel(const WfParams& w, uint64_t i, bool last_light, uint32_t& li) {
     const float4 hp = load_block(w, F_PX, i);
     li = last_light ? w.ltiles.light : (U(w, F_PHASE, i) >> kPhaseLightShift);
     Ray ray;
     float nlx, nly, nlz;
-    shadow_ray_to<FUSED>(w.rp.scene.lights[li], hp.x, hp.y, hp.z, ray, nlx, nly, nlz);
+    shadow_ray_to<AM>(w.rp.scene.lights[li], hp.x, hp.y, hp.z, ray, nlx, nly, nlz);
     return ray;
 }
 
@@ -292,7 +292,7 @@ __device__ __forceinline__ bool begin_pixel(const WfParams& w, uint64_t i) {
 }
 
 // ---- lean traversal kernels ----------------------------------------------------------------------------------------
-template <bool FUSED, bool DW0>
+template <int AM, bool DW0>
 __global__ __launch_bounds__(256) void wf_trace_closest(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void wf_trace_closest(const WfParams wk) {
     const Ray ray = closest_ray(w, i, w.first_round != 0u);
     float T = kMaxFloat;
     int idx = -1;
-    closest_hit<FUSED, DW0>(w.rp.scene.pairs, w.rp.scene.n_pairs, ray, T, idx);
+    closest_hit<AM, DW0>(w.rp.scene.pairs, w.rp.scene.n_pairs, ray, T, idx);
     store_closest_result(w, i, T, idx);
     const unsigned long long lanes = (unsigned long long)__popcll(__ballot(true));
     if (w.count_rays && (threadIdx.x & 63u) == 0u)  // 2 tests per pair for every ray of the wave
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void wf_trace_closest(const WfParams wk) {
 }
 
 // one object of a wave-uniform list (scalar loads) against this lane's ray
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void tile_candidate(const RT_CONST HotObjectC* o, int k, const Ray& ray, float& T, int& idx, bool& cur_sphere) {
     const uint32_t type = o->type;
     if (type == 2u) {  // triangle (extension)
@@ -321,14 +321,14 @@ __device__ __forceinline__ void tile_candidate(const RT_CONST HotObjectC* o, int
         return;
     }
     float sx, sy, sz, dx, dy, dz;
-    object_space_one<FUSED, true>(o, ray, sx, sy, sz, dx, dy, dz);
-    closest_update_unordered<FUSED>(type, sx, sy, sz, dx, dy, dz, k, T, idx, cur_sphere);
+    object_space_one<AM, true>(o, ray, sx, sy, sz, dx, dy, dz);
+    closest_update_unordered<AM>(type, sx, sy, sz, dx, dy, dz, k, T, idx, cur_sphere);
 }
 
 // First round of a pinhole frame: a wave holds 64 consecutive pixels of one row, i.e. one 64x8 screen tile, and
 // walks that tile's object list with wave-uniform scalar loads (plus the always-list). Waves that straddle tiles
 // (ragged ends) fall back to the per-lane grid walk. Order-free tie rules, so the result is the same either way.
-template <bool FUSED>
+template <int AM>
 __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -349,20 +349,20 @@ __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk)
         const RT_CONST HotObjectC* hot = (const RT_CONST HotObjectC*)(p.scene.hot);
         for (uint32_t a = 0; a < w.grid.n_always; ++a) {
             const int k = (int)w.grid.always[a];
-            tile_candidate<FUSED>(hot + k, k, ray, T, idx, cur_sphere);
+            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
         }
         for (uint32_t a = 0; a < w.tiles.n_global; ++a) {  // objects that project onto the whole screen
             const int k = (int)w.tiles.entries[w.tiles.global_begin + a];
-            tile_candidate<FUSED>(hot + k, k, ray, T, idx, cur_sphere);
+            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
         }
         const uint32_t e0 = w.tiles.tile_start[first], e1 = w.tiles.tile_start[first + 1];
         tested = w.grid.n_always + w.tiles.n_global + (e1 - e0);
         for (uint32_t e = e0; e < e1; ++e) {
             const int k = (int)w.tiles.entries[e];
-            tile_candidate<FUSED>(hot + k, k, ray, T, idx, cur_sphere);
+            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
         }
     } else {
-        closest_hit_grid<FUSED, true>(w.grid, p.scene.hot, ray, T, idx, tested);
+        closest_hit_grid<AM, true>(w.grid, p.scene.hot, ray, T, idx, tested);
     }
     store_closest_result(w, i, T, idx);
     if (w.count_rays) atomicAdd(&w.rp.counters->tests, (unsigned long long)tested);
@@ -496,7 +496,7 @@ struct RunCursor {
 // instructions - runs for the whole wave when enough lanes hold one (or are stuck behind theirs), so it executes
 // with tens of lanes instead of the 3-5 that happen to need it in any single trip. The closest-hit update is
 // order-free and T only ever shrinks, so a late update can only make a lane look at MORE cells than necessary.
-template <bool FUSED, bool ANY, bool STATS, bool TRI>
+template <int AM, bool ANY, bool STATS, bool TRI>
 __device__ __forceinline__ void trace_segment(const WfParams& w, const uint32_t* __restrict__ queue, uint32_t n_queue,
                                               uint32_t wave, uint32_t n_waves, uint32_t* __restrict__ run_ctr,
                                               unsigned long long& tested) {
@@ -538,7 +538,7 @@ __device__ __forceinline__ void trace_segment(const WfParams& w, const uint32_t*
                 pix = (!ANY && w.identity_queue) ? mine : (entry & kQueuePixel);
                 uint32_t ray_light;  // shadow rays: the light they go to; reflection rays: begin_shade_lit's note (the object they leave)
                 if (ANY && !TRI) {
-                    ray = shadow_of_pixel<FUSED>(w, pix, (entry & kQueueLastLight) != 0u, ray_light);
+                    ray = shadow_of_pixel<AM>(w, pix, (entry & kQueueLastLight) != 0u, ray_light);
                 } else if (ANY) {
                     ray = load_ray(w, pix, kSlotShadow);
                     ray_light = __float_as_uint(ray.dw);
@@ -557,7 +557,7 @@ __device__ __forceinline__ void trace_segment(const WfParams& w, const uint32_t*
                     const int k = (int)g.always[a];
                     float t;
                     bool sphere;
-                    const bool cand = lane_candidate<FUSED, true, TRI>(hot + k, ray, t, sphere);
+                    const bool cand = lane_candidate<AM, true, TRI>(hot + k, ray, t, sphere);
                     if (STATS) ++tested;
                     if (ANY) done = cand && !(t >= 1.f);
                     else if (cand) closest_take(t, k, sphere, T, idx, cur_sphere);
@@ -738,7 +738,7 @@ __device__ __forceinline__ void trace_segment(const WfParams& w, const uint32_t*
                 if (pend) {
                     float t;
                     bool sphere;
-                    const bool cand = lane_candidate<FUSED, true, TRI>(hot + pend_k, ray, t, sphere);
+                    const bool cand = lane_candidate<AM, true, TRI>(hot + pend_k, ray, t, sphere);
                     if (STATS) ++tested;
                     pend = false;
                     done_k = pend_k;
@@ -775,7 +775,7 @@ __device__ __forceinline__ void trace_segment(const WfParams& w, const uint32_t*
 #ifndef RT_WAVES_PER_EU_TRI
 #define RT_WAVES_PER_EU_TRI 6  // the variants that know triangles would like ~90 VGPRs; 5 waves without spills measured slower (97.6 vs 93 ms, cfg5)
 #endif
-template <bool FUSED, bool ANY, bool STATS, bool TRI>
+template <int AM, bool ANY, bool STATS, bool TRI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRI ? RT_WAVES_PER_EU_TRI : (ANY ? RT_WAVES_PER_EU_ANY : RT_WAVES_PER_EU)))) void wf_trace_grid_persistent(const WfParams wk,
                                                                  uint32_t* __restrict__ run_ctr) {
     WfParams w = wk;
@@ -786,7 +786,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRI ? RT_WA
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * 256u) >> 6;
     unsigned long long tested = 0;
-    trace_segment<FUSED, ANY, STATS, TRI>(w, queue, n_queue, wave, n_waves, run_ctr, tested);
+    trace_segment<AM, ANY, STATS, TRI>(w, queue, n_queue, wave, n_waves, run_ctr, tested);
     if (STATS && tested) atomicAdd(&w.rp.counters->tests, tested);
 }
 
@@ -813,7 +813,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRI ? RT_WA
 
 
 
-template <bool FUSED, bool ANY, bool STATS>
+template <int AM, bool ANY, bool STATS>
 __device__ __forceinline__ void walk_segment(const WfParams& w, const uint32_t* __restrict__ queue, uint32_t n_queue,
                                              uint32_t wave, uint32_t n_waves, uint32_t* __restrict__ run_ctr,
                                              unsigned long long& tested) {
@@ -857,7 +857,7 @@ __device__ __forceinline__ void walk_segment(const WfParams& w, const uint32_t* 
                 uint32_t note;  // shadow rays: the light they go to; reflection rays: begin_shade_lit's note (the object they leave)
                 Ray ray;
                 if (ANY) {
-                    ray = shadow_of_pixel<FUSED>(w, pix, (entry & kQueueLastLight) != 0u, note);
+                    ray = shadow_of_pixel<AM>(w, pix, (entry & kQueueLastLight) != 0u, note);
                 } else {
                     ray = closest_ray(w, pix, w.first_round != 0u);
                     note = __float_as_uint(ray.dw);
@@ -927,7 +927,7 @@ __device__ __forceinline__ void walk_segment(const WfParams& w, const uint32_t* 
                         const int k = brute ? (int)a : (int)g.always[a];
                         float t;
                         bool sphere;
-                        const bool cand = lane_candidate<FUSED, true, false>(hot + k, ray, t, sphere);
+                        const bool cand = lane_candidate<AM, true, false>(hot + k, ray, t, sphere);
                         if (STATS) ++tested;
                         if (ANY) done = cand && !(t >= 1.f);
                         else if (cand) closest_take(t, k, sphere, T, idx, cur_sphere);
@@ -1034,7 +1034,7 @@ __device__ __forceinline__ void walk_segment(const WfParams& w, const uint32_t* 
                     float t;
                     bool sphere;
                     const Ray ray = {rsx, rsy, rsz, 1.0f, rdx, rdy, rdz, 0.0f};
-                    const bool cand = lane_candidate<FUSED, true, false>(hot + pend_k, ray, t, sphere);
+                    const bool cand = lane_candidate<AM, true, false>(hot + pend_k, ray, t, sphere);
                     if (STATS) ++tested;
                     pend = false;
                     done_k = pend_k;
@@ -1063,7 +1063,7 @@ __device__ __forceinline__ void walk_segment(const WfParams& w, const uint32_t* 
     }
 }
 
-template <bool FUSED, bool ANY, bool STATS>
+template <int AM, bool ANY, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WAVES))) void wf_walk(const WfParams wk, uint32_t* __restrict__ run_ctr) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WA
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * 256u) >> 6;
     unsigned long long tested = 0;
-    walk_segment<FUSED, ANY, STATS>(w, queue, n_queue, wave, n_waves, run_ctr, tested);
+    walk_segment<AM, ANY, STATS>(w, queue, n_queue, wave, n_waves, run_ctr, tested);
     if (STATS && tested) atomicAdd(&w.rp.counters->tests, tested);
 }
 
@@ -1148,7 +1148,7 @@ __device__ __forceinline__ uint32_t block_pretests(const uint4 q0, const uint4 q
     return lattice_pretest(pm, q0.y, olx, oly, olz, dx, dy, dz, neg_dd, one_minus_alpha);
 }
 
-template <bool FUSED, bool STATS, bool TRI>
+template <int AM, bool STATS, bool TRI>
 __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t* __restrict__ queue, uint32_t n_queue,
                                               uint32_t wave, uint32_t n_waves, uint32_t* __restrict__ run_ctr,
                                               unsigned long long& tested) {
@@ -1224,7 +1224,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                         const int k = brute ? (int)a : (int)g.always[a];
                         float t;
                         bool sphere;
-                        const bool cand = lane_candidate<FUSED, true, TRI>(hot + k, ray, t, sphere);
+                        const bool cand = lane_candidate<AM, true, TRI>(hot + k, ray, t, sphere);
                         if (STATS) ++tested;
                         if (cand) closest_take(t, k, sphere, T, idx, cur_sphere);
                     }
@@ -1322,7 +1322,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                     float t;
                     bool sphere;
                     const Ray ray = {rsx, rsy, rsz, 1.0f, rdx, rdy, rdz, 0.0f};
-                    const bool cand = lane_candidate<FUSED, true, TRI>(hot + pend_k, ray, t, sphere);
+                    const bool cand = lane_candidate<AM, true, TRI>(hot + pend_k, ray, t, sphere);
                     if (STATS) ++tested;
                     done_k = pend_k;
                     bool cur_sphere = (fl & kSphere) != 0u;
@@ -1362,7 +1362,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
 // fetches - cfg5: 28 blocks + the empty-space steps their headers allow, against 64 cells of the fine grid). Same blocks, same
 // pre-test, same exact tests, order-free update: the result of closest_hit_grid. False: not this walk's kind of ray
 // (block_segment's `tame`), nothing was done.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool closest_hit_blocks(const BlockGrid& bg, const GridDesc& g, const HotObject* __restrict__ hot, const Ray& ray,
                                                    uint32_t skip_object, float& T, int& index, uint32_t& tested) {
     const float dd = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
@@ -1395,7 +1395,7 @@ __device__ __forceinline__ bool closest_hit_blocks(const BlockGrid& bg, const Gr
             float t;
             bool sphere;
             ++tested;
-            if (lane_candidate<FUSED, true, true>(hot + k, ray, t, sphere)) closest_take(t, (int)k, sphere, T, index, cur_sphere);
+            if (lane_candidate<AM, true, true>(hot + k, ray, t, sphere)) closest_take(t, (int)k, sphere, T, index, cur_sphere);
         }
         const uint32_t nxt = q0.x & 0xffffffu;
         if (nxt != 0u) { b = nxt; continue; }
@@ -1418,7 +1418,7 @@ __device__ __forceinline__ bool closest_hit_blocks(const BlockGrid& bg, const Gr
 
 // ... and "is anything in the way before t = 1" for one shadow ray in one thread (wf_finish: the light scans of the frame's
 // tail go to lights that have no tiles). Same answer as any_hit_grid. `done`: false = not this walk's kind of ray.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool any_hit_blocks(const BlockGrid& bg, const GridDesc& g, const HotObject* __restrict__ hot, const Ray& ray,
                                                bool& done, uint32_t& tested) {
     done = true;
@@ -1451,7 +1451,7 @@ __device__ __forceinline__ bool any_hit_blocks(const BlockGrid& bg, const GridDe
             float t;
             bool sphere;
             ++tested;
-            if (lane_candidate<FUSED, true, true>(hot + k, ray, t, sphere) && !(t >= 1.f)) return true;
+            if (lane_candidate<AM, true, true>(hot + k, ray, t, sphere) && !(t >= 1.f)) return true;
         }
         const uint32_t nxt = q0.x & 0xffffffu;
         if (nxt != 0u) { b = nxt; continue; }
@@ -1473,7 +1473,7 @@ __device__ __forceinline__ bool any_hit_blocks(const BlockGrid& bg, const GridDe
 #ifndef RT_WALK3_WAVES_TRI
 #define RT_WALK3_WAVES_TRI RT_WALK3_WAVES   // the variant with the triangle branch wants ~95 registers: 6 waves = 17 spilled
 #endif
-template <bool FUSED, bool STATS, bool TRI>
+template <int AM, bool STATS, bool TRI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRI ? RT_WALK3_WAVES_TRI : RT_WALK3_WAVES))) void wf_walk_blocks(const WfParams wk, uint32_t* __restrict__ run_ctr) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -1487,12 +1487,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TRI ? RT_WA
     const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
     const uint32_t n_waves = (gridDim.x * 256u) >> 6;
     unsigned long long tested = 0;
-    block_segment<FUSED, STATS, TRI>(w, w.q_prev_closest, n_queue, wave, n_waves, run_ctr, tested);
+    block_segment<AM, STATS, TRI>(w, w.q_prev_closest, n_queue, wave, n_waves, run_ctr, tested);
     if (STATS && tested) atomicAdd(&w.rp.counters->tests, tested);
 }
 
 // Literal shadow test: the reference's full closest hit, then its `time >= 1 || time < 0` (:229).
-template <bool FUSED>
+template <int AM>
 __global__ __launch_bounds__(256) void wf_trace_any_literal(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -1502,7 +1502,7 @@ __global__ __launch_bounds__(256) void wf_trace_any_literal(const WfParams wk) {
     const Ray ray = load_ray(w, i, kSlotShadow);
     float T = kMaxFloat;
     int idx = -1;
-    closest_hit<FUSED, true>(w.rp.scene.pairs, w.rp.scene.n_pairs, ray, T, idx);
+    closest_hit<AM, true>(w.rp.scene.pairs, w.rp.scene.n_pairs, ray, T, idx);
     U(w, F_RES_ANY, i) = (T >= 1.f || T < 0) ? 1u : 0u;
     const unsigned long long lanes = (unsigned long long)__popcll(__ballot(true));
     if (w.count_rays && (threadIdx.x & 63u) == 0u)
@@ -1515,7 +1515,7 @@ __global__ __launch_bounds__(256) void wf_trace_any_literal(const WfParams wk) {
 // (visibility 0); only the survivors are queued for the next slice. Every ray thus stops within one slice of
 // its first occluder no matter what the other 63 lanes of its wave are doing - the wave-wide early exit of a
 // single long loop almost never fires, because one lit lane keeps the whole wave going.
-template <bool FUSED>
+template <int AM>
 __global__ __launch_bounds__(256) void wf_trace_any_slice(const WfParams wk, const uint32_t* __restrict__ q_in, const uint32_t* __restrict__ n_in,
                                                           uint32_t pair_lo, uint32_t pair_hi, uint32_t* __restrict__ q_out,
                                                           uint32_t* __restrict__ out_count, uint32_t first_slice) {
@@ -1534,7 +1534,7 @@ __global__ __launch_bounds__(256) void wf_trace_any_slice(const WfParams wk, con
         U(w, F_RES_ANY, i) = (nan_kind == kNanRayTimeNaN) ? 0u : 1u;
         return;
     }
-    const bool occluded = any_hit_before_one<FUSED>(w.shadow_pairs + pair_lo, pair_hi - pair_lo, ray, &visited);
+    const bool occluded = any_hit_before_one<AM>(w.shadow_pairs + pair_lo, pair_hi - pair_lo, ray, &visited);
     if (w.count_rays) {  // `visited` is wave-uniform: every lane rides along until the wave leaves
         const unsigned long long lanes = (unsigned long long)__popcll(__ballot(true));
         if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__ballot(true)))
@@ -1599,7 +1599,7 @@ __device__ __forceinline__ void write_pixel(Ctx& c, float r, float g, float b) {
 }
 
 // queue the shadow ray of light `li` for the hit `h` (its geometry is recomputed when the result arrives)
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void emit_shadow(Ctx& c, const HitRec& h, uint32_t li, uint32_t phase, bool new_hit) {
     const Scene& S = c.w.rp.scene;
     // Through the grid the shadow ray is not stored: the trace kernels rebuild it from the hit point (shadow_of_pixel) - 32 bytes
@@ -1611,11 +1611,11 @@ __device__ __forceinline__ void emit_shadow(Ctx& c, const HitRec& h, uint32_t li
         c.any_flag = (c.w.ltiles.enabled && li == c.w.ltiles.light) ? kQueueLastLight : 0u;
     } else {
         float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-        normalize3(nvx, nvy, nvz);
+        normalize3_<AM>(nvx, nvy, nvz);
         float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-        normalize3(vvx, vvy, vvz);
+        normalize3_<AM>(vvx, vvy, vvz);
         LightGeom g;
-        light_geometry<FUSED>(S.lights[li], h, nvx, nvy, nvz, vvx, vvy, vvz, g);
+        light_geometry<AM>(S.lights[li], h, nvx, nvy, nvz, vvx, vvy, vvz, g);
         g.shadow.dw = __uint_as_float(li);
         store_ray(c.w, c.i, g.shadow, kSlotShadow);
     }
@@ -1625,14 +1625,14 @@ __device__ __forceinline__ void emit_shadow(Ctx& c, const HitRec& h, uint32_t li
     c.traced += 1;
 }
 
-template <int KERNEL, bool FUSED> __device__ __forceinline__ void shade_done(Ctx& c, const HitRec& h, bool primary, float cr, float cg, float cb);
-__device__ __forceinline__ void finish_reflect(Ctx& c, bool fused, float abr, float abg, float abb, float rr, float rg, float rb, float ap, uint32_t bounces);
+template <int KERNEL, int AM> __device__ __forceinline__ void shade_done(Ctx& c, const HitRec& h, bool primary, float cr, float cg, float cb);
+__device__ __forceinline__ void finish_reflect(Ctx& c, int am, float abr, float abg, float abb, float rr, float rg, float rb, float ap, uint32_t bounces);
 
 // Is the shadow ray towards the LAST light (the light of the light tiles) blocked? One thread, the whole list: the same
 // tile, the same cut, the same pre-test and the same exact tests as the light-tile mode of the persistent walk
 // (trace_segment, in_lt) - an any-hit answer does not depend on the order or on who asks. (Light tiles are only built for
 // scenes without always-tested objects: build_light_tiles.)
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, uint32_t& tests) {
     ray.sw = 1.0f; ray.dw = 0.0f;  // as the walk's hand-out (rt_create checks the preconditions of a grid-able frame)
     const HotObject* __restrict__ hot = w.rp.scene.hot;
@@ -1657,7 +1657,7 @@ __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, u
                 float t;
                 bool sphere_type;
                 ++tests;
-                if (lane_candidate<FUSED, true, true>(hot + ids[e], ray, t, sphere_type) && !(t >= 1.f)) return true;
+                if (lane_candidate<AM, true, true>(hot + ids[e], ray, t, sphere_type) && !(t >= 1.f)) return true;
             }
             if (q0.x == 0u) return false;
             b = q0.x;
@@ -1673,7 +1673,7 @@ __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, u
             float t;
             bool sphere;
             ++tests;
-            if (lane_candidate<FUSED, true, true>(hot + __float_as_uint(aux.y), ray, t, sphere) && !(t >= 1.f)) return true;
+            if (lane_candidate<AM, true, true>(hot + __float_as_uint(aux.y), ray, t, sphere) && !(t >= 1.f)) return true;
         }
         return false;
     }
@@ -1685,7 +1685,7 @@ __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, u
 // walk, a wf_resume pass - for the last hit of every path. With light tiles the last light's shadow test is a short list:
 // it is run HERE, and the light loop's backward scan (shade_last_light_wins) finishes on the spot. False (nothing done,
 // nothing counted) when the scan has to go on to an earlier light (stale specular: lit, nDotL <= 0) - the queued path takes over.
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ bool shade_last_light_inline(Ctx& c, const HitRec& h, bool primary) {
     const Scene& S = c.w.rp.scene;
     const uint32_t li = S.n_lights - 1u;
@@ -1694,13 +1694,13 @@ __device__ __forceinline__ bool shade_last_light_inline(Ctx& c, const HitRec& h,
     uint32_t tests = 0;
     {   // the shadow test first, with as little else alive as possible (the step runs at 4 waves per SIMD, 128 registers)
         float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-        normalize3_shading(S.fast_phong != 0u, nvx, nvy, nvz);
+        normalize3_shading<AM>(S.fast_phong != 0u, nvx, nvy, nvz);
         float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-        normalize3_shading(S.fast_phong != 0u, vvx, vvy, vvz);
+        normalize3_shading<AM>(S.fast_phong != 0u, vvx, vvy, vvz);
         LightGeom g;
-        light_geometry<FUSED>(S.lights[li], h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
+        light_geometry<AM>(S.lights[li], h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
         nDotL = g.nDotL; rDotV = g.rDotV;
-        lit = !last_light_blocked<FUSED>(c.w, g.shadow, tests);
+        lit = !last_light_blocked<AM>(c.w, g.shadow, tests);
     }
     const LightRec L = S.lights[li];
     const ColdObject* co = S.cold + h.index;
@@ -1736,7 +1736,7 @@ __device__ __forceinline__ bool shade_last_light_inline(Ctx& c, const HitRec& h,
         ap = acc.w;
         abr = acc.x; abg = acc.y; abb = acc.z;
         const float ra = (1.f - ap) * amb.w;
-        abr = fma_<FUSED>(ra, cr, abr); abg = fma_<FUSED>(ra, cg, abg); abb = fma_<FUSED>(ra, cb, abb);
+        abr = fma_<AM>(ra, cr, abr); abg = fma_<AM>(ra, cg, abg); abb = fma_<AM>(ra, cb, abb);
         ap = ap + ra;
         rr = cr; rg = cg; rb = cb;
         bounces = c.pre ? __float_as_uint(c.pre_res.w) : U(c.w, F_BOUNCES, c.i);
@@ -1745,7 +1745,7 @@ __device__ __forceinline__ bool shade_last_light_inline(Ctx& c, const HitRec& h,
     c.traced += 1;
     c.tests += tests;
     if (bounces > 0u) c.reference += 1;  // (loop_step: the iteration whose absorption test ends the loop)
-    finish_reflect(c, FUSED, abr, abg, abb, rr, rg, rb, ap, bounces - 1u);
+    finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces - 1u);
     return true;
 }
 
@@ -1756,7 +1756,7 @@ __device__ __forceinline__ bool shade_last_light_inline(Ctx& c, const HitRec& h,
 // shading (`bounces > 0 && absorptionPercent <= 0.999`, the latter already including this hit). A frame then needs
 // D + 2 big rounds instead of 2D + 2, every round traces shadow and reflection rays side by side, and wf_resume
 // touches the pixel state half as often. `spec_bounces` / `spec_ap`: the loop state as it will be after this hit.
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool primary, uint32_t spec_bounces, float spec_ap, const ObjRows& rows) {
     const Scene& S = c.w.rp.scene;
     c.reference += S.n_lights;
@@ -1766,11 +1766,11 @@ __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool pr
     if (!(KERNEL == 2 && !S.literal)) store_hit_extra(c.w, c.i, h);
     const bool sends = KERNEL == 2 && !S.literal && spec_bounces > 0u && spec_ap <= 0.999f;
     if (KERNEL == 2 && RT_INLINE_LAST_SHADOW && !S.literal && !sends && c.w.ltiles.enabled && S.n_lights - 1u == c.w.ltiles.light) {
-        if (shade_last_light_inline<FUSED>(c, h, primary)) return;
+        if (shade_last_light_inline<AM>(c, h, primary)) return;
     }
     if (sends) {
         Ray ray;
-        reflection_ray<FUSED>(h, ray);
+        reflection_ray<AM>(h, ray);
         if (c.w.grid.enabled) {
             // The ray starts a skin's width off the object it leaves, i.e. inside that object's registration sphere: the
             // grid walk would park it as its first candidate and spend a (sparsely filled) exact-test round on it. Its
@@ -1779,7 +1779,7 @@ __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool pr
             // slot) that this object is done. If the test ever reports a hit, nothing is said and the walk tests it as usual.
             float t_self;
             bool sphere_self;
-            const bool self_hit = rows_candidate<FUSED, true>(rows, ray, t_self, sphere_self);  // (the record materialise() just read)
+            const bool self_hit = rows_candidate<AM, true>(rows, ray, t_self, sphere_self);  // (the record materialise() just read)
             ray.dw = __uint_as_float(self_hit ? 0xffffffffu : (uint32_t)h.index);
         }
         store_ray(c.w, c.i, ray, kSlotClosest);
@@ -1790,19 +1790,19 @@ __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool pr
     const bool forward = (KERNEL == 1) || S.literal;
     // the carried light-loop terms start at zero: resume_shadow() knows the first light of a scan and does not
     // read them, so nothing is written here
-    emit_shadow<FUSED>(c, h, forward ? 0u : S.n_lights - 1u, (primary ? PH_SHADOW_PRIMARY : PH_SHADOW_REFLECT) | flag, true);
+    emit_shadow<AM>(c, h, forward ? 0u : S.n_lights - 1u, (primary ? PH_SHADOW_PRIMARY : PH_SHADOW_REFLECT) | flag, true);
 }
 
 // ... or, without lights, go straight on (shade() returns black)
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __device__ __forceinline__ void begin_shade(Ctx& c, const HitRec& h, bool primary, uint32_t spec_bounces, float spec_ap, const ObjRows& rows) {
-    if (c.w.rp.scene.n_lights == 0) { shade_done<KERNEL, FUSED>(c, h, primary, 0.f, 0.f, 0.f); return; }  // (h travels in registers)
-    begin_shade_lit<KERNEL, FUSED>(c, h, primary, spec_bounces, spec_ap, rows);
+    if (c.w.rp.scene.n_lights == 0) { shade_done<KERNEL, AM>(c, h, primary, 0.f, 0.f, 0.f); return; }  // (h travels in registers)
+    begin_shade_lit<KERNEL, AM>(c, h, primary, spec_bounces, spec_ap, rows);
 }
 
 // one light-loop iteration, resumed with the visibility of light `li`; mirrors shade_forward /
 // shade_last_light_wins in rt_device.h statement for statement
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __device__ __forceinline__ void resume_shadow(Ctx& c, bool primary) {
     const Scene& S = c.w.rp.scene;
     const uint64_t i = c.i;
@@ -1820,12 +1820,12 @@ __device__ __forceinline__ void resume_shadow(Ctx& c, bool primary) {
     const ColdObject* co = S.cold + h.index;
     const float4 amb = co->amb_absorb, dif = co->dif_shine, spec = co->spec_type;
     float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-    normalize3_shading(S.fast_phong != 0u, nvx, nvy, nvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, nvx, nvy, nvz);
     float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-    normalize3_shading(S.fast_phong != 0u, vvx, vvy, vvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, vvx, vvy, vvz);
     const LightRec L = S.lights[li];
     LightGeom g;
-    light_geometry<FUSED>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
+    light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
     // (by the time a shadow result is resumed, a reflection ray sent with the hit's first shadow ray has been traced)
     const uint32_t phase = (primary ? PH_SHADOW_PRIMARY : PH_SHADOW_REFLECT) | (c.flags & ~PH_FLAG_REFLECTION_PENDING);
     const bool forward = (KERNEL == 1) || S.literal;
@@ -1853,9 +1853,9 @@ __device__ __forceinline__ void resume_shadow(Ctx& c, bool primary) {
         if (li + 1u < S.n_lights) {
             F(c.w, F_SR, i) = sr; F(c.w, F_SG, i) = sg; F(c.w, F_SB, i) = sb;
             F(c.w, F_CR, i) = cr; F(c.w, F_CG, i) = cg; F(c.w, F_CB, i) = cb;
-            emit_shadow<FUSED>(c, h, li + 1u, phase, false);
+            emit_shadow<AM>(c, h, li + 1u, phase, false);
         } else {
-            shade_done<KERNEL, FUSED>(c, h, primary, cr, cg, cb);
+            shade_done<KERNEL, AM>(c, h, primary, cr, cg, cb);
         }
         return;
     }
@@ -1884,19 +1884,19 @@ __device__ __forceinline__ void resume_shadow(Ctx& c, bool primary) {
         F(c.w, F_AR, i) = ar; F(c.w, F_AG, i) = ag; F(c.w, F_AB, i) = ab;
         F(c.w, F_DR, i) = dr; F(c.w, F_DG, i) = dg; F(c.w, F_DB, i) = db;
         F(c.w, F_SR, i) = sr; F(c.w, F_SG, i) = sg; F(c.w, F_SB, i) = sb;
-        emit_shadow<FUSED>(c, h, li - 1u, phase, false);
+        emit_shadow<AM>(c, h, li - 1u, phase, false);
     } else {
-        shade_done<KERNEL, FUSED>(c, h, primary, (ar + dr) + sr, (ag + dg) + sg, (ab + db) + sb);
+        shade_done<KERNEL, AM>(c, h, primary, (ar + dr) + sr, (ag + dg) + sg, (ab + db) + sb);
     }
 }
 
 // the tail of shade_and_reflect (:281-284)
-__device__ __forceinline__ void finish_reflect(Ctx& c, bool fused, float abr, float abg, float abb, float rr, float rg,
+__device__ __forceinline__ void finish_reflect(Ctx& c, int am, float abr, float abg, float abb, float rr, float rg,
                                                float rb, float ap, uint32_t bounces) {
     if (bounces == 0u && ap < 1.f) {
         const float wgt = 1.f - ap;
-        if (fused) { abr = fma_<true>(wgt, rr, abr); abg = fma_<true>(wgt, rg, abg); abb = fma_<true>(wgt, rb, abb); }
-        else { abr = fma_<false>(wgt, rr, abr); abg = fma_<false>(wgt, rg, abg); abb = fma_<false>(wgt, rb, abb); }
+        if (am != kUnfused) { abr = fma_<kFused>(wgt, rr, abr); abg = fma_<kFused>(wgt, rg, abg); abb = fma_<kFused>(wgt, rb, abb); }
+        else { abr = fma_<kUnfused>(wgt, rr, abr); abg = fma_<kUnfused>(wgt, rg, abg); abb = fma_<kUnfused>(wgt, rb, abb); }
     }
     write_pixel<2>(c, abr, abg, abb);
 }
@@ -1913,16 +1913,16 @@ __device__ __forceinline__ void store_loop_state(Ctx& c, float abr, float abg, f
 }
 
 // top of one iteration of `while (bounces-- > 0 && raycast(...) && absorptionPercent <= 0.999f)` (:268)
-template <bool FUSED>
+template <int AM>
 __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr, float abg, float abb, float rr, float rg,
                                           float rb, float ap, uint32_t bounces) {
     const Scene& S = c.w.rp.scene;
     const uint32_t before = bounces;
     bounces = bounces - 1u;
-    if (!(before > 0u)) { finish_reflect(c, FUSED, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
+    if (!(before > 0u)) { finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
     c.reference += 1;
     const bool absorbing = (ap <= 0.999f);
-    if (!absorbing && !S.literal) { finish_reflect(c, FUSED, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
+    if (!absorbing && !S.literal) { finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
     if (c.flags & PH_FLAG_REFLECTION_SENT) {
         // the ray left together with this hit's first shadow ray (begin_shade_lit) and has been traced: carry on
         // with its result, as the PH_REFLECT branch of wf_resume does one round later in the other modes
@@ -1938,24 +1938,24 @@ __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr,
         } else {
             closest_result(c.w, i, false, T, idx);
         }
-        if (T == kMaxFloat) { finish_reflect(c, FUSED, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
+        if (T == kMaxFloat) { finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
         if (!c.pre) ray = load_ray(c.w, i, kSlotClosest);
         ray.dw = 0.0f;  // (a reflection ray's direction.w; the slot may carry begin_shade_lit's note to the walk)
         HitRec rh;
         ObjRows rows;
         float absorb_rh;
-        materialise<FUSED>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
+        materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
         store_loop_state(c, abr, abg, abb, rr, rg, rb, ap, bounces, false);
         if (c.pre) {  // the step may go on to shade rh on the spot (shade_last_light_inline): what it preloaded is now this
             c.pre_acc = make_float4(abr, abg, abb, ap);
             c.pre_res.w = __uint_as_float(bounces);
         }
         const float ra = (1.f - ap) * absorb_rh;  // shade_done's update, ahead of time (the absorption came with the record)
-        begin_shade_lit<2, FUSED>(c, rh, false, bounces, ap + ra, rows);
+        begin_shade_lit<2, AM>(c, rh, false, bounces, ap + ra, rows);
         return;
     }
     Ray ray;
-    reflection_ray<FUSED>(from, ray);
+    reflection_ray<AM>(from, ray);
     ray.dw = __uint_as_float(0xffffffffu);  // (no note for the walk - see begin_shade_lit; no traversal reads direction.w of a reflection ray)
     store_ray(c.w, c.i, ray, kSlotClosest);
     store_loop_state(c, abr, abg, abb, rr, rg, rb, ap, bounces, true);
@@ -1964,7 +1964,7 @@ __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr,
     c.traced += 1;
 }
 
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __device__ __forceinline__ void shade_done(Ctx& c, const HitRec& h, bool primary, float cr, float cg, float cb) {
     const Scene& S = c.w.rp.scene;
     if (KERNEL == 1) { write_pixel<1>(c, cr, cg, cb); return; }
@@ -1972,20 +1972,20 @@ __device__ __forceinline__ void shade_done(Ctx& c, const HitRec& h, bool primary
     if (primary) {
         // absorbColor = hit.mat.absorption * shade(hit) (:255-256); bounces = MAX_BOUNCES (:258)
         const float ap = S.cold[h.index].amb_absorb.w;
-        loop_step<FUSED>(c, h, cr * ap, cg * ap, cb * ap, 0.f, 0.f, 0.f, ap, c.w.rp.max_bounces);
+        loop_step<AM>(c, h, cr * ap, cg * ap, cb * ap, 0.f, 0.f, 0.f, ap, c.w.rp.max_bounces);
     } else {
         const float4 acc = c.pre ? c.pre_acc : load_block(c.w, F_ABR, i);
         float ap = acc.w;
         float abr = acc.x, abg = acc.y, abb = acc.z;
         const float ra = (1.f - ap) * S.cold[h.index].amb_absorb.w;
-        abr = fma_<FUSED>(ra, cr, abr); abg = fma_<FUSED>(ra, cg, abg); abb = fma_<FUSED>(ra, cb, abb);
+        abr = fma_<AM>(ra, cr, abr); abg = fma_<AM>(ra, cg, abg); abb = fma_<AM>(ra, cb, abb);
         ap = ap + ra;
-        loop_step<FUSED>(c, h, abr, abg, abb, cr, cg, cb, ap, c.pre ? __float_as_uint(c.pre_res.w) : U(c.w, F_BOUNCES, i));
+        loop_step<AM>(c, h, abr, abg, abb, cr, cg, cb, ap, c.pre ? __float_as_uint(c.pre_res.w) : U(c.w, F_BOUNCES, i));
     }
 }
 
 // one step of a pixel's state machine: consume the results of the ray(s) it had in flight, queue what it needs next
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __device__ __forceinline__ void resume_pixel(Ctx& c) {
     const WfParams& w = c.w;
     const uint64_t i = c.i;
@@ -2014,8 +2014,8 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
             HitRec h;
             ObjRows rows;
             float absorb_h;
-            materialise<FUSED>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u, &rows, &absorb_h);
-            begin_shade<KERNEL, FUSED>(c, h, true, w.rp.max_bounces, absorb_h, rows);
+            materialise<AM>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u, &rows, &absorb_h);
+            begin_shade<KERNEL, AM>(c, h, true, w.rp.max_bounces, absorb_h, rows);
         }
     } else if (phase == PH_SHADOW_PRIMARY || phase == PH_SHADOW_REFLECT) {
         c.pre = true;
@@ -2023,7 +2023,7 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
         c.pre_res = load_block(w, F_RES_T, i);
         c.pre_acc = load_block(w, F_ABR, i);       // (not yet written in the primary phase: not read there either)
         c.pre_ray0 = load_ray(w, i, kSlotClosest);  // (only meaningful when a reflection ray left with the hit)
-        resume_shadow<KERNEL, FUSED>(c, phase == PH_SHADOW_PRIMARY);
+        resume_shadow<KERNEL, AM>(c, phase == PH_SHADOW_PRIMARY);
     } else if (phase == PH_REFLECT) {
         float T;
         int idx;
@@ -2034,15 +2034,15 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
         const float abr = acc.x, abg = acc.y, abb = acc.z;
         const float rr = rc.x, rg = rc.y, rb = rc.z;
         if (T == kMaxFloat || !(ap <= 0.999f)) {  // raycast() false, or the absorption test of the loop condition
-            finish_reflect(c, FUSED, abr, abg, abb, rr, rg, rb, ap, bounces);
+            finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces);
         } else {
             Ray ray = load_ray(w, i, kSlotClosest);
             ray.dw = 0.0f;  // (a reflection ray's direction.w; the slot may carry begin_shade_lit's note to the walk)
             HitRec rh;
             ObjRows rows;
             float absorb_rh;
-            materialise<FUSED>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
-            begin_shade<KERNEL, FUSED>(c, rh, false, bounces, ap + (1.f - ap) * absorb_rh, rows);
+            materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
+            begin_shade<KERNEL, AM>(c, rh, false, bounces, ap + (1.f - ap) * absorb_rh, rows);
         }
     }
 }
@@ -2065,7 +2065,7 @@ __device__ __forceinline__ void add_ray_counters(const WfParams& w, const Ctx& c
 #ifndef RT_RESUME_WAVES_PER_EU
 #define RT_RESUME_WAVES_PER_EU 4
 #endif
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(RT_RESUME_WAVES_PER_EU))) void wf_resume(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -2076,7 +2076,7 @@ __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(
     if (t < total) {
         const uint32_t entry = w.identity_queue ? t : ((t < w.n_prev_closest) ? w.q_prev_closest[t] : w.q_prev_any[t - w.n_prev_closest]);
         c.i = entry & kQueuePixel;
-        if (!duplicate_entry(w, t, entry)) resume_pixel<KERNEL, FUSED>(c);
+        if (!duplicate_entry(w, t, entry)) resume_pixel<KERNEL, AM>(c);
     }
     block_push(c.want_closest, c.want_any, (uint32_t)c.i, w.q_closest, w.q_any, w.counts, c.any_flag);
     if (w.count_rays) add_ray_counters(w, c);
@@ -2087,7 +2087,7 @@ __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(
 // and that price does not shrink when the frame is split over more GPUs. Here every remaining pixel runs its state
 // machine to the end in one thread, tracing its rays itself through the grid (closest_hit_grid / any_hit_grid: same
 // cells, same exact tests, same results as the wave-level walk).
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 __global__ __launch_bounds__(256) void wf_finish(const WfParams wk) {
     WfParams w = wk;
     (void)resolve_round(w);
@@ -2108,23 +2108,23 @@ __global__ __launch_bounds__(256) void wf_finish(const WfParams wk) {
                     uint32_t li;
                     Ray ray;
                     if (shadow_rays_rebuilt(w)) {
-                        ray = shadow_of_pixel<FUSED>(w, c.i, false, li);
+                        ray = shadow_of_pixel<AM>(w, c.i, false, li);
                     } else {
                         ray = load_ray(w, c.i, kSlotShadow);
                         li = __float_as_uint(ray.dw);
                     }
                     bool blocked;
                     if (w.ltiles.enabled && li == w.ltiles.light) {
-                        blocked = last_light_blocked<FUSED>(w, ray, tested);   // (the walk's choice: trace_segment)
+                        blocked = last_light_blocked<AM>(w, ray, tested);   // (the walk's choice: trace_segment)
                     } else {
                         bool walked = false;
                         blocked = false;
                         if (w.bgrid.enabled && w.grid.n_always == 0u) {
                             Ray r1 = ray;
                             r1.sw = 1.0f; r1.dw = 0.0f;
-                            blocked = any_hit_blocks<FUSED>(w.bgrid, w.grid, w.rp.scene.hot, r1, walked, tested);
+                            blocked = any_hit_blocks<AM>(w.bgrid, w.grid, w.rp.scene.hot, r1, walked, tested);
                         }
-                        if (!walked) blocked = any_hit_grid<FUSED>(w.grid, w.rp.scene, ray, tested);
+                        if (!walked) blocked = any_hit_grid<AM>(w.grid, w.rp.scene, ray, tested);
                     }
                     U(w, F_RES_ANY, c.i) = blocked ? 0u : 1u;
                 }
@@ -2136,14 +2136,14 @@ __global__ __launch_bounds__(256) void wf_finish(const WfParams wk) {
                     if (w.bgrid.enabled && w.grid.n_always == 0u) {  // the block grid (the ray's note names the object it leaves)
                         const uint32_t note = __float_as_uint(ray.dw);
                         ray.sw = 1.0f; ray.dw = 0.0f;
-                        walked = closest_hit_blocks<FUSED>(w.bgrid, w.grid, w.rp.scene.hot, ray, note, T, idx, tested);
+                        walked = closest_hit_blocks<AM>(w.bgrid, w.grid, w.rp.scene.hot, ray, note, T, idx, tested);
                     }
-                    if (!walked) closest_hit_grid<FUSED, true>(w.grid, w.rp.scene.hot, ray, T, idx, tested);
+                    if (!walked) closest_hit_grid<AM, true>(w.grid, w.rp.scene.hot, ray, T, idx, tested);
                     store_closest_result(w, c.i, T, idx);
                 }
                 c.want_closest = false;
                 c.want_any = false;
-                resume_pixel<KERNEL, FUSED>(c);
+                resume_pixel<KERNEL, AM>(c);
                 if (!c.want_closest && !c.want_any) break;  // the pixel has been written
                 do_closest = c.want_closest;
                 do_any = c.want_any;
@@ -2194,15 +2194,15 @@ struct FrameAcc {
 // belongs to the last light that was either blocked or lit with nDotL > 0 - scan backwards and stop there. The last light's
 // shadow ray goes through its light tile (last_light_blocked), an earlier light's - the stale-specular case, a per cent of
 // the hits - through the fine grid in one thread (any_hit_grid, as wf_finish traces it where the block walk does not apply).
-template <bool FUSED, bool BLOCKS>
+template <int AM, bool BLOCKS>
 __device__ __forceinline__ void shade_scan_now(const WfParams& w, const HitRec& h, float& cr, float& cg, float& cb, float& absorb, uint32_t& tests,
                                                uint32_t& shadow_rays) {
     const Scene& S = w.rp.scene;
     const ColdObject* co = S.cold + h.index;
     float nvx = h.nx, nvy = h.ny, nvz = h.nz;
-    normalize3_shading(S.fast_phong != 0u, nvx, nvy, nvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, nvx, nvy, nvz);
     float vvx = -h.px, vvy = -h.py, vvz = -h.pz;
-    normalize3_shading(S.fast_phong != 0u, vvx, vvy, vvz);
+    normalize3_shading<AM>(S.fast_phong != 0u, vvx, vvy, vvz);
     float sr = 0.f, sg = 0.f, sb = 0.f;
     float dr = 0.f, dg = 0.f, db = 0.f;
     float ar = 0.f, ag = 0.f, ab = 0.f;
@@ -2210,11 +2210,11 @@ __device__ __forceinline__ void shade_scan_now(const WfParams& w, const HitRec& 
     for (uint32_t li = S.n_lights; li-- > 0 && need_specular;) {
         const LightRec L = S.lights[li];
         LightGeom g;
-        light_geometry<FUSED>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
+        light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
         shadow_rays += 1u;
         bool blocked;
         if (li == w.ltiles.light) {
-            blocked = last_light_blocked<FUSED>(w, g.shadow, tests);
+            blocked = last_light_blocked<AM>(w, g.shadow, tests);
         } else {
             // a light without tiles: one thread through the block grid, or - rays that walk is not made for, and always in wf_frame's
             // stepper (BLOCKS = false), where the second walk inlined cost every step 56 spilled registers, as a real call 151 -
@@ -2224,9 +2224,9 @@ __device__ __forceinline__ void shade_scan_now(const WfParams& w, const HitRec& 
             if (BLOCKS) {
                 Ray r1 = g.shadow;
                 r1.sw = 1.0f; r1.dw = 0.0f;
-                blocked = any_hit_blocks<FUSED>(w.bgrid, w.grid, S.hot, r1, walked, tests);
+                blocked = any_hit_blocks<AM>(w.bgrid, w.grid, S.hot, r1, walked, tests);
             }
-            if (!walked) blocked = any_hit_grid<FUSED>(w.grid, S, g.shadow, tests);
+            if (!walked) blocked = any_hit_grid<AM>(w.grid, S, g.shadow, tests);
         }
         const bool lit = !blocked;
         if (li == S.n_lights - 1u) {
@@ -2335,7 +2335,7 @@ struct StateIO {   // ray slot 0, F_RES_T / F_RES_I, the F_ABR block, the F_RR b
 // the reflection ray is built and tested against its own object right after materialise() - while the object's rows are in
 // registers - and put down before the shading starts (whether the loop will cast it depends on the loop state, not on the
 // colour: begin_shade_lit's `sends`).
-template <bool FUSED, bool BLOCKS, typename IO>
+template <int AM, bool BLOCKS, typename IO>
 __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool primary, uint32_t pix, Ctx& cnt) {
     const RenderParams& p = w.rp;
     const Scene& S = p.scene;
@@ -2357,7 +2357,7 @@ __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool
         float abr = a.abr, abg = a.abg, abb = a.abb;
         if (a.bounces == 0u && a.ap < 1.f) {
             const float wgt = 1.f - a.ap;
-            abr = fma_<FUSED>(wgt, a.rr, abr); abg = fma_<FUSED>(wgt, a.rg, abg); abb = fma_<FUSED>(wgt, a.rb, abb);
+            abr = fma_<AM>(wgt, a.rr, abr); abg = fma_<AM>(wgt, a.rg, abg); abb = fma_<AM>(wgt, a.rb, abb);
         }
         out[px] = make_float4(abr, abg, abb, 1.0f);
     };
@@ -2378,7 +2378,7 @@ __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool
     {
         HitRec h;
         ObjRows rows;
-        materialise<FUSED>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u, &rows, &absorb_h);
+        materialise<AM>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u, &rows, &absorb_h);
         hpx = h.px; hpy = h.py; hpz = h.pz; hnx = h.nx; hny = h.ny; hnz = h.nz; hindex = h.index;
         // Will the loop cast this hit's reflection ray? (the statements below are shade_done's and loop_step's, ahead of time)
         uint32_t bounces_in = p.max_bounces;
@@ -2392,10 +2392,10 @@ __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool
         sends = bounces_in > 0u && ap_after <= 0.999f;
         if (sends) {
             Ray nr;
-            reflection_ray<FUSED>(h, nr);
+            reflection_ray<AM>(h, nr);
             float t_self;
             bool sphere_self;
-            const bool self_hit = rows_candidate<FUSED, true>(rows, nr, t_self, sphere_self);  // begin_shade_lit: the ray's own object, tested here
+            const bool self_hit = rows_candidate<AM, true>(rows, nr, t_self, sphere_self);  // begin_shade_lit: the ray's own object, tested here
             io.put_ray(nr, self_hit ? 0xffffffffu : (uint32_t)h.index, pix);
         }
     }
@@ -2404,7 +2404,7 @@ __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool
     {
         HitRec h;
         h.px = hpx; h.py = hpy; h.pz = hpz; h.pw = 1.0f; h.nx = hnx; h.ny = hny; h.nz = hnz; h.rx = 0.f; h.ry = 0.f; h.rz = 0.f; h.index = hindex;
-        shade_scan_now<FUSED, BLOCKS>(w, h, cr, cg, cb, absorb, tests, shadow_rays);
+        shade_scan_now<AM, BLOCKS>(w, h, cr, cg, cb, absorb, tests, shadow_rays);
     }
     cnt.traced += shadow_rays;     // the shadow rays just tested
     cnt.reference += S.n_lights;   // the light loop's rays (begin_shade_lit)
@@ -2418,7 +2418,7 @@ __device__ __forceinline__ bool frame_step(const WfParams& w, const IO& io, bool
     } else {        // (:270-274)
         io.acc(a);
         const float ra = (1.f - a.ap) * absorb;
-        a.abr = fma_<FUSED>(ra, cr, a.abr); a.abg = fma_<FUSED>(ra, cg, a.abg); a.abb = fma_<FUSED>(ra, cb, a.abb);
+        a.abr = fma_<AM>(ra, cr, a.abr); a.abg = fma_<AM>(ra, cg, a.abg); a.abb = fma_<AM>(ra, cb, a.abb);
         a.ap = a.ap + ra;
         a.rr = cr; a.rg = cg; a.rb = cb;
     }
@@ -2461,7 +2461,7 @@ __device__ __forceinline__ void ctl_store(uint32_t* p, uint32_t v) { __hip_atomi
 constexpr uint32_t kFrameSpinLimit = 1u << 22;  // idle polls in a row before a wave gives up (a logic error's cost bound; each poll sleeps)
 
 // A WALKER: block_segment's loop, fed from its `rdy` ring instead of a queue, parking results in its `due` ring.
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ void frame_walker(const WfParams& w, FrameRings& R, FrameCtl& C, unsigned long long& tested) {
     const uint32_t lane = threadIdx.x & 63u;
     const GridDesc& g = w.grid;
@@ -2558,7 +2558,7 @@ __device__ __forceinline__ void frame_walker(const WfParams& w, FrameRings& R, F
                         for (uint32_t k2 = 0; k2 < w.rp.scene.n_objs; ++k2) {
                             float t;
                             bool sphere;
-                            const bool cand = lane_candidate<FUSED, true, false>(hot + k2, ray, t, sphere);
+                            const bool cand = lane_candidate<AM, true, false>(hot + k2, ray, t, sphere);
                             if (COUNT) ++tested;
                             if (cand) closest_take(t, (int)k2, sphere, T, idx, cur_sphere);
                         }
@@ -2673,7 +2673,7 @@ __device__ __forceinline__ void frame_walker(const WfParams& w, FrameRings& R, F
                     float t;
                     bool sphere;
                     const Ray ray = {rsx, rsy, rsz, 1.0f, rdx, rdy, rdz, 0.0f};
-                    const bool cand = lane_candidate<FUSED, true, false>(hot + pend_k, ray, t, sphere);
+                    const bool cand = lane_candidate<AM, true, false>(hot + pend_k, ray, t, sphere);
                     if (COUNT) ++tested;
                     done_k = pend_k;
                     bool cur_sphere = (fl & kSphere) != 0u;
@@ -2700,7 +2700,7 @@ __device__ __forceinline__ void frame_walker(const WfParams& w, FrameRings& R, F
 
 // The STEPPER of a workgroup: draws the runs of new pixels, and for each of its walkers in turn runs the steps that are due -
 // one pixel per lane, topped up with new pixels - and queues what goes on in that walker's `rdy`.
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __device__ __forceinline__ void frame_stepper(const WfParams& w, const uint32_t* __restrict__ queue, uint32_t n_queue, uint32_t wave, uint32_t n_waves,
                                               uint32_t* __restrict__ run_ctr, FrameRings* __restrict__ rings, FrameCtl* __restrict__ ctl, uint32_t* __restrict__ mine_state, Ctx& cnt) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -2763,7 +2763,7 @@ __device__ __forceinline__ void frame_stepper(const WfParams& w, const uint32_t*
                     const uint32_t entry = w.identity_queue ? mine : queue[mine];
                     spix = w.identity_queue ? mine : (entry & kQueuePixel);
                 }
-                goes_on = frame_step<FUSED, false>(w, RingIO{R, dslot, pslot}, primary, spix, cnt);
+                goes_on = frame_step<AM, false>(w, RingIO{R, dslot, pslot}, primary, spix, cnt);
             }
             const unsigned long long gm = __ballot(goes_on);
             {   // close the gaps the pixels that ended have left (reads before writes: one wave, LDS in order)
@@ -2812,7 +2812,7 @@ __device__ __forceinline__ void frame_stepper(const WfParams& w, const uint32_t*
     }
 }
 
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_FRAME_WAVES, RT_FRAME_WAVES))) void wf_frame(const WfParams wk, uint32_t* __restrict__ run_ctr) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -2827,8 +2827,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_FRAME_WA
     const uint32_t role = threadIdx.x >> 6;
     Ctx cnt{w, 0, 0ull, 0ull, 0ull, false, false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f), false, {}, {}, {}, {}};
     unsigned long long tested = 0;
-    if (role == 0u) frame_stepper<FUSED, COUNT>(w, w.q_prev_closest, n_queue, blockIdx.x, gridDim.x, run_ctr, s_rings, s_ctl, s_stepper, cnt);
-    else frame_walker<FUSED, COUNT>(w, s_rings[role - 1u], s_ctl[role - 1u], tested);
+    if (role == 0u) frame_stepper<AM, COUNT>(w, w.q_prev_closest, n_queue, blockIdx.x, gridDim.x, run_ctr, s_rings, s_ctl, s_stepper, cnt);
+    else frame_walker<AM, COUNT>(w, s_rings[role - 1u], s_ctl[role - 1u], tested);
     if (COUNT) {
         add_ray_counters(w, cnt);
         if (tested) atomicAdd(&w.rp.counters->tests, tested);
@@ -2850,7 +2850,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_FRAME_WA
 #ifndef RT_STEP_BLOCKS
 #define RT_STEP_BLOCKS 0   // 1: the stale-specular scans' shadow rays through the block grid first (as wf_finish), 0: the fine grid only
 #endif
-template <bool FUSED, bool COUNT>
+template <int AM, bool COUNT>
 __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(RT_RESUME_WAVES_PER_EU))) void wf_step(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -2862,7 +2862,7 @@ __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(
     if (t < w.n_prev_closest) {
         const uint32_t entry = w.identity_queue ? t : w.q_prev_closest[t];
         pix = entry & kQueuePixel;
-        goes_on = frame_step<FUSED, RT_STEP_BLOCKS != 0>(w, StateIO{w, pix}, w.first_round != 0u, pix, cnt);
+        goes_on = frame_step<AM, RT_STEP_BLOCKS != 0>(w, StateIO{w, pix}, w.first_round != 0u, pix, cnt);
     }
     block_push(goes_on, false, pix, w.q_closest, w.q_any, w.counts);
     if (COUNT) add_ray_counters(w, cnt);
@@ -2947,7 +2947,7 @@ size_t wavefront_counter_bytes() { return sizeof(uint32_t) * (size_t)(kTicketBas
 
 // one launch of the persistent grid walk (the template arguments pick the compiled variant); `n_max` = the most the
 // queue can hold, the kernel reads its real length from the round state
-template <bool FUSED, bool ANY>
+template <int AM, bool ANY>
 static void launch_persistent(const WfParams& w, uint64_t n_max, uint32_t* ticket, hipStream_t s, bool shared) {
     // The shadow walk (light tiles: two or three short trips per ray) is bound by what a wave costs to start, not by how many
     // rays are in flight: MEASURED, rank 0's share of the cfg4 frame at world = 1 / 2 / 4 / 8 with its wave cap at 8192:
@@ -2970,26 +2970,26 @@ static void launch_persistent(const WfParams& w, uint64_t n_max, uint32_t* ticke
     const char* walk3_env = std::getenv("RT_WALK3");  // "0": closest-hit rays through walk_segment / trace_segment instead
     if (!ANY && w.bgrid.enabled && !(walk3_env && walk3_env[0] == '0')) {
         if (tri) {  // (meshes: the same walk with the triangle branch in its exact tests)
-            if (w.count_rays) hipLaunchKernelGGL((wf_walk_blocks<FUSED, true, true>), grid, block, 0, s, w, ticket);
-            else hipLaunchKernelGGL((wf_walk_blocks<FUSED, false, true>), grid, block, 0, s, w, ticket);
+            if (w.count_rays) hipLaunchKernelGGL((wf_walk_blocks<AM, true, true>), grid, block, 0, s, w, ticket);
+            else hipLaunchKernelGGL((wf_walk_blocks<AM, false, true>), grid, block, 0, s, w, ticket);
         } else {
-            if (w.count_rays) hipLaunchKernelGGL((wf_walk_blocks<FUSED, true, false>), grid, block, 0, s, w, ticket);
-            else hipLaunchKernelGGL((wf_walk_blocks<FUSED, false, false>), grid, block, 0, s, w, ticket);
+            if (w.count_rays) hipLaunchKernelGGL((wf_walk_blocks<AM, true, false>), grid, block, 0, s, w, ticket);
+            else hipLaunchKernelGGL((wf_walk_blocks<AM, false, false>), grid, block, 0, s, w, ticket);
         }
         return;
     }
     const bool walk2_allowed = !walk2_env || (ANY ? std::strcmp(walk2_env, "any") == 0 : std::strcmp(walk2_env, "closest") == 0) || std::strcmp(walk2_env, "both") == 0;
     if (!tri && w.grid.walk_rec && walk2_allowed && (!ANY || !w.ltiles.enabled || w.ltiles.walk_base != 0u || w.ltiles.blocks_enabled)) {
-        if (w.count_rays) hipLaunchKernelGGL((wf_walk<FUSED, ANY, true>), grid, block, 0, s, w, ticket);
-        else hipLaunchKernelGGL((wf_walk<FUSED, ANY, false>), grid, block, 0, s, w, ticket);
+        if (w.count_rays) hipLaunchKernelGGL((wf_walk<AM, ANY, true>), grid, block, 0, s, w, ticket);
+        else hipLaunchKernelGGL((wf_walk<AM, ANY, false>), grid, block, 0, s, w, ticket);
         return;
     }
     if (w.count_rays) {
-        if (tri) hipLaunchKernelGGL((wf_trace_grid_persistent<FUSED, ANY, true, true>), grid, block, 0, s, w, ticket);
-        else hipLaunchKernelGGL((wf_trace_grid_persistent<FUSED, ANY, true, false>), grid, block, 0, s, w, ticket);
+        if (tri) hipLaunchKernelGGL((wf_trace_grid_persistent<AM, ANY, true, true>), grid, block, 0, s, w, ticket);
+        else hipLaunchKernelGGL((wf_trace_grid_persistent<AM, ANY, true, false>), grid, block, 0, s, w, ticket);
     } else {
-        if (tri) hipLaunchKernelGGL((wf_trace_grid_persistent<FUSED, ANY, false, true>), grid, block, 0, s, w, ticket);
-        else hipLaunchKernelGGL((wf_trace_grid_persistent<FUSED, ANY, false, false>), grid, block, 0, s, w, ticket);
+        if (tri) hipLaunchKernelGGL((wf_trace_grid_persistent<AM, ANY, false, true>), grid, block, 0, s, w, ticket);
+        else hipLaunchKernelGGL((wf_trace_grid_persistent<AM, ANY, false, false>), grid, block, 0, s, w, ticket);
     }
 }
 
@@ -2997,7 +2997,7 @@ static void launch_persistent(const WfParams& w, uint64_t n_max, uint32_t* ticke
 // rounds are enqueued in batches without looking at the queue lengths (device-side round state); the host reads the
 // state back once per batch - once per frame when the first batch (as many rounds as the kernel's control flow
 // needs at least) gets the frame down to wf_finish's share, which is the normal case.
-template <int KERNEL, bool FUSED>
+template <int KERNEL, int AM>
 static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t stream, uint32_t* rounds_out) {
     hipError_t e;
     const uint64_t n = w.rp.n_local;
@@ -3034,8 +3034,9 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
     }
 
     static const bool one_stream = std::getenv("RT_WF_ONE_STREAM") != nullptr;  // measurement knob
-    const bool use_frame = KERNEL == 2 && frame_kernel_applies(w, KERNEL);
-    const bool use_step = KERNEL == 2 && !use_frame && step_rounds_apply(w, KERNEL);  // rounds of {closest-hit walk, wf_step}: no shadow queue, no wf_finish
+    // (the opt-in organisations are not built for RT_FLAG_DEVICE_OPENCL: the default one renders it)
+    const bool use_frame = KERNEL == 2 && AM != kDeviceCL && frame_kernel_applies(w, KERNEL);
+    const bool use_step = KERNEL == 2 && AM != kDeviceCL && !use_frame && step_rounds_apply(w, KERNEL);  // rounds of {closest-hit walk, wf_step}: no shadow queue, no wf_finish
     auto enqueue_round = [&](bool first, uint64_t nc_max, uint64_t na_max) -> hipError_t {
         hipError_t e2;
         w.first_round = first ? 1u : 0u;
@@ -3049,18 +3050,18 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
             any_stream = buf.side_stream;
             if ((e2 = hipEventRecord(buf.ev_fork, stream)) != hipSuccess) return e2;
             if ((e2 = hipStreamWaitEvent(any_stream, buf.ev_fork, 0)) != hipSuccess) return e2;
-            launch_persistent<FUSED, true>(w, na_max, rs + kTicketBase + kTicketWords, any_stream, true);
+            launch_persistent<AM, true>(w, na_max, rs + kTicketBase + kTicketWords, any_stream, true);
             if ((e2 = hipGetLastError()) != hipSuccess) return e2;
             if ((e2 = hipEventRecord(buf.ev_join, any_stream)) != hipSuccess) return e2;
         }
         if (nc_max) {
             if (use_grid && first && w.tiles.enabled && w.rp.pinhole) {
-                hipLaunchKernelGGL((wf_trace_primary_tiles<FUSED>), grid_for(nc_max), dim3(256), 0, stream, w);
+                hipLaunchKernelGGL((wf_trace_primary_tiles<AM>), grid_for(nc_max), dim3(256), 0, stream, w);
             } else if (use_grid) {
-                launch_persistent<FUSED, false>(w, nc_max, rs + kTicketBase, stream, side_by_side);  // (a grid implies direction.w = 0)
+                launch_persistent<AM, false>(w, nc_max, rs + kTicketBase, stream, side_by_side);  // (a grid implies direction.w = 0)
             } else {
-                if (first && !w.rp.dir_w_zero) hipLaunchKernelGGL((wf_trace_closest<FUSED, false>), grid_for(nc_max), dim3(256), 0, stream, w);
-                else hipLaunchKernelGGL((wf_trace_closest<FUSED, true>), grid_for(nc_max), dim3(256), 0, stream, w);
+                if (first && !w.rp.dir_w_zero) hipLaunchKernelGGL((wf_trace_closest<AM, false>), grid_for(nc_max), dim3(256), 0, stream, w);
+                else hipLaunchKernelGGL((wf_trace_closest<AM, true>), grid_for(nc_max), dim3(256), 0, stream, w);
             }
             if ((e2 = hipGetLastError()) != hipSuccess) return e2;
         }
@@ -3068,10 +3069,10 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
             if ((e2 = hipStreamWaitEvent(stream, buf.ev_join, 0)) != hipSuccess) return e2;
         } else if (na_max) {
             if (w.rp.scene.literal) {
-                hipLaunchKernelGGL((wf_trace_any_literal<FUSED>), grid_for(na_max), dim3(256), 0, stream, w);
+                hipLaunchKernelGGL((wf_trace_any_literal<AM>), grid_for(na_max), dim3(256), 0, stream, w);
                 if ((e2 = hipGetLastError()) != hipSuccess) return e2;
             } else if (use_grid) {
-                launch_persistent<FUSED, true>(w, na_max, rs + kTicketBase + kTicketWords, stream, false);
+                launch_persistent<AM, true>(w, na_max, rs + kTicketBase + kTicketWords, stream, false);
                 if ((e2 = hipGetLastError()) != hipSuccess) return e2;
             } else {
                 // slices of >= kMinSlicePairs pairs (amortises each launch's pipeline fill), at most kMaxSlices; the
@@ -3088,27 +3089,30 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
                     const uint32_t* q_in = sl ? buf.q_slice[(sl - 1u) & 1u] : nullptr;
                     const uint32_t* n_in = rs + ((sl - 1u) & 1u ? RS_SLICE_B : RS_SLICE_A);
                     if (!last && (e2 = hipMemsetAsync(n_out, 0, sizeof(uint32_t), stream)) != hipSuccess) return e2;
-                    hipLaunchKernelGGL((wf_trace_any_slice<FUSED>), grid_for(na_max), dim3(256), 0, stream, w, q_in, n_in, lo, hi,
+                    hipLaunchKernelGGL((wf_trace_any_slice<AM>), grid_for(na_max), dim3(256), 0, stream, w, q_in, n_in, lo, hi,
                                        q_out, n_out, sl == 0 ? 1u : 0u);
                     if ((e2 = hipGetLastError()) != hipSuccess) return e2;
                 }
             }
         }
         const uint64_t total_max = nc_max + na_max;
-        if (first && use_frame) {
+        if constexpr (AM == kDeviceCL) {
+            hipLaunchKernelGGL((wf_resume<KERNEL, AM>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
+                               dim3(kResumeThreads), 0, stream, w);
+        } else if (first && use_frame) {
             // wf_frame: every pixel from its primary hit to its final store in one persistent launch (the first round's shadow
             // tickets are unused: the first round traces primary rays only)
             uint64_t waves = 256ull * 4ull * (uint64_t)RT_FRAME_WAVES;  // every wave that can be resident
             if (const char* env = std::getenv("RT_WAVES_FRAME")) waves = (uint64_t)std::max(64, std::atoi(env));  // measurement knob
             const dim3 grid = persistent_grid(nc_max, waves);
-            if (w.count_rays) hipLaunchKernelGGL((wf_frame<FUSED, true>), grid, dim3(256), 0, stream, w, rs + kTicketBase + kTicketWords);
-            else hipLaunchKernelGGL((wf_frame<FUSED, false>), grid, dim3(256), 0, stream, w, rs + kTicketBase + kTicketWords);
+            if (w.count_rays) hipLaunchKernelGGL((wf_frame<AM, true>), grid, dim3(256), 0, stream, w, rs + kTicketBase + kTicketWords);
+            else hipLaunchKernelGGL((wf_frame<AM, false>), grid, dim3(256), 0, stream, w, rs + kTicketBase + kTicketWords);
         } else if (use_step) {
             const dim3 grid((uint32_t)((nc_max + kResumeThreads - 1) / kResumeThreads));
-            if (w.count_rays) hipLaunchKernelGGL((wf_step<FUSED, true>), grid, dim3(kResumeThreads), 0, stream, w);
-            else hipLaunchKernelGGL((wf_step<FUSED, false>), grid, dim3(kResumeThreads), 0, stream, w);
+            if (w.count_rays) hipLaunchKernelGGL((wf_step<AM, true>), grid, dim3(kResumeThreads), 0, stream, w);
+            else hipLaunchKernelGGL((wf_step<AM, false>), grid, dim3(kResumeThreads), 0, stream, w);
         } else {
-            hipLaunchKernelGGL((wf_resume<KERNEL, FUSED>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
+            hipLaunchKernelGGL((wf_resume<KERNEL, AM>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
                                dim3(kResumeThreads), 0, stream, w);
         }
         if ((e2 = hipGetLastError()) != hipSuccess) return e2;
@@ -3138,7 +3142,7 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
             //  round, RT_WF_BATCH=1, `w` would still carry the first round's flags here)
             w.first_round = 0u;
             w.identity_queue = 0u;
-            hipLaunchKernelGGL((wf_finish<KERNEL, FUSED>), grid_for(finish_threshold ? finish_threshold : 1), dim3(256), 0, stream, w);
+            hipLaunchKernelGGL((wf_finish<KERNEL, AM>), grid_for(finish_threshold ? finish_threshold : 1), dim3(256), 0, stream, w);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
         if ((e = hipMemcpyAsync(buf.h_counts, rs, RS_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
@@ -3159,7 +3163,17 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
     return hipSuccess;
 }
 
-hipError_t launch_wavefront(const RenderParams& p, int kernel, bool fused, bool count, WavefrontBuffers& buf,
+template <int KERNEL>
+static hipError_t run_wavefront_arith(const WfParams& w, int arith, WavefrontBuffers& buf, hipStream_t stream, uint32_t* rounds_out) {
+    switch (arith) {
+        case kUnfused: return run_wavefront<KERNEL, kUnfused>(w, buf, stream, rounds_out);
+        case kFused: return run_wavefront<KERNEL, kFused>(w, buf, stream, rounds_out);
+        case kDeviceCL: return run_wavefront<KERNEL, kDeviceCL>(w, buf, stream, rounds_out);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_wavefront(const RenderParams& p, int kernel, int arith, bool count, WavefrontBuffers& buf,
                             hipStream_t stream, uint32_t* rounds_out) {
     if (p.n_local >= 0x7fffffffull) return hipErrorInvalidValue;  // queue entries are pixel ids in 31 bits + a flag
     WfParams w;
@@ -3168,9 +3182,9 @@ hipError_t launch_wavefront(const RenderParams& p, int kernel, bool fused, bool 
     w.kernel = kernel;
     w.count_rays = count ? 1u : 0u;
     switch (kernel) {
-        case 0: return fused ? run_wavefront<0, true>(w, buf, stream, rounds_out) : run_wavefront<0, false>(w, buf, stream, rounds_out);
-        case 1: return fused ? run_wavefront<1, true>(w, buf, stream, rounds_out) : run_wavefront<1, false>(w, buf, stream, rounds_out);
-        case 2: return fused ? run_wavefront<2, true>(w, buf, stream, rounds_out) : run_wavefront<2, false>(w, buf, stream, rounds_out);
+        case 0: return run_wavefront_arith<0>(w, arith, buf, stream, rounds_out);
+        case 1: return run_wavefront_arith<1>(w, arith, buf, stream, rounds_out);
+        case 2: return run_wavefront_arith<2>(w, arith, buf, stream, rounds_out);
         default: return hipErrorInvalidValue;
     }
 }
