@@ -107,7 +107,8 @@ typedef enum rt_kernel {
                                     an AMD GPU gets that picture. Refused (RT_ERR_INVALID_ARGUMENT) together with RT_FLAG_UNFUSED or
                                     RT_FLAG_FAST_PHONG, and for scenes with triangles (type 2). The default organisation renders it
                                     (RT_FRAME_KERNEL / RT_STEP_ROUNDS do not apply); a scene with a light inside an object's bounding
-                                    sphere, or a directional light of direction 0, is rendered with RT_FLAG_LITERAL set by rt_create. */
+                                    sphere, or a directional light of direction 0 or of |d|^2 outside (1e-30, 1e30), is rendered with
+                                    RT_FLAG_LITERAL set by rt_create. */
 
 typedef struct rt_stats_t {
     uint64_t rays_traced;     /* rays this backend actually issued in the last counted render (R_act)          */

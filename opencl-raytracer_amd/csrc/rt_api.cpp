@@ -1864,11 +1864,14 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     // light of direction 0) has a finite start and direction 0. Every sphere of the reference's loop then accepts it with a NaN
     // time and every box that contains the start with MAX_FLOAT: the outcome depends on the order of the loop, which only the
     // literal loops follow. Such a ray needs a light on a surface, i.e. inside an object's bounding sphere.
+    // A directional light's shadow rays have the light's own direction, unnormalised: one of |d|^2 outside the walks' window
+    // (direction_in_domain; a denormal direction, say) gives an object-space direction that can round to 0 and the same NaN
+    // times, so it goes literal too.
     if ((flags & RT_FLAG_DEVICE_OPENCL) && !(c->flags & RT_FLAG_LITERAL) && n_lights) {
         const rt_light* L = static_cast<const rt_light*>(lights);
         bool ordered = false;
         for (uint32_t l = 0; l < n_lights && !ordered; ++l)
-            if (L[l].position[3] == 0.f && L[l].position[0] == 0.f && L[l].position[1] == 0.f && L[l].position[2] == 0.f) ordered = true;
+            if (L[l].position[3] == 0.f && !direction_in_domain(L[l].position[0], L[l].position[1], L[l].position[2])) ordered = true;
         std::atomic<bool> near{ordered};
         parallel_for(n_objs, 8192, [&](size_t i0, size_t i1) {
             for (size_t i = i0; i < i1 && !near.load(std::memory_order_relaxed); ++i) {

@@ -174,3 +174,174 @@ def f64_degenerate(name):
 
 def f64_needs_hits(name):
     return not f64_degenerate(name) and not any(name.startswith(p) for p in F64_NO_HIT_MINIMUM)
+
+
+# ---- fuzz generators shared by the suite and tools/fuzz ---------------------------------------------------------------
+def pinhole_fuzz_scene(rng, n):
+    """Scene of tools/fuzz/fuzz_pinhole.py: n spheres / boxes in a cloud in front of a pinhole camera (10 % of them around
+    or behind the camera plane), sizes 0.01-8, axis ratios up to 4, lights anywhere in a box around the cloud."""
+    zc = float(rng.choice([-3.0, -10.0, -40.0, -200.0]))
+    spread = float(rng.choice([1.0, 5.0, 30.0]))
+    smin, smax = [(0.01, 0.1), (0.1, 1.0), (1.0, 8.0)][int(rng.integers(0, 3))]
+    aniso = float(rng.choice([1.0, 1.0, 4.0]))
+    recs = []
+    for _ in range(n):
+        pos = np.array([rng.uniform(-spread, spread), rng.uniform(-spread, spread), zc + rng.uniform(-spread, spread)])
+        if rng.uniform() < 0.1:
+            pos[2] = rng.uniform(-1.0, 3.0)      # around / behind the camera plane
+        s = rng.uniform(smin, smax)
+        sc = (s, s * rng.uniform(1, aniso), s / rng.uniform(1, aniso)) if aniso > 1 else (s, s, s)
+        rot = rotation(rng.normal(size=3), rng.uniform(0, 6.3)) if rng.uniform() < 0.7 else None
+        mv, inv = instance(pos, rot, sc)
+        mat = R.Material(tuple(rng.uniform(0, 1, 3)), tuple(rng.uniform(0, 1, 3)), tuple(rng.uniform(0, 1, 3)),
+                         absorption=float(rng.choice([0.2, 0.6, 1.0])), shininess=float(rng.uniform(1, 40)))
+        recs.append(R.make_object(R.BOX if rng.uniform() < 0.4 else R.SPHERE, mat, mv, inv))
+    objs = R.objects_array(recs)
+    lights = R.lights_array([R.make_light(R.LightProperties(tuple(rng.uniform(0, .3, 3)), tuple(rng.uniform(0, .5, 3)), tuple(rng.uniform(0, .5, 3))),
+                                          position=(rng.uniform(-20, 20), rng.uniform(-20, 20), rng.uniform(-50, 20), 1.0)) for _ in range(int(rng.integers(1, 4)))])
+    return objs, lights
+
+
+def misc_fuzz_case(rng):
+    """Scene and frame of tools/fuzz/fuzz_misc.py (the draws before its shard layout): 3-1 200 objects, 1-4 lights (up to
+    one directional), 64x48 - 200x120 pixels, kernel, depth, flavour, in-kernel or uploaded rays."""
+    n_s, n_b = [(2, 1), (20, 10), (150, 60), (900, 300)][int(rng.integers(0, 4))]
+    objs, lights = random_scene(n_s, n_b, int(rng.integers(1, 5)), seed=int(rng.integers(0, 1 << 30)), spread=float(rng.choice([3.0, 12.0])),
+                                zrange=(-40.0, -6.0), directional_lights=int(rng.integers(0, 2)))
+    W, H = [(64, 48), (128, 80), (200, 120), (96, 96)][int(rng.integers(0, 4))]
+    kernel = ["shade_and_reflect", "shade", "hittest"][int(rng.integers(0, 3))]
+    depth = int(rng.integers(0, 4))
+    fused = bool(rng.integers(0, 2))
+    pin = bool(rng.integers(0, 2))
+    return dict(objs=objs, lights=lights, W=W, H=H, kernel=kernel, depth=depth, fused=fused, pin=pin)
+
+
+# ---- RT_FLAG_DEVICE_OPENCL: where rt_create switches a scene to the literal loops --------------------------------------
+def object_reach(objs):
+    """Per object, the float64 centre (n, 3) and radius (n,) of the ball in which a positional light makes rt_create render
+    an RT_FLAG_DEVICE_OPENCL scene with the literal loops: object_bound() of rt_api.cpp (bounding sphere of the instanced
+    unit sphere / box from rows x, y, z of mvInverse, sigma_max from the closed-form eigenvalue, padded by 1e-6), then
+    R (1 + 1e-4) + 1e-4 (|cx| + |cy| + |cz| + R). The same expressions in the same order; radius +inf where rt_create has
+    no usable bound (every light is near), -inf for a type that is never hit."""
+    n = len(objs)
+    m = objs["mvInverse"].astype(np.float64).reshape(n, 4, 4)      # column-major: m[c][r]
+    A = [[m[:, j, i] for j in range(3)] for i in range(3)]          # A[i][j] = mvInverse[4 j + i]
+    b = [m[:, 3, i] for i in range(3)]
+    with np.errstate(all="ignore"):
+        finite = np.ones(n, bool)
+        for i in range(3):
+            finite &= np.isfinite(b[i])
+            for j in range(3):
+                finite &= np.isfinite(A[i][j])
+        det = (A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+               A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]))
+        norm2 = np.zeros(n)
+        for i in range(3):
+            for j in range(3):
+                norm2 = norm2 + A[i][j] * A[i][j]
+        ok = finite & (np.abs(det) > 1e-12 * np.power(norm2, 1.5))
+        inv = [[(A[1][1] * A[2][2] - A[1][2] * A[2][1]) / det, (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det,
+                (A[0][1] * A[1][2] - A[0][2] * A[1][1]) / det],
+               [(A[1][2] * A[2][0] - A[1][0] * A[2][2]) / det, (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det,
+                (A[0][2] * A[1][0] - A[0][0] * A[1][2]) / det],
+               [(A[1][0] * A[2][1] - A[1][1] * A[2][0]) / det, (A[0][1] * A[2][0] - A[0][0] * A[2][1]) / det,
+                (A[0][0] * A[1][1] - A[0][1] * A[1][0]) / det]]
+        c, fro2 = [], np.zeros(n)
+        for i in range(3):
+            c.append(-(inv[i][0] * b[0] + inv[i][1] * b[1] + inv[i][2] * b[2]))
+            for j in range(3):
+                fro2 = fro2 + inv[i][j] * inv[i][j]
+        S = [[inv[i][0] * inv[j][0] + inv[i][1] * inv[j][1] + inv[i][2] * inv[j][2] for j in range(3)] for i in range(3)]
+        q = (S[0][0] + S[1][1] + S[2][2]) / 3.0
+        p1 = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[1][2] * S[1][2]
+        p2 = (S[0][0] - q) * (S[0][0] - q) + (S[1][1] - q) * (S[1][1] - q) + (S[2][2] - q) * (S[2][2] - q) + 2.0 * p1
+        pp = np.sqrt(p2 / 6.0)
+        Bm = [[(S[i][j] - (q if i == j else 0.0)) / pp for j in range(3)] for i in range(3)]
+        r = (Bm[0][0] * (Bm[1][1] * Bm[2][2] - Bm[1][2] * Bm[2][1]) - Bm[0][1] * (Bm[1][0] * Bm[2][2] - Bm[1][2] * Bm[2][0]) +
+             Bm[0][2] * (Bm[1][0] * Bm[2][1] - Bm[1][1] * Bm[2][0])) / 2.0
+        r = np.where(r < -1.0, -1.0, np.where(r > 1.0, 1.0, r))
+        lam = q + 2.0 * pp * np.cos(np.arccos(r) / 3.0)
+        lam_max = fro2
+        use = (pp > 0) & np.isfinite(pp)
+        lam_max = np.where(use & np.isfinite(lam) & (lam > 0), lam * (1.0 + 1e-6), lam_max)
+        lam_max = np.where(pp == 0, q * (1.0 + 1e-6), lam_max)
+        lam_max = np.where(lam_max > fro2, fro2, lam_max)
+        lam_max = np.where(lam_max < fro2 / 3.0, fro2 / 3.0, lam_max)
+        r0 = np.where(objs["type"] == R.SPHERE, 1.0, np.sqrt(0.75))
+        Rad = r0 * np.sqrt(lam_max)
+        kappa2 = lam_max * lam_max * lam_max * det * det * (1.0 + 1e-6)
+        ok &= np.isfinite(Rad) & np.isfinite(kappa2) & (kappa2 >= 0.999) & np.isfinite(c[0] + c[1] + c[2])
+        centre = np.stack(c, 1)
+        reach = Rad * (1.0 + 1e-4) + 1e-4 * (np.abs(c[0]) + np.abs(c[1]) + np.abs(c[2]) + Rad)
+    centre = np.where(ok[:, None], centre, 0.0)
+    reach = np.where(ok, reach, np.inf)
+    reach = np.where(objs["type"] > R.BOX, -np.inf, reach)
+    return centre, reach
+
+
+def light_in_reach(objs, position, slack=0.0):
+    """True if rt_create, under RT_FLAG_DEVICE_OPENCL, sends a scene with a positional light at `position` (float32 xyz)
+    to the literal loops (`slack` widens every reach by that fraction, for generators that want a margin)."""
+    centre, reach = object_reach(objs)
+    p = np.asarray(position, np.float32)[:3].astype(np.float64)
+    d = p[None, :] - centre
+    d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+    rr = reach * (1.0 + slack)
+    near = (reach >= 0.0) & ~(d2 > rr * rr)
+    return bool(near.any())
+
+
+def clear_lights(objs, lights, rng, tries=32, slack=1e-3):
+    """A copy of `lights` whose positional lights lie outside every object's reach (object_reach, widened by `slack`), so
+    that an RT_FLAG_DEVICE_OPENCL scene keeps the default path. A light in reach is redrawn uniformly in the box of the
+    object centres widened 1.5 times (where the generators put their lights) up to `tries` times, and otherwise put
+    beyond every object, at a random direction from the box centre. Returns (lights, number of lights moved)."""
+    out = lights.copy()
+    centre, reach = object_reach(objs)
+    pos = objs["mv"].reshape(-1, 4, 4)[:, 3, :3].astype(np.float64)
+    lo, hi = pos.min(0), pos.max(0)
+    mid, half = (lo + hi) / 2, (hi - lo) / 2 * 1.5
+    moved = 0
+    for k in range(len(out)):
+        if out["position"][k][3] == 0:
+            continue
+        if not light_in_reach(objs, out["position"][k], slack):
+            continue
+        moved += 1
+        for _ in range(tries):
+            out["position"][k][:3] = mid + rng.uniform(-1, 1, 3) * half
+            if not light_in_reach(objs, out["position"][k], slack):
+                break
+        else:
+            u = rng.normal(size=3)
+            u /= np.linalg.norm(u)
+            far = np.max(np.linalg.norm(centre - mid, axis=1) + reach[np.isfinite(reach)].max(initial=0.0)) * 1.5 + 1.0
+            out["position"][k][:3] = mid + u * far
+            assert not light_in_reach(objs, out["position"][k], slack)
+    return out, moved
+
+
+def device_fuzz_lights(objs, lights, rays, rng):
+    """The lights of a grid-fuzz scene (test_fuzz_gpu.fuzz_scene) for RT_FLAG_DEVICE_OPENCL: a second light at the first ray's
+    origin where it draws one (so that shade_and_reflect's backward light scan shows the default path: rays_traced <
+    rays_reference), then clear_lights. Returns (lights, number of lights moved)."""
+    if len(lights) < 2:
+        lights = R.lights_array([lights[0], lights[0]])
+        lights["position"][1][:3] = rays["start"][0][:3]
+    return clear_lights(objs, lights, rng)
+
+
+def device_mismatch(objs, lights, rays, kernel, depth, out, t):
+    """A frame of RT_FLAG_DEVICE_OPENCL against oracle.DeviceReference with the bars of test_device_opencl_gpu.py (primary t
+    bit-identical but for the sign of a zero, the same hit/miss mask, |dRGB| <= 1e-5). None if it passes, else what differs."""
+    from oracle import oracle
+    dev_t = oracle.DeviceReference("hittest").render(objs, lights, rays)["out"]
+    a, b = np.asarray(dev_t, np.float32), np.asarray(out if kernel == "hittest" else t, np.float32)
+    same = (a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))
+    if not same.all():
+        return f"primary t differs on {int((~same).sum())} rays"
+    if kernel == "hittest":
+        return None
+    dev = oracle.DeviceReference(kernel).render(objs, lights, rays, depth)["out"]
+    err = compare_frames(out, dev)
+    return None if err <= 1e-5 else f"max |dRGB| {err:.3e}"

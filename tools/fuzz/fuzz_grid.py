@@ -3,7 +3,9 @@ import sys, time, os
 ROOT = __import__('pathlib').Path(__file__).resolve().parents[2]; sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / 'tests'))
 import numpy as np
 import _pkg; _pkg.load()
-from helpers import R, rotation, instance, same_floats
+from helpers import R, rotation, instance, same_floats, device_fuzz_lights, device_mismatch
+DEVICE = bool(os.environ.get("FUZZ_DEVICE_OPENCL"))      # RT_FLAG_DEVICE_OPENCL; >= 2 lights, out of every object's reach
+XCHECK = int(os.environ.get("FUZZ_XCHECK", "0"))         # every Nth seed also against oracle.DeviceReference (with DEVICE)
 from opencl_raytracer_amd.hip_raytracer import HIPRaytracer
 
 def scene(rng):
@@ -47,9 +49,10 @@ def scene(rng):
     rays["start"][:, 3] = 1.0
     import os
     if os.environ.get("FUZZ_DW"): rays["direction"][:, 3] = float(os.environ["FUZZ_DW"])
+    if DEVICE: lights, _ = device_fuzz_lights(objs, lights, rays, rng)
     return objs, lights, rays
 
-bad = 0
+bad = xchecked = 0
 t0 = time.time()
 n_seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -60,9 +63,9 @@ for seed in range(first, first + n_seeds):
         res = []
         for grid in (True, False):
             try:
-                with HIPRaytracer(objs, lights, rays, depth, kernel=kernel, path="wavefront", grid=grid, fused=not os.environ.get("FUZZ_UNFUSED")) as rt:
+                with HIPRaytracer(objs, lights, rays, depth, kernel=kernel, path="wavefront", grid=grid, fused=not os.environ.get("FUZZ_UNFUSED"), device_opencl=DEVICE) as rt:
                     out = rt.Render(); t, i = rt.render_aux(); st = rt.count_rays()
-                    res.append((out.copy(), t.copy(), i.copy(), st.rays_reference, rt.stats().object_tests))
+                    res.append((out.copy(), t.copy(), i.copy(), st.rays_reference, rt.stats().object_tests, st.rays_traced))
             except Exception as ex:
                 res.append(None); print('seed', seed, 'exception', ex)
         a, b = res
@@ -71,5 +74,11 @@ for seed in range(first, first + n_seeds):
         if not ok:
             bad += 1
             print('MISMATCH seed', seed, kernel, 'pixels', int(np.any(a[0].reshape(len(rays), -1) != b[0].reshape(len(rays), -1), axis=1).sum()), flush=True)
+        if DEVICE and kernel == "shade_and_reflect" and (a[2] >= 0).any() and not a[5] < a[3]:  # the backward light scan ran
+            bad += 1; print('LITERAL seed', seed, 'rays traced', a[5], 'reference', a[3], flush=True)
+        if DEVICE and XCHECK and seed % XCHECK == 0:
+            why = device_mismatch(objs, lights, rays, kernel, depth, a[0], a[1])
+            xchecked += 1
+            if why: bad += 1; print('DEVICE MISMATCH seed', seed, kernel, why, flush=True)
     if seed % 10 == 9: print('seed', seed, 'done, mismatches so far', bad, f'{time.time()-t0:.0f}s', 'grid tests/brute tests', a[4], b[4], flush=True)
-print('TOTAL mismatches', bad)
+print('TOTAL mismatches', bad, 'device cross-checks', xchecked)
