@@ -51,7 +51,10 @@ extern "C" {
  *      primary directions leave the default path's domain (|d|^2 == 0, < 1e-30, > 1e30) to RT_FLAG_LITERAL by themselves.
  *      Additions only: a caller built against version 2 keeps working.
  *      Later addition, same version: RT_FLAG_DEVICE_OPENCL (0x80). A library without it refuses the bit with "unknown flag bits",
- *      which is how a caller detects support. */
+ *      which is how a caller detects support.
+ *      Later addition, same version: 8-bit frames - rt_pixel_format, rt_packed_pixel_bytes, rt_pack_device,
+ *      rt_render_device_packed, rt_render_packed, rt_render_multi_packed. Additions only; a caller detects support by the
+ *      symbol (dlsym of rt_packed_pixel_bytes). */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -196,6 +199,46 @@ typedef struct rt_setup_times_t {
 } rt_setup_times_t;
 int rt_get_setup_times(rt_context* ctx, rt_setup_times_t* times);
 
+/* ---- 8-bit frames ----------------------------------------------------------------------------------------------------------
+ * What a picture's consumers take - the reference's PPMExporter::ExportP3 (PPMExporter.cpp:7-30), a window, an encoder - is 8
+ * bits per channel. These entry points quantise ON THE DEVICE (one streaming pass over the float4 frame, csrc/rt_pack.hip) and
+ * move a quarter (RGBA8) or 3/16 (RGB8) of the float frame's bytes. The float entry points are untouched.
+ *
+ * The byte a channel value v (fp32) becomes:  p = v * 255.0f (ONE fp32 multiplication), f = floorf(p), then
+ *     f is NaN, or f < 0 (-inf included; -0.0f gives 0 anyway)  ->  0
+ *     f >= 255 (+inf included)                                  ->  255
+ *     otherwise                                                 ->  (uint8_t)f
+ * This is the reference's min(255, (int)floorf(v * 255.f)) wherever that expression yields 0..255, i.e. wherever the P3 file
+ * it writes is a valid PPM. Outside that range the reference's (int) conversion is undefined behaviour in C (x86 gives
+ * INT_MIN for NaN and +inf, a negative number for v < 0): a byte cannot carry that, and the table above is what it gets
+ * instead. The fourth byte of an RGBA8 pixel is the same function of w (1 -> 255 for every pixel the kernels write).
+ * Pixels are in work-item order, RGB8 tightly packed (3 bytes per pixel, no row padding). */
+typedef enum rt_pixel_format { RT_PIXEL_RGBA8 = 1, RT_PIXEL_RGB8 = 2 } rt_pixel_format;
+size_t rt_packed_pixel_bytes(int format); /* 4, 3; 0 for an unknown format. Needs no device. */
+
+/* Convert n_pixels float4 pixels that already are in DEVICE memory (any colour frame of this library; d_rgba_f32 16-byte
+ * aligned) into n_pixels * rt_packed_pixel_bytes(format) bytes at d_out, asynchronously on hip_stream (NULL = legacy default
+ * stream), on any context whatever its kernel. d_out must be 4-BYTE ALIGNED (RT_ERR_INVALID_ARGUMENT otherwise); beyond that
+ * any offset is fine and not one byte behind the last pixel is written. Unknown format or a NULL pointer with n_pixels > 0:
+ * RT_ERR_INVALID_ARGUMENT. n_pixels == 0: RT_OK, nothing launched. */
+int rt_pack_device(rt_context* ctx, const void* d_rgba_f32, uint64_t n_pixels, int format, void* d_out, void* hip_stream);
+
+/* rt_render_device, then the pass, on the same stream: d_out is rt_local_rays() * rt_packed_pixel_bytes(format) bytes of
+ * caller DEVICE memory, 4-byte aligned. The float frame lives in a context-owned scratch buffer (allocated by the first
+ * call, freed by rt_destroy); calls that share a context must be ordered by the caller, as for every other entry point.
+ * Same stream semantics as rt_render_device (NULL = legacy default stream). Shards (rt_set_shard) work unchanged: packed
+ * tiles back to back. RT_KERNEL_HITTEST contexts are refused (RT_ERR_STATE: one float per ray is not a colour).
+ * Timing: rt_get_stats' last_kernel_ms and rt_timing_summary keep meaning the RENDER's kernels - the pass is launched behind
+ * the event pair, not inside it. */
+int rt_render_device_packed(rt_context* ctx, int format, void* d_out, void* hip_stream);
+
+/* rt_render's synchronous twin: rt_local_rays() pixels of bytes in a context-owned PINNED host buffer, overwritten by the next
+ * packed call and freed by rt_destroy (rt_render's float buffer is a different one and keeps its contents). A large frame goes
+ * through rt_render's passes under rt_render's conditions - per pass: render, pack that pass's pixels, strided copy of bytes -
+ * with RT_RENDER_PASSES / RT_RENDER_SPLIT read alike; the default split of a byte frame is "7,1" (its copy is a quarter as long,
+ * so a smaller last pass leaves less of it behind the kernels). */
+int rt_render_packed(rt_context* ctx, int format, const uint8_t** out);
+
 void rt_destroy(rt_context* ctx);
 
 /* ---- several GPUs from one process ------------------------------------------------------------------------------------
@@ -225,6 +268,9 @@ int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);
 int rt_render_multi_device(rt_multi* m, void* d_frame);
+/* rt_render_multi in bytes (8-bit frames, above): every shard packs its own tiles on its own device and stream, then ONE
+ * strided device-to-host copy of bytes per shard into a pinned portable byte frame owned by `m` (n_rays pixels). */
+int rt_render_multi_packed(rt_multi* m, int format, const uint8_t** out);
 int rt_count_rays_multi(rt_multi* m);
 int rt_get_stats_multi(rt_multi* m, rt_stats_t* stats);
 rt_context* rt_multi_context(rt_multi* m, uint32_t r);

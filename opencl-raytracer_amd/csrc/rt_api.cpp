@@ -5,6 +5,7 @@
 #include "hip_raytracer.h"
 #include "rt_records.h"
 #include "rt_kernels.h"
+#include "rt_pack.h"
 
 #include <hip/hip_runtime.h>
 
@@ -111,6 +112,13 @@ struct rt_context {
     size_t d_out_bytes = 0;
     void* h_out = nullptr;  // context-owned pinned host framebuffer (Render()'s return value)
     size_t h_out_bytes = 0;
+    // 8-bit frames (rt_pack.hip): rt_render_packed's device and pinned byte frames, rt_render_device_packed's float scratch
+    void* d_pack = nullptr;
+    size_t d_pack_bytes = 0;
+    void* h_pack = nullptr;
+    size_t h_pack_bytes = 0;
+    void* d_scratch = nullptr;
+    size_t d_scratch_bytes = 0;
     // rt_render in passes (render_in_passes): the stream the read-backs run on, an event per pass
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_pass[kMaxPasses] = {};
@@ -464,6 +472,33 @@ int ensure_host_out(rt_context* c) {
         c->h_out_bytes = need;
     }
     return RT_OK;
+}
+
+// a context-owned buffer that only ever grows: device memory, or pinned host memory
+int grow_buffer(rt_context* c, void*& p, size_t& have, size_t need, bool pinned_host) {
+    if (p && need <= have) return RT_OK;
+    if (p) (void)(pinned_host ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    have = 0;
+    if (pinned_host) RT_HIP(c, hipHostMalloc(&p, need ? need : 16, hipHostMallocDefault));
+    else RT_HIP(c, hipMalloc(&p, need ? need : 16));
+    have = need;
+    return RT_OK;
+}
+
+size_t packed_bytes(int format) { return format == RT_PIXEL_RGBA8 ? 4 : (format == RT_PIXEL_RGB8 ? 3 : 0); }
+
+// what the three packed render entry points refuse before they touch anything
+int check_packed(rt_context* c, int format) {
+    if (!packed_bytes(format)) return fail(c, RT_ERR_INVALID_ARGUMENT, "unknown pixel format (RT_PIXEL_RGBA8 = 1, RT_PIXEL_RGB8 = 2)");
+    if (c->kernel == RT_KERNEL_HITTEST)
+        return fail(c, RT_ERR_STATE, "an RT_KERNEL_HITTEST context renders one float (the nearest t) per ray, not a colour: there is no 8-bit frame of it");
+    return RT_OK;
+}
+
+int pack_on(rt_context* c, const void* d_src, uint64_t n, int format, void* d_dst, hipStream_t stream) {
+    const hipError_t e = rt::launch_pack(static_cast<const float4*>(d_src), n, format, d_dst, stream);
+    return e == hipSuccess ? RT_OK : fail_hip(c, e, "pack launch");
 }
 
 // Path choice unless a flag says otherwise. Measured at 2048^2 (scratch sweep, depth 3, 4 lights): the small-scene
@@ -2010,9 +2045,14 @@ int rt_render_device(rt_context* c, void* d_out, void* hip_stream) {
 // the last quarter's render. Only for frames of the large-scene path with >= 4 M rays that the caller has not sharded himself;
 // RT_RENDER_PASSES=1 switches it off, RT_RENDER_SPLIT="a,b,.." chooses another split. The pixels are the one-pass frame's, bit for
 // bit (a shard is the same arithmetic on a subset of the rays).
-static int render_in_passes(rt_context* c, const float** out) {
-    // the split: spans of consecutive ranks of a world of their sum ("3,1": three tiles of every four, then the fourth)
-    uint32_t spans[kMaxPasses] = {3, 1, 0, 0}, K = 2, world = 0;
+// Float and 8-bit frames share it: `format` 0 is rt_render's float frame (elements of elem_bytes(c), straight from d_out to h_out);
+// an rt_pixel_format adds the step after a pass's render - pack that pass's pixels into d_pack on the render stream - and
+// what then travels is bytes, from d_pack to h_pack. The tile arithmetic is the same with another element size.
+static int render_in_passes(rt_context* c, int format, const void** out) {
+    // the split: spans of consecutive ranks of a world of their sum ("3,1": three tiles of every four, then the fourth). A byte
+    // frame's copy is a quarter as long, so a smaller last pass pays: "7,1" (cfg4, RGBA8: 12.55 ms against 12.80 for "3,1", 13.22
+    // for "1,1", 13.11 in one pass - profiles/packed_output_timing.json)
+    uint32_t spans[kMaxPasses] = {format ? 7u : 3u, 1, 0, 0}, K = 2, world = 0;
     if (const char* env = std::getenv("RT_RENDER_SPLIT")) {
         K = 0;
         for (const char* q = env; *q && K < kMaxPasses;) {
@@ -2027,27 +2067,20 @@ static int render_in_passes(rt_context* c, const float** out) {
     const uint64_t n_rays = c->n_rays;
     const uint64_t tile_rays = (c->pinhole && c->width) ? 16ull * c->width : 65536ull;
     const uint64_t tiles = (n_rays + tile_rays - 1) / tile_rays;
-    const size_t elem = elem_bytes(c), tile_bytes = (size_t)tile_rays * elem;
+    const size_t render_elem = elem_bytes(c);                             // what a kernel writes per work-item
+    const size_t elem = format ? packed_bytes(format) : render_elem;     // what travels to the host per work-item
+    const size_t tile_bytes = (size_t)tile_rays * elem;
     const size_t frame_bytes = (size_t)tiles * tile_bytes;  // whole tiles: the ragged last one is padded behind the frame's end
-    if (frame_bytes > c->h_out_bytes) {
-        if (c->h_out) (void)hipHostFree(c->h_out);
-        c->h_out = nullptr;
-        c->h_out_bytes = 0;
-        RT_HIP(c, hipHostMalloc(&c->h_out, frame_bytes, hipHostMallocDefault));
-        c->h_out_bytes = frame_bytes;
-    }
-    if (frame_bytes > c->d_out_bytes) {  // the passes' outputs one behind the other
-        if (c->d_out) (void)hipFree(c->d_out);
-        c->d_out = nullptr;
-        c->d_out_bytes = 0;
-        RT_HIP(c, hipMalloc(&c->d_out, frame_bytes));
-        c->d_out_bytes = frame_bytes;
-    }
+    int rc = grow_buffer(c, format ? c->h_pack : c->h_out, format ? c->h_pack_bytes : c->h_out_bytes, frame_bytes, true);
+    if (rc == RT_OK) rc = grow_buffer(c, c->d_out, c->d_out_bytes, (size_t)tiles * tile_rays * render_elem, false);  // the passes' outputs one behind the other
+    if (rc == RT_OK && format) rc = grow_buffer(c, c->d_pack, c->d_pack_bytes, frame_bytes, false);
+    if (rc != RT_OK) return rc;
+    char* const d_frame = static_cast<char*>(format ? c->d_pack : c->d_out);  // what the copies read
+    char* const h_frame = static_cast<char*>(format ? c->h_pack : c->h_out);
     if (!c->copy_stream) RT_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     for (uint32_t k = 0; k < K; ++k)
         if (!c->ev_pass[k]) RT_HIP(c, hipEventCreateWithFlags(&c->ev_pass[k], hipEventDisableTiming));
-    int rc = RT_OK;
-    size_t at = 0;        // this pass's output within d_out
+    uint64_t at = 0;      // this pass's first work-item within the device frame(s)
     uint32_t rank = 0;    // its first rank
     const uint64_t groups = tiles / world, rest = tiles % world;
     for (uint32_t k = 0; k < K && rc == RT_OK; rank += spans[k], ++k) {
@@ -2056,15 +2089,17 @@ static int render_in_passes(rt_context* c, const float** out) {
         c->world = world;
         c->span = spans[k];
         c->n_local = local_count(n_rays, tile_rays, rank, world, spans[k]);
-        char* buf = static_cast<char*>(c->d_out) + at;
+        char* const rendered = static_cast<char*>(c->d_out) + (size_t)at * render_elem;
+        char* buf = d_frame + (size_t)at * elem;
         const size_t run_bytes = (size_t)spans[k] * tile_bytes;
-        at += (size_t)c->n_local * elem;
+        at += c->n_local;
         if (c->n_local == 0) continue;
-        rc = do_launch(c, buf, c->stream, false);
+        rc = do_launch(c, rendered, c->stream, false);
+        if (rc == RT_OK && format) rc = pack_on(c, rendered, c->n_local, format, buf, c->stream);
         if (rc != RT_OK) break;
         hipError_t e = hipEventRecord(c->ev_pass[k], c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pass[k], 0);
-        char* dst = static_cast<char*>(c->h_out) + (size_t)rank * tile_bytes;
+        char* dst = h_frame + (size_t)rank * tile_bytes;
         if (e == hipSuccess && groups)  // run j of this pass is tiles j * world + rank ... of the frame
             e = hipMemcpy2DAsync(dst, (size_t)world * tile_bytes, buf, run_bytes, run_bytes, (size_t)groups, hipMemcpyDeviceToHost, c->copy_stream);
         if (e == hipSuccess && rest > rank)  // the short run of the frame's last, incomplete group of tiles
@@ -2082,19 +2117,26 @@ static int render_in_passes(rt_context* c, const float** out) {
     if (rc != RT_OK) return rc;
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail_hip(c, e, "hipStreamSynchronize");
-    *out = static_cast<const float*>(c->h_out);
+    *out = h_frame;
     return RT_OK;
+}
+
+// the conditions that send a synchronous render through render_in_passes (float and 8-bit frames alike)
+static bool wants_passes(const rt_context* c) {
+    const char* env = std::getenv("RT_RENDER_PASSES");  // "1": one pass whatever the frame; "2": two passes whatever its size (tests)
+    const bool off = env && env[0] == '1', forced = env && env[0] == '2';
+    return !off && c->world <= 1 && (forced || c->n_rays >= (1ull << 22)) && c->n_rays > 0 && c->n_local == c->n_rays && use_wavefront(c) &&
+           (c->pinhole || c->have_rays) && !c->aux_t && !c->aux_index;  // (aux buffers are indexed by work-item of ONE whole-frame launch)
 }
 
 int rt_render(rt_context* c, const float** out) {
     if (!c || !out) return RT_ERR_INVALID_ARGUMENT;
     RT_DEVICE(c);
-    {
-        const char* env = std::getenv("RT_RENDER_PASSES");  // "1": one pass whatever the frame; "2": two passes whatever its size (tests)
-        const bool off = env && env[0] == '1', forced = env && env[0] == '2';
-        if (!off && c->world <= 1 && (forced || c->n_rays >= (1ull << 22)) && c->n_rays > 0 && c->n_local == c->n_rays && use_wavefront(c) &&
-            (c->pinhole || c->have_rays) && !c->aux_t && !c->aux_index)  // (aux buffers are indexed by work-item of ONE whole-frame launch)
-            return render_in_passes(c, out);
+    if (wants_passes(c)) {
+        const void* frame = nullptr;
+        const int rc = render_in_passes(c, 0, &frame);
+        if (rc == RT_OK) *out = static_cast<const float*>(frame);
+        return rc;
     }
     int rc = ensure_out(c);
     if (rc) return rc;
@@ -2106,6 +2148,66 @@ int rt_render(rt_context* c, const float** out) {
     if (bytes) RT_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));  // Render() is synchronous (OpenCLRaytracer.cpp:94)
     *out = static_cast<const float*>(c->h_out);
+    return RT_OK;
+}
+
+size_t rt_packed_pixel_bytes(int format) { return packed_bytes(format); }
+
+int rt_pack_device(rt_context* c, const void* d_rgba_f32, uint64_t n_pixels, int format, void* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (!packed_bytes(format)) return fail(c, RT_ERR_INVALID_ARGUMENT, "unknown pixel format (RT_PIXEL_RGBA8 = 1, RT_PIXEL_RGB8 = 2)");
+    if (n_pixels == 0) return RT_OK;
+    if (!d_rgba_f32 || !d_out) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_pack_device: NULL frame");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rgba_f32) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the float4 frame must be 16-byte aligned");
+    RT_DEVICE(c);
+    int lane_pixels = 0;  // the measured choice (rt_pack.hip)
+    if (const char* env = std::getenv("RT_PACK_LANE_PIXELS")) lane_pixels = env[0] == '1' ? 1 : (env[0] == '4' ? 4 : 0);  // measurement knob (tools/ab/packed_timing.py)
+    const hipError_t e = rt::launch_pack(static_cast<const float4*>(d_rgba_f32), n_pixels, format, d_out, static_cast<hipStream_t>(hip_stream), lane_pixels);
+    return e == hipSuccess ? RT_OK : fail_hip(c, e, "pack launch");
+}
+
+int rt_render_device_packed(rt_context* c, int format, void* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    int rc = check_packed(c, format);
+    if (rc) return rc;
+    if (c->n_local == 0) return RT_OK;
+    if (!d_out) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out must be 4-byte aligned");
+    RT_DEVICE(c);
+    rc = grow_buffer(c, c->d_scratch, c->d_scratch_bytes, (size_t)c->n_local * elem_bytes(c), false);
+    if (rc) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);  // NULL: the legacy default stream, as for rt_render_device
+    rc = do_launch(c, c->d_scratch, stream, false);
+    if (rc) return rc;
+    return pack_on(c, c->d_scratch, c->n_local, format, d_out, stream);
+}
+
+int rt_render_packed(rt_context* c, int format, const uint8_t** out) {
+    if (!c || !out) return RT_ERR_INVALID_ARGUMENT;
+    int rc = check_packed(c, format);
+    if (rc) return rc;
+    RT_DEVICE(c);
+    if (wants_passes(c)) {
+        const void* frame = nullptr;
+        rc = render_in_passes(c, format, &frame);
+        if (rc == RT_OK) *out = static_cast<const uint8_t*>(frame);
+        return rc;
+    }
+    const size_t bytes = (size_t)c->n_local * packed_bytes(format);
+    rc = ensure_out(c);  // the float frame: the context's own device framebuffer
+    if (rc == RT_OK) rc = grow_buffer(c, c->d_pack, c->d_pack_bytes, bytes, false);
+    if (rc == RT_OK) rc = grow_buffer(c, c->h_pack, c->h_pack_bytes, bytes, true);
+    if (rc) return rc;
+    rc = do_launch(c, c->d_out, c->stream, false);
+    if (rc) return rc;
+    if (bytes) {
+        rc = pack_on(c, c->d_out, c->n_local, format, c->d_pack, c->stream);
+        if (rc) return rc;
+        RT_HIP(c, hipMemcpyAsync(c->h_pack, c->d_pack, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    RT_HIP(c, hipStreamSynchronize(c->stream));  // synchronous, like rt_render
+    *out = static_cast<const uint8_t*>(c->h_pack);
     return RT_OK;
 }
 
@@ -2233,6 +2335,9 @@ void rt_destroy(rt_context* c) {
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->h_out) (void)hipHostFree(c->h_out);
+    if (c->d_pack) (void)hipFree(c->d_pack);
+    if (c->h_pack) (void)hipHostFree(c->h_pack);
+    if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);
     if (c->d_counters) (void)hipFree(c->d_counters);
@@ -2254,6 +2359,8 @@ struct rt_multi {
     uint64_t n_rays = 0, tile_rays = 0, tiles = 0;
     size_t elem = 16;
     void* h_frame = nullptr;         // rt_render_multi's frame: pinned, portable host memory (whole tiles) every device copies its tiles into
+    std::vector<void*> d_bytes;      // per context: its tiles as bytes (rt_render_multi_packed; room for RGBA8), on its own device
+    void* h_bytes = nullptr;         // rt_render_multi_packed's frame: pinned, portable, whole tiles of RGBA8 (RGB8 uses 3/4 of it)
     std::string error;
     // One host thread per further shard, alive from rt_create_multi to rt_destroy_multi (round 3 created and joined n - 1
     // threads per frame). A frame = one job: every worker renders its shard and puts its tiles in place, the calling thread
@@ -2266,6 +2373,7 @@ struct rt_multi {
     bool quit = false;
     void* job_target = nullptr;      // where the tiles go: a frame on devices[0], or the pinned host frame
     bool job_to_host = false;
+    int job_format = 0;              // 0: float elements; an rt_pixel_format: every shard packs its tiles before they travel
     std::vector<int> rcs;
     std::vector<std::string> errs;
 };
@@ -2283,7 +2391,7 @@ int multi_fail(rt_multi* m, int code, const std::string& msg) {
 // one shard: render on the context's own stream, then put its tiles where they belong - in the frame on devices[0]
 // (rt_render_multi_device) or STRAIGHT in the pinned host frame (rt_render_multi: the reference's blocking read-back,
 // OpenCLRaytracer.cpp:94, over every GPU's own PCIe link at once instead of a hop to devices[0] and one link for the lot)
-int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, std::string& err) {
+int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, int format, std::string& err) {
     rt_context* c = m->ctx[r];
     DeviceGuard guard(c->device);
     if (!guard.ok) { err = std::string("hipSetDevice: ") + hipGetErrorString(guard.err); return RT_ERR_HIP; }
@@ -2291,18 +2399,28 @@ int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, std::
     if (rc != RT_OK) { err = c->error; return rc; }
     const uint32_t n = (uint32_t)m->ctx.size();
     const uint64_t mine = m->tiles / n + ((m->tiles % n) > r ? 1 : 0);
-    const size_t tile_bytes = (size_t)m->tile_rays * m->elem;
+    const size_t tile_bytes = (size_t)m->tile_rays * (format ? packed_bytes(format) : m->elem);
     hipError_t e = hipSuccess;
+    void* local = m->d_local[r];  // what travels: the float tiles, or their bytes
+    if (format) {
+        if (!m->d_bytes[r]) {
+            e = hipMalloc(&m->d_bytes[r], c->n_local ? (size_t)c->n_local * 4 : 16);
+            if (e != hipSuccess) { err = std::string("byte tiles: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP; }
+        }
+        local = m->d_bytes[r];
+        rc = rt_pack_device(c, m->d_local[r], c->n_local, format, local, c->stream);
+        if (rc != RT_OK) { err = c->error; return rc; }
+    }
     if (mine) {
         // tile j of this shard is tile j * n + r of the frame: one strided copy
         char* dst = static_cast<char*>(frame) + (size_t)r * tile_bytes;
         if (to_host) {
-            e = hipMemcpy2DAsync(dst, (size_t)n * tile_bytes, m->d_local[r], tile_bytes, tile_bytes, (size_t)mine, hipMemcpyDeviceToHost, c->stream);
+            e = hipMemcpy2DAsync(dst, (size_t)n * tile_bytes, local, tile_bytes, tile_bytes, (size_t)mine, hipMemcpyDeviceToHost, c->stream);
         } else if (c->device == m->devices[0] || m->peer_ok[r]) {
-            e = hipMemcpy2DAsync(dst, (size_t)n * tile_bytes, m->d_local[r], tile_bytes, tile_bytes, (size_t)mine, hipMemcpyDeviceToDevice, c->stream);
+            e = hipMemcpy2DAsync(dst, (size_t)n * tile_bytes, local, tile_bytes, tile_bytes, (size_t)mine, hipMemcpyDeviceToDevice, c->stream);
         } else {
             for (uint64_t j = 0; j < mine && e == hipSuccess; ++j)
-                e = hipMemcpyPeerAsync(dst + (size_t)j * n * tile_bytes, m->devices[0], static_cast<char*>(m->d_local[r]) + (size_t)j * tile_bytes,
+                e = hipMemcpyPeerAsync(dst + (size_t)j * n * tile_bytes, m->devices[0], static_cast<char*>(local) + (size_t)j * tile_bytes,
                                        c->device, tile_bytes, c->stream);
         }
     }
@@ -2316,6 +2434,7 @@ void multi_worker(rt_multi* m, uint32_t r) {
     for (;;) {
         void* target;
         bool to_host;
+        int format;
         {
             std::unique_lock<std::mutex> lk(m->mu);
             m->cv_go.wait(lk, [&] { return m->quit || m->generation != seen; });
@@ -2323,9 +2442,10 @@ void multi_worker(rt_multi* m, uint32_t r) {
             seen = m->generation;
             target = m->job_target;
             to_host = m->job_to_host;
+            format = m->job_format;
         }
         std::string err;
-        const int rc = multi_render_shard(m, r, target, to_host, err);
+        const int rc = multi_render_shard(m, r, target, to_host, format, err);
         {
             std::lock_guard<std::mutex> lk(m->mu);
             m->rcs[r] = rc;
@@ -2336,18 +2456,19 @@ void multi_worker(rt_multi* m, uint32_t r) {
 }
 
 // every shard renders and places its tiles; returns when the frame is complete
-int multi_run_frame(rt_multi* m, void* target, bool to_host) {
+int multi_run_frame(rt_multi* m, void* target, bool to_host, int format = 0) {
     const uint32_t n = (uint32_t)m->ctx.size();
     {
         std::lock_guard<std::mutex> lk(m->mu);
         m->job_target = target;
         m->job_to_host = to_host;
+        m->job_format = format;
         m->pending = (uint32_t)m->workers.size();
         m->generation += 1;
     }
     m->cv_go.notify_all();
     std::string err0;
-    const int rc0 = multi_render_shard(m, 0, target, to_host, err0);
+    const int rc0 = multi_render_shard(m, 0, target, to_host, format, err0);
     {
         std::unique_lock<std::mutex> lk(m->mu);
         m->cv_done.wait(lk, [&] { return m->pending == 0; });
@@ -2378,11 +2499,16 @@ void rt_destroy_multi(rt_multi* m) {
             DeviceGuard guard(m->ctx[r]->device);
             (void)hipFree(m->d_local[r]);
         }
+        if (m->ctx[r] && r < m->d_bytes.size() && m->d_bytes[r]) {
+            DeviceGuard guard(m->ctx[r]->device);
+            (void)hipFree(m->d_bytes[r]);
+        }
         rt_destroy(m->ctx[r]);
     }
     if (!m->devices.empty()) {
         DeviceGuard guard(m->devices[0]);
         if (m->h_frame) (void)hipHostFree(m->h_frame);
+        if (m->h_bytes) (void)hipHostFree(m->h_bytes);
     }
     delete m;
 }
@@ -2399,6 +2525,7 @@ int rt_create_multi(rt_multi** out, const void* objs, uint32_t n_objs, const voi
     m->devices.assign(devices, devices + n_devices);
     m->ctx.assign(n_devices, nullptr);
     m->d_local.assign(n_devices, nullptr);
+    m->d_bytes.assign(n_devices, nullptr);
     m->peer_ok.assign(n_devices, 0);
     m->n_rays = n_rays;
     m->elem = kernel == RT_KERNEL_HITTEST ? sizeof(float) : 4 * sizeof(float);
@@ -2490,6 +2617,24 @@ int rt_render_multi(rt_multi* m, const float** out) {
     const int rc = multi_run_frame(m, m->h_frame, true);  // Render() is synchronous (OpenCLRaytracer.cpp:94): every shard has waited for its copy
     if (rc != RT_OK) return rc;
     *out = static_cast<const float*>(m->h_frame);
+    return RT_OK;
+}
+
+int rt_render_multi_packed(rt_multi* m, int format, const uint8_t** out) {
+    if (!m || !out) return RT_ERR_INVALID_ARGUMENT;
+    if (!packed_bytes(format)) return multi_fail(m, RT_ERR_INVALID_ARGUMENT, "unknown pixel format (RT_PIXEL_RGBA8 = 1, RT_PIXEL_RGB8 = 2)");
+    if (m->elem != 4 * sizeof(float))
+        return multi_fail(m, RT_ERR_STATE, "RT_KERNEL_HITTEST contexts render one float (the nearest t) per ray, not a colour: there is no 8-bit frame of it");
+    if (!m->h_bytes) {  // whole tiles, pinned and portable like rt_render_multi's float frame
+        DeviceGuard guard(m->devices[0]);
+        if (!guard.ok) return multi_fail(m, RT_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard.err));
+        const size_t frame_bytes = (size_t)rt_multi_frame_elems(m) * 4;
+        const hipError_t e = hipHostMalloc(&m->h_bytes, frame_bytes ? frame_bytes : 16, hipHostMallocPortable);
+        if (e != hipSuccess) return multi_fail(m, e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP, std::string("host byte frame: ") + hipGetErrorString(e));
+    }
+    const int rc = multi_run_frame(m, m->h_bytes, true, format);
+    if (rc != RT_OK) return rc;
+    *out = static_cast<const uint8_t*>(m->h_bytes);
     return RT_OK;
 }
 

@@ -56,6 +56,8 @@ class FrameGather:
         self.placed = [None] * n_slots   # dst: event after which frames[slot] is complete and locals / stagings[slot] are free again
         self.keep = [None] * n_slots     # (rehearsal over gloo: the host copy a send is reading)
         self.debug_poison = False        # tests: overwrite every buffer with NaN before it is reused, so that stale data cannot pass for a frame
+        # (an integer buffer has no NaN: 0x5a in every byte - a level no rendered RGBA8 / RGB8 frame is made of throughout)
+        self.poison = float("nan") if torch.empty((), dtype=dtype).is_floating_point() else 0x5A
         self.render_stream = torch.cuda.Stream(device) if self.pipeline else None
         self.place_stream = torch.cuda.Stream(device) if (self.pipeline and self.rank == dst) else None
 
@@ -102,9 +104,9 @@ class FrameGather:
             if self.placed[slot] is not None:
                 self.render_stream.wait_event(self.placed[slot])
             if self.debug_poison:
-                self.locals[slot].fill_(float("nan"))
+                self.locals[slot].fill_(self.poison)
                 for buf in self.stagings[slot].values():
-                    buf.fill_(float("nan"))
+                    buf.fill_(self.poison)
         return self.render_stream
 
     def exchange_pipelined(self):
@@ -129,7 +131,7 @@ class FrameGather:
         self.place_stream.wait_stream(self.render_stream)   # own tiles rendered
         with torch.cuda.stream(self.place_stream):
             if self.debug_poison:
-                frame.fill_(float("nan"))
+                frame.fill_(self.poison)
             self._place(local, self.dst, frame)
             for req in reqs:
                 req.wait()
@@ -177,12 +179,19 @@ class FrameGather:
 
 
 class ShardedHIPRaytracer:
-    """IRaytracer-shaped front for N ranks: Render() returns the full frame on rank 0 (None elsewhere)."""
+    """IRaytracer-shaped front for N ranks: Render() returns the full frame on rank 0 (None elsewhere).
+
+    output="float" (default): the reference's float4 frame. "rgba8" / "rgb8": every rank quantises its own tiles on its GPU
+    (HIPRaytracer.render_device_packed) and the exchange moves uint8 - a quarter / 3/16 of the bytes per peer; the frame on
+    rank 0 is (n_rays, 4 | 3) uint8."""
 
     def __init__(self, objects, lights, rays, MAX_BOUNCES, *, camera=None, kernel="shade_and_reflect",
                  tile_rows: int = 16, width: int | None = None, device_index: int = 0, group=None,
-                 pipeline: bool = False, **kw):
+                 pipeline: bool = False, output: str = "float", **kw):
         from .hip_raytracer import HIPRaytracer
+        if output not in ("float", "rgba8", "rgb8"):
+            raise ValueError('output is "float", "rgba8" or "rgb8"')
+        self.output = output
         self.rt = HIPRaytracer(objects, lights, rays, MAX_BOUNCES, kernel=kernel, device=device_index,
                                camera=camera, **kw)
         self.n_rays = self.rt.n_rays
@@ -194,13 +203,22 @@ class ShardedHIPRaytracer:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.rt.set_shard(self.tile_rays, rank, world)
         self.device = torch.device("cuda", device_index)
-        self.gatherer = FrameGather(self.n_rays, self.tile_rays, self.rt.elem_floats, self.device, group=group, pipeline=pipeline)
+        if output == "float":
+            self.gatherer = FrameGather(self.n_rays, self.tile_rays, self.rt.elem_floats, self.device, group=group, pipeline=pipeline)
+        else:
+            self.gatherer = FrameGather(self.n_rays, self.tile_rays, 4 if output == "rgba8" else 3, self.device, dtype=torch.uint8,
+                                        group=group, pipeline=pipeline)
         assert self.gatherer.local_rays == self.rt.local_rays  # exact share: nothing is padded to the largest one
 
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.rt.render_device(self.gatherer.local.data_ptr(), stream)
+        self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _render_into(self, local, stream_ptr: int):
+        if self.output == "float":
+            self.rt.render_device(local.data_ptr(), stream_ptr)
+        else:
+            self.rt.render_device_packed(local.data_ptr(), self.output, stream_ptr)
 
     def Render(self):
         g = self.gatherer
@@ -211,7 +229,7 @@ class ShardedHIPRaytracer:
         # still travelling to rank 0 and being put in place (FrameGather.exchange_pipelined). The returned frame is valid in
         # the caller's stream order and is overwritten by the second-next Render().
         stream = g.begin_frame()
-        self.rt.render_device(g.local.data_ptr(), stream.cuda_stream)
+        self._render_into(g.local, stream.cuda_stream)
         return g.exchange_pipelined()
 
     def render_synchronous(self):

@@ -26,6 +26,8 @@ KERNEL_HITTEST, KERNEL_SHADE, KERNEL_SHADE_AND_REFLECT = 0, 1, 2
 KERNELS = {"hittest": 0, "shade": 1, "shade_and_reflect": 2}
 FLAG_UNFUSED, FLAG_LITERAL, FLAG_NO_RAYGEN, FLAG_WAVEFRONT, FLAG_MONOLITHIC, FLAG_NO_GRID, FLAG_FAST_PHONG = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 FLAG_DEVICE_OPENCL = 0x80
+PIXEL_RGBA8, PIXEL_RGB8 = 1, 2
+PIXEL_FORMATS = {"rgba8": PIXEL_RGBA8, "rgb8": PIXEL_RGB8}
 
 EXPORTS = [
     "rt_abi_version", "rt_create", "rt_set_camera", "rt_set_shard", "rt_local_rays", "rt_render",
@@ -33,6 +35,7 @@ EXPORTS = [
     "rt_timing_reset", "rt_timing_summary", "rt_destroy", "rt_last_error", "rt_get_setup_times",
     "rt_create_multi", "rt_set_camera_multi", "rt_multi_frame_elems", "rt_render_multi", "rt_render_multi_device",
     "rt_multi_context", "rt_multi_last_error", "rt_destroy_multi", "rt_count_rays_multi", "rt_get_stats_multi",
+    "rt_packed_pixel_bytes", "rt_pack_device", "rt_render_device_packed", "rt_render_packed", "rt_render_multi_packed",
 ]
 
 
@@ -125,9 +128,38 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
     lib.rt_multi_last_error.argtypes = [vp]
     lib.rt_destroy_multi.restype = None
     lib.rt_destroy_multi.argtypes = [vp]
+    u8pp = ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))
+    if hasattr(lib, "rt_packed_pixel_bytes"):  # an older build named by RT_LIB_OVERRIDE (A/B runs) has no 8-bit entry points; calling one raises
+        lib.rt_packed_pixel_bytes.restype = ctypes.c_size_t
+        lib.rt_packed_pixel_bytes.argtypes = [i32]
+        lib.rt_pack_device.restype = i32
+        lib.rt_pack_device.argtypes = [vp, vp, u64, i32, vp, vp]
+        lib.rt_render_device_packed.restype = i32
+        lib.rt_render_device_packed.argtypes = [vp, i32, vp, vp]
+        lib.rt_render_packed.restype = i32
+        lib.rt_render_packed.argtypes = [vp, i32, u8pp]
+        lib.rt_render_multi_packed.restype = i32
+        lib.rt_render_multi_packed.argtypes = [vp, i32, u8pp]
     if path is None:
         _lib = lib
     return lib
+
+
+def pixel_format(format) -> int:
+    """'rgba8' / 'rgb8' (or the rt_pixel_format number itself) -> rt_pixel_format. Unknown numbers pass: the library refuses them."""
+    if isinstance(format, str):
+        try:
+            return PIXEL_FORMATS[format.lower()]
+        except KeyError:
+            raise ValueError(f"unknown pixel format {format!r}: one of {sorted(PIXEL_FORMATS)}") from None
+    return int(format)
+
+
+def _byte_frame(lib, out, n: int, fmt: int) -> np.ndarray:
+    channels = int(lib.rt_packed_pixel_bytes(fmt))
+    if n == 0:
+        return np.zeros((0, channels), dtype=np.uint8)
+    return np.ctypeslib.as_array(out, shape=(n * channels,)).copy().reshape(n, channels)
 
 
 def _ptr(a: np.ndarray | None):
@@ -227,6 +259,38 @@ class HIPRaytracer:
             dt = (time.perf_counter() - t0) * 1e3
             best = dt if best is None else min(best, dt)
         return best
+
+    # -- 8-bit frames (hip_raytracer.h: quantised on the device, a quarter / 3/16 of the bytes cross the bus) -----
+    def render_packed(self, format="rgba8") -> np.ndarray:
+        """Synchronous render of bytes: a copy of the context-owned pinned byte frame, (local_rays, 4 | 3) uint8, the byte of
+        every channel as ppm.quantise_bytes defines it."""
+        fmt = pixel_format(format)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        self._check(self._lib.rt_render_packed(self._ctx, fmt, ctypes.byref(out)))
+        return _byte_frame(self._lib, out, self.local_rays, fmt)
+
+    def render_packed_host_ms(self, format="rgba8", frames: int = 3) -> float:
+        """render_host_ms for the 8-bit frame: wall time of rt_render_packed without this wrapper's numpy copy, best of `frames`."""
+        import time
+        fmt = pixel_format(format)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        best = None
+        for _ in range(max(1, frames)):
+            t0 = time.perf_counter()
+            self._check(self._lib.rt_render_packed(self._ctx, fmt, ctypes.byref(out)))
+            dt = (time.perf_counter() - t0) * 1e3
+            best = dt if best is None else min(best, dt)
+        return best
+
+    def render_device_packed(self, d_out_ptr: int, format="rgba8", stream_ptr: int = 0):
+        """Asynchronous render of bytes into device memory (local_rays * 4 | 3 bytes, 4-byte aligned) on a HIP stream."""
+        self._check(self._lib.rt_render_device_packed(self._ctx, pixel_format(format), ctypes.c_void_p(d_out_ptr),
+                                                      ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def pack_device(self, d_rgba_ptr: int, n_pixels: int, d_out_ptr: int, format="rgba8", stream_ptr: int = 0):
+        """Convert n_pixels float4 pixels in device memory to bytes in device memory, asynchronously on a HIP stream."""
+        self._check(self._lib.rt_pack_device(self._ctx, ctypes.c_void_p(d_rgba_ptr), int(n_pixels), pixel_format(format),
+                                             ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def setup_times(self) -> dict:
         """One-time host-side work outside every render timer (rt_setup_times_t), milliseconds."""
@@ -328,6 +392,26 @@ class MultiHIPRaytracer:
             return np.zeros((0, 4) if self.elem_floats == 4 else (0,), dtype=np.float32)
         arr = np.ctypeslib.as_array(out, shape=(self.n_rays * self.elem_floats,)).copy()
         return arr.reshape(self.n_rays, 4) if self.elem_floats == 4 else arr
+
+    def render_packed(self, format="rgba8") -> np.ndarray:
+        """The whole frame as bytes, (n_rays, 4 | 3) uint8: every device packs its own tiles and copies bytes."""
+        fmt = pixel_format(format)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        self._check(self._lib.rt_render_multi_packed(self._m, fmt, ctypes.byref(out)))
+        return _byte_frame(self._lib, out, self.n_rays, fmt)
+
+    def render_packed_host_ms(self, format="rgba8", repeats: int = 3) -> float:
+        """Wall clock of the synchronous render_packed without the numpy copy, best of `repeats`."""
+        import time
+        fmt = pixel_format(format)
+        best = None
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        for _ in range(max(1, repeats)):
+            t0 = time.perf_counter()
+            self._check(self._lib.rt_render_multi_packed(self._m, fmt, ctypes.byref(out)))
+            dt = (time.perf_counter() - t0) * 1e3
+            best = dt if best is None else min(best, dt)
+        return best
 
     def count_rays(self) -> RTStats:
         """Untimed counted render on every shard; the counters summed over the shards (the whole frame's)."""

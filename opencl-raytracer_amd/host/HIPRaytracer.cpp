@@ -86,6 +86,17 @@ cl_float4* HIPRaytracer::Render() {
     return reinterpret_cast<cl_float4*>(const_cast<float*>(out));
 }
 
+const uint8_t* HIPRaytracer::RenderPacked(rt_pixel_format format) {
+    const uint8_t* out = nullptr;
+    if (multi) {
+        if (rt_render_multi_packed(multi, format, &out) != RT_OK)
+            throw std::runtime_error(std::string("HIPRaytracer::RenderPacked: ") + rt_multi_last_error(multi));
+        return out;
+    }
+    if (rt_render_packed(ctx, format, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::RenderPacked: ") + rt_last_error(ctx));
+    return out;
+}
+
 rt_stats_t HIPRaytracer::Stats() {
     rt_stats_t s;
     if (multi) {  // several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures

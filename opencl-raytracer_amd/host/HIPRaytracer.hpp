@@ -4,6 +4,7 @@
 // The host side sees only the C ABI (include/hip_raytracer.h); kernels live in libhip_raytracer.so.
 #pragma once
 
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -32,6 +33,11 @@ public:
     // Inherited via IRaytracer: synchronous; the returned buffer is owned by this object and overwritten by
     // the next call (OpenCLRaytracer.cpp:94,104).
     cl_float4* Render() override;
+
+    // The frame as 8-bit pixels (hip_raytracer.h, "8-bit frames"): quantised on the GPU(s), a quarter (RGBA8) or 3/16 (RGB8) of
+    // Render()'s bytes cross the bus. Synchronous; width * height pixels of 4 or 3 bytes in work-item order, in a buffer owned
+    // by the library and overwritten by the next RenderPacked(). Works for the one-GPU and the several-GPU object.
+    const uint8_t* RenderPacked(rt_pixel_format format = RT_PIXEL_RGBA8);
 
     rt_stats_t Stats();
     rt_context* Context() { return ctx; }

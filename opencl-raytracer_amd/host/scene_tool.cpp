@@ -3,6 +3,9 @@
 //   scene_tool render  <scene.txt> <W> <H> <D> <out.ppm> [z-bits|-] [hip|cpu]
 //                       parse, build rays, render, write a PPM. Backend: `hip` (default) = HIPRaytracer on the GPU;
 //                       `cpu` = CPURaytracer, no GPU (the reference's main() has both lines, OpenCL-Raytracer.cpp:74-75)
+//   scene_tool render8 <scene.txt> <W> <H> <D> <out.ppm> [z-bits|-] [p3|p6] [rgba8|rgb8]
+//                       the same frame as 8-bit pixels quantised on the GPU (HIPRaytracer::RenderPacked), written from the
+//                       bytes: `p3` (default) the reference's ASCII file, `p6` the binary PPM
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,7 +44,7 @@ static void dump_records(const std::vector<ObjectData>& objects, const std::vect
 
 int main(int argc, char** argv) {
     try {
-        if (argc < 4) { std::fprintf(stderr, "usage: scene_tool records|render ...\n"); return 1; }
+        if (argc < 4) { std::fprintf(stderr, "usage: scene_tool records|render|render8 ...\n"); return 1; }
         std::vector<ObjectData> objects;
         std::vector<Light> lights;
         SceneLoader loader;
@@ -61,6 +64,17 @@ int main(int argc, char** argv) {
         for (int jj = 0; jj < height; ++jj)
             for (int ii = 0; ii < width; ++ii)
                 rays.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - width / 2.0f, (float)(height - jj) - height / 2.0f, z));
+        if (std::strcmp(argv[1], "render8") == 0) {
+            const bool p6 = argc > 8 && std::strcmp(argv[8], "p6") == 0;
+            const rt_pixel_format format = (argc > 9 && std::strcmp(argv[9], "rgb8") == 0) ? RT_PIXEL_RGB8 : RT_PIXEL_RGBA8;
+            HIPRaytracer raytracer8(objects, lights, rays, depth);
+            const uint8_t* bytes = raytracer8.RenderPacked(format);
+            const size_t stride = rt_packed_pixel_bytes(format);
+            if (p6) PPMExporter::ExportP6(argv[6], (size_t)width, (size_t)height, bytes, stride);
+            else PPMExporter::ExportP3(argv[6], (size_t)width, (size_t)height, bytes, stride);
+            std::printf("wrote %s\n", argv[6]);
+            return 0;
+        }
         std::unique_ptr<IRaytracer> raytracer;
         if (cpu) raytracer.reset(new CPURaytracer(objects, lights, rays, depth));
         else raytracer.reset(new HIPRaytracer(objects, lights, rays, depth));
