@@ -139,12 +139,25 @@ int rt_create(rt_context** ctx, const void* objs, uint32_t n_objs, const void* l
               const void* rays, uint64_t n_rays, uint32_t max_bounces, int kernel, int device, uint32_t flags);
 
 /* Primary rays = the reference's pinhole grid, generated in-kernel (bit-exact):
- * start (0,0,0,1), direction (i - W/2, (H - j) - H/2, z, 0) for work-item j*W + i. width*height must equal n_rays. */
+ * start (0,0,0,1), direction (i - W/2, (H - j) - H/2, z, 0) for work-item j*W + i. width*height must equal n_rays.
+ * Callable any number of times between renders, also on a context that has rendered: the NEXT render uses the new camera, and
+ * the frame is the one a context created directly with that camera renders, bit for bit - whatever was rendered before
+ * (tests/test_context_lifecycle_gpu.py). A camera replaces uploaded rays for good; there is no way back to the ray buffer.
+ * The ray-domain guard (RT_FLAG_LITERAL, above) follows the camera: one whose grid holds a direction of |d|^2 outside
+ * (1e-30, 1e30) - z = 0 with an even width and height, say - renders with the literal loops, and the next camera inside the
+ * domain takes the context back to the default path. A scene with triangles REFUSES such a camera
+ * (RT_ERR_INVALID_ARGUMENT: the literal loops do not know triangle records) and keeps rendering the previous one. The shard
+ * setting (rt_set_shard) survives a camera change unchanged. */
 int rt_set_camera(rt_context* ctx, uint32_t width, uint32_t height, float z);
 
 /* Multi-GPU partition: work-items are cut into tiles of `tile_rays` consecutive rays (a row-tile is
  * tile_rows*width rays); tile j belongs to rank j % world. After this call the context renders only its
- * own tiles, packed back to back in its output buffer (rt_local_rays() work-items). */
+ * own tiles, packed back to back in its output buffer (rt_local_rays() work-items); the ragged last tile of the frame is
+ * padded to a whole tile with background pixels (misses). world == 1 is the whole frame again.
+ * Callable any number of times between renders, also after renders with another shard (rt_local_rays() may grow or shrink; the
+ * context's buffers grow as needed and never shrink): the next render is the one a fresh context with that shard renders.
+ * The partition is expressed in RAYS, not rows: a later rt_set_camera with another width keeps tile_rays, so the tiles need
+ * not be whole rows any more (any tile_rays is valid; whole rows in multiples of 8 only render faster). */
 int rt_set_shard(rt_context* ctx, uint64_t tile_rays, uint32_t rank, uint32_t world);
 uint64_t rt_local_rays(const rt_context* ctx);
 
@@ -169,7 +182,11 @@ int rt_render(rt_context* ctx, const float** out);
 int rt_render_device(rt_context* ctx, void* d_out, void* hip_stream);
 
 /* Optional per-work-item primary-hit record of the NEXT render: t (float) and winning object index
- * (int32, -1 on a miss) into caller-provided DEVICE buffers of rt_local_rays() elements (either may be NULL). */
+ * (int32, -1 on a miss) into caller-provided DEVICE buffers of rt_local_rays() elements (either may be NULL).
+ * A miss is what the KERNEL takes for one, as rt_stats_t::hit_pixels counts it: a primary ray whose time is NaN (a direction of
+ * 0: the reference's loop ends with the last sphere / box and a NaN time) is a miss for RT_KERNEL_HITTEST and RT_KERNEL_SHADE
+ * (index -1; `t < MAX_FLOAT` fails, shade_kernel.cl:167) and a hit of that object for RT_KERNEL_SHADE_AND_REFLECT (`t ==
+ * MAX_FLOAT` fails, shade_and_reflect_kernel.cl:173). t is the loop's value in both cases (NaN). */
 int rt_set_aux_device(rt_context* ctx, void* d_hit_t, void* d_hit_index);
 /* Host-side convenience: render once and copy t / index to host arrays (either may be NULL). */
 int rt_render_aux(rt_context* ctx, float* hit_t, int32_t* hit_index);
@@ -264,6 +281,9 @@ typedef struct rt_multi rt_multi;
 int rt_create_multi(rt_multi** m, const void* objs, uint32_t n_objs, const void* lights, uint32_t n_lights,
                     const void* rays, uint64_t n_rays, uint32_t max_bounces, int kernel,
                     const int* devices, uint32_t n_devices, uint64_t tile_rays, uint32_t flags);
+/* rt_set_camera on every context, any number of times between renders. An rt_multi KEEPS ITS TILE SIZE: the tile_rays given to
+ * rt_create_multi (or derived there from the first pinhole width: 16 rows of it), in rays - after a camera of another width
+ * the tiles are no whole rows, the frame is the same. rt_multi_frame_elems() therefore never changes. */
 int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);

@@ -299,6 +299,11 @@ class HIPRaytracer:
         return t.as_dict()
 
     # -- extensions over the reference interface -----------------------------------------------
+    def set_camera(self, width: int, height: int, z: float):
+        """Re-aim a live context (rt_set_camera): the next render is the width x height pinhole grid at z; width * height must
+        equal n_rays. Uploaded rays are replaced for good; the shard setting stays."""
+        self._check(self._lib.rt_set_camera(self._ctx, int(width), int(height), float(z)))
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -384,6 +389,10 @@ class MultiHIPRaytracer:
     @property
     def frame_elems(self) -> int:
         return int(self._lib.rt_multi_frame_elems(self._m))
+
+    def set_camera(self, width: int, height: int, z: float):
+        """Re-aim every shard (rt_set_camera_multi). The tile size stays the one chosen at creation (in rays, not rows)."""
+        self._check(self._lib.rt_set_camera_multi(self._m, int(width), int(height), float(z)))
 
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()
