@@ -54,7 +54,10 @@ extern "C" {
  *      which is how a caller detects support.
  *      Later addition, same version: 8-bit frames - rt_pixel_format, rt_packed_pixel_bytes, rt_pack_device,
  *      rt_render_device_packed, rt_render_packed, rt_render_multi_packed. Additions only; a caller detects support by the
- *      symbol (dlsym of rt_packed_pixel_bytes). */
+ *      symbol (dlsym of rt_packed_pixel_bytes).
+ *      Later addition, same version: supersampled frames - rt_set_supersampling, rt_supersampling, rt_local_pixels,
+ *      rt_resolve_device, rt_set_supersampling_multi, rt_multi_frame_pixels. Additions only; a caller detects support by the
+ *      symbol (dlsym of rt_set_supersampling). */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -256,6 +259,53 @@ int rt_render_device_packed(rt_context* ctx, int format, void* d_out, void* hip_
  * so a smaller last pass leaves less of it behind the kernels). */
 int rt_render_packed(rt_context* ctx, int format, const uint8_t** out);
 
+/* ---- supersampled frames -----------------------------------------------------------------------------------------------------
+ * Anti-aliasing by a box filter ON THE DEVICE (csrc/rt_resolve.hip): the context renders its SAMPLE grid exactly as without it and
+ * delivers one PIXEL per s x s block of samples, so s^2 times fewer bytes cross the bus.
+ *
+ * Primary directions are not normalised - (i - W/2, (H - j) - H/2, z) - so the pinhole grid (s W, s H, s z) is a regular s x s
+ * lattice of sub-pixel rays inside every pixel of the (W, H, z) grid: sample (s i + a, s j + b) has direction
+ * s * (i - W/2 + a/s, (H - j) - H/2 - b/s, z). A supersampled W x H frame IS what the reference renders at s W x s H with s z,
+ * box-filtered s x s; every sample is a ray every existing path of this library already agrees on with the reference.
+ *
+ * Definition. A context whose camera is the pinhole grid (w, h, z) and whose factor is s (1, 2, 3 or 4; 1 = off) renders w x h
+ * samples and delivers (w/s) x (h/s) pixels. Pixel (i, j) (row-major, j outer), each of the four channels by itself, in fp32
+ * with every addition rounded, nothing contracted, ONE multiplication at the end:
+ *     acc = sample[(s j + 0) w + s i + 0]
+ *     for b in 0..s-1: for a in 0..s-1 (b outer, a inner, the first one skipped):  acc = acc + sample[(s j + b) w + s i + a]
+ *     pixel = acc * fl(1.0f / (float)(s s))
+ * NaN and infinities propagate as IEEE says. The ORDER is part of the definition (another one changes the bits of some pixels).
+ * w is filtered like a colour channel and comes out as exactly 1 for s = 2, 3, 4. The bytes of a supersampled frame are the
+ * table of "8-bit frames" applied to that float pixel (filter first, then quantise).
+ *
+ * The camera keeps describing the SAMPLE grid (width * height == n_rays stays rt_set_camera's rule): work-items, shards,
+ * rt_local_rays(), rt_stats_t, rt_count_rays and rt_timing_* keep counting samples, and the filter is launched behind the
+ * render's event pair (last_kernel_ms keeps meaning the render's kernels). With s > 1 rt_render, rt_render_device,
+ * rt_render_packed, rt_render_device_packed and the rt_render_multi* calls deliver rt_local_pixels() (rt_multi_frame_pixels())
+ * elements; the sample frame lives in context-owned device memory (allocated by the first such call, grown never shrunk, freed
+ * by rt_destroy; a context that never supersamples allocates nothing for it). Stream semantics are the entry point's.
+ *
+ * rt_set_supersampling is callable any number of times between renders, like rt_set_camera and rt_set_shard: the next frame
+ * depends on the current (camera, shard, factor) only. The three setters validate against each other, and a refused call leaves
+ * the context as it was. Refused with RT_ERR_INVALID_ARGUMENT: s outside 1..4; s > 1 without a pinhole camera; width % s or
+ * height % s != 0 (also a later rt_set_camera while s > 1); s > 1 with world > 1 and tile_rays % (s width) != 0 - a tile must
+ * hold whole pixel rows, then a shard's pixels are tile_rays / s^2 per tile, packed back to back, and the padding of a ragged
+ * last tile filters to the background (0,0,0,1) exactly - checked by whichever of the three setters comes last. Refused with
+ * RT_ERR_STATE: s > 1 on an RT_KERNEL_HITTEST context (a time is not a colour); s > 1 while aux buffers are set, and
+ * rt_set_aux_device (with a buffer) / rt_render_aux while s > 1 (aux is per work-item).
+ * A large frame goes through rt_render's passes (render -> filter (-> pack) -> strided copy of PIXELS per pass) over tiles of
+ * 16 sample rows (48 for s = 3), RT_RENDER_PASSES / RT_RENDER_SPLIT read as ever; the frame is the one-pass frame bit for bit. */
+int      rt_set_supersampling(rt_context* ctx, uint32_t s);
+uint32_t rt_supersampling(const rt_context* ctx);   /* 0 for NULL */
+uint64_t rt_local_pixels(const rt_context* ctx);    /* rt_local_rays() / s^2: what every render call delivers; 0 for NULL */
+/* The pass alone, like rt_pack_device: sample_rows rows of sample_width float4 samples in DEVICE memory (16-byte aligned) ->
+ * (sample_width / s) x (sample_rows / s) pixels at d_out, asynchronously on hip_stream (NULL = legacy default stream), on any
+ * context. format 0 = float4 pixels (d_out 16-byte aligned), RT_PIXEL_RGBA8 / RT_PIXEL_RGB8 = bytes (d_out 4-byte aligned), filter
+ * and quantisation fused. s = 1..4 (1: a copy, or rt_pack_device); sample_width and sample_rows multiples of s; nothing is written
+ * behind the last pixel; zero pixels: RT_OK, nothing launched. Anything else: RT_ERR_INVALID_ARGUMENT. */
+int      rt_resolve_device(rt_context* ctx, const void* d_samples, uint32_t sample_width, uint32_t sample_rows, uint32_t s,
+                           int format, void* d_out, void* hip_stream);
+
 void rt_destroy(rt_context* ctx);
 
 /* ---- several GPUs from one process ------------------------------------------------------------------------------------
@@ -291,6 +341,12 @@ int rt_render_multi_device(rt_multi* m, void* d_frame);
 /* rt_render_multi in bytes (8-bit frames, above): every shard packs its own tiles on its own device and stream, then ONE
  * strided device-to-host copy of bytes per shard into a pinned portable byte frame owned by `m` (n_rays pixels). */
 int rt_render_multi_packed(rt_multi* m, int format, const uint8_t** out);
+/* rt_set_supersampling on every context ("supersampled frames", above), all or none. The multi's fixed tile_rays must hold whole
+ * pixel rows: tile_rays % (s * width) == 0 (the derived default, 16 rows, is fine for s = 2 and 4 and refused for s = 3: such a
+ * caller passes tile_rays to rt_create_multi). Every shard filters its own tiles; the rt_render_multi* calls then deliver
+ * rt_multi_frame_pixels() = rt_multi_frame_elems() / s^2 elements (n_rays / s^2 of them the picture). */
+int      rt_set_supersampling_multi(rt_multi* m, uint32_t s);
+uint64_t rt_multi_frame_pixels(const rt_multi* m);
 int rt_count_rays_multi(rt_multi* m);
 int rt_get_stats_multi(rt_multi* m, rt_stats_t* stats);
 rt_context* rt_multi_context(rt_multi* m, uint32_t r);

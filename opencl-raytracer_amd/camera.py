@@ -58,3 +58,28 @@ def crop_rays(width: int, height: int, x0: int, y0: int, w: int, h: int, fov_deg
     """The rays of a w x h window of the full W x H grid (for bounded CPU baselines)."""
     full_rows = primary_rays(width, height, fov_degrees, y0, y0 + h).reshape(h, width)
     return np.ascontiguousarray(full_rows[:, x0:x0 + w]).reshape(-1)
+
+
+def supersampled(width: int, height: int, z: float, s: int) -> tuple[int, int, np.float32]:
+    """The SAMPLE grid of a supersampled width x height picture at z (hip_raytracer.h, "supersampled frames"): the pinhole
+    grid (s W, s H, fl(s z)) is a regular s x s lattice of sub-pixel rays inside every pixel of (W, H, z), because the
+    directions are not normalised. This is the camera a context with factor s is given; it delivers W x H pixels."""
+    s = int(s)
+    if s not in (1, 2, 3, 4):
+        raise ValueError("the supersampling factor is 1, 2, 3 or 4")
+    return s * int(width), s * int(height), F(F(s) * F(z))
+
+
+def grid_rays(width: int, height: int, z: float) -> np.ndarray:
+    """Ray3D array of the pinhole grid (width, height, z) with z given (rt_set_camera's rays): `primary_rays` for a depth that
+    does not come from a field of view - a sample grid's fl(s z), say."""
+    half_w = F(F(width) / F(2.0))
+    half_h = F(F(height) / F(2.0))
+    x = (np.arange(width, dtype=F) - half_w).astype(F)
+    y = ((F(height) - np.arange(height, dtype=F)) - half_h).astype(F)
+    rays = np.zeros((height, width), dtype=RAY_DTYPE)
+    rays["start"][..., 3] = 1.0
+    rays["direction"][..., 0] = x[None, :]
+    rays["direction"][..., 1] = y[:, None]
+    rays["direction"][..., 2] = F(z)
+    return rays.reshape(-1)

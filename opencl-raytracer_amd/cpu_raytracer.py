@@ -29,13 +29,20 @@ def load_library():
         lib.cpu_rt_render.restype = ctypes.c_int
         lib.cpu_rt_render.argtypes = [ctypes.c_int, u32, vp, u32, vp, u32, vp, u64, vp, ctypes.c_uint, ctypes.POINTER(u64),
                                       ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint)]
+        if hasattr(lib, "cpu_rt_render_supersampled"):
+            lib.cpu_rt_render_supersampled.restype = ctypes.c_int
+            lib.cpu_rt_render_supersampled.argtypes = lib.cpu_rt_render.argtypes + [u32, u64]
         _lib = lib
     return _lib
 
 
 class CPURaytracer:
-    def __init__(self, objects, lights, rays, MAX_BOUNCES: int = 0, *, kernel="shade_and_reflect", threads: int = 0):
+    def __init__(self, objects, lights, rays, MAX_BOUNCES: int = 0, *, kernel="shade_and_reflect", threads: int = 0,
+                 supersample: int = 1, sample_width: int = 0):
+        """supersample=s, sample_width=w: `rays` are the SAMPLE grid in rows of w; Render() returns len(rays) / s^2 pixels, box-filtered
+        on the host with the loop of resolve.box_filter (CPURaytracer::SetSupersampling) - the option HIPRaytracer has."""
         self._lib = load_library()
+        self.supersample, self.sample_width = int(supersample), int(sample_width)
         self.objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
         self.lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         self.rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
@@ -48,15 +55,22 @@ class CPURaytracer:
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)
-        out = np.empty((n, 4) if self.kernel else (n,), dtype=np.float32)
+        n_out = n // (self.supersample * self.supersample) if self.supersample in (2, 3, 4) else n
+        out = np.empty((n_out, 4) if self.kernel else (n_out,), dtype=np.float32)
         traced, hits = ctypes.c_uint64(0), ctypes.c_uint64(0)
         secs, used = ctypes.c_double(0), ctypes.c_uint(0)
 
         def ptr(a):
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
-        rc = self._lib.cpu_rt_render(self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights),
-                                     len(self.lights), ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced),
-                                     ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
+        args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
+                ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
+        if self.supersample != 1:
+            rc = self._lib.cpu_rt_render_supersampled(*args, self.supersample, self.sample_width)
+            if rc != 0:
+                raise ValueError("cpu_rt_render_supersampled: unsupported arguments (factor 1..4, a colour kernel, rays in whole rows of "
+                                 "sample_width with width and height multiples of the factor)")
+        else:
+            rc = self._lib.cpu_rt_render(*args)
         if rc != 0:
             raise ValueError("cpu_rt_render: unsupported arguments (kernel must be 0..2; triangle records are a HIP-backend extension)")
         self.rays_traced, self.hit_pixels = int(traced.value), int(hits.value)

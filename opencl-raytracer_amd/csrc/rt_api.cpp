@@ -6,6 +6,7 @@
 #include "rt_records.h"
 #include "rt_kernels.h"
 #include "rt_pack.h"
+#include "rt_resolve.h"
 
 #include <hip/hip_runtime.h>
 
@@ -119,6 +120,10 @@ struct rt_context {
     size_t h_pack_bytes = 0;
     void* d_scratch = nullptr;
     size_t d_scratch_bytes = 0;
+    // supersampled frames (rt_resolve.hip): the factor, and the sample frame every render call with a factor > 1 filters from
+    uint32_t ss = 1;
+    void* d_samples = nullptr;
+    size_t d_samples_bytes = 0;
     // rt_render in passes (render_in_passes): the stream the read-backs run on, an event per pass
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_pass[kMaxPasses] = {};
@@ -499,6 +504,31 @@ int check_packed(rt_context* c, int format) {
 int pack_on(rt_context* c, const void* d_src, uint64_t n, int format, void* d_dst, hipStream_t stream) {
     const hipError_t e = rt::launch_pack(static_cast<const float4*>(d_src), n, format, d_dst, stream);
     return e == hipSuccess ? RT_OK : fail_hip(c, e, "pack launch");
+}
+
+// ---- supersampled frames ----
+uint64_t local_pixels(const rt_context* c) { return c->n_local / ((uint64_t)c->ss * c->ss); }
+
+// what rt_set_supersampling, rt_set_camera and rt_set_shard hold a (factor, camera, shard) combination to; nothing is changed here
+int check_supersampling(rt_context* c, uint32_t s, bool pinhole, uint32_t width, uint32_t height, uint64_t tile_rays, uint32_t world) {
+    if (s < 1 || s > 4) return fail(c, RT_ERR_INVALID_ARGUMENT, "the supersampling factor is 1, 2, 3 or 4");
+    if (s == 1) return RT_OK;
+    if (c->kernel == RT_KERNEL_HITTEST)
+        return fail(c, RT_ERR_STATE, "an RT_KERNEL_HITTEST context renders the nearest t per ray: a time is not a colour, there is nothing to filter");
+    if (c->aux_t || c->aux_index) return fail(c, RT_ERR_STATE, "aux buffers are per work-item: not together with a supersampling factor > 1");
+    if (!pinhole || !width || !height)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "supersampling needs a pinhole camera (rt_set_camera): the samples are the sub-pixel rays of its grid");
+    if (width % s || height % s) return fail(c, RT_ERR_INVALID_ARGUMENT, "width and height of the sample grid must be multiples of the supersampling factor");
+    if (world > 1 && tile_rays % ((uint64_t)s * width))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "with supersampling a tile must hold whole pixel rows: tile_rays % (s * width) == 0");
+    return RT_OK;
+}
+
+// s x s samples -> one pixel: `n_samples` consecutive samples of whole sample rows of the context's camera (a shard's tiles are that)
+int resolve_on(rt_context* c, const void* d_src, uint64_t n_samples, int format, void* d_dst, hipStream_t stream) {
+    if (n_samples == 0) return RT_OK;
+    const hipError_t e = rt::launch_resolve(static_cast<const float4*>(d_src), c->width, (uint32_t)(n_samples / c->width), c->ss, format, d_dst, stream);
+    return e == hipSuccess ? RT_OK : fail_hip(c, e, "resolve launch");
 }
 
 // Path choice unless a flag says otherwise. Measured at 2048^2 (scratch sweep, depth 3, 4 lights): the small-scene
@@ -1995,6 +2025,10 @@ int rt_set_camera(rt_context* c, uint32_t width, uint32_t height, float z) {
     const bool out = !camera_in_domain(width, height, z);
     if (out && c->has_triangles)
         return fail(c, RT_ERR_INVALID_ARGUMENT, "a camera with a direction of |d|^2 outside (1e-30, 1e30) needs the literal loops, which do not know triangle records");
+    if (c->ss > 1) {
+        const int rc = check_supersampling(c, c->ss, true, width, height, c->tile_rays, c->world);
+        if (rc) return rc;
+    }
     c->camera_out_of_domain = out;
     c->pinhole = true;
     apply_ray_domain(c);
@@ -2010,6 +2044,10 @@ int rt_set_shard(rt_context* c, uint64_t tile_rays, uint32_t rank, uint32_t worl
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (world == 0 || rank >= world || (world > 1 && tile_rays == 0))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "need world >= 1, rank < world, tile_rays > 0");
+    if (c->ss > 1) {
+        const int rc = check_supersampling(c, c->ss, c->pinhole, c->width, c->height, tile_rays, world);
+        if (rc) return rc;
+    }
     c->tile_rays = tile_rays;
     c->rank = rank;
     c->world = world;
@@ -2019,8 +2057,48 @@ int rt_set_shard(rt_context* c, uint64_t tile_rays, uint32_t rank, uint32_t worl
 
 uint64_t rt_local_rays(const rt_context* c) { return c ? c->n_local : 0; }
 
+int rt_set_supersampling(rt_context* c, uint32_t s) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const int rc = check_supersampling(c, s, c->pinhole, c->width, c->height, c->tile_rays, c->world);
+    if (rc) return rc;
+    c->ss = s;
+    return RT_OK;
+}
+
+uint32_t rt_supersampling(const rt_context* c) { return c ? c->ss : 0; }
+
+uint64_t rt_local_pixels(const rt_context* c) { return c ? local_pixels(c) : 0; }
+
+int rt_resolve_device(rt_context* c, const void* d_samples, uint32_t sample_width, uint32_t sample_rows, uint32_t s, int format,
+                      void* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (s < 1 || s > 4) return fail(c, RT_ERR_INVALID_ARGUMENT, "the supersampling factor is 1, 2, 3 or 4");
+    if (format != 0 && !packed_bytes(format)) return fail(c, RT_ERR_INVALID_ARGUMENT, "unknown output (0 = float4, RT_PIXEL_RGBA8 = 1, RT_PIXEL_RGB8 = 2)");
+    if (sample_width % s || sample_rows % s) return fail(c, RT_ERR_INVALID_ARGUMENT, "sample_width and sample_rows must be multiples of s");
+    const uint64_t n_pixels = (uint64_t)(sample_width / s) * (sample_rows / s);
+    if (n_pixels == 0) return RT_OK;
+    if (!d_samples || !d_out) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_resolve_device: NULL frame");
+    if (reinterpret_cast<uintptr_t>(d_samples) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the sample frame must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_out) & (format ? 3u : 15u))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, format ? "d_out must be 4-byte aligned" : "a float4 d_out must be 16-byte aligned");
+    RT_DEVICE(c);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (s == 1) {  // nothing to filter: the samples are the pixels
+        if (format) return pack_on(c, d_samples, n_pixels, format, d_out, stream);
+        RT_HIP(c, hipMemcpyAsync(d_out, d_samples, (size_t)n_pixels * 16, hipMemcpyDeviceToDevice, stream));
+        return RT_OK;
+    }
+    int form = rt::kResolveAuto;  // the measured choice (rt_resolve.hip)
+    if (const char* env = std::getenv("RT_RESOLVE_FORM"))  // measurement knob (tools/ab/supersample_timing.py): "pixel" / "sample"
+        form = env[0] == 'p' ? rt::kResolveLanePerPixel : (env[0] == 's' ? rt::kResolveLanePerSample : rt::kResolveAuto);
+    const hipError_t e = rt::launch_resolve(static_cast<const float4*>(d_samples), sample_width, sample_rows, s, format, d_out, stream, form);
+    return e == hipSuccess ? RT_OK : fail_hip(c, e, "resolve launch");
+}
+
 int rt_set_aux_device(rt_context* c, void* d_hit_t, void* d_hit_index) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->ss > 1 && (d_hit_t || d_hit_index))
+        return fail(c, RT_ERR_STATE, "aux buffers are per work-item: not together with a supersampling factor > 1");
     c->aux_t = static_cast<float*>(d_hit_t);
     c->aux_index = static_cast<int32_t*>(d_hit_index);
     return RT_OK;
@@ -2031,6 +2109,15 @@ int rt_render_device(rt_context* c, void* d_out, void* hip_stream) {
     if (!d_out && c->n_local) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out is NULL");
     // NULL is the legacy default stream - NOT the context's private stream: a caller that passes its framework's
     // "current stream" handle (0 for torch's default stream) gets a render that is ordered with its own work
+    if (c->ss > 1) {  // samples into the context's sample frame, their pixels into d_out, on the caller's stream
+        if (c->n_local == 0) return RT_OK;
+        if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "a float4 d_out must be 16-byte aligned");
+        RT_DEVICE(c);
+        int rc = grow_buffer(c, c->d_samples, c->d_samples_bytes, (size_t)c->n_local * elem_bytes(c), false);
+        if (rc == RT_OK) rc = do_launch(c, c->d_samples, static_cast<hipStream_t>(hip_stream), false);
+        if (rc == RT_OK) rc = resolve_on(c, c->d_samples, c->n_local, 0, d_out, static_cast<hipStream_t>(hip_stream));
+        return rc;
+    }
     return do_launch(c, d_out, static_cast<hipStream_t>(hip_stream), false);
 }
 
@@ -2051,8 +2138,8 @@ int rt_render_device(rt_context* c, void* d_out, void* hip_stream) {
 static int render_in_passes(rt_context* c, int format, const void** out) {
     // the split: spans of consecutive ranks of a world of their sum ("3,1": three tiles of every four, then the fourth). A byte
     // frame's copy is a quarter as long, so a smaller last pass pays: "7,1" (cfg4, RGBA8: 12.55 ms against 12.80 for "3,1", 13.22
-    // for "1,1", 13.11 in one pass - profiles/packed_output_timing.json)
-    uint32_t spans[kMaxPasses] = {format ? 7u : 3u, 1, 0, 0}, K = 2, world = 0;
+    // for "1,1", 13.11 in one pass - profiles/packed_output_timing.json); a filtered float frame's copy is as short (wants_passes)
+    uint32_t spans[kMaxPasses] = {(format || c->ss > 1) ? 7u : 3u, 1, 0, 0}, K = 2, world = 0;
     if (const char* env = std::getenv("RT_RENDER_SPLIT")) {
         K = 0;
         for (const char* q = env; *q && K < kMaxPasses;) {
@@ -2065,14 +2152,19 @@ static int render_in_passes(rt_context* c, int format, const void** out) {
     }
     for (uint32_t k = 0; k < K; ++k) world += spans[k];
     const uint64_t n_rays = c->n_rays;
-    const uint64_t tile_rays = (c->pinhole && c->width) ? 16ull * c->width : 65536ull;
+    // supersampled frames: a tile holds whole pixel rows (16 sample rows for s = 2 and 4, lcm(16, 3) = 48 for s = 3), a pass filters
+    // its samples (from d_samples) into its pixels, and everything behind the filter - pack, copy, host frame - counts in pixels
+    const uint32_t ss = c->ss, ss2 = ss * ss;
+    const uint64_t tile_rays = (c->pinhole && c->width) ? (ss == 3 ? 48ull : 16ull) * c->width : 65536ull;
     const uint64_t tiles = (n_rays + tile_rays - 1) / tile_rays;
     const size_t render_elem = elem_bytes(c);                             // what a kernel writes per work-item
-    const size_t elem = format ? packed_bytes(format) : render_elem;     // what travels to the host per work-item
-    const size_t tile_bytes = (size_t)tile_rays * elem;
+    const size_t elem = format ? packed_bytes(format) : render_elem;     // what travels to the host per pixel
+    const size_t tile_bytes = (size_t)(tile_rays / ss2) * elem;
     const size_t frame_bytes = (size_t)tiles * tile_bytes;  // whole tiles: the ragged last one is padded behind the frame's end
     int rc = grow_buffer(c, format ? c->h_pack : c->h_out, format ? c->h_pack_bytes : c->h_out_bytes, frame_bytes, true);
-    if (rc == RT_OK) rc = grow_buffer(c, c->d_out, c->d_out_bytes, (size_t)tiles * tile_rays * render_elem, false);  // the passes' outputs one behind the other
+    if (rc == RT_OK && ss > 1) rc = grow_buffer(c, c->d_samples, c->d_samples_bytes, (size_t)tiles * tile_rays * render_elem, false);
+    if (rc == RT_OK && (ss == 1 || !format))
+        rc = grow_buffer(c, c->d_out, c->d_out_bytes, (size_t)tiles * (tile_rays / ss2) * render_elem, false);  // the passes' outputs one behind the other
     if (rc == RT_OK && format) rc = grow_buffer(c, c->d_pack, c->d_pack_bytes, frame_bytes, false);
     if (rc != RT_OK) return rc;
     char* const d_frame = static_cast<char*>(format ? c->d_pack : c->d_out);  // what the copies read
@@ -2089,13 +2181,14 @@ static int render_in_passes(rt_context* c, int format, const void** out) {
         c->world = world;
         c->span = spans[k];
         c->n_local = local_count(n_rays, tile_rays, rank, world, spans[k]);
-        char* const rendered = static_cast<char*>(c->d_out) + (size_t)at * render_elem;
-        char* buf = d_frame + (size_t)at * elem;
+        char* const rendered = static_cast<char*>(ss > 1 ? c->d_samples : c->d_out) + (size_t)at * render_elem;
+        char* buf = d_frame + (size_t)(at / ss2) * elem;
         const size_t run_bytes = (size_t)spans[k] * tile_bytes;
         at += c->n_local;
         if (c->n_local == 0) continue;
         rc = do_launch(c, rendered, c->stream, false);
-        if (rc == RT_OK && format) rc = pack_on(c, rendered, c->n_local, format, buf, c->stream);
+        if (rc == RT_OK && ss > 1) rc = resolve_on(c, rendered, c->n_local, format, buf, c->stream);  // the byte forms fused
+        else if (rc == RT_OK && format) rc = pack_on(c, rendered, c->n_local, format, buf, c->stream);
         if (rc != RT_OK) break;
         hipError_t e = hipEventRecord(c->ev_pass[k], c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pass[k], 0);
@@ -2122,10 +2215,15 @@ static int render_in_passes(rt_context* c, int format, const void** out) {
 }
 
 // the conditions that send a synchronous render through render_in_passes (float and 8-bit frames alike)
-static bool wants_passes(const rt_context* c) {
+// A supersampled BYTE frame is small enough to go in one pass by default: its copy (a sixteenth of the sample frame's bytes for
+// s = 2: 16.7 MB, 0.3 ms) hides less than a second pass's drains cost - cfg4, s = 2, RGBA8: 11.76 ms in one pass against 12.31 for
+// "7,1", 12.42 "15,1", 12.44 "3,1", 12.53 "1,1" (profiles/supersample_timing.json). A supersampled FLOAT frame's copy is the byte
+// frame's of an unfiltered one, and so is its best split: "7,1" (12.42 against 12.49 "15,1", 12.63 one pass, 12.69 "3,1", 13.04 "1,1").
+static bool wants_passes(const rt_context* c, int format = 0) {
     const char* env = std::getenv("RT_RENDER_PASSES");  // "1": one pass whatever the frame; "2": two passes whatever its size (tests)
     const bool off = env && env[0] == '1', forced = env && env[0] == '2';
-    return !off && c->world <= 1 && (forced || c->n_rays >= (1ull << 22)) && c->n_rays > 0 && c->n_local == c->n_rays && use_wavefront(c) &&
+    const bool large = c->n_rays >= (1ull << 22) && !(c->ss > 1 && format);
+    return !off && c->world <= 1 && (forced || large) && c->n_rays > 0 && c->n_local == c->n_rays && use_wavefront(c) &&
            (c->pinhole || c->have_rays) && !c->aux_t && !c->aux_index;  // (aux buffers are indexed by work-item of ONE whole-frame launch)
 }
 
@@ -2142,9 +2240,13 @@ int rt_render(rt_context* c, const float** out) {
     if (rc) return rc;
     rc = ensure_host_out(c);
     if (rc) return rc;
-    rc = do_launch(c, c->d_out, c->stream, false);
+    if (c->ss > 1) rc = grow_buffer(c, c->d_samples, c->d_samples_bytes, (size_t)c->n_local * elem_bytes(c), false);
     if (rc) return rc;
-    const size_t bytes = (size_t)c->n_local * elem_bytes(c);
+    rc = do_launch(c, c->ss > 1 ? c->d_samples : c->d_out, c->stream, false);
+    if (rc) return rc;
+    if (c->ss > 1) rc = resolve_on(c, c->d_samples, c->n_local, 0, c->d_out, c->stream);
+    if (rc) return rc;
+    const size_t bytes = (size_t)local_pixels(c) * elem_bytes(c);
     if (bytes) RT_HIP(c, hipMemcpyAsync(c->h_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));  // Render() is synchronous (OpenCLRaytracer.cpp:94)
     *out = static_cast<const float*>(c->h_out);
@@ -2175,9 +2277,15 @@ int rt_render_device_packed(rt_context* c, int format, void* d_out, void* hip_st
     if (!d_out) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out is NULL");
     if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "d_out must be 4-byte aligned");
     RT_DEVICE(c);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);  // NULL: the legacy default stream, as for rt_render_device
+    if (c->ss > 1) {  // filter and quantise in one pass over the sample frame
+        rc = grow_buffer(c, c->d_samples, c->d_samples_bytes, (size_t)c->n_local * elem_bytes(c), false);
+        if (rc == RT_OK) rc = do_launch(c, c->d_samples, stream, false);
+        if (rc == RT_OK) rc = resolve_on(c, c->d_samples, c->n_local, format, d_out, stream);
+        return rc;
+    }
     rc = grow_buffer(c, c->d_scratch, c->d_scratch_bytes, (size_t)c->n_local * elem_bytes(c), false);
     if (rc) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);  // NULL: the legacy default stream, as for rt_render_device
     rc = do_launch(c, c->d_scratch, stream, false);
     if (rc) return rc;
     return pack_on(c, c->d_scratch, c->n_local, format, d_out, stream);
@@ -2188,21 +2296,23 @@ int rt_render_packed(rt_context* c, int format, const uint8_t** out) {
     int rc = check_packed(c, format);
     if (rc) return rc;
     RT_DEVICE(c);
-    if (wants_passes(c)) {
+    if (wants_passes(c, format)) {
         const void* frame = nullptr;
         rc = render_in_passes(c, format, &frame);
         if (rc == RT_OK) *out = static_cast<const uint8_t*>(frame);
         return rc;
     }
-    const size_t bytes = (size_t)c->n_local * packed_bytes(format);
-    rc = ensure_out(c);  // the float frame: the context's own device framebuffer
+    const size_t bytes = (size_t)local_pixels(c) * packed_bytes(format);
+    if (c->ss > 1) rc = grow_buffer(c, c->d_samples, c->d_samples_bytes, (size_t)c->n_local * elem_bytes(c), false);
+    else rc = ensure_out(c);  // the float frame: the context's own device framebuffer
     if (rc == RT_OK) rc = grow_buffer(c, c->d_pack, c->d_pack_bytes, bytes, false);
     if (rc == RT_OK) rc = grow_buffer(c, c->h_pack, c->h_pack_bytes, bytes, true);
     if (rc) return rc;
-    rc = do_launch(c, c->d_out, c->stream, false);
+    rc = do_launch(c, c->ss > 1 ? c->d_samples : c->d_out, c->stream, false);
     if (rc) return rc;
     if (bytes) {
-        rc = pack_on(c, c->d_out, c->n_local, format, c->d_pack, c->stream);
+        if (c->ss > 1) rc = resolve_on(c, c->d_samples, c->n_local, format, c->d_pack, c->stream);  // filter + quantise, fused
+        else rc = pack_on(c, c->d_out, c->n_local, format, c->d_pack, c->stream);
         if (rc) return rc;
         RT_HIP(c, hipMemcpyAsync(c->h_pack, c->d_pack, bytes, hipMemcpyDeviceToHost, c->stream));
     }
@@ -2213,6 +2323,7 @@ int rt_render_packed(rt_context* c, int format, const uint8_t** out) {
 
 int rt_render_aux(rt_context* c, float* hit_t, int32_t* hit_index) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (c->ss > 1) return fail(c, RT_ERR_STATE, "aux records are per work-item: not together with a supersampling factor > 1");
     int rc = ensure_out(c);
     if (rc) return rc;
     float* d_t = nullptr;
@@ -2338,6 +2449,7 @@ void rt_destroy(rt_context* c) {
     if (c->d_pack) (void)hipFree(c->d_pack);
     if (c->h_pack) (void)hipHostFree(c->h_pack);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
+    if (c->d_samples) (void)hipFree(c->d_samples);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);
     if (c->d_counters) (void)hipFree(c->d_counters);
@@ -2357,6 +2469,7 @@ struct rt_multi {
     std::vector<void*> d_local;      // per context: its packed tiles, on its own device
     std::vector<char> peer_ok;       // per context: devices[0] and its device can address each other's memory
     uint64_t n_rays = 0, tile_rays = 0, tiles = 0;
+    uint32_t ss = 1;                 // supersampling factor of every context (rt_set_supersampling_multi)
     size_t elem = 16;
     void* h_frame = nullptr;         // rt_render_multi's frame: pinned, portable host memory (whole tiles) every device copies its tiles into
     std::vector<void*> d_bytes;      // per context: its tiles as bytes (rt_render_multi_packed; room for RGBA8), on its own device
@@ -2395,11 +2508,12 @@ int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, int f
     rt_context* c = m->ctx[r];
     DeviceGuard guard(c->device);
     if (!guard.ok) { err = std::string("hipSetDevice: ") + hipGetErrorString(guard.err); return RT_ERR_HIP; }
-    int rc = rt_render_device(c, m->d_local[r], c->stream);
+    const bool fused = format && m->ss > 1;  // a supersampled byte frame: filter + quantise in one pass, straight into the byte tiles
+    int rc = fused ? RT_OK : rt_render_device(c, m->d_local[r], c->stream);  // (with a factor: this shard's PIXELS, tile_rays / s^2 per tile)
     if (rc != RT_OK) { err = c->error; return rc; }
     const uint32_t n = (uint32_t)m->ctx.size();
     const uint64_t mine = m->tiles / n + ((m->tiles % n) > r ? 1 : 0);
-    const size_t tile_bytes = (size_t)m->tile_rays * (format ? packed_bytes(format) : m->elem);
+    const size_t tile_bytes = (size_t)(m->tile_rays / ((uint64_t)m->ss * m->ss)) * (format ? packed_bytes(format) : m->elem);
     hipError_t e = hipSuccess;
     void* local = m->d_local[r];  // what travels: the float tiles, or their bytes
     if (format) {
@@ -2408,7 +2522,8 @@ int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, int f
             if (e != hipSuccess) { err = std::string("byte tiles: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP; }
         }
         local = m->d_bytes[r];
-        rc = rt_pack_device(c, m->d_local[r], c->n_local, format, local, c->stream);
+        if (fused) rc = rt_render_device_packed(c, format, local, c->stream);
+        else rc = rt_pack_device(c, m->d_local[r], c->n_local, format, local, c->stream);
         if (rc != RT_OK) { err = c->error; return rc; }
     }
     if (mine) {
@@ -2594,6 +2709,23 @@ int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z) {
 }
 
 uint64_t rt_multi_frame_elems(const rt_multi* m) { return m ? m->tiles * m->tile_rays : 0; }
+
+int rt_set_supersampling_multi(rt_multi* m, uint32_t s) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    if (s >= 2 && s <= 4 && !m->ctx.empty() && m->ctx[0]->pinhole && m->ctx[0]->width && m->tile_rays % ((uint64_t)s * m->ctx[0]->width))
+        return multi_fail(m, RT_ERR_INVALID_ARGUMENT, "with supersampling a tile must hold whole pixel rows: pass a tile_rays with tile_rays % (s * width) == 0 to rt_create_multi");
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = rt_set_supersampling(m->ctx[r], s);
+        if (rc != RT_OK) {  // all or none
+            for (size_t q = 0; q < r; ++q) (void)rt_set_supersampling(m->ctx[q], m->ss);
+            return multi_fail(m, rc, m->ctx[r]->error);
+        }
+    }
+    m->ss = s;
+    return RT_OK;
+}
+
+uint64_t rt_multi_frame_pixels(const rt_multi* m) { return m ? rt_multi_frame_elems(m) / ((uint64_t)m->ss * m->ss) : 0; }
 
 rt_context* rt_multi_context(rt_multi* m, uint32_t r) { return (m && r < m->ctx.size()) ? m->ctx[r] : nullptr; }
 

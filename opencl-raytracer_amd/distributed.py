@@ -183,32 +183,41 @@ class ShardedHIPRaytracer:
 
     output="float" (default): the reference's float4 frame. "rgba8" / "rgb8": every rank quantises its own tiles on its GPU
     (HIPRaytracer.render_device_packed) and the exchange moves uint8 - a quarter / 3/16 of the bytes per peer; the frame on
-    rank 0 is (n_rays, 4 | 3) uint8."""
+    rank 0 is (n_rays, 4 | 3) uint8.
+
+    supersample=s (with camera=(W, H, z), the PICTURE's camera): every rank renders s x s samples per pixel and filters its own
+    tiles on its GPU (hip_raytracer.h, "supersampled frames"); `tile_rows` counts sample rows and is rounded up to whole pixel
+    rows (sharding.whole_pixel_rows). The exchange is built over PIXELS - n_rays / s^2, tile_rays / s^2 - so s^2 times fewer
+    bytes travel; the frame on rank 0 is the W x H picture, float or bytes."""
 
     def __init__(self, objects, lights, rays, MAX_BOUNCES, *, camera=None, kernel="shade_and_reflect",
                  tile_rows: int = 16, width: int | None = None, device_index: int = 0, group=None,
-                 pipeline: bool = False, output: str = "float", **kw):
+                 pipeline: bool = False, output: str = "float", supersample: int = 1, **kw):
         from .hip_raytracer import HIPRaytracer
         if output not in ("float", "rgba8", "rgb8"):
             raise ValueError('output is "float", "rgba8" or "rgb8"')
         self.output = output
+        self.supersample = s = int(supersample)
+        if s != 1:
+            kw["supersample"] = s     # (HIPRaytracer turns the picture's camera into the sample grid's)
         self.rt = HIPRaytracer(objects, lights, rays, MAX_BOUNCES, kernel=kernel, device=device_index,
                                camera=camera, **kw)
         self.n_rays = self.rt.n_rays
-        w = width if width is not None else (camera[0] if camera is not None else self.rt.stats().width)
+        w = width if width is not None else (camera[0] * s if camera is not None else self.rt.stats().width)
         if not w:
             raise ValueError("width is required to cut row tiles when the rays are not a pinhole grid")
-        self.tile_rays = sharding.tile_rays_for_rows(int(w), tile_rows)
+        self.tile_rays = sharding.tile_rays_for_rows(int(w), sharding.whole_pixel_rows(tile_rows, s))
         world = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         self.rt.set_shard(self.tile_rays, rank, world)
         self.device = torch.device("cuda", device_index)
+        self.n_pixels, tile_pixels = self.n_rays // (s * s), self.tile_rays // (s * s)   # what is exchanged: pixels
         if output == "float":
-            self.gatherer = FrameGather(self.n_rays, self.tile_rays, self.rt.elem_floats, self.device, group=group, pipeline=pipeline)
+            self.gatherer = FrameGather(self.n_pixels, tile_pixels, self.rt.elem_floats, self.device, group=group, pipeline=pipeline)
         else:
-            self.gatherer = FrameGather(self.n_rays, self.tile_rays, 4 if output == "rgba8" else 3, self.device, dtype=torch.uint8,
+            self.gatherer = FrameGather(self.n_pixels, tile_pixels, 4 if output == "rgba8" else 3, self.device, dtype=torch.uint8,
                                         group=group, pipeline=pipeline)
-        assert self.gatherer.local_rays == self.rt.local_rays  # exact share: nothing is padded to the largest one
+        assert self.gatherer.local_rays == self.rt.local_pixels  # exact share: nothing is padded to the largest one
 
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""

@@ -36,6 +36,8 @@ EXPORTS = [
     "rt_create_multi", "rt_set_camera_multi", "rt_multi_frame_elems", "rt_render_multi", "rt_render_multi_device",
     "rt_multi_context", "rt_multi_last_error", "rt_destroy_multi", "rt_count_rays_multi", "rt_get_stats_multi",
     "rt_packed_pixel_bytes", "rt_pack_device", "rt_render_device_packed", "rt_render_packed", "rt_render_multi_packed",
+    "rt_set_supersampling", "rt_supersampling", "rt_local_pixels", "rt_resolve_device", "rt_set_supersampling_multi",
+    "rt_multi_frame_pixels",
 ]
 
 
@@ -140,6 +142,19 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_render_packed.argtypes = [vp, i32, u8pp]
         lib.rt_render_multi_packed.restype = i32
         lib.rt_render_multi_packed.argtypes = [vp, i32, u8pp]
+    if hasattr(lib, "rt_set_supersampling"):  # (the same: a build from before supersampled frames)
+        lib.rt_set_supersampling.restype = i32
+        lib.rt_set_supersampling.argtypes = [vp, u32]
+        lib.rt_supersampling.restype = u32
+        lib.rt_supersampling.argtypes = [vp]
+        lib.rt_local_pixels.restype = u64
+        lib.rt_local_pixels.argtypes = [vp]
+        lib.rt_resolve_device.restype = i32
+        lib.rt_resolve_device.argtypes = [vp, vp, u32, u32, u32, i32, vp, vp]
+        lib.rt_set_supersampling_multi.restype = i32
+        lib.rt_set_supersampling_multi.argtypes = [vp, u32]
+        lib.rt_multi_frame_pixels.restype = u64
+        lib.rt_multi_frame_pixels.argtypes = [vp]
     if path is None:
         _lib = lib
     return lib
@@ -175,9 +190,18 @@ class HIPRaytracer:
     def __init__(self, objects: np.ndarray, lights: np.ndarray, rays: np.ndarray | None, MAX_BOUNCES: int = 0, *,
                  kernel="shade_and_reflect", device: int = 0, fused: bool = True, literal: bool = False,
                  raygen: bool = True, camera: tuple[int, int, float] | None = None, path: str = "auto",
-                 grid: bool = True, fast_phong: bool = False, device_opencl: bool = False):
+                 grid: bool = True, fast_phong: bool = False, device_opencl: bool = False, supersample: int = 1):
+        """supersample=s with camera=(W, H, z): a W x H picture of s x s samples per pixel (hip_raytracer.h, "supersampled
+        frames") - the context is created with s^2 W H work-items, given the sample camera (camera.supersampled), then the factor.
+        With rays, or with supersample=1 (the default), not one call changes."""
         self._lib = load_library()
         self._ctx = ctypes.c_void_p()
+        supersample = int(supersample)
+        if supersample != 1:
+            if camera is None or rays is not None:
+                raise ValueError("supersample needs camera=(W, H, z) and no ray buffer: the samples are the sub-pixel rays of a pinhole grid")
+            from .camera import supersampled
+            camera = supersampled(camera[0], camera[1], camera[2], supersample)
         objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
         lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         self.kernel = KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
@@ -203,6 +227,12 @@ class HIPRaytracer:
         if camera is not None:
             self._check(self._lib.rt_set_camera(self._ctx, int(camera[0]), int(camera[1]), float(camera[2])))
         self.n_rays = n_rays
+        if supersample != 1:
+            try:
+                self.set_supersampling(supersample)
+            except RTError:
+                self.close()
+                raise
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -217,6 +247,17 @@ class HIPRaytracer:
     @property
     def local_rays(self) -> int:
         return int(self._lib.rt_local_rays(self._ctx))
+
+    @property
+    def local_pixels(self) -> int:
+        """What every render call delivers: local_rays / s^2 (rt_local_pixels)."""
+        if not hasattr(self._lib, "rt_local_pixels"):
+            return self.local_rays
+        return int(self._lib.rt_local_pixels(self._ctx))
+
+    @property
+    def supersampling(self) -> int:
+        return int(self._lib.rt_supersampling(self._ctx))
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:
@@ -241,7 +282,7 @@ class HIPRaytracer:
         (local_rays, 4) float32 for shade / shade_and_reflect, (local_rays,) for hittest."""
         out = ctypes.POINTER(ctypes.c_float)()
         self._check(self._lib.rt_render(self._ctx, ctypes.byref(out)))
-        n = self.local_rays
+        n = self.local_pixels
         if n == 0:
             return np.zeros((0, 4) if self.elem_floats == 4 else (0,), dtype=np.float32)
         arr = np.ctypeslib.as_array(out, shape=(n * self.elem_floats,)).copy()
@@ -267,7 +308,7 @@ class HIPRaytracer:
         fmt = pixel_format(format)
         out = ctypes.POINTER(ctypes.c_uint8)()
         self._check(self._lib.rt_render_packed(self._ctx, fmt, ctypes.byref(out)))
-        return _byte_frame(self._lib, out, self.local_rays, fmt)
+        return _byte_frame(self._lib, out, self.local_pixels, fmt)
 
     def render_packed_host_ms(self, format="rgba8", frames: int = 3) -> float:
         """render_host_ms for the 8-bit frame: wall time of rt_render_packed without this wrapper's numpy copy, best of `frames`."""
@@ -291,6 +332,20 @@ class HIPRaytracer:
         """Convert n_pixels float4 pixels in device memory to bytes in device memory, asynchronously on a HIP stream."""
         self._check(self._lib.rt_pack_device(self._ctx, ctypes.c_void_p(d_rgba_ptr), int(n_pixels), pixel_format(format),
                                              ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
+    # -- supersampled frames (hip_raytracer.h: s x s samples per pixel, box-filtered on the device) ------------------------
+    def set_supersampling(self, s: int):
+        """rt_set_supersampling: the next render delivers local_rays / s^2 pixels (resolve.box_filter of the sample frame)."""
+        self._check(self._lib.rt_set_supersampling(self._ctx, int(s)))
+
+    def resolve_device(self, d_samples_ptr: int, sample_width: int, sample_rows: int, s: int, d_out_ptr: int, format=None,
+                       stream_ptr: int = 0):
+        """The filter alone (rt_resolve_device): sample_rows x sample_width float4 samples in device memory -> pixels in device
+        memory, float4 (format None) or bytes ('rgba8' / 'rgb8'), asynchronously on a HIP stream."""
+        fmt = 0 if format is None else pixel_format(format)
+        self._check(self._lib.rt_resolve_device(self._ctx, ctypes.c_void_p(d_samples_ptr), int(sample_width), int(sample_rows),
+                                                int(s), fmt, ctypes.c_void_p(d_out_ptr),
+                                                ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def setup_times(self) -> dict:
         """One-time host-side work outside every render timer (rt_setup_times_t), milliseconds."""
@@ -347,9 +402,18 @@ class MultiHIPRaytracer:
 
     def __init__(self, objects, lights, rays, MAX_BOUNCES: int = 0, *, devices=(0,), kernel="shade_and_reflect",
                  camera: tuple[int, int, float] | None = None, tile_rays: int = 0, fused: bool = True, literal: bool = False,
-                 grid: bool = True, device_opencl: bool = False):
+                 grid: bool = True, device_opencl: bool = False, supersample: int = 1):
+        """supersample=s with camera=(W, H, z): as for HIPRaytracer; the derived tile is 16 sample rows (48 for s = 3)."""
         self._lib = load_library()
         self._m = ctypes.c_void_p()
+        supersample = int(supersample)
+        if supersample != 1:
+            if camera is None or rays is not None:
+                raise ValueError("supersample needs camera=(W, H, z) and no ray buffer: the samples are the sub-pixel rays of a pinhole grid")
+            from .camera import supersampled
+            camera = supersampled(camera[0], camera[1], camera[2], supersample)
+            if tile_rays == 0:
+                tile_rays = (48 if supersample == 3 else 16) * int(camera[0])
         objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
         lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         self.kernel = KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
@@ -376,6 +440,13 @@ class MultiHIPRaytracer:
             self._check(self._lib.rt_set_camera_multi(self._m, int(camera[0]), int(camera[1]), float(camera[2])))
         self.n_rays = n_rays
         self.n_devices = len(devices)
+        self.supersample = 1
+        if supersample != 1:
+            try:
+                self.set_supersampling(supersample)
+            except RTError:
+                self.close()
+                raise
 
     def _check(self, rc: int):
         if rc != 0:
@@ -390,6 +461,21 @@ class MultiHIPRaytracer:
     def frame_elems(self) -> int:
         return int(self._lib.rt_multi_frame_elems(self._m))
 
+    @property
+    def frame_pixels(self) -> int:
+        """frame_elems / s^2 (rt_multi_frame_pixels): what render_device fills."""
+        return int(self._lib.rt_multi_frame_pixels(self._m))
+
+    @property
+    def n_pixels(self) -> int:
+        """Pixels of the picture: n_rays / s^2."""
+        return self.n_rays // (self.supersample * self.supersample)
+
+    def set_supersampling(self, s: int):
+        """rt_set_supersampling_multi: every shard filters its own tiles; all shards or none."""
+        self._check(self._lib.rt_set_supersampling_multi(self._m, int(s)))
+        self.supersample = int(s)
+
     def set_camera(self, width: int, height: int, z: float):
         """Re-aim every shard (rt_set_camera_multi). The tile size stays the one chosen at creation (in rays, not rows)."""
         self._check(self._lib.rt_set_camera_multi(self._m, int(width), int(height), float(z)))
@@ -397,17 +483,18 @@ class MultiHIPRaytracer:
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()
         self._check(self._lib.rt_render_multi(self._m, ctypes.byref(out)))
-        if self.n_rays == 0:
+        n = self.n_pixels
+        if n == 0:
             return np.zeros((0, 4) if self.elem_floats == 4 else (0,), dtype=np.float32)
-        arr = np.ctypeslib.as_array(out, shape=(self.n_rays * self.elem_floats,)).copy()
-        return arr.reshape(self.n_rays, 4) if self.elem_floats == 4 else arr
+        arr = np.ctypeslib.as_array(out, shape=(n * self.elem_floats,)).copy()
+        return arr.reshape(n, 4) if self.elem_floats == 4 else arr
 
     def render_packed(self, format="rgba8") -> np.ndarray:
         """The whole frame as bytes, (n_rays, 4 | 3) uint8: every device packs its own tiles and copies bytes."""
         fmt = pixel_format(format)
         out = ctypes.POINTER(ctypes.c_uint8)()
         self._check(self._lib.rt_render_multi_packed(self._m, fmt, ctypes.byref(out)))
-        return _byte_frame(self._lib, out, self.n_rays, fmt)
+        return _byte_frame(self._lib, out, self.n_pixels, fmt)
 
     def render_packed_host_ms(self, format="rgba8", repeats: int = 3) -> float:
         """Wall clock of the synchronous render_packed without the numpy copy, best of `repeats`."""

@@ -7,6 +7,8 @@
 // the second), everything else rounds after every operation. dot() and normalize() are the plain left-to-right forms.
 #include "CPURaytracer.hpp"
 
+#include <stdexcept>
+
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -319,6 +321,17 @@ CPURaytracer::CPURaytracer(const std::vector<ObjectData>& objects_, const std::v
 
 CPURaytracer::~CPURaytracer() {}
 
+void CPURaytracer::SetSupersampling(unsigned int s, size_t sample_width) {
+    if (s < 1 || s > 4) throw std::invalid_argument("the supersampling factor is 1, 2, 3 or 4");
+    if (s > 1) {
+        if (kernel == kHittest) throw std::invalid_argument("a time is not a colour: hittest frames are not filtered");
+        if (sample_width == 0 || rays.size() % sample_width || sample_width % s || (rays.size() / sample_width) % s)
+            throw std::invalid_argument("the rays must be whole rows of sample_width, width and height multiples of the factor");
+    }
+    ss = s;
+    ss_width = sample_width;
+}
+
 cl_float4* CPURaytracer::Render() {
     const size_t n = rays.size();
     for (size_t i = 0; i < n; ++i) {  // the buffer as the reference uploads it: {0,0,0,1} (OpenCLRaytracer.cpp:32); hittest: "no hit"
@@ -352,5 +365,22 @@ cl_float4* CPURaytracer::Render() {
     for (std::thread& t : pool) t.join();
     rays_traced = total_rays.load();
     hit_pixels = total_hits.load();
+    if (ss > 1) {  // the box filter of hip_raytracer.h: (b, a) order, every addition a rounded fp32 addition, one multiplication
+        const size_t w = ss_width, pw = w / ss, ph = rays.size() / w / ss;
+        const float k = 1.0f / (float)(ss * ss);
+        filtered.resize(pw * ph);
+        for (size_t j = 0; j < ph; ++j)
+            for (size_t i = 0; i < pw; ++i) {
+                const cl_float4* q = pixels.data() + j * ss * w + i * ss;
+                cl_float4 acc = q[0];
+                for (unsigned int b = 0; b < ss; ++b)
+                    for (unsigned int a = 0; a < ss; ++a)
+                        if (a | b)
+                            for (int ch = 0; ch < 4; ++ch) acc.s[ch] = acc.s[ch] + q[b * w + a].s[ch];
+                for (int ch = 0; ch < 4; ++ch) acc.s[ch] = acc.s[ch] * k;
+                filtered[j * pw + i] = acc;
+            }
+        return filtered.data();
+    }
     return pixels.data();
 }

@@ -30,6 +30,13 @@ public:
     // value {0,0,0,1} (OpenCLRaytracer.cpp:32). hittest: nearest t in s[0] (MAX_FLOAT on a miss).
     cl_float4* Render() override;
 
+    // Supersampled frames (hip_raytracer.h, "supersampled frames"), the same option as HIPRaytracer's so that the two backends
+    // stay interchangeable: the rays are the SAMPLE grid, rows of `sample_width`; Render() then returns Pixels() = rays / s^2
+    // pixels, the s x s samples of each added in fp32 in (b, a) order and multiplied once by fl(1 / s^2) - the same loop on the
+    // host. s = 1 (the default) is off. Throws std::invalid_argument for what rt_set_supersampling refuses.
+    void SetSupersampling(unsigned int s, size_t sample_width);
+    size_t Pixels() const { return rays.size() / ((size_t)ss * ss); }
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }
@@ -44,6 +51,9 @@ private:
     std::vector<Instance> instances;
     std::vector<Surface> surfaces;
     std::vector<cl_float4> pixels;
+    unsigned int ss = 1;                // supersampling factor; > 1: Render() returns `filtered`
+    size_t ss_width = 0;
+    std::vector<cl_float4> filtered;
     uint64_t rays_traced = 0, hit_pixels = 0;
 
 public:

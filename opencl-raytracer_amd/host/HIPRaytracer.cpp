@@ -97,6 +97,22 @@ const uint8_t* HIPRaytracer::RenderPacked(rt_pixel_format format) {
     return out;
 }
 
+void HIPRaytracer::SetSupersampling(unsigned int s) {
+    if (multi) {
+        if (rt_set_supersampling_multi(multi, s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetSupersampling: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_supersampling(ctx, s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetSupersampling: ") + rt_last_error(ctx));
+}
+
+size_t HIPRaytracer::Pixels() const {
+    if (multi) {
+        const size_t s = rt_supersampling(rt_multi_context(multi, 0));
+        return s ? rays.size() / (s * s) : rays.size();
+    }
+    return (size_t)rt_local_pixels(ctx);
+}
+
 rt_stats_t HIPRaytracer::Stats() {
     rt_stats_t s;
     if (multi) {  // several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures

@@ -39,6 +39,12 @@ public:
     // by the library and overwritten by the next RenderPacked(). Works for the one-GPU and the several-GPU object.
     const uint8_t* RenderPacked(rt_pixel_format format = RT_PIXEL_RGBA8);
 
+    // Supersampled frames (hip_raytracer.h, "supersampled frames"): the rays are the SAMPLE grid (s W x s H at s z, accepted as a
+    // pinhole grid by rt_create); after SetSupersampling(s) Render() / RenderPacked() return Pixels() = rays / s^2 pixels, box-filtered
+    // on the GPU(s). s = 1 is off. Throws std::runtime_error with the library's message for what it refuses.
+    void SetSupersampling(unsigned int s);
+    size_t Pixels() const;
+
     rt_stats_t Stats();
     rt_context* Context() { return ctx; }
 

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <stdexcept>
 #include <vector>
 
 #include "CPURaytracer.hpp"
@@ -12,11 +13,24 @@
 
 extern "C" {
 
+int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                               const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                               uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, uint32_t supersample, uint64_t sample_width);
+
 // out: n_rays x 4 floats (kernels 1, 2) or n_rays floats (kernel 0). Returns 0, or -1 for arguments it cannot serve
 // (unknown kernel; type-2 triangle records, which are the HIP backend's own extension).
 int cpu_rt_render(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
                   const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced, uint64_t* hit_pixels,
                   double* seconds, unsigned int* threads_used) {
+    return cpu_rt_render_supersampled(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced, hit_pixels,
+                                      seconds, threads_used, 1, 0);
+}
+
+// The same with CPURaytracer::SetSupersampling(supersample, sample_width): out holds n_rays / supersample^2 pixels. -1 also for a
+// factor / width the backend refuses.
+int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                               const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                               uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, uint32_t supersample, uint64_t sample_width) {
     if (kernel < 0 || kernel > 2 || (!out && n_rays)) return -1;
     const rt_object_data* objs = static_cast<const rt_object_data*>(objs_);
     const rt_light* lights = static_cast<const rt_light*>(lights_);
@@ -60,11 +74,15 @@ int cpu_rt_render(int kernel, uint32_t max_bounces, const void* objs_, uint32_t 
         rs.push_back(r);
     }
     std::unique_ptr<CPURaytracer> backend(new CPURaytracer(objects, ls, rs, max_bounces, static_cast<CPURaytracer::Kernel>(kernel), threads));
+    if (supersample != 1) {
+        try { backend->SetSupersampling(supersample, (size_t)sample_width); } catch (const std::exception&) { return -1; }
+    }
+    const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
     const auto t0 = std::chrono::steady_clock::now();
     const cl_float4* px = raytracer->Render();
     const auto t1 = std::chrono::steady_clock::now();
-    for (uint64_t i = 0; i < n_rays; ++i) {
+    for (uint64_t i = 0; i < n_out; ++i) {
         if (kernel == 0) out[i] = px[i].s[0];
         else std::memcpy(out + 4 * i, px[i].s, 16);
     }

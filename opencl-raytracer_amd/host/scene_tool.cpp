@@ -6,6 +6,8 @@
 //   scene_tool render8 <scene.txt> <W> <H> <D> <out.ppm> [z-bits|-] [p3|p6] [rgba8|rgb8]
 //                       the same frame as 8-bit pixels quantised on the GPU (HIPRaytracer::RenderPacked), written from the
 //                       bytes: `p3` (default) the reference's ASCII file, `p6` the binary PPM
+//   render and render8 take `--ss S` (S = 2, 3, 4) anywhere behind the command: S x S samples per pixel, box-filtered by the
+//                       backend (SetSupersampling). The picture stays W x H; the sample grid is S W x S H at S z.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +46,15 @@ static void dump_records(const std::vector<ObjectData>& objects, const std::vect
 
 int main(int argc, char** argv) {
     try {
+        unsigned ss = 1;  // --ss S: taken out of the argument list, whatever its position
+        for (int k = 2; k + 1 < argc; ++k)
+            if (std::strcmp(argv[k], "--ss") == 0) {
+                ss = (unsigned)std::atoi(argv[k + 1]);
+                for (int q = k; q + 2 < argc; ++q) argv[q] = argv[q + 2];
+                argc -= 2;
+                break;
+            }
+        if (ss < 1 || ss > 4) { std::fprintf(stderr, "--ss takes 1, 2, 3 or 4\n"); return 1; }
         if (argc < 4) { std::fprintf(stderr, "usage: scene_tool records|render|render8 ...\n"); return 1; }
         std::vector<ObjectData> objects;
         std::vector<Light> lights;
@@ -59,15 +70,19 @@ int main(int argc, char** argv) {
         float z = -((height / 2.0f) / tanf(fov));
         if (argc > 7 && std::strcmp(argv[7], "-") != 0) { const uint32_t bits = (uint32_t)std::strtoul(argv[7], nullptr, 16); std::memcpy(&z, &bits, 4); }
         const bool cpu = argc > 8 && std::strcmp(argv[8], "cpu") == 0;
+        // the sample grid: (ss W, ss H, fl(ss z)) - the picture's own grid for ss = 1
+        const int sw = (int)ss * width, sh = (int)ss * height;
+        const float sz = (float)ss * z;
         std::vector<Ray3D> rays;
-        rays.reserve((size_t)width * height);
-        for (int jj = 0; jj < height; ++jj)
-            for (int ii = 0; ii < width; ++ii)
-                rays.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - width / 2.0f, (float)(height - jj) - height / 2.0f, z));
+        rays.reserve((size_t)sw * sh);
+        for (int jj = 0; jj < sh; ++jj)
+            for (int ii = 0; ii < sw; ++ii)
+                rays.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - sw / 2.0f, (float)(sh - jj) - sh / 2.0f, sz));
         if (std::strcmp(argv[1], "render8") == 0) {
             const bool p6 = argc > 8 && std::strcmp(argv[8], "p6") == 0;
             const rt_pixel_format format = (argc > 9 && std::strcmp(argv[9], "rgb8") == 0) ? RT_PIXEL_RGB8 : RT_PIXEL_RGBA8;
             HIPRaytracer raytracer8(objects, lights, rays, depth);
+            if (ss > 1) raytracer8.SetSupersampling(ss);
             const uint8_t* bytes = raytracer8.RenderPacked(format);
             const size_t stride = rt_packed_pixel_bytes(format);
             if (p6) PPMExporter::ExportP6(argv[6], (size_t)width, (size_t)height, bytes, stride);
@@ -76,8 +91,15 @@ int main(int argc, char** argv) {
             return 0;
         }
         std::unique_ptr<IRaytracer> raytracer;
-        if (cpu) raytracer.reset(new CPURaytracer(objects, lights, rays, depth));
-        else raytracer.reset(new HIPRaytracer(objects, lights, rays, depth));
+        if (cpu) {
+            CPURaytracer* backend = new CPURaytracer(objects, lights, rays, depth);
+            raytracer.reset(backend);
+            if (ss > 1) backend->SetSupersampling(ss, (size_t)sw);
+        } else {
+            HIPRaytracer* backend = new HIPRaytracer(objects, lights, rays, depth);
+            raytracer.reset(backend);
+            if (ss > 1) backend->SetSupersampling(ss);
+        }
         cl_float4* pixels = raytracer->Render();
         PPMExporter::ExportP3(argv[6], (size_t)width, (size_t)height, PPMExporter::RGBAtoRGB(reinterpret_cast<const float*>(pixels), (size_t)width * height));
         std::printf("wrote %s\n", argv[6]);

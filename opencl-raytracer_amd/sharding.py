@@ -34,6 +34,15 @@ def tile_rays_for_rows(width: int, tile_rows: int) -> int:
     return width * tile_rows
 
 
+def whole_pixel_rows(tile_rows: int, s: int) -> int:
+    """Sample rows of a tile of a supersampled frame: `tile_rows` rounded up to a multiple of the factor s, so that a tile holds
+    whole pixel rows (rt_set_shard refuses anything else while the factor is > 1). Its pixels are tile_rays / s^2."""
+    s = int(s)
+    if s < 1 or tile_rows < 1:
+        raise ValueError("tile_rows and the supersampling factor are positive")
+    return (int(tile_rows) + s - 1) // s * s
+
+
 def assemble_frame(pieces, tile_rays: int, n_rays: int):
     """Un-interleave the per-rank packed buffers (index = rank) into the full frame. Works on numpy arrays
     and torch tensors alike (CPU or GPU): pieces[r] has shape (>= local_rays(r), C...)."""
