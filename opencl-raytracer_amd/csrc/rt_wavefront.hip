@@ -69,6 +69,8 @@ enum : uint32_t {
     RS_FINISH = 7,                          // 0: rounds go on, 1: the rest belongs to wf_finish, 2: nothing left
     RS_ROUNDS = 8,                          // rounds that had work (statistics)
     RS_FRAME_STUCK = 9,                     // wf_frame: waves that gave up on a state in which nothing could move (a logic error: the host fails the frame)
+    RS_NEXT_SINGLES = 10,                   // some closest-queue entry appended this round is NOT also in the shadow queue (block_push) ...
+    RS_N_SINGLES = 11,                      // ... and the same of the queue the current round consumes: 0 = every entry of it is a duplicate
     RS_WORDS = 16
 };
 
@@ -210,7 +212,11 @@ __device__ __forceinline__ void block_push(bool want_closest, bool want_any, uin
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t n_waves = (blockDim.x + 63u) >> 6;
     const unsigned long long bc = __ballot(want_closest), ba = __ballot(want_any);
-    if (lane == 0u) { s_cnt[0][wave] = (uint32_t)__popcll(bc); s_cnt[1][wave] = (uint32_t)__popcll(ba); }
+    if (lane == 0u) {
+        s_cnt[0][wave] = (uint32_t)__popcll(bc); s_cnt[1][wave] = (uint32_t)__popcll(ba);
+        // (a plain store of the same value from every wave that has one: no counter, no atomic - in the default flow no wave has)
+        if ((bc & ~ba) != 0ull) *(volatile uint32_t*)&counts[RS_NEXT_SINGLES] = 1u;
+    }
     __syncthreads();
     if (threadIdx.x < 2u) {
         uint32_t total = 0;
@@ -2070,6 +2076,10 @@ __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(
     WfParams w = wk;
     if (!resolve_round(w)) return;
     if (blockIdx.x * kResumeThreads >= w.n_prev_closest + w.n_prev_any) return;  // the grid is sized for the most the queues can hold
+    // In the default flow the reflection ray leaves with its hit's first shadow ray: every closest-queue entry of a big round is a
+    // duplicate (resumed from its shadow entry), and the workgroups over that queue - half of the launch - would load their entries,
+    // take part in a block_push that appends nothing, and leave. The round state says when that is so (RS_N_SINGLES: block_push, wf_advance).
+    if (w.counts[RS_N_SINGLES] == 0u && (blockIdx.x + 1u) * kResumeThreads <= w.n_prev_closest) return;
     const uint32_t t = blockIdx.x * kResumeThreads + threadIdx.x;
     const uint32_t total = w.n_prev_closest + w.n_prev_any;
     Ctx c{w, 0, 0ull, 0ull, 0ull, false, false, 0u, 0u, make_float4(0.f, 0.f, 0.f, 0.f), false, {}, {}, {}, {}};
@@ -2901,6 +2911,8 @@ __global__ __launch_bounds__(256) void wf_advance(uint32_t* __restrict__ rs, uin
     rs[RS_N_ANY] = na;
     rs[RS_NEXT_CLOSEST] = 0u;
     rs[RS_NEXT_ANY] = 0u;
+    rs[RS_N_SINGLES] = rs[RS_NEXT_SINGLES];
+    rs[RS_NEXT_SINGLES] = 0u;
     rs[RS_CUR] ^= 1u;
     if (nc + na == 0u) rs[RS_FINISH] = 2u;
     else if (allow_finish && nc + na <= finish_threshold) rs[RS_FINISH] = 1u;
@@ -2911,6 +2923,7 @@ __global__ __launch_bounds__(256) void wf_advance(uint32_t* __restrict__ rs, uin
 // has to be put down.
 __global__ void wf_identity_round(uint32_t* __restrict__ rs, uint32_t n) {
     rs[RS_N_CLOSEST] = n;
+    rs[RS_N_SINGLES] = 1u;  // (the identity queue has no shadow queue next to it)
     rs[RS_ROUNDS] = 1u;
 }
 
