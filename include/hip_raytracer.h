@@ -111,8 +111,7 @@ typedef enum rt_kernel {
                                     v_sqrt_f32, normalize as the OpenCL library's scaled v_rsq_f32 (a zero vector stays zero), dot as an
                                     fma chain, contraction as the default. Someone who renders with the reference's OpenCLRaytracer on
                                     an AMD GPU gets that picture. Refused (RT_ERR_INVALID_ARGUMENT) together with RT_FLAG_UNFUSED or
-                                    RT_FLAG_FAST_PHONG, and for scenes with triangles (type 2). The default organisation renders it
-                                    (RT_FRAME_KERNEL / RT_STEP_ROUNDS do not apply); a scene with a light inside an object's bounding
+                                    RT_FLAG_FAST_PHONG, and for scenes with triangles (type 2). A scene with a light inside an object's bounding
                                     sphere, or a directional light of direction 0 or of |d|^2 outside (1e-30, 1e30), is rendered with
                                     RT_FLAG_LITERAL set by rt_create. */
 

@@ -23,7 +23,7 @@ INVALID_ARGUMENT = -1
 
 
 def clean_env(monkeypatch):
-    for k in ("RT_RENDER_PASSES", "RT_RENDER_SPLIT", "RT_FRAME_KERNEL", "RT_STEP_ROUNDS"):
+    for k in ("RT_RENDER_PASSES", "RT_RENDER_SPLIT"):
         monkeypatch.delenv(k, raising=False)
 
 

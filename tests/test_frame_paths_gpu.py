@@ -1,8 +1,8 @@
-"""GPU: round 4's two other routes through a large-scene shade_and_reflect frame - rounds of {closest-hit walk, wf_step}
-(RT_STEP_ROUNDS=1) and the whole frame in one persistent launch (wf_frame, RT_FRAME_KERNEL=1: stepper / walker waves, LDS
-rings) - against the round machine and the oracle. Both test every shadow ray inside the step (the last light's through its
-light tile, the stale-specular scans' through the grid) and call the round machine's own device functions: frames and ray
-counts must be identical, bit for bit, whatever the route (shade_and_reflect_kernel.cl:244-285)."""
+"""GPU: a large-scene shade_and_reflect frame through the default organisation (the round machine over grid, block grid and
+light tiles) against independent witnesses: the brute-force wavefront context (path="wavefront", grid=False: no grid, no tiles,
+every ray against every object), the oracle, and - for a shard - the whole frame of the same kind of context. Frames, primary
+hits and reference ray counts must be identical, bit for bit, whatever the acceleration structure leaves out
+(shade_and_reflect_kernel.cl:244-285). Then: Render() in passes is the one-pass frame."""
 import numpy as np
 import pytest
 
@@ -11,50 +11,42 @@ from test_block_walk_gpu import _scene
 
 pytestmark = pytest.mark.gpu
 
-ROUTES = {"rounds": {}, "step_rounds": {"RT_STEP_ROUNDS": "1"}, "frame_kernel": {"RT_FRAME_KERNEL": "1"}}
-
 
 def hip(*a, **k):
     from opencl_raytracer_amd.hip_raytracer import HIPRaytracer
     return HIPRaytracer(*a, **k)
 
 
-def _render_all(monkeypatch, make, want_stats=True):
-    out = {}
-    for name, env in ROUTES.items():
-        for k in ("RT_STEP_ROUNDS", "RT_FRAME_KERNEL"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        with make() as rt:
-            frame = rt.Render()
-            again = rt.Render()
-            st = rt.count_rays() if want_stats else None
-            t, idx = rt.render_aux()
-        assert np.array_equal(frame.view(np.uint32), again.view(np.uint32)), name
-        out[name] = (frame, (st.rays_reference, st.rays_traced, st.hit_pixels) if st else None, t, idx, st.rounds if st else 0)
-    return out
+def _render(make):
+    """frame, (rays_reference, rays_traced, hit_pixels), primary t, primary index - of a context whose repeated Render() is
+    the same frame, bit for bit"""
+    with make() as rt:
+        frame = rt.Render()
+        again = rt.Render()
+        st = rt.count_rays()
+        t, idx = rt.render_aux()
+    assert np.array_equal(frame.view(np.uint32), again.view(np.uint32))
+    return frame, (st.rays_reference, st.rays_traced, st.hit_pixels), t, idx
 
 
 @pytest.mark.parametrize("depth", [0, 1, 4])
-def test_three_routes_one_frame(monkeypatch, depth):
+def test_default_frame_is_the_brute_force_frame(depth):
     rng = np.random.default_rng(21 + depth)
     objs, lights = _scene(rng, 1600, 4, 40, lights=3)
     W, H = 192, 136
     z = float(camera.camera_z(H))
-    got = _render_all(monkeypatch, lambda: hip(objs, lights, None, depth, camera=(W, H, z)))
-    base = got["rounds"]
+    base = _render(lambda: hip(objs, lights, None, depth, camera=(W, H, z)))
+    brute = _render(lambda: hip(objs, lights, None, depth, camera=(W, H, z), path="wavefront", grid=False))
     assert (base[3] >= 0).sum() > 2000
-    for name in ("step_rounds", "frame_kernel"):
-        assert np.array_equal(got[name][0].view(np.uint32), base[0].view(np.uint32)), name
-        assert got[name][1] == base[1], name
-        assert np.array_equal(got[name][3], base[3]) and same_floats(got[name][2], base[2]), name
-    assert got["step_rounds"][4] <= depth + 1 and got["frame_kernel"][4] <= 1   # no shadow rounds, no stragglers
+    assert np.array_equal(base[0].view(np.uint32), brute[0].view(np.uint32))
+    assert (base[1][0], base[1][2]) == (brute[1][0], brute[1][2])   # rays_reference, hit_pixels
+    assert np.array_equal(base[3], brute[3]) and same_floats(base[2], brute[2])
+    assert base[1][1] <= base[1][0]   # rays_traced <= rays_reference: the tiles only ever leave rays out
 
 
-def test_routes_against_the_oracle_with_stale_specular_scans(monkeypatch, restatement):
+def test_default_frame_against_the_oracle_with_stale_specular_scans(restatement):
     """Many hits face away from the last light but not from earlier ones (lights on opposite sides of the cloud): the light
-    loop's backward scan goes on to earlier lights - inside the step on the new routes, as queued shadow rays on the old one."""
+    loop's backward scan goes on to earlier lights, as queued shadow rays of further rounds."""
     rng = np.random.default_rng(5)
     objs, _ = _scene(rng, 700, 2, 20, lights=1)
     props = R.LightProperties((.1, .1, .1), (.5, .5, .5), (.6, .6, .6))
@@ -62,33 +54,41 @@ def test_routes_against_the_oracle_with_stale_specular_scans(monkeypatch, restat
                              R.make_light(props, position=(0.3, -0.2, -1.0, 0.0)), R.make_light(props, position=(55.0, -5.0, 12.0, 1.0))])
     rays = camera.crop_rays(1024, 1024, 512 - 48, 512 - 32, 96, 64)
     want = restatement[True].render("shade_and_reflect", objs, lights, rays, 3)
-    got = _render_all(monkeypatch, lambda: hip(objs, lights, rays, 3))
-    for name, (frame, counts, t, idx, _) in got.items():
-        assert compare_frames(frame, want["out"]) <= 1e-5, name
-        assert counts[0] == want["rays_ref"], name
-        assert np.array_equal(idx, want["hit_index"]) and same_floats(t, want["hit_t"]), name
-    for name in ("step_rounds", "frame_kernel"):
-        assert np.array_equal(got[name][0].view(np.uint32), got["rounds"][0].view(np.uint32)), name
-        assert got[name][1] == got["rounds"][1], name
+    frame, counts, t, idx = _render(lambda: hip(objs, lights, rays, 3))
+    assert compare_frames(frame, want["out"]) <= 1e-5
+    assert counts[0] == want["rays_ref"]
+    assert np.array_equal(idx, want["hit_index"]) and same_floats(t, want["hit_t"])
+    brute = _render(lambda: hip(objs, lights, rays, 3, path="wavefront", grid=False))
+    assert np.array_equal(frame.view(np.uint32), brute[0].view(np.uint32))
+    assert (counts[0], counts[2]) == (brute[1][0], brute[1][2])
 
 
-def test_routes_on_a_shard_with_a_ragged_last_tile(monkeypatch):
-    """Interleaved row-tiles with padding work-items (wf_begin builds the first queue): rank 1 of 3."""
+def test_a_shard_is_its_tiles_of_the_whole_frame():
+    """Interleaved row-tiles, 6.5 of them: rank 1 of 3, and rank 0, whose last tile is the ragged one (padding work-items:
+    wf_begin builds the first queue). A shard holds its tiles of the whole frame, back to back, bit for bit; the padding
+    work-items behind the frame's end are background."""
     from opencl_raytracer_amd import sharding, synthetic
     objs, lights = synthetic.spheres_and_lights(1200, 5)
     W, H = 160, 104  # 104 rows in tiles of 16: 6.5 tiles
+    n = W * H
     z = float(camera.camera_z(H))
-    frames = {}
-    for name, env in ROUTES.items():
-        for k in ("RT_STEP_ROUNDS", "RT_FRAME_KERNEL"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    tr = sharding.tile_rays_for_rows(W, 16)
+    with hip(objs, lights, None, 3, camera=(W, H, z)) as rt:
+        whole = rt.Render()
+    padding = 0
+    for rank in (1, 0):
         with hip(objs, lights, None, 3, camera=(W, H, z)) as rt:
-            rt.set_shard(sharding.tile_rays_for_rows(W, 16), 1, 3)
-            frames[name] = rt.Render()
-    for name in ("step_rounds", "frame_kernel"):
-        assert np.array_equal(frames[name].view(np.uint32), frames["rounds"].view(np.uint32)), name
+            rt.set_shard(tr, rank, 3)
+            shard = rt.Render()
+        tiles = sharding.local_tiles(n, tr, rank, 3)
+        assert shard.shape == (len(tiles) * tr, 4), rank
+        for k, tile in enumerate(tiles):
+            rows = min(tr, n - tile * tr)   # (the ragged last tile is the short one)
+            got = shard[k * tr:(k + 1) * tr]
+            assert np.array_equal(got[:rows].view(np.uint32), whole[tile * tr:tile * tr + rows].view(np.uint32)), (rank, tile)
+            assert np.array_equal(got[rows:], np.tile(np.float32([0, 0, 0, 1]), (tr - rows, 1))), (rank, tile)
+            padding += tr - rows
+    assert padding == sharding.n_tiles(n, tr) * tr - n > 0
 
 
 @pytest.mark.parametrize("mode,H,split", [("camera", 104, None), ("ray_buffer", 104, None), ("camera", 200, None), ("camera", 104, "1,1"),

@@ -7,8 +7,7 @@ Per scene x shape, for hittest, shade and shade_and_reflect at depth 3:
   2. bit for bit the same frame from uploaded rays, the other path, brute force, the literal loops; the unfused arithmetic
      against the unfused oracle; RT_FLAG_DEVICE_OPENCL as HIP against HIP (in-kernel = uploaded = brute force);
   3. every partition: the shards of all ranks stitched, Render() through forced passes with each split, the 8-bit frames,
-     three contexts on one GPU - the unsharded frame, bit for bit;
-  4. the 300-object scene under RT_FRAME_KERNEL=1 and RT_STEP_ROUNDS=1: the default organisation's frame, bit for bit.
+     three contexts on one GPU - the unsharded frame, bit for bit.
 `pytest -s` prints one summary line per scene."""
 import time
 
@@ -141,7 +140,7 @@ def check_partitions(monkeypatch, name, kernel, make, base, W, H, label):
 @pytest.mark.parametrize("name", SCENES)
 def test_every_route_to_a_frame(monkeypatch, restatement, name, shape):
     from opencl_raytracer_amd.hip_raytracer import MultiHIPRaytracer
-    for k in ("RT_RENDER_PASSES", "RT_RENDER_SPLIT", "RT_FRAME_KERNEL", "RT_STEP_ROUNDS"):
+    for k in ("RT_RENDER_PASSES", "RT_RENDER_SPLIT"):
         monkeypatch.delenv(k, raising=False)
     started = time.perf_counter()
     objs, lights = scene(name)
@@ -208,16 +207,6 @@ def test_every_route_to_a_frame(monkeypatch, restatement, name, shape):
             for fmt, _ in FORMATS if kernel != "hittest" else ():
                 assert np.array_equal(m.render_packed(fmt), packed_of(base["frame"], fmt)), f"{label}: three contexts, {fmt}"
                 tally["renders"] += 3
-        # 4. the other organisations of a large-scene frame
-        if name == "s300" and kernel == "shade_and_reflect":
-            for env in ("RT_FRAME_KERNEL", "RT_STEP_ROUNDS"):
-                monkeypatch.setenv(env, "1")
-                with make() as rt:
-                    got = snapshot(rt)
-                    tally["renders"] += 3
-                monkeypatch.delenv(env)
-                assert_same_snapshot(got, base, f"{label} {env}=1")
-                assert got["traced"] <= base["rays_ref"]
     tally["shapes"] += 1
     tally["seconds"] += time.perf_counter() - started
 
