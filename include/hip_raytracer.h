@@ -57,7 +57,9 @@ extern "C" {
  *      symbol (dlsym of rt_packed_pixel_bytes).
  *      Later addition, same version: supersampled frames - rt_set_supersampling, rt_supersampling, rt_local_pixels,
  *      rt_resolve_device, rt_set_supersampling_multi, rt_multi_frame_pixels. Additions only; a caller detects support by the
- *      symbol (dlsym of rt_set_supersampling). */
+ *      symbol (dlsym of rt_set_supersampling).
+ *      Later addition, same version: replaceable rays - rt_set_rays_device, rt_set_rays, rt_get_rays_info. Additions only; a caller
+ *      detects support by the symbol (dlsym of rt_set_rays_device). */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -144,7 +146,8 @@ int rt_create(rt_context** ctx, const void* objs, uint32_t n_objs, const void* l
  * start (0,0,0,1), direction (i - W/2, (H - j) - H/2, z, 0) for work-item j*W + i. width*height must equal n_rays.
  * Callable any number of times between renders, also on a context that has rendered: the NEXT render uses the new camera, and
  * the frame is the one a context created directly with that camera renders, bit for bit - whatever was rendered before
- * (tests/test_context_lifecycle_gpu.py). A camera replaces uploaded rays for good; there is no way back to the ray buffer.
+ * (tests/test_context_lifecycle_gpu.py). A camera replaces the ray buffer in use until the next rt_set_rays_device / rt_set_rays
+ * ("replaceable rays", below) puts a buffer in its place: the buffer uploaded at rt_create is not kept behind a camera's back.
  * The ray-domain guard (RT_FLAG_LITERAL, above) follows the camera: one whose grid holds a direction of |d|^2 outside
  * (1e-30, 1e30) - z = 0 with an even width and height, say - renders with the literal loops, and the next camera inside the
  * domain takes the context back to the default path. A scene with triangles REFUSES such a camera
@@ -304,6 +307,56 @@ uint64_t rt_local_pixels(const rt_context* ctx);    /* rt_local_rays() / s^2: wh
  * behind the last pixel; zero pixels: RT_OK, nothing launched. Anything else: RT_ERR_INVALID_ARGUMENT. */
 int      rt_resolve_device(rt_context* ctx, const void* d_samples, uint32_t sample_width, uint32_t sample_rows, uint32_t s,
                            int format, void* d_out, void* hip_stream);
+
+/* ---- replaceable rays ----------------------------------------------------------------------------------------------------------
+ * The fourth piece of a live context's state next to camera, shard and factor: its primary rays, replaced from DEVICE memory (rays
+ * another kernel or a host framework computed on the GPU: a panned, rolled or moved pinhole, a fisheye) or from host memory. The next
+ * frame is the one a context created with those rays and RT_FLAG_NO_RAYGEN renders, bit for bit, whatever was rendered before.
+ *
+ * rt_set_rays_device: d_rays is n_rays records of 32 bytes (start, direction) in work-item order, 16-byte aligned, on the context's
+ * device; n_rays must equal the context's ray count (rt_set_camera's width * height == n_rays: the state buffers are sized by it).
+ * The call enqueues a read-only scan of the rays (csrc/rt_rays.hip) on hip_stream (NULL = legacy default stream) - behind the
+ * caller's own kernels that produce them - waits for its verdict, and, if the context can render these rays, copies them
+ * device-to-device into a buffer of its own (allocated by the first call, also for a context created with rays = NULL) and waits
+ * for the copy. It is synchronous like rt_create: when it returns the caller may overwrite or free d_rays, and the next render on
+ * any stream sees the new rays. Renders of this context still in flight on ANOTHER stream must be ordered by the caller, as for
+ * every other entry point. A refused call leaves the context exactly as it was (the scan runs before the copy).
+ * Refused with RT_ERR_INVALID_ARGUMENT: a NULL or misaligned pointer, another n_rays, a supersampling factor > 1 (it needs a pinhole
+ * grid; rt_set_supersampling(s > 1) after this call is refused by its own rule), and - for a scene with triangles, which only the
+ * grid path traces - rays that would need the literal loops or brute force (below); the context keeps rendering what it rendered.
+ * rt_set_rays is the host twin: it stages the array in device memory and takes the same route.
+ *
+ * The scan computes what rt_create's loops over an uploaded array compute, in fp32, nothing contracted, left to right:
+ *   dir_w_zero            every direction.w == 0.0f
+ *   directions_in_domain  every dd = (dx*dx + dy*dy) + dz*dz has dd > 1e-30f && dd < 1e30f (a NaN fails)
+ *   starts_ok             every start.w == 1.0f and (sx + sy) + sz finite (finite components whose fp32 sum overflows fail)
+ *   origin_lo / origin_hi the numeric minimum / maximum of start.x, .y, .z (meaningful only when starts_ok)
+ * and the verdict follows the rays in use, frame by frame:
+ *   - not directions_in_domain: the literal loops (RT_FLAG_LITERAL, above), until the next rays or camera inside the domain;
+ *   - the conservative grid built at rt_create (fine grid, block grid, light tiles) serves the frame only if dir_w_zero, starts_ok
+ *     and the origin box lies inside the box the grid's radii were derived for (box_lo / box_hi: the create-time origins united with
+ *     the padded object bounds). Otherwise the frame is rendered as RT_FLAG_NO_GRID renders it - same pixels,
+ *     every object tested - and the next rays inside the box, or the next camera, bring the grid back. No grid is rebuilt.
+ * No pinhole grid is recognised in replaced rays (as with RT_FLAG_NO_RAYGEN): rt_stats_t::pinhole is 0, width and height are 0. A
+ * later rt_set_camera takes the context back to in-kernel rays, a later rt_set_rays* back to a buffer. Shards, rt_render's passes,
+ * aux buffers, 8-bit frames and rt_count_rays work as for rays uploaded at rt_create. */
+typedef struct rt_rays_info_t {
+    uint32_t source;                /* 0 none yet (rays = NULL and no camera), 1 in-kernel pinhole grid, 2 the ray buffer     */
+    uint32_t dir_w_zero;            /* the three predicates of the rays in use (a pinhole grid: 1, domain by its camera, 1)   */
+    uint32_t directions_in_domain;
+    uint32_t starts_ok;
+    float    origin_lo[3];          /* box of the origins; (0,0,0) for a pinhole grid and when !starts_ok. For rays uploaded at */
+    float    origin_hi[3];          /* rt_create: united with (0,0,0), as the grid's box took them                             */
+    double   box_lo[3];             /* the box the grid's radii were derived for (0 when grid_built == 0)                      */
+    double   box_hi[3];
+    uint32_t grid_built;            /* rt_create built a conservative grid                                                     */
+    uint32_t grid_in_use;           /* ... and the next frame's rays are served by it (0 also while `literal`)                 */
+    uint32_t literal;               /* the next frame renders with the literal loops                                           */
+    uint32_t reserved;
+} rt_rays_info_t;
+int rt_set_rays_device(rt_context* ctx, const void* d_rays, uint64_t n_rays, void* hip_stream);
+int rt_set_rays(rt_context* ctx, const void* rays, uint64_t n_rays);
+int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid for every context, also one that never called the setters */
 
 void rt_destroy(rt_context* ctx);
 

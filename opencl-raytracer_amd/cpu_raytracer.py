@@ -29,6 +29,9 @@ def load_library():
         lib.cpu_rt_render.restype = ctypes.c_int
         lib.cpu_rt_render.argtypes = [ctypes.c_int, u32, vp, u32, vp, u32, vp, u64, vp, ctypes.c_uint, ctypes.POINTER(u64),
                                       ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint)]
+        if hasattr(lib, "cpu_rt_render_set_rays"):
+            lib.cpu_rt_render_set_rays.restype = ctypes.c_int
+            lib.cpu_rt_render_set_rays.argtypes = lib.cpu_rt_render.argtypes + [vp]
         if hasattr(lib, "cpu_rt_render_supersampled"):
             lib.cpu_rt_render_supersampled.restype = ctypes.c_int
             lib.cpu_rt_render_supersampled.argtypes = lib.cpu_rt_render.argtypes + [u32, u64]
@@ -52,6 +55,15 @@ class CPURaytracer:
         self.rays_traced = self.hit_pixels = 0
         self.seconds = 0.0
         self.threads_used = 0
+        self.new_rays = None
+
+    def set_rays(self, rays):
+        """CPURaytracer::SetRays, the option HIPRaytracer.set_rays is on the GPU: the next Render() traces these rays - as many as
+        the object was constructed with - instead of the constructor's."""
+        rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        if len(rays) != len(self.rays):
+            raise ValueError("set_rays: as many rays as the object was constructed with")
+        self.new_rays = rays
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)
@@ -64,7 +76,11 @@ class CPURaytracer:
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
         args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
                 ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
-        if self.supersample != 1:
+        if self.new_rays is not None:
+            if self.supersample != 1:
+                raise ValueError("replaced rays are no sample grid: set_rays and supersample exclude each other")
+            rc = self._lib.cpu_rt_render_set_rays(*args, ptr(self.new_rays))
+        elif self.supersample != 1:
             rc = self._lib.cpu_rt_render_supersampled(*args, self.supersample, self.sample_width)
             if rc != 0:
                 raise ValueError("cpu_rt_render_supersampled: unsupported arguments (factor 1..4, a colour kernel, rays in whole rows of "

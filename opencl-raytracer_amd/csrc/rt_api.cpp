@@ -7,6 +7,7 @@
 #include "rt_kernels.h"
 #include "rt_pack.h"
 #include "rt_resolve.h"
+#include "rt_rays.h"
 
 #include <hip/hip_runtime.h>
 
@@ -167,6 +168,14 @@ struct rt_context {
     bool affine_w = true;                   // every mv / mvInverse has bottom row (0,0,0,1) exactly
     bool primary_w_one = true;              // every uploaded primary ray has start.w == 1
     double origin_lo[3] = {0, 0, 0}, origin_hi[3] = {0, 0, 0};  // box of the primary ray origins
+    // Replaceable rays (rt_set_rays_device): the box build_grid's radii were derived for - the create-time origins united with the
+    // padded object bounds, before the one-cell padding - and whether the ray buffer in use may be served by
+    // the grid: direction.w = 0, start.w = 1, every origin inside that box. Off the grid a frame is rendered as RT_FLAG_NO_GRID
+    // renders it (grid_in_use); a camera's rays start at the origin, which the box always holds.
+    double grid_box_lo[3] = {0, 0, 0}, grid_box_hi[3] = {0, 0, 0};
+    bool rays_off_grid = false;
+    rt::RayScan* d_scan = nullptr;          // the ray scan's result (rt_rays.hip) and its pinned host mirror
+    rt::RayScan* h_scan = nullptr;
     rt::WavefrontBuffers wf;
     bool last_wavefront = false;
     uint32_t last_rounds = 0;
@@ -557,12 +566,15 @@ void apply_ray_domain(rt_context* c) {
     c->flags = c->base_flags | (out ? RT_FLAG_LITERAL : 0u);
 }
 
+// the grid (fine grid, block grid, light tiles) serves the rays in use: always a camera's, a ray buffer's unless a scan said no
+bool grid_in_use(const rt_context* c) { return c->grid.enabled && (c->pinhole || !c->rays_off_grid); }
+
 bool use_wavefront(const rt_context* c) {
     if (c->has_triangles) return true;
     if (c->flags & RT_FLAG_WAVEFRONT) return true;
     if (c->flags & RT_FLAG_MONOLITHIC) return false;
     if (c->n_objs >= kWavefrontMinObjects) return true;
-    return c->n_objs >= kWavefrontGridMinObjects && c->grid.enabled && !(c->flags & RT_FLAG_LITERAL);
+    return c->n_objs >= kWavefrontGridMinObjects && grid_in_use(c) && !(c->flags & RT_FLAG_LITERAL);
 }
 
 void free_wavefront(rt_context* c) {
@@ -705,6 +717,12 @@ int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count) {
         int rc = ensure_wavefront(c);
         if (rc) return rc;
         if (!had_buffers) c->setup.buffers_ms += sw.lap_ms();
+        {   // per frame: the grid's tables, or - for a ray buffer they were not built for - none, which is RT_FLAG_NO_GRID's frame
+            const bool on = grid_in_use(c);
+            c->wf.grid = on ? c->grid : rt::GridDesc{};
+            c->wf.light_tiles = on ? c->light_tiles : rt::LightTiles{};
+            c->wf.blocks = on ? c->blocks : rt::BlockGrid{};
+        }
         // a first-round wave is an 8 x 8 block of pixels (work-items in tile order) or 64 pixels of one row: the tile lists follow
         const uint32_t col_shift = p.wf_tile_order ? 3u : 6u;
         if (c->tiles_dirty || c->tiles_built_for != col_shift) {
@@ -1256,6 +1274,9 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
         if (dim[a] < 1) dim[a] = 1;
         if (dim[a] > 1040) return RT_OK;
     }
+    // the box D and S_max above were taken over: a later ray buffer (rt_set_rays_device) whose origins lie inside it is covered
+    // by the radii as built
+    for (int a = 0; a < 3; ++a) { c->grid_box_lo[a] = lo[a]; c->grid_box_hi[a] = hi[a]; }
     const float cellf = (float)cell;
     const float lof[3] = {(float)glo[0], (float)glo[1], (float)glo[2]};
     // cell range of a sphere's box, computed with the SAME float origin / cell edge the kernels use (rg already
@@ -2040,6 +2061,118 @@ int rt_set_camera(rt_context* c, uint32_t width, uint32_t height, float z) {
     return RT_OK;
 }
 
+// ---- replaceable rays (hip_raytracer.h) ----
+// Scan (rt_rays.hip) on the caller's stream, verdict on the host, then - only if the context can render these rays - the copy
+// into the context's own buffer and the new state. Nothing of the context changes before the verdict is accepted.
+static int check_set_rays(rt_context* c, const void* rays, uint64_t n_rays) {
+    if (!rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "the ray array is NULL");
+    if (n_rays != c->n_rays || n_rays == 0)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "n_rays must equal the context's ray count (the state buffers are sized by it)");
+    if (c->ss > 1)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "a supersampling factor > 1 needs a pinhole camera: set the factor to 1 before replacing the rays");
+    return RT_OK;
+}
+
+static int set_rays_from_device(rt_context* c, const void* d_src, uint64_t n_rays, hipStream_t stream) {
+    const int refused = check_set_rays(c, d_src, n_rays);
+    if (refused) return refused;
+    if (reinterpret_cast<uintptr_t>(d_src) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the ray array must be 16-byte aligned");
+    RT_DEVICE(c);
+    if (!c->d_scan) RT_HIP(c, hipMalloc((void**)&c->d_scan, sizeof(rt::RayScan)));
+    if (!c->h_scan) RT_HIP(c, hipHostMalloc((void**)&c->h_scan, sizeof(rt::RayScan), hipHostMallocDefault));
+    // engineering aid (RT_RAYS_TRACE=1, tools/ab/set_rays_timing.py): device time of the scan and of the copy, on stderr
+    const bool trace = std::getenv("RT_RAYS_TRACE") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EventPair { hipEvent_t* e; ~EventPair() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    if (trace) { RT_HIP(c, hipEventCreate(&ev[0])); RT_HIP(c, hipEventCreate(&ev[1])); }
+    if (trace) RT_HIP(c, hipEventRecord(ev[0], stream));
+    const hipError_t e = rt::launch_ray_scan(static_cast<const float4*>(d_src), n_rays, c->d_scan, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "ray scan launch");
+    if (trace) RT_HIP(c, hipEventRecord(ev[1], stream));
+    RT_HIP(c, hipMemcpyAsync(c->h_scan, c->d_scan, sizeof(rt::RayScan), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    const rt::RayScan v = *c->h_scan;
+    const bool dir_w_zero = !(v.flags & rt::kRayDirW), in_domain = !(v.flags & rt::kRayDomain), starts_ok = !(v.flags & rt::kRayStart);
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool inside = starts_ok;
+    for (int a = 0; a < 3 && starts_ok; ++a) {
+        const uint32_t lo_bits = rt::ray_unkey(~v.lo_inv[a]), hi_bits = rt::ray_unkey(v.hi[a]);
+        float f_lo, f_hi;
+        std::memcpy(&f_lo, &lo_bits, 4);
+        std::memcpy(&f_hi, &hi_bits, 4);
+        lo[a] = (double)f_lo;
+        hi[a] = (double)f_hi;
+        inside = inside && lo[a] >= c->grid_box_lo[a] && hi[a] <= c->grid_box_hi[a];
+    }
+    const bool on_grid = c->grid.enabled && dir_w_zero && starts_ok && inside;
+    if (c->has_triangles && (!on_grid || !in_domain))
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "triangle records are traced by the grid path only: these rays need the literal loops (a direction of |d|^2 outside "
+                    "(1e-30, 1e30)) or brute force (direction.w != 0, start.w != 1 or not finite, or an origin outside the box the grid was built for)");
+    float scan_ms = 0.f, copy_ms = 0.f;
+    if (trace) RT_HIP(c, hipEventElapsedTime(&scan_ms, ev[0], ev[1]));
+    if (!c->d_rays) RT_HIP(c, hipMalloc((void**)&c->d_rays, sizeof(rt_ray) * (size_t)n_rays));
+    if (trace) RT_HIP(c, hipEventRecord(ev[0], stream));
+    RT_HIP(c, hipMemcpyAsync(c->d_rays, d_src, sizeof(rt_ray) * (size_t)n_rays, hipMemcpyDeviceToDevice, stream));
+    if (trace) RT_HIP(c, hipEventRecord(ev[1], stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (trace) {
+        RT_HIP(c, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+        std::fprintf(stderr, "[rt_set_rays] scan %.4f ms copy %.4f ms rays %llu\n", (double)scan_ms, (double)copy_ms, (unsigned long long)n_rays);
+    }
+    c->have_rays = true;
+    c->pinhole = false;
+    c->width = c->height = 0;
+    c->z = 0.f;
+    c->dir_w_zero = dir_w_zero;
+    c->primary_w_one = starts_ok;
+    c->rays_out_of_domain = !in_domain;
+    c->rays_off_grid = !on_grid;
+    for (int a = 0; a < 3; ++a) { c->origin_lo[a] = lo[a]; c->origin_hi[a] = hi[a]; }
+    apply_ray_domain(c);
+    c->rects_dirty = true;
+    c->tiles_dirty = true;
+    return RT_OK;
+}
+
+int rt_set_rays_device(rt_context* c, const void* d_rays, uint64_t n_rays, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    return set_rays_from_device(c, d_rays, n_rays, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_set_rays(rt_context* c, const void* rays, uint64_t n_rays) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const int refused = check_set_rays(c, rays, n_rays);
+    if (refused) return refused;
+    RT_DEVICE(c);
+    void* staged = nullptr;  // the context's own buffer keeps the rays in use until the scan has accepted the new ones
+    RT_HIP(c, hipMalloc(&staged, sizeof(rt_ray) * (size_t)n_rays));
+    hipError_t e = hipMemcpy(staged, rays, sizeof(rt_ray) * (size_t)n_rays, hipMemcpyHostToDevice);
+    const int rc = e == hipSuccess ? set_rays_from_device(c, staged, n_rays, c->stream) : fail_hip(c, e, "upload of the rays");
+    (void)hipFree(staged);
+    return rc;
+}
+
+int rt_get_rays_info(const rt_context* c, rt_rays_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    std::memset(info, 0, sizeof(*info));
+    info->source = c->pinhole ? 1u : (c->have_rays ? 2u : 0u);
+    const bool buffer = info->source == 2u;
+    info->dir_w_zero = (!buffer || c->dir_w_zero) ? 1u : 0u;
+    info->directions_in_domain = (c->pinhole ? !c->camera_out_of_domain : !c->rays_out_of_domain) ? 1u : 0u;
+    info->starts_ok = (!buffer || c->primary_w_one) ? 1u : 0u;
+    for (int a = 0; a < 3; ++a) {
+        info->origin_lo[a] = (buffer && c->primary_w_one) ? (float)c->origin_lo[a] : 0.f;
+        info->origin_hi[a] = (buffer && c->primary_w_one) ? (float)c->origin_hi[a] : 0.f;
+        info->box_lo[a] = c->grid.enabled ? c->grid_box_lo[a] : 0.0;
+        info->box_hi[a] = c->grid.enabled ? c->grid_box_hi[a] : 0.0;
+    }
+    info->grid_built = c->grid.enabled ? 1u : 0u;
+    info->grid_in_use = (grid_in_use(c) && !(c->flags & RT_FLAG_LITERAL)) ? 1u : 0u;
+    info->literal = (c->flags & RT_FLAG_LITERAL) ? 1u : 0u;
+    return RT_OK;
+}
+
 int rt_set_shard(rt_context* c, uint64_t tile_rays, uint32_t rank, uint32_t world) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (world == 0 || rank >= world || (world > 1 && tile_rays == 0))
@@ -2450,6 +2583,8 @@ void rt_destroy(rt_context* c) {
     if (c->h_pack) (void)hipHostFree(c->h_pack);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_samples) (void)hipFree(c->d_samples);
+    if (c->d_scan) (void)hipFree(c->d_scan);
+    if (c->h_scan) (void)hipHostFree(c->h_scan);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);
     if (c->d_counters) (void)hipFree(c->d_counters);

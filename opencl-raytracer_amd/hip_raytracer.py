@@ -38,6 +38,7 @@ EXPORTS = [
     "rt_packed_pixel_bytes", "rt_pack_device", "rt_render_device_packed", "rt_render_packed", "rt_render_multi_packed",
     "rt_set_supersampling", "rt_supersampling", "rt_local_pixels", "rt_resolve_device", "rt_set_supersampling_multi",
     "rt_multi_frame_pixels",
+    "rt_set_rays_device", "rt_set_rays", "rt_get_rays_info",
 ]
 
 
@@ -62,6 +63,24 @@ class RTSetupTimes(ctypes.Structure):
 
     def as_dict(self):
         return {n: float(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RTRaysInfo(ctypes.Structure):
+    _fields_ = [
+        ("source", ctypes.c_uint32), ("dir_w_zero", ctypes.c_uint32), ("directions_in_domain", ctypes.c_uint32),
+        ("starts_ok", ctypes.c_uint32), ("origin_lo", ctypes.c_float * 3), ("origin_hi", ctypes.c_float * 3),
+        ("box_lo", ctypes.c_double * 3), ("box_hi", ctypes.c_double * 3), ("grid_built", ctypes.c_uint32),
+        ("grid_in_use", ctypes.c_uint32), ("literal", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        out = {}
+        for n, t in self._fields_:
+            if n == "reserved":
+                continue
+            v = getattr(self, n)
+            out[n] = int(v) if t is ctypes.c_uint32 else np.array(list(v), dtype=np.float32 if t._type_ is ctypes.c_float else np.float64)
+        return out
 
 
 _lib = None
@@ -155,6 +174,13 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_set_supersampling_multi.argtypes = [vp, u32]
         lib.rt_multi_frame_pixels.restype = u64
         lib.rt_multi_frame_pixels.argtypes = [vp]
+    if hasattr(lib, "rt_set_rays_device"):  # (the same: a build from before replaceable rays)
+        lib.rt_set_rays_device.restype = i32
+        lib.rt_set_rays_device.argtypes = [vp, vp, u64, vp]
+        lib.rt_set_rays.restype = i32
+        lib.rt_set_rays.argtypes = [vp, vp, u64]
+        lib.rt_get_rays_info.restype = i32
+        lib.rt_get_rays_info.argtypes = [vp, ctypes.POINTER(RTRaysInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -356,8 +382,34 @@ class HIPRaytracer:
     # -- extensions over the reference interface -----------------------------------------------
     def set_camera(self, width: int, height: int, z: float):
         """Re-aim a live context (rt_set_camera): the next render is the width x height pinhole grid at z; width * height must
-        equal n_rays. Uploaded rays are replaced for good; the shard setting stays."""
+        equal n_rays. It replaces the ray buffer in use until the next set_rays; the shard setting stays."""
         self._check(self._lib.rt_set_camera(self._ctx, int(width), int(height), float(z)))
+
+    def set_rays(self, rays):
+        """Replace a live context's primary rays (hip_raytracer.h, "replaceable rays"): the next render is the one a context
+        created with these rays and raygen=False renders. `rays` is a numpy ray array as the constructor takes it
+        (rt_set_rays), or a torch tensor on the context's device - float32, contiguous, 8 n_rays elements: start.xyzw,
+        direction.xyzw per ray - which is scanned and copied on the GPU, ordered behind the work of torch's current stream
+        (rt_set_rays_device). Synchronous: on return the tensor may be overwritten."""
+        if isinstance(rays, np.ndarray):
+            rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+            self._check(self._lib.rt_set_rays(self._ctx, _ptr(rays), int(rays.shape[0])))
+            return
+        import torch
+        if not isinstance(rays, torch.Tensor):
+            raise TypeError("set_rays takes a numpy ray array or a torch tensor on the context's device")
+        if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+            raise ValueError("a device ray tensor is float32, contiguous, on the GPU, with 8 elements per ray")
+        with torch.cuda.device(rays.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        self._check(self._lib.rt_set_rays_device(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.numel() // 8,
+                                                 ctypes.c_void_p(stream) if stream else None))
+
+    def rays_info(self) -> dict:
+        """rt_get_rays_info: where the next frame's primary rays come from, what the scan found, and whether the grid serves them."""
+        info = RTRaysInfo()
+        self._check(self._lib.rt_get_rays_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
 
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))

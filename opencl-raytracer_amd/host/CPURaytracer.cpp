@@ -332,7 +332,14 @@ void CPURaytracer::SetSupersampling(unsigned int s, size_t sample_width) {
     ss_width = sample_width;
 }
 
+void CPURaytracer::SetRays(const std::vector<Ray3D>& rays_) {
+    if (rays_.size() != rays.size()) throw std::invalid_argument("SetRays: as many rays as the object was constructed with");
+    own_rays = rays_;
+    replaced = true;
+}
+
 cl_float4* CPURaytracer::Render() {
+    const std::vector<Ray3D>& rays = Rays();  // (the constructor's, or SetRays' copy: everything below reads these)
     const size_t n = rays.size();
     for (size_t i = 0; i < n; ++i) {  // the buffer as the reference uploads it: {0,0,0,1} (OpenCLRaytracer.cpp:32); hittest: "no hit"
         if (kernel == kHittest) pixels[i] = cl_float4{{MAX_FLOAT, 0.f, 0.f, 0.f}};

@@ -35,7 +35,11 @@ public:
     // pixels, the s x s samples of each added in fp32 in (b, a) order and multiplied once by fl(1 / s^2) - the same loop on the
     // host. s = 1 (the default) is off. Throws std::invalid_argument for what rt_set_supersampling refuses.
     void SetSupersampling(unsigned int s, size_t sample_width);
-    size_t Pixels() const { return rays.size() / ((size_t)ss * ss); }
+    size_t Pixels() const { return Rays().size() / ((size_t)ss * ss); }
+
+    // Replaceable rays, the same option as HIPRaytracer's: the next Render() traces a copy of `rays` - as many as the object was
+    // constructed with, std::invalid_argument otherwise - instead of the constructor's.
+    void SetRays(const std::vector<Ray3D>& rays);
 
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
@@ -55,6 +59,9 @@ private:
     size_t ss_width = 0;
     std::vector<cl_float4> filtered;
     uint64_t rays_traced = 0, hit_pixels = 0;
+    std::vector<Ray3D> own_rays;        // SetRays' copy; empty: the constructor's rays (IRaytracer holds them by reference)
+    bool replaced = false;
+    const std::vector<Ray3D>& Rays() const { return replaced ? own_rays : rays; }
 
 public:
     ~CPURaytracer() override;

@@ -105,6 +105,16 @@ void HIPRaytracer::SetSupersampling(unsigned int s) {
     if (rt_set_supersampling(ctx, s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetSupersampling: ") + rt_last_error(ctx));
 }
 
+void HIPRaytracer::SetRays(const std::vector<Ray3D>& rays_) {
+    if (multi) throw std::runtime_error("HIPRaytracer::SetRays: not available on the several-GPU object");
+    if (rt_set_rays(ctx, rays_.data(), rays_.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRays: ") + rt_last_error(ctx));
+}
+
+void HIPRaytracer::SetRaysDevice(const void* d_rays, size_t n, void* stream) {
+    if (multi) throw std::runtime_error("HIPRaytracer::SetRaysDevice: not available on the several-GPU object");
+    if (rt_set_rays_device(ctx, d_rays, n, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRaysDevice: ") + rt_last_error(ctx));
+}
+
 size_t HIPRaytracer::Pixels() const {
     if (multi) {
         const size_t s = rt_supersampling(rt_multi_context(multi, 0));

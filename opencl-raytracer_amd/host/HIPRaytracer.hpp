@@ -45,6 +45,14 @@ public:
     void SetSupersampling(unsigned int s);
     size_t Pixels() const;
 
+    // Replaceable rays (hip_raytracer.h, "replaceable rays"): the next Render() uses these primary rays - as many as the object was
+    // constructed with - instead of the constructor's (which are not touched: the reference's interface holds them by const
+    // reference). SetRays takes host rays, SetRaysDevice n records of 32 bytes in DEVICE memory, scanned and copied on the GPU
+    // behind the work already on `stream` (a hipStream_t; nullptr = the legacy default stream). Both are synchronous. One-GPU
+    // objects only; throws std::runtime_error with the library's message for what it refuses.
+    void SetRays(const std::vector<Ray3D>& rays);
+    void SetRaysDevice(const void* d_rays, size_t n, void* stream = nullptr);
+
     rt_stats_t Stats();
     rt_context* Context() { return ctx; }
 

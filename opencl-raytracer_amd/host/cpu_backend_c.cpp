@@ -11,6 +11,17 @@
 #include "CPURaytracer.hpp"
 #include "rt_records.h"
 
+namespace {
+thread_local const rt_ray* g_new_rays = nullptr;  // cpu_rt_render_set_rays: the rays SetRays gets before Render()
+
+Ray3D host_ray(const rt_ray& r) {
+    Ray3D h(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f));
+    h.start = rtm::vec4(r.start[0], r.start[1], r.start[2], r.start[3]);
+    h.direction = rtm::vec4(r.direction[0], r.direction[1], r.direction[2], r.direction[3]);
+    return h;
+}
+}  // namespace
+
 extern "C" {
 
 int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
@@ -67,15 +78,16 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
     }
     std::vector<Ray3D> rs;
     rs.reserve(n_rays);
-    for (uint64_t i = 0; i < n_rays; ++i) {
-        Ray3D r(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f));
-        r.start = rtm::vec4(rays[i].start[0], rays[i].start[1], rays[i].start[2], rays[i].start[3]);
-        r.direction = rtm::vec4(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2], rays[i].direction[3]);
-        rs.push_back(r);
-    }
+    for (uint64_t i = 0; i < n_rays; ++i) rs.push_back(host_ray(rays[i]));
     std::unique_ptr<CPURaytracer> backend(new CPURaytracer(objects, ls, rs, max_bounces, static_cast<CPURaytracer::Kernel>(kernel), threads));
     if (supersample != 1) {
         try { backend->SetSupersampling(supersample, (size_t)sample_width); } catch (const std::exception&) { return -1; }
+    }
+    if (g_new_rays) {
+        std::vector<Ray3D> replaced;
+        replaced.reserve(n_rays);
+        for (uint64_t i = 0; i < n_rays; ++i) replaced.push_back(host_ray(g_new_rays[i]));
+        try { backend->SetRays(replaced); } catch (const std::exception&) { return -1; }
     }
     const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
@@ -91,6 +103,19 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
     if (seconds) *seconds = std::chrono::duration<double>(t1 - t0).count();
     if (threads_used) *threads_used = backend->Threads();
     return 0;
+}
+
+// CPURaytracer::SetRays through the C entry: the backend is constructed with `rays_` and renders `new_rays_` (as many) after
+// SetRays - the frame must not depend on the constructor's rays. Same outputs and return value as cpu_rt_render.
+int cpu_rt_render_set_rays(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                           const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                           uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, const void* new_rays_) {
+    g_new_rays = static_cast<const rt_ray*>(new_rays_);
+    const int rc = new_rays_ ? cpu_rt_render_supersampled(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced,
+                                                          hit_pixels, seconds, threads_used, 1, 0)
+                             : -1;
+    g_new_rays = nullptr;
+    return rc;
 }
 
 }  // extern "C"
