@@ -135,9 +135,24 @@ __device__ __forceinline__ T table_at(const T* __restrict__ base, uint32_t index
 }
 
 // screen tiles for pinhole primary rays (built on the host per camera, rt_api.cpp: build_screen_tiles)
+//
+// Depth key of an entry: a lower bound on any t the exact test can report for that object on a pinhole primary ray. Such a
+// ray starts at the origin with direction (x, y, z), z < 0 the same for every pixel, so the point o + t d has view-space
+// depth t z (one exact product of two fp32 numbers). By the invariant above (kWalkSlackCells) a reported hit with t not above
+// the current best has that point inside the object's registration sphere (c, R_grid) - the surface plus the fp32 error of
+// t - hence c.z - R <= t z <= c.z + R, and dividing by z < 0:   t >= (c.z + R) / z.   (A sphere that reaches the camera
+// plane, c.z + R >= 0, gets a key <= 0: no bound, t >= 0 anyway.)
+// Margin: build_screen_tiles forms (c.z + R) / z in double from the doubles the grid was registered with and z converted
+// exactly: two roundings, |error| <= 2^-52 |key|. It subtracts 2^-40 |key| (4096 times that), converts to float - which may
+// round UP by half an fp32 ulp - and takes the next float below, so the stored key is <= the real quotient. Beyond the fp32
+// range the key becomes -inf or FLT_MAX, a NaN becomes -inf: both only ever make the kernel test more.
+// A tile's entries ascend by key (equal keys: by index). wf_trace_primary_tiles leaves a list at the first entry whose key
+// is ABOVE the T of every lane (strict: T < key): every object from there on has t >= key > T on every lane, so it can
+// neither win nor tie, and since closest_take is order-free the objects before it give the brute-force loop's result. A lane
+// without a hit (T = kMaxFloat) or with a NaN fails the comparison: its wave walks the whole list.
 struct ScreenTiles {
     const uint32_t* __restrict__ tile_start;  // tiles_x * tiles_y + 1 offsets
-    const uint32_t* __restrict__ entries;     // object indices, ascending inside a tile
+    const uint2* __restrict__ entries;        // {object index, depth key (float bits)}, ascending key inside a tile
     uint32_t tiles_x;                         // tiles are 8 rows tall and 1 << col_shift pixels wide:
     uint32_t col_shift;                       //   3 (8 x 8, exactly a wave's block when work-items walk 8 x 8 blocks) or 6 (64 x 8: a wave is 64 pixels of a row)
     uint32_t global_begin, n_global;          // entries[global_begin ..): objects whose projection is the whole screen

@@ -315,25 +315,45 @@ __global__ __launch_bounds__(256) void wf_trace_closest(const WfParams wk) {
         atomicAdd(&w.rp.counters->tests, 2ull * w.rp.scene.n_pairs * lanes);
 }
 
-// one object of a wave-uniform list (scalar loads) against this lane's ray
+// one object of a wave-uniform list (scalar loads) against this lane's ray; the record by value, so that a caller can
+// have the next one on its way while this one is tested
+struct TileRecord {
+    f4 r0, r1, r2;
+    uint32_t type, pad0;
+};
+typedef uint32_t TileEntry __attribute__((ext_vector_type(2)));  // ScreenTiles::entries as a native vector (constant address space)
+__device__ __forceinline__ TileRecord tile_record(const RT_CONST HotObjectC* o) {
+    TileRecord r;
+    r.r0 = o->row0; r.r1 = o->row1; r.r2 = o->row2;
+    r.type = o->type;
+    r.pad0 = o->pad[0];
+    return r;
+}
 template <int AM>
-__device__ __forceinline__ void tile_candidate(const RT_CONST HotObjectC* o, int k, const Ray& ray, float& T, int& idx, bool& cur_sphere) {
-    const uint32_t type = o->type;
-    if (type == 2u) {  // triangle (extension)
-        const f4 r0 = o->row0, r1 = o->row1, r2 = o->row2;
+__device__ __forceinline__ void tile_candidate(const TileRecord& o, int k, const Ray& ray, float& T, int& idx, bool& cur_sphere) {
+    const f4 r0 = o.r0, r1 = o.r1, r2 = o.r2;
+    if (o.type == 2u) {  // triangle (extension)
         float t;
-        if (triangle_candidate(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z, r0.w, r1.w, r2.w, __uint_as_float(o->pad[0]), ray, t))
+        if (triangle_candidate(r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, r2.x, r2.y, r2.z, r0.w, r1.w, r2.w, __uint_as_float(o.pad0), ray, t))
             closest_take(t, k, false, T, idx, cur_sphere);
         return;
     }
-    float sx, sy, sz, dx, dy, dz;
-    object_space_one<AM, true>(o, ray, sx, sy, sz, dx, dy, dz);
-    closest_update_unordered<AM>(type, sx, sy, sz, dx, dy, dz, k, T, idx, cur_sphere);
+    // (object_space_one's arithmetic, rt_device.h, on a record in registers)
+    const float sx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float sz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
+    const float dx = row3<AM>(r0.x, r0.y, r0.z, ray.dx, ray.dy, ray.dz);
+    const float dy = row3<AM>(r1.x, r1.y, r1.z, ray.dx, ray.dy, ray.dz);
+    const float dz = row3<AM>(r2.x, r2.y, r2.z, ray.dx, ray.dy, ray.dz);
+    closest_update_unordered<AM>(o.type, sx, sy, sz, dx, dy, dz, k, T, idx, cur_sphere);
 }
 
 // First round of a pinhole frame: a wave holds 64 consecutive pixels of one row, i.e. one 64x8 screen tile, and
 // walks that tile's object list with wave-uniform scalar loads (plus the always-list). Waves that straddle tiles
 // (ragged ends) fall back to the per-lane grid walk. Order-free tie rules, so the result is the same either way.
+// The list is in depth order (rt_grid.h: ScreenTiles): the wave leaves it at the first entry whose key - the smallest t
+// that object can report - is above every lane's T. Entry e + 2 and the record of entry e + 1 are loaded while entry e is
+// tested; the look-ahead stops at the list's last entry, so nothing beyond the list is read.
 template <int AM>
 __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk) {
     WfParams w = wk;
@@ -355,17 +375,30 @@ __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk)
         const RT_CONST HotObjectC* hot = (const RT_CONST HotObjectC*)(p.scene.hot);
         for (uint32_t a = 0; a < w.grid.n_always; ++a) {
             const int k = (int)w.grid.always[a];
-            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
+            tile_candidate<AM>(tile_record(hot + k), k, ray, T, idx, cur_sphere);
         }
+        const RT_CONST TileEntry* entries = (const RT_CONST TileEntry*)(w.tiles.entries);
         for (uint32_t a = 0; a < w.tiles.n_global; ++a) {  // objects that project onto the whole screen
-            const int k = (int)w.tiles.entries[w.tiles.global_begin + a];
-            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
+            const int k = (int)entries[w.tiles.global_begin + a].x;
+            tile_candidate<AM>(tile_record(hot + k), k, ray, T, idx, cur_sphere);
         }
         const uint32_t e0 = w.tiles.tile_start[first], e1 = w.tiles.tile_start[first + 1];
-        tested = w.grid.n_always + w.tiles.n_global + (e1 - e0);
-        for (uint32_t e = e0; e < e1; ++e) {
-            const int k = (int)w.tiles.entries[e];
-            tile_candidate<AM>(hot + k, k, ray, T, idx, cur_sphere);
+        tested = w.grid.n_always + w.tiles.n_global;
+        if (e0 < e1) {
+            const uint32_t last = e1 - 1u;
+            TileEntry cur = entries[e0], next = entries[e0 < last ? e0 + 1u : last];
+            TileRecord rec = tile_record(hot + cur.x);
+            for (uint32_t e = e0;;) {
+                // every lane has a hit in front of this entry's nearest possible t, hence of every later entry's: done
+                // (a lane without a hit, T = kMaxFloat, or a NaN fails the comparison and keeps the wave going)
+                if (__ballot(!(T < __uint_as_float(cur.y))) == 0ull) break;
+                const TileRecord rec_next = tile_record(hot + next.x);
+                const TileEntry next2 = entries[e + 2u < last ? e + 2u : last];
+                tile_candidate<AM>(rec, (int)cur.x, ray, T, idx, cur_sphere);
+                ++tested;
+                if (++e == e1) break;
+                cur = next; next = next2; rec = rec_next;
+            }
         }
     } else {
         closest_hit_grid<AM, true>(w.grid, p.scene.hot, ray, T, idx, tested);
