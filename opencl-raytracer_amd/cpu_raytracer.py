@@ -35,6 +35,10 @@ def load_library():
         if hasattr(lib, "cpu_rt_render_supersampled"):
             lib.cpu_rt_render_supersampled.restype = ctypes.c_int
             lib.cpu_rt_render_supersampled.argtypes = lib.cpu_rt_render.argtypes + [u32, u64]
+        if hasattr(lib, "cpu_rt_render_set_pose"):
+            fp = ctypes.POINTER(ctypes.c_float)
+            lib.cpu_rt_render_set_pose.restype = ctypes.c_int
+            lib.cpu_rt_render_set_pose.argtypes = lib.cpu_rt_render.argtypes + [u32, u32, ctypes.c_float, fp, fp]
         _lib = lib
     return _lib
 
@@ -56,6 +60,22 @@ class CPURaytracer:
         self.seconds = 0.0
         self.threads_used = 0
         self.new_rays = None
+        self.pose = None
+
+    def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
+        """CPURaytracer::SetPose, the option HIPRaytracer.set_pose is on the GPU: the next Render() traces
+        rays.posed_rays(width, height, z, rotation3x3, origin), built in C++ in the same float order; width * height is the number
+        of rays the object was constructed with. Replaces set_rays' rays, and the other way round."""
+        m = np.asarray(rotation3x3, dtype=np.float64).astype(np.float32)
+        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+        if m.shape != (3, 3):
+            raise ValueError("rotation3x3 must be a 3 x 3 matrix")
+        if o.shape != (3,):
+            raise ValueError("origin must have 3 components")
+        if int(width) <= 0 or int(height) <= 0 or int(width) * int(height) != len(self.rays):
+            raise ValueError("set_pose: width * height must be the number of rays the object was constructed with")
+        self.pose = (int(width), int(height), float(np.float32(z)), np.ascontiguousarray(m.reshape(9)), np.ascontiguousarray(o))
+        self.new_rays = None
 
     def set_rays(self, rays):
         """CPURaytracer::SetRays, the option HIPRaytracer.set_rays is on the GPU: the next Render() traces these rays - as many as
@@ -64,6 +84,7 @@ class CPURaytracer:
         if len(rays) != len(self.rays):
             raise ValueError("set_rays: as many rays as the object was constructed with")
         self.new_rays = rays
+        self.pose = None
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)
@@ -76,7 +97,13 @@ class CPURaytracer:
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
         args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
                 ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
-        if self.new_rays is not None:
+        if self.pose is not None:
+            if self.supersample != 1:
+                raise ValueError("this front filters the constructor's sample grid only: set_pose and supersample exclude each other")
+            w, h, z, m, o = self.pose
+            fp = ctypes.POINTER(ctypes.c_float)
+            rc = self._lib.cpu_rt_render_set_pose(*args, w, h, z, m.ctypes.data_as(fp), o.ctypes.data_as(fp))
+        elif self.new_rays is not None:
             if self.supersample != 1:
                 raise ValueError("replaced rays are no sample grid: set_rays and supersample exclude each other")
             rc = self._lib.cpu_rt_render_set_rays(*args, ptr(self.new_rays))

@@ -8,6 +8,7 @@
 #include "rt_pack.h"
 #include "rt_resolve.h"
 #include "rt_rays.h"
+#include "rt_raygen.h"
 
 #include <hip/hip_runtime.h>
 
@@ -176,6 +177,9 @@ struct rt_context {
     bool rays_off_grid = false;
     rt::RayScan* d_scan = nullptr;          // the ray scan's result (rt_rays.hip) and its pinned host mirror
     rt::RayScan* h_scan = nullptr;
+    // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
+    // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
+    uint32_t pose_w = 0, pose_h = 0;
     rt::WavefrontBuffers wf;
     bool last_wavefront = false;
     uint32_t last_rounds = 0;
@@ -516,6 +520,11 @@ int pack_on(rt_context* c, const void* d_src, uint64_t n, int format, void* d_ds
 }
 
 // ---- supersampled frames ----
+// the sample grid a factor > 1 filters over: the pinhole camera's, or the pose's the ray buffer was generated from (0: neither)
+uint32_t sample_width(const rt_context* c) { return c->pinhole ? c->width : c->pose_w; }
+uint32_t sample_height(const rt_context* c) { return c->pinhole ? c->height : c->pose_h; }
+bool has_sample_grid(const rt_context* c) { return c->pinhole || c->pose_w != 0; }
+
 uint64_t local_pixels(const rt_context* c) { return c->n_local / ((uint64_t)c->ss * c->ss); }
 
 // what rt_set_supersampling, rt_set_camera and rt_set_shard hold a (factor, camera, shard) combination to; nothing is changed here
@@ -526,7 +535,7 @@ int check_supersampling(rt_context* c, uint32_t s, bool pinhole, uint32_t width,
         return fail(c, RT_ERR_STATE, "an RT_KERNEL_HITTEST context renders the nearest t per ray: a time is not a colour, there is nothing to filter");
     if (c->aux_t || c->aux_index) return fail(c, RT_ERR_STATE, "aux buffers are per work-item: not together with a supersampling factor > 1");
     if (!pinhole || !width || !height)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "supersampling needs a pinhole camera (rt_set_camera): the samples are the sub-pixel rays of its grid");
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "supersampling needs a pinhole camera (rt_set_camera, rt_set_pose): the samples are the sub-pixel rays of its grid");
     if (width % s || height % s) return fail(c, RT_ERR_INVALID_ARGUMENT, "width and height of the sample grid must be multiples of the supersampling factor");
     if (world > 1 && tile_rays % ((uint64_t)s * width))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "with supersampling a tile must hold whole pixel rows: tile_rays % (s * width) == 0");
@@ -536,7 +545,7 @@ int check_supersampling(rt_context* c, uint32_t s, bool pinhole, uint32_t width,
 // s x s samples -> one pixel: `n_samples` consecutive samples of whole sample rows of the context's camera (a shard's tiles are that)
 int resolve_on(rt_context* c, const void* d_src, uint64_t n_samples, int format, void* d_dst, hipStream_t stream) {
     if (n_samples == 0) return RT_OK;
-    const hipError_t e = rt::launch_resolve(static_cast<const float4*>(d_src), c->width, (uint32_t)(n_samples / c->width), c->ss, format, d_dst, stream);
+    const hipError_t e = rt::launch_resolve(static_cast<const float4*>(d_src), sample_width(c), (uint32_t)(n_samples / sample_width(c)), c->ss, format, d_dst, stream);
     return e == hipSuccess ? RT_OK : fail_hip(c, e, "resolve launch");
 }
 
@@ -2074,6 +2083,7 @@ int rt_set_camera(rt_context* c, uint32_t width, uint32_t height, float z) {
     }
     c->camera_out_of_domain = out;
     c->pinhole = true;
+    c->pose_w = c->pose_h = 0;
     apply_ray_domain(c);
     c->width = width;
     c->height = height;
@@ -2145,6 +2155,7 @@ static int set_rays_from_device(rt_context* c, const void* d_src, uint64_t n_ray
     c->have_rays = true;
     c->pinhole = false;
     c->width = c->height = 0;
+    c->pose_w = c->pose_h = 0;
     c->z = 0.f;
     c->dir_w_zero = dir_w_zero;
     c->primary_w_one = starts_ok;
@@ -2175,11 +2186,133 @@ int rt_set_rays(rt_context* c, const void* rays, uint64_t n_rays) {
     return rc;
 }
 
+// ---- posed cameras (hip_raytracer.h) ----
+// The ray buffer of a live context written by the generator (rt_raygen.hip) instead of copied into it: the verdict pass stores no
+// ray, the refusals follow, and only then the context's own buffer is overwritten. pose_check changes nothing of the context's
+// state (it may allocate the scan record); pose_commit cannot be refused any more. rt_set_pose_multi runs the first on every shard
+// before the second on any.
+struct PoseVerdict {
+    bool in_domain = false, starts_ok = false, on_grid = false;
+    double origin[3] = {0, 0, 0};
+    float verdict_ms = 0.f;
+};
+
+static bool pose_trace() { return std::getenv("RT_RAYS_TRACE") != nullptr; }  // (set_rays_from_device's aid, for the two passes here)
+
+static int pose_grid(rt_context* c, uint32_t width, uint32_t height, float z, const float* m, const float* origin, rt::PoseGrid& g) {
+    if (!m || !origin) return fail(c, RT_ERR_INVALID_ARGUMENT, "the pose's matrix or origin is NULL");
+    if (width > 0x1000000u || height > 0x1000000u) return fail(c, RT_ERR_INVALID_ARGUMENT, "grid too large");
+    g.width = width;
+    g.height = height;
+    g.z = z;
+    std::memcpy(g.m, m, sizeof(g.m));
+    std::memcpy(g.origin, origin, sizeof(g.origin));
+    return RT_OK;
+}
+
+static int pose_check(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, PoseVerdict& v) {
+    if (g.width == 0 || g.height == 0 || (uint64_t)g.width * g.height != c->n_rays)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "width*height must equal n_rays");
+    if (c->ss > 1) {
+        const int rc = check_supersampling(c, c->ss, true, g.width, g.height, c->tile_rays, c->world);
+        if (rc) return rc;
+    }
+    RT_DEVICE(c);
+    if (!c->d_scan) RT_HIP(c, hipMalloc((void**)&c->d_scan, sizeof(rt::RayScan)));
+    if (!c->h_scan) RT_HIP(c, hipHostMalloc((void**)&c->h_scan, sizeof(rt::RayScan), hipHostMallocDefault));
+    const bool trace = pose_trace();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EventPair { hipEvent_t* e; ~EventPair() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    if (trace) { RT_HIP(c, hipEventCreate(&ev[0])); RT_HIP(c, hipEventCreate(&ev[1])); }
+    if (trace) RT_HIP(c, hipEventRecord(ev[0], stream));
+    const hipError_t e = rt::launch_pose_verdict(g, c->d_scan, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "pose verdict launch");
+    if (trace) RT_HIP(c, hipEventRecord(ev[1], stream));
+    RT_HIP(c, hipMemcpyAsync(c->h_scan, c->d_scan, sizeof(rt::RayScan), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (trace) RT_HIP(c, hipEventElapsedTime(&v.verdict_ms, ev[0], ev[1]));
+    v.in_domain = !(c->h_scan->flags & rt::kRayDomain);
+    // the starts are one point: the scan's predicate and box on it, in fp32 with every sum rounded (start.w is 1)
+    const volatile float s1 = g.origin[0] + g.origin[1];
+    const volatile float s2 = s1 + g.origin[2];
+    v.starts_ok = std::isfinite((float)s2);
+    bool inside = v.starts_ok;
+    for (int a = 0; a < 3; ++a) {
+        v.origin[a] = v.starts_ok ? (double)g.origin[a] : 0.0;
+        inside = inside && v.origin[a] >= c->grid_box_lo[a] && v.origin[a] <= c->grid_box_hi[a];
+    }
+    v.on_grid = c->grid.enabled && v.starts_ok && inside;
+    if (c->has_triangles && (!v.on_grid || !v.in_domain))
+        return fail(c, RT_ERR_INVALID_ARGUMENT,
+                    "triangle records are traced by the grid path only: this pose needs the literal loops (a direction of |d|^2 outside "
+                    "(1e-30, 1e30)) or brute force (an origin that is not finite or lies outside the box the grid was built for)");
+    return RT_OK;
+}
+
+static int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const PoseVerdict& v) {
+    RT_DEVICE(c);
+    const bool trace = pose_trace();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EventPair { hipEvent_t* e; ~EventPair() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{ev};
+    if (trace) { RT_HIP(c, hipEventCreate(&ev[0])); RT_HIP(c, hipEventCreate(&ev[1])); }
+    if (!c->d_rays) RT_HIP(c, hipMalloc((void**)&c->d_rays, sizeof(rt_ray) * (size_t)c->n_rays));
+    if (trace) RT_HIP(c, hipEventRecord(ev[0], stream));
+    const hipError_t e = rt::launch_pose_rays(g, c->d_rays, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "pose generation launch");
+    if (trace) RT_HIP(c, hipEventRecord(ev[1], stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (trace) {
+        float gen_ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&gen_ms, ev[0], ev[1]));
+        std::fprintf(stderr, "[rt_set_pose] verdict %.4f ms generate %.4f ms rays %llu\n", (double)v.verdict_ms, (double)gen_ms, (unsigned long long)c->n_rays);
+    }
+    c->have_rays = true;
+    c->pinhole = false;
+    c->width = c->height = 0;
+    c->z = 0.f;
+    c->pose_w = g.width;
+    c->pose_h = g.height;
+    c->dir_w_zero = true;
+    c->primary_w_one = v.starts_ok;
+    c->rays_out_of_domain = !v.in_domain;
+    c->rays_off_grid = !v.on_grid;
+    for (int a = 0; a < 3; ++a) c->origin_lo[a] = c->origin_hi[a] = v.origin[a];
+    apply_ray_domain(c);
+    c->rects_dirty = true;
+    c->tiles_dirty = true;
+    return RT_OK;
+}
+
+int rt_set_pose(rt_context* c, uint32_t width, uint32_t height, float z, const float* m, const float* origin, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    rt::PoseGrid g;
+    int rc = pose_grid(c, width, height, z, m, origin, g);
+    if (rc) return rc;
+    PoseVerdict v;
+    rc = pose_check(c, g, static_cast<hipStream_t>(hip_stream), v);
+    if (rc) return rc;
+    return pose_commit(c, g, static_cast<hipStream_t>(hip_stream), v);
+}
+
+int rt_generate_rays_device(rt_context* c, uint32_t width, uint32_t height, float z, const float* m, const float* origin, void* d_rays,
+                            void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    rt::PoseGrid g;
+    const int rc = pose_grid(c, width, height, z, m, origin, g);
+    if (rc) return rc;
+    if (width == 0 || height == 0) return RT_OK;
+    if (!d_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_generate_rays_device: NULL ray array");
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the ray array must be 16-byte aligned");
+    RT_DEVICE(c);
+    const hipError_t e = rt::launch_pose_rays(g, static_cast<float4*>(d_rays), static_cast<hipStream_t>(hip_stream));
+    return e == hipSuccess ? RT_OK : fail_hip(c, e, "pose generation launch");
+}
+
 int rt_get_rays_info(const rt_context* c, rt_rays_info_t* info) {
     if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
     std::memset(info, 0, sizeof(*info));
-    info->source = c->pinhole ? 1u : (c->have_rays ? 2u : 0u);
-    const bool buffer = info->source == 2u;
+    info->source = c->pinhole ? 1u : (c->have_rays ? (c->pose_w ? 3u : 2u) : 0u);
+    const bool buffer = info->source >= 2u;
     info->dir_w_zero = (!buffer || c->dir_w_zero) ? 1u : 0u;
     info->directions_in_domain = (c->pinhole ? !c->camera_out_of_domain : !c->rays_out_of_domain) ? 1u : 0u;
     info->starts_ok = (!buffer || c->primary_w_one) ? 1u : 0u;
@@ -2200,7 +2333,7 @@ int rt_set_shard(rt_context* c, uint64_t tile_rays, uint32_t rank, uint32_t worl
     if (world == 0 || rank >= world || (world > 1 && tile_rays == 0))
         return fail(c, RT_ERR_INVALID_ARGUMENT, "need world >= 1, rank < world, tile_rays > 0");
     if (c->ss > 1) {
-        const int rc = check_supersampling(c, c->ss, c->pinhole, c->width, c->height, tile_rays, world);
+        const int rc = check_supersampling(c, c->ss, has_sample_grid(c), sample_width(c), sample_height(c), tile_rays, world);
         if (rc) return rc;
     }
     c->tile_rays = tile_rays;
@@ -2214,7 +2347,7 @@ uint64_t rt_local_rays(const rt_context* c) { return c ? c->n_local : 0; }
 
 int rt_set_supersampling(rt_context* c, uint32_t s) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int rc = check_supersampling(c, s, c->pinhole, c->width, c->height, c->tile_rays, c->world);
+    const int rc = check_supersampling(c, s, has_sample_grid(c), sample_width(c), sample_height(c), c->tile_rays, c->world);
     if (rc) return rc;
     c->ss = s;
     return RT_OK;
@@ -2310,7 +2443,7 @@ static int render_in_passes(rt_context* c, int format, const void** out) {
     // supersampled frames: a tile holds whole pixel rows (16 sample rows for s = 2 and 4, lcm(16, 3) = 48 for s = 3), a pass filters
     // its samples (from d_samples) into its pixels, and everything behind the filter - pack, copy, host frame - counts in pixels
     const uint32_t ss = c->ss, ss2 = ss * ss;
-    const uint64_t tile_rays = (c->pinhole && c->width) ? (ss == 3 ? 48ull : 16ull) * c->width : 65536ull;
+    const uint64_t tile_rays = sample_width(c) ? (ss == 3 ? 48ull : 16ull) * sample_width(c) : 65536ull;
     const uint64_t tiles = (n_rays + tile_rays - 1) / tile_rays;
     const size_t render_elem = elem_bytes(c);                             // what a kernel writes per work-item
     const size_t elem = format ? packed_bytes(format) : render_elem;     // what travels to the host per pixel
@@ -2865,11 +2998,38 @@ int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z) {
     return RT_OK;
 }
 
+// rt_set_pose on every context, all or none: every shard's verdict pass and refusals first, each on a host thread of its own and
+// its context's device and stream; only when no shard refuses, every shard generates.
+int rt_set_pose_multi(rt_multi* m, uint32_t width, uint32_t height, float z, const float* mat, const float* origin) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    const size_t n = m->ctx.size();
+    rt::PoseGrid g;
+    for (rt_context* c : m->ctx) {
+        const int rc = pose_grid(c, width, height, z, mat, origin, g);
+        if (rc != RT_OK) return multi_fail(m, rc, c->error);
+    }
+    std::vector<PoseVerdict> verdicts(n);
+    std::vector<int> rcs(n, RT_OK);
+    for (int phase = 0; phase < 2; ++phase) {
+        auto shard = [&](size_t r) {
+            rt_context* c = m->ctx[r];
+            rcs[r] = phase == 0 ? pose_check(c, g, c->stream, verdicts[r]) : pose_commit(c, g, c->stream, verdicts[r]);
+        };
+        std::vector<std::thread> workers;
+        for (size_t r = 1; r < n; ++r) workers.emplace_back(shard, r);
+        if (n) shard(0);
+        for (std::thread& t : workers) t.join();
+        for (size_t r = 0; r < n; ++r)
+            if (rcs[r] != RT_OK) return multi_fail(m, rcs[r], "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
+    }
+    return RT_OK;
+}
+
 uint64_t rt_multi_frame_elems(const rt_multi* m) { return m ? m->tiles * m->tile_rays : 0; }
 
 int rt_set_supersampling_multi(rt_multi* m, uint32_t s) {
     if (!m) return RT_ERR_INVALID_ARGUMENT;
-    if (s >= 2 && s <= 4 && !m->ctx.empty() && m->ctx[0]->pinhole && m->ctx[0]->width && m->tile_rays % ((uint64_t)s * m->ctx[0]->width))
+    if (s >= 2 && s <= 4 && !m->ctx.empty() && sample_width(m->ctx[0]) && m->tile_rays % ((uint64_t)s * sample_width(m->ctx[0])))
         return multi_fail(m, RT_ERR_INVALID_ARGUMENT, "with supersampling a tile must hold whole pixel rows: pass a tile_rays with tile_rays % (s * width) == 0 to rt_create_multi");
     for (size_t r = 0; r < m->ctx.size(); ++r) {
         const int rc = rt_set_supersampling(m->ctx[r], s);

@@ -219,6 +219,14 @@ class ShardedHIPRaytracer:
                                         group=group, pipeline=pipeline)
         assert self.gatherer.local_rays == self.rt.local_pixels  # exact share: nothing is padded to the largest one
 
+    def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
+        """Turn or move the camera of this rank's context (HIPRaytracer.set_pose; every rank makes the same call): the rank
+        generates the whole frame's rays on its GPU and keeps rendering its own tiles. width * height is n_rays; the tiles stay the
+        ones cut at construction, in rays. With supersample=s, (width, height, z) is the sample grid (camera.supersampled)."""
+        self.gatherer.drain()   # (a pipelined frame still reads the rays in use)
+        torch.cuda.synchronize(self.device)
+        self.rt.set_pose(width, height, z, rotation3x3, origin)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

@@ -39,6 +39,7 @@ EXPORTS = [
     "rt_set_supersampling", "rt_supersampling", "rt_local_pixels", "rt_resolve_device", "rt_set_supersampling_multi",
     "rt_multi_frame_pixels",
     "rt_set_rays_device", "rt_set_rays", "rt_get_rays_info",
+    "rt_set_pose", "rt_generate_rays_device", "rt_set_pose_multi",
 ]
 
 
@@ -181,9 +182,29 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_set_rays.argtypes = [vp, vp, u64]
         lib.rt_get_rays_info.restype = i32
         lib.rt_get_rays_info.argtypes = [vp, ctypes.POINTER(RTRaysInfo)]
+    if hasattr(lib, "rt_set_pose"):  # (the same: a build from before posed cameras)
+        f9, f3 = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)
+        lib.rt_set_pose.restype = i32
+        lib.rt_set_pose.argtypes = [vp, u32, u32, ctypes.c_float, f9, f3, vp]
+        lib.rt_generate_rays_device.restype = i32
+        lib.rt_generate_rays_device.argtypes = [vp, u32, u32, ctypes.c_float, f9, f3, vp, vp]
+        lib.rt_set_pose_multi.restype = i32
+        lib.rt_set_pose_multi.argtypes = [vp, u32, u32, ctypes.c_float, f9, f3]
     if path is None:
         _lib = lib
     return lib
+
+
+def pose_arguments(rotation3x3, origin=(0.0, 0.0, 0.0)):
+    """(float[9], float[3]) for rt_set_pose: the matrix row-major and the origin, rounded to float32 from float64 as
+    rays.posed_rays rounds them. Raises ValueError for another shape."""
+    m = np.asarray(rotation3x3, dtype=np.float64).astype(np.float32)
+    if m.shape != (3, 3):
+        raise ValueError("rotation3x3 must be a 3 x 3 matrix")
+    o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    if o.shape != (3,):
+        raise ValueError("origin must have 3 components")
+    return (ctypes.c_float * 9)(*m.reshape(9).tolist()), (ctypes.c_float * 3)(*o.tolist())
 
 
 def pixel_format(format) -> int:
@@ -405,6 +426,47 @@ class HIPRaytracer:
         self._check(self._lib.rt_set_rays_device(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.numel() // 8,
                                                  ctypes.c_void_p(stream) if stream else None))
 
+    # -- posed cameras (hip_raytracer.h: the rays of rays.posed_rays, generated on the device) -----------------------------
+    def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0), stream=None):
+        """Turn or move a live context's camera (rt_set_pose): the next render is the one a context created with
+        rays.posed_rays(width, height, z, rotation3x3, origin) and raygen=False renders; the rays are generated on the GPU into the
+        context's own buffer. width * height must equal n_rays. `stream` is a raw HIP stream handle (None: the legacy default
+        stream). With a supersampling factor > 1, (width, height, z) is the sample grid (camera.supersampled). Synchronous."""
+        m, o = pose_arguments(rotation3x3, origin)
+        self._check(self._lib.rt_set_pose(self._ctx, int(width), int(height), float(z), m, o,
+                                          ctypes.c_void_p(int(stream)) if stream else None))
+
+    def generate_rays(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0), out=None, stream=None):
+        """The generator alone (rt_generate_rays_device): rays.posed_rays(...) written to device memory, asynchronously on a HIP
+        stream. `out` is a torch tensor on the context's device (float32, contiguous, at least 8 width height elements), a raw
+        device pointer (16-byte aligned, room for 32 width height bytes), or None for a new tensor of shape (width height, 8), which
+        is returned. With a tensor and stream=None the pass is ordered on torch's current stream; touches no context state."""
+        m, o = pose_arguments(rotation3x3, origin)
+        width, height = int(width), int(height)
+        if width < 0 or height < 0:
+            raise ValueError("width and height must not be negative")
+        n = width * height
+        tensor = None
+        if out is None or not isinstance(out, int):
+            import torch
+            if out is None:
+                out = torch.empty((n, 8), dtype=torch.float32, device="cuda")
+            if not isinstance(out, torch.Tensor):
+                raise TypeError("generate_rays writes into a torch tensor on the context's device or a raw device pointer")
+            if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < 8 * n:
+                raise ValueError("a device ray tensor is float32, contiguous, on the GPU, with 8 elements per ray")
+            tensor = out
+            if stream is None:
+                with torch.cuda.device(out.device):
+                    stream = torch.cuda.current_stream().cuda_stream
+            ptr = out.data_ptr()
+        else:
+            ptr = out
+        self._check(self._lib.rt_generate_rays_device(self._ctx, width, height, float(z), m, o,
+                                                      ctypes.c_void_p(ptr) if ptr else None,
+                                                      ctypes.c_void_p(int(stream)) if stream else None))
+        return tensor
+
     def rays_info(self) -> dict:
         """rt_get_rays_info: where the next frame's primary rays come from, what the scan found, and whether the grid serves them."""
         info = RTRaysInfo()
@@ -531,6 +593,11 @@ class MultiHIPRaytracer:
     def set_camera(self, width: int, height: int, z: float):
         """Re-aim every shard (rt_set_camera_multi). The tile size stays the one chosen at creation (in rays, not rows)."""
         self._check(self._lib.rt_set_camera_multi(self._m, int(width), int(height), float(z)))
+
+    def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
+        """Turn or move every shard's camera (rt_set_pose_multi): all shards or none; each generates on its own device."""
+        m, o = pose_arguments(rotation3x3, origin)
+        self._check(self._lib.rt_set_pose_multi(self._m, int(width), int(height), float(z), m, o))
 
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()

@@ -338,6 +338,30 @@ void CPURaytracer::SetRays(const std::vector<Ray3D>& rays_) {
     replaced = true;
 }
 
+void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]) {
+    if (!m || !origin) throw std::invalid_argument("SetPose: the matrix or the origin is null");
+    if (width > 0x1000000u || height > 0x1000000u || width * height != rays.size())
+        throw std::invalid_argument("SetPose: width * height must be the number of rays the object was constructed with");
+    std::vector<Ray3D> posed;
+    posed.reserve(rays.size());
+    const float half_w = (float)width / 2.0f, half_h = (float)height / 2.0f, height_f = (float)height;
+    const rtm::vec3 start(origin[0], origin[1], origin[2]);
+    for (size_t j = 0; j < height; ++j) {
+        const float y = (height_f - (float)j) - half_h;
+        for (size_t i = 0; i < width; ++i) {
+            const float x = (float)i - half_w;
+            float d[3];
+            for (int r = 0; r < 3; ++r) {
+                const float mx = m[3 * r] * x, my = m[3 * r + 1] * y, mz = m[3 * r + 2] * z;
+                const float acc = mx + my;
+                d[r] = acc + mz;
+            }
+            posed.emplace_back(start, rtm::vec3(d[0], d[1], d[2]));
+        }
+    }
+    SetRays(posed);
+}
+
 cl_float4* CPURaytracer::Render() {
     const std::vector<Ray3D>& rays = Rays();  // (the constructor's, or SetRays' copy: everything below reads these)
     const size_t n = rays.size();

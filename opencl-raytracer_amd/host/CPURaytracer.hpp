@@ -41,6 +41,12 @@ public:
     // constructed with, std::invalid_argument otherwise - instead of the constructor's.
     void SetRays(const std::vector<Ray3D>& rays);
 
+    // Posed cameras, the same option as HIPRaytracer's: the pinhole grid (width, height, z) seen through the fp32 matrix m
+    // (row-major) from `origin`, built here in the float order hip_raytracer.h states ("posed cameras": every product and sum
+    // rounded, nothing fused - this library is built with -ffp-contract=off) and handed to SetRays. width * height must be the
+    // number of rays the object was constructed with; std::invalid_argument otherwise.
+    void SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]);
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

@@ -110,6 +110,14 @@ void HIPRaytracer::SetRays(const std::vector<Ray3D>& rays_) {
     if (rt_set_rays(ctx, rays_.data(), rays_.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRays: ") + rt_last_error(ctx));
 }
 
+void HIPRaytracer::SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream) {
+    if (multi) {
+        if (rt_set_pose_multi(multi, width, height, z, m, origin) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetPose: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_pose(ctx, width, height, z, m, origin, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetPose: ") + rt_last_error(ctx));
+}
+
 void HIPRaytracer::SetRaysDevice(const void* d_rays, size_t n, void* stream) {
     if (multi) throw std::runtime_error("HIPRaytracer::SetRaysDevice: not available on the several-GPU object");
     if (rt_set_rays_device(ctx, d_rays, n, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRaysDevice: ") + rt_last_error(ctx));

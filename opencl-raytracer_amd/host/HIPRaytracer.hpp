@@ -53,6 +53,13 @@ public:
     void SetRays(const std::vector<Ray3D>& rays);
     void SetRaysDevice(const void* d_rays, size_t n, void* stream = nullptr);
 
+    // Posed cameras (hip_raytracer.h, "posed cameras"): the next Render() sees the pinhole grid (width, height, z) through the fp32
+    // matrix m (row-major) from `origin`; the rays are generated on the GPU(s) into the library's own buffer. width * height is the
+    // number of rays the object was constructed with; with SetSupersampling(s > 1) it is the sample grid. Synchronous; `stream` (a
+    // hipStream_t; nullptr = the legacy default stream) counts for the one-GPU object, the several-GPU object uses every shard's own.
+    // Throws std::runtime_error with the library's message for what it refuses.
+    void SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream = nullptr);
+
     rt_stats_t Stats();
     rt_context* Context() { return ctx; }
 

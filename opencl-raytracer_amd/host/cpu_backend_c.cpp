@@ -13,6 +13,8 @@
 
 namespace {
 thread_local const rt_ray* g_new_rays = nullptr;  // cpu_rt_render_set_rays: the rays SetRays gets before Render()
+struct Pose { uint32_t width, height; float z; const float* m; const float* origin; };
+thread_local const Pose* g_pose = nullptr;        // cpu_rt_render_set_pose: what SetPose gets before Render()
 
 Ray3D host_ray(const rt_ray& r) {
     Ray3D h(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f));
@@ -89,6 +91,9 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
         for (uint64_t i = 0; i < n_rays; ++i) replaced.push_back(host_ray(g_new_rays[i]));
         try { backend->SetRays(replaced); } catch (const std::exception&) { return -1; }
     }
+    if (g_pose) {
+        try { backend->SetPose(g_pose->width, g_pose->height, g_pose->z, g_pose->m, g_pose->origin); } catch (const std::exception&) { return -1; }
+    }
     const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
     const auto t0 = std::chrono::steady_clock::now();
@@ -115,6 +120,21 @@ int cpu_rt_render_set_rays(int kernel, uint32_t max_bounces, const void* objs_, 
                                                           hit_pixels, seconds, threads_used, 1, 0)
                              : -1;
     g_new_rays = nullptr;
+    return rc;
+}
+
+// CPURaytracer::SetPose through the C entry: the backend is constructed with `rays_` and renders the posed grid (width, height, z,
+// m[9] row-major, origin[3]; width * height == n_rays) after SetPose. Same outputs and return value as cpu_rt_render.
+int cpu_rt_render_set_pose(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                           const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                           uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, uint32_t width, uint32_t height, float z,
+                           const float* m, const float* origin) {
+    if (!m || !origin) return -1;
+    const Pose pose{width, height, z, m, origin};
+    g_pose = &pose;
+    const int rc = cpu_rt_render_supersampled(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced,
+                                              hit_pixels, seconds, threads_used, 1, 0);
+    g_pose = nullptr;
     return rc;
 }
 

@@ -8,6 +8,8 @@
 //                       bytes: `p3` (default) the reference's ASCII file, `p6` the binary PPM
 //   render and render8 take `--ss S` (S = 2, 3, 4) anywhere behind the command: S x S samples per pixel, box-filtered by the
 //                       backend (SetSupersampling). The picture stays W x H; the sample grid is S W x S H at S z.
+//   render and render8 take `--pose m00,m01,m02,m10,m11,m12,m20,m21,m22,ox,oy,oz` likewise: the camera seen through the 3 x 3
+//                       matrix (row-major) from the origin (ox, oy, oz) - the backend's SetPose on the (sample) grid; also with --ss.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -55,6 +57,27 @@ int main(int argc, char** argv) {
                 break;
             }
         if (ss < 1 || ss > 4) { std::fprintf(stderr, "--ss takes 1, 2, 3 or 4\n"); return 1; }
+        bool posed = false;  // --pose twelve numbers: taken out likewise
+        float pose[12];
+        for (int k = 2; k + 1 < argc; ++k)
+            if (std::strcmp(argv[k], "--pose") == 0) {
+                const char* q = argv[k + 1];
+                int got = 0;
+                while (got < 12) {
+                    char* end = nullptr;
+                    pose[got] = std::strtof(q, &end);
+                    if (end == q) break;
+                    ++got;
+                    q = end;
+                    if (*q != ',') break;
+                    ++q;
+                }
+                if (got != 12 || *q) { std::fprintf(stderr, "--pose takes m00,m01,m02,m10,m11,m12,m20,m21,m22,ox,oy,oz\n"); return 1; }
+                posed = true;
+                for (int r = k; r + 2 < argc; ++r) argv[r] = argv[r + 2];
+                argc -= 2;
+                break;
+            }
         if (argc < 4) { std::fprintf(stderr, "usage: scene_tool records|render|render8 ...\n"); return 1; }
         std::vector<ObjectData> objects;
         std::vector<Light> lights;
@@ -83,6 +106,7 @@ int main(int argc, char** argv) {
             const rt_pixel_format format = (argc > 9 && std::strcmp(argv[9], "rgb8") == 0) ? RT_PIXEL_RGB8 : RT_PIXEL_RGBA8;
             HIPRaytracer raytracer8(objects, lights, rays, depth);
             if (ss > 1) raytracer8.SetSupersampling(ss);
+            if (posed) raytracer8.SetPose((unsigned)sw, (unsigned)sh, sz, pose, pose + 9);
             const uint8_t* bytes = raytracer8.RenderPacked(format);
             const size_t stride = rt_packed_pixel_bytes(format);
             if (p6) PPMExporter::ExportP6(argv[6], (size_t)width, (size_t)height, bytes, stride);
@@ -95,10 +119,12 @@ int main(int argc, char** argv) {
             CPURaytracer* backend = new CPURaytracer(objects, lights, rays, depth);
             raytracer.reset(backend);
             if (ss > 1) backend->SetSupersampling(ss, (size_t)sw);
+            if (posed) backend->SetPose((size_t)sw, (size_t)sh, sz, pose, pose + 9);
         } else {
             HIPRaytracer* backend = new HIPRaytracer(objects, lights, rays, depth);
             raytracer.reset(backend);
             if (ss > 1) backend->SetSupersampling(ss);
+            if (posed) backend->SetPose((unsigned)sw, (unsigned)sh, sz, pose, pose + 9);
         }
         cl_float4* pixels = raytracer->Render();
         PPMExporter::ExportP3(argv[6], (size_t)width, (size_t)height, PPMExporter::RGBAtoRGB(reinterpret_cast<const float*>(pixels), (size_t)width * height));

@@ -4,7 +4,8 @@ ray_verdict(rays)  what the ray scan (csrc/rt_rays.hip) reports about a ray arra
                    in float32 with the same order of operations, and the box of the origins.
 posed_rays(...)    a pinhole grid seen through a rotation, from a common origin: the rays of a panned, tilted, rolled or
                    moved camera, in a stated float32 order, so that a caller who computes them elsewhere (on the GPU) can
-                   reproduce them bit for bit.
+                   reproduce them bit for bit. rt_set_pose / rt_generate_rays_device (hip_raytracer.h, "posed cameras";
+                   csrc/rt_raygen.hip; HIPRaytracer.set_pose, generate_rays) do: these rays, written on the device.
 """
 from __future__ import annotations
 
