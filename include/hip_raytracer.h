@@ -383,9 +383,13 @@ int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid fo
  * origin outside box_lo .. box_hi renders by brute force, as for any ray buffer (no grid is rebuilt).
  * Refused with RT_ERR_INVALID_ARGUMENT: a NULL m or origin; width * height != n_rays; for a scene with triangles a pose that needs
  * the literal loops or brute force; and, while the supersampling factor is > 1, what rt_set_camera is refused for (below).
- * rt_get_rays_info reports source 3; rt_stats_t::pinhole, width and height stay 0 as for any buffer (the primary rays of a posed
- * frame are traced as a buffer's are: the screen tiles belong to the fixed camera). A later rt_set_camera or rt_set_rays* replaces
- * the pose, and the other way round. Shards, rt_render's passes, aux buffers, 8-bit frames and rt_count_rays work as for a buffer; a
+ * rt_get_rays_info reports source 3; rt_stats_t::pinhole, width and height stay 0 as for any buffer. The RAYS of a posed frame are
+ * read from the buffer, but its primary round is the fixed camera's: the context keeps the pose, and the first large-scene frame
+ * after it builds the pose's depth-ordered screen tiles ON THE DEVICE from the objects' registration spheres ("screen tiles"
+ * below; csrc/rt_tiles.hip) - 64 x 8 tiles, since a posed frame's work-items are in linear order - and traces the primary rays
+ * through them instead of the grid walk. Same pixels, bit for bit. A pose whose table is refused (rt_tiles_info_t::refused) is
+ * traced through the grid walk as before; RT_POSE_TILES=0 in the environment keeps every pose there (a measurement knob). A later
+ * rt_set_camera or rt_set_rays* replaces the pose, and the other way round. Shards, rt_render's passes, aux buffers, 8-bit frames and rt_count_rays work as for a buffer; a
  * sharded context generates the whole frame's rays.
  *
  * Supersampling. The sample grid of a posed camera is defined, so a factor > 1 is open to it: the pose's (width, height, z) is the
@@ -400,6 +404,47 @@ int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid fo
 int rt_set_pose(rt_context* ctx, uint32_t width, uint32_t height, float z, const float m[9], const float origin[3], void* hip_stream);
 int rt_generate_rays_device(rt_context* ctx, uint32_t width, uint32_t height, float z, const float m[9], const float origin[3],
                             void* d_rays, void* hip_stream);
+
+/* ---- screen tiles ---------------------------------------------------------------------------------------------------------------
+ * The first trace round of a large-scene frame walks, per screen tile, a depth-ordered list of the objects a primary ray of that
+ * tile can meet (csrc/rt_grid.h: ScreenTiles). The fixed camera's table is built on the host (per rt_set_camera), a posed camera's
+ * on the device (per rt_set_pose; opencl-raytracer_amd/tiles.py: pose_screen_tiles is the executable definition). Both are an
+ * acceleration only: a frame is the same with and without them.
+ * rt_get_tiles_info is valid for every context and reports the table the NEXT large-scene frame would use; it builds the table
+ * if the rays changed since the last build (on the context's own stream, synchronously), so a caller need not render first.
+ * rt_read_tiles copies that table to host arrays: tile_start[tiles_x * tiles_y + 1] offsets and `entries` as pairs of 32-bit words
+ * {object index, depth key (float bits)} - n_entries + n_global of them, a tile's ascending by (key, index), the whole-screen
+ * objects behind the last tile's. n_start and n_entries are the arrays' capacities in elements / pairs; too small, or no table:
+ * RT_ERR_INVALID_ARGUMENT / RT_ERR_STATE. rt_read_grid_spheres copies the registration spheres the tables are built from: 4
+ * doubles per object (centre, radius; inf: tested by every ray, negative: never hit), n = the object count; RT_ERR_STATE for a
+ * context without a grid. All three are accessors for tests and tools, as rt_get_rays_info is. */
+#define RT_TILES_REFUSED_NO_GRID 0x1u   /* the grid does not serve the rays in use (no grid, origin outside its box, literal loops,
+                                           small-scene path) or the rays are neither a camera's nor a pose's                      */
+#define RT_TILES_REFUSED_Z       0x2u   /* z is not < 0                                                                          */
+#define RT_TILES_REFUSED_MATRIX  0x4u   /* the pose's matrix or origin is not finite, or the matrix is singular                  */
+#define RT_TILES_REFUSED_EPS     0x8u   /* eps >= |z| / 2 or pad > 1: the pose is too ill-conditioned for the table's margins    */
+#define RT_TILES_REFUSED_WIDTH   0x10u  /* width is not a multiple of the tile's                                                 */
+#define RT_TILES_REFUSED_GLOBAL  0x20u  /* more than 64 objects cover the whole screen                                           */
+#define RT_TILES_REFUSED_BUDGET  0x40u  /* more (object, tile) pairs than 256 n_objs + 4096                                      */
+#define RT_TILES_REFUSED_LIST    0x80u  /* a tile's list is longer than 1024 entries                                             */
+#define RT_TILES_REFUSED_TILES   0x100u /* more than 2^20 tiles                                                                  */
+#define RT_TILES_REFUSED_KNOB    0x200u /* RT_POSE_TILES=0                                                                       */
+typedef struct rt_tiles_info_t {
+    uint32_t enabled;               /* the next large-scene frame's primary round walks tile lists                             */
+    uint32_t source;                /* 0 none, 1 the fixed camera's (host), 2 the pose's (device)                              */
+    uint32_t tiles_x, tiles_y;      /* tiles are 8 rows tall ...                                                               */
+    uint32_t col_shift;             /* ... and 1 << col_shift pixels wide (3 or 6; a pose's: 6)                                */
+    uint32_t n_global;              /* whole-screen objects, tested by every wave                                              */
+    uint32_t max_list;              /* longest tile list                                                                       */
+    uint32_t refused;               /* RT_TILES_REFUSED_* of the last build (0 when enabled; a camera's table reports NO_GRID,
+                                       Z, WIDTH, or BUDGET for its pair and whole-screen limits together)                       */
+    uint64_t n_entries;             /* (object, tile) pairs of the table (also of a pose's refused for GLOBAL or LIST)         */
+    double   build_device_ms;       /* device time of the last build's passes (a pose's; 0 for the host's)                     */
+    double   eps, pad;              /* a pose's: the bound on |v' - v| and the rectangle's pad in direction units (rt_grid.h)  */
+} rt_tiles_info_t;
+int rt_get_tiles_info(const rt_context* ctx, rt_tiles_info_t* info);
+int rt_read_tiles(rt_context* ctx, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries);
+int rt_read_grid_spheres(const rt_context* ctx, double* spheres, uint64_t n);
 
 void rt_destroy(rt_context* ctx);
 

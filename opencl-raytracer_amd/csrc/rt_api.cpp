@@ -9,6 +9,7 @@
 #include "rt_resolve.h"
 #include "rt_rays.h"
 #include "rt_raygen.h"
+#include "rt_tiles.h"
 
 #include <hip/hip_runtime.h>
 
@@ -156,6 +157,16 @@ struct rt_context {
     rt::ScreenTiles tiles = {};
     bool tiles_dirty = true;
     uint32_t tiles_built_for = 0;           // the tile width (as a shift) the last build was asked for
+    // A posed camera's table (rt_tiles.hip): the pose the ray buffer in use was generated from, the registration spheres on the
+    // device (uploaded by the first posed build), the builder's device memory (grow-only), its record's pinned mirror, the
+    // events around its passes, and what rt_get_tiles_info reports of the last build of either kind.
+    rt::PoseGrid pose = {};
+    double* d_pose_spheres = nullptr;
+    rt::PoseTileBuffers ptb = {};
+    size_t ptb_tiles = 0, ptb_entries = 0;
+    rt::PoseTileRecord* h_pose_record = nullptr;
+    hipEvent_t ev_tiles[4] = {};
+    rt_tiles_info_t tiles_info = {};
     bool has_triangles = false;             // type-2 records (extension): only the grid path knows them
     int nan_winner = -1;                    // the last sphere / box of the scene decides what a NaN ray ends with (rt_device.h)
     bool nan_winner_sphere = false;
@@ -647,6 +658,7 @@ int ensure_wavefront(rt_context* c) {
 }
 
 int build_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift);
+int refresh_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift);
 
 int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count) {
     if (c->n_local == 0) {  // empty launch: nothing to render, nothing to time
@@ -735,17 +747,9 @@ int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count) {
         // a first-round wave is an 8 x 8 block of pixels (work-items in tile order) or 64 pixels of one row: the tile lists follow
         const uint32_t col_shift = p.wf_tile_order ? 3u : 6u;
         if (c->tiles_dirty || c->tiles_built_for != col_shift) {
-            rc = build_screen_tiles(c, stream, col_shift);
+            rc = refresh_screen_tiles(c, stream, col_shift);
             if (rc) return rc;
-            // objects that cover much of the screen can exceed the pair budget at 8 x 8: the 64 x 8 tiles of round 1 serve an
-            // 8 x 8 wave as well (its block lies inside one of them)
-            if (!c->tiles.enabled && col_shift == 3u) {
-                rc = build_screen_tiles(c, stream, 6u);
-                if (rc) return rc;
-            }
-            c->tiles_built_for = col_shift;
-            RT_HIP(c, hipStreamSynchronize(stream));
-            c->setup.screen_tiles_ms += sw.lap_ms();
+            c->setup.screen_tiles_ms += sw.lap_ms();  // (wall: a posed build's device passes - rt_tiles_info_t::build_device_ms - are inside it)
         }
         c->wf.tiles = c->tiles;
     }
@@ -774,9 +778,12 @@ int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count) {
 // tests what only the seven other blocks of its 64 x 8 tile can see. Depth order: with the list by nearest possible t a wave
 // stops at the first entry that lies behind what all of its lanes have already hit - about 2 exact tests per 8 x 8 tile of
 // the cfg4 frame instead of its whole list of ~10.)
+int build_pose_tiles(rt_context* c, hipStream_t stream);
+
 int build_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift) {
     c->tiles = rt::ScreenTiles{};
     c->tiles_dirty = false;
+    if (!c->pinhole && c->have_rays && c->pose_w) return build_pose_tiles(c, stream);  // the rays in use come from a pose
     const uint32_t tile_w = 1u << col_shift;
     if (!c->grid.enabled || !c->pinhole || !(c->z < 0.f) || c->width % tile_w != 0 || c->h_grid_spheres.empty()) return RT_OK;
     const uint32_t tx = c->width / tile_w, ty = (c->height + 7u) / 8u;
@@ -874,6 +881,237 @@ int build_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift) {
     c->tiles.global_begin = (uint32_t)total;
     c->tiles.n_global = (uint32_t)global.size();
     c->tiles.enabled = 1u;
+    return RT_OK;
+}
+
+// The build a frame (do_launch) or rt_get_tiles_info asks for when the rays changed, and what rt_get_tiles_info reports of it.
+int refresh_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift) {
+    c->tiles_info = rt_tiles_info_t{};
+    int rc = build_screen_tiles(c, stream, col_shift);
+    if (rc) return rc;
+    // objects that cover much of the screen can exceed the pair budget at 8 x 8: the 64 x 8 tiles of round 1 serve an
+    // 8 x 8 wave as well (its block lies inside one of them)
+    if (!c->tiles.enabled && col_shift == 3u && c->pinhole) {
+        rc = build_screen_tiles(c, stream, 6u);
+        if (rc) return rc;
+    }
+    c->tiles_built_for = col_shift;
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (c->pinhole) {  // the camera's table (a pose's build fills the record itself; any other buffer has none)
+        rt_tiles_info_t& ti = c->tiles_info;
+        ti.enabled = c->tiles.enabled;
+        ti.source = c->tiles.enabled ? 1u : 0u;
+        ti.col_shift = c->tiles.enabled ? c->tiles.col_shift : col_shift;
+        ti.tiles_x = c->width >> ti.col_shift;
+        ti.tiles_y = (c->height + 7u) / 8u;
+        ti.n_global = c->tiles.n_global;
+        ti.n_entries = c->tiles.global_begin;
+        if (!c->tiles.enabled)
+            ti.refused = (!c->grid.enabled || c->h_grid_spheres.empty()) ? RT_TILES_REFUSED_NO_GRID
+                         : (!(c->z < 0.f) ? RT_TILES_REFUSED_Z : (c->width % 64u != 0 ? RT_TILES_REFUSED_WIDTH : RT_TILES_REFUSED_BUDGET));
+    } else if (!c->pose_w) {
+        c->tiles_info.refused = RT_TILES_REFUSED_NO_GRID;
+    }
+    return RT_OK;
+}
+
+// sigma_max of a 3 x 3 matrix: sqrt of the largest eigenvalue of N N^T in object_bound's closed form (same padding and clamps)
+double sigma_max3(const double N[3][3]) {
+    double S[3][3], fro2 = 0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            S[i][j] = N[i][0] * N[j][0] + N[i][1] * N[j][1] + N[i][2] * N[j][2];
+            fro2 += N[i][j] * N[i][j];
+        }
+    double lam_max = fro2;
+    const double q = (S[0][0] + S[1][1] + S[2][2]) / 3.0;
+    const double p1 = S[0][1] * S[0][1] + S[0][2] * S[0][2] + S[1][2] * S[1][2];
+    const double p2 = (S[0][0] - q) * (S[0][0] - q) + (S[1][1] - q) * (S[1][1] - q) + (S[2][2] - q) * (S[2][2] - q) + 2.0 * p1;
+    const double pp = std::sqrt(p2 / 6.0);
+    if (pp > 0 && std::isfinite(pp)) {
+        double B[3][3];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) B[i][j] = (S[i][j] - (i == j ? q : 0.0)) / pp;
+        double r = (B[0][0] * (B[1][1] * B[2][2] - B[1][2] * B[2][1]) - B[0][1] * (B[1][0] * B[2][2] - B[1][2] * B[2][0]) +
+                    B[0][2] * (B[1][0] * B[2][1] - B[1][1] * B[2][0])) / 2.0;
+        r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+        const double lam = q + 2.0 * pp * std::cos(std::acos(r) / 3.0);
+        if (std::isfinite(lam) && lam > 0) lam_max = lam * (1.0 + 1e-6);
+    } else if (pp == 0) {
+        lam_max = q * (1.0 + 1e-6);
+    }
+    if (lam_max > fro2) lam_max = fro2;
+    if (lam_max < fro2 / 3.0) lam_max = fro2 / 3.0;
+    return std::sqrt(lam_max);
+}
+
+// A posed camera's table, built on the device (rt_tiles.hip; tiles.py: pose_screen_tiles is the definition, rt_grid.h has the
+// derivation). The host computes what depends on the pose alone, in double - N = M^-1, sigma_max(N), eps, pad, z - eps - and
+// the refusals that need no object; the device projects the registration spheres, counts, scans, fills and sorts. One
+// synchronise in the middle: the host reads the record (pairs, whole-screen objects, longest list), accepts or refuses the
+// table and grows the entry arrays. Refused: c->tiles stays disabled and the frame goes through the grid walk as before.
+int build_pose_tiles(rt_context* c, hipStream_t stream) {
+    rt_tiles_info_t& ti = c->tiles_info;
+    ti = rt_tiles_info_t{};
+    const rt::PoseGrid& g = c->pose;
+    const uint32_t W = g.width, H = g.height, n = c->n_objs;
+    ti.col_shift = 6u;
+    ti.tiles_x = W >> 6;
+    ti.tiles_y = (H + 7u) / 8u;
+    uint32_t refused = 0;
+    if (const char* env = std::getenv("RT_POSE_TILES"))  // measurement knob: "0" keeps a posed frame on the grid walk
+        if (env[0] == '0') refused |= RT_TILES_REFUSED_KNOB;
+    if (!grid_in_use(c) || (c->flags & RT_FLAG_LITERAL) || c->h_grid_spheres.size() != 4 * (size_t)n || n == 0) refused |= RT_TILES_REFUSED_NO_GRID;
+    if (W % 64u != 0 || W == 0) refused |= RT_TILES_REFUSED_WIDTH;
+    if (!(g.z < 0.f)) refused |= RT_TILES_REFUSED_Z;
+    const uint64_t n_tiles64 = (uint64_t)ti.tiles_x * ti.tiles_y;
+    if (n_tiles64 > rt::kPoseMaxTiles) refused |= RT_TILES_REFUSED_TILES;
+    rt::PoseTileArgs a;
+    std::memset(&a, 0, sizeof(a));
+    {
+        double M[3][3], N[3][3], norm2 = 0;
+        bool finite = true;
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k) {
+                M[r][k] = (double)g.m[3 * r + k];
+                norm2 += M[r][k] * M[r][k];
+                finite = finite && std::isfinite(M[r][k]);
+            }
+        for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(g.origin[k]);
+        const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) +
+                           M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+        if (!finite || !std::isfinite(det) || !(std::fabs(det) > 1e-12 * std::pow(norm2, 1.5))) {
+            refused |= RT_TILES_REFUSED_MATRIX;
+        } else {
+            N[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det;
+            N[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det;
+            N[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
+            N[1][0] = (M[1][2] * M[2][0] - M[1][0] * M[2][2]) / det;
+            N[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) / det;
+            N[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) / det;
+            N[2][0] = (M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det;
+            N[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det;
+            N[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det;
+            double nrow = 0, worst = 0;
+            const double zd = (double)g.z, vmax[3] = {(double)W / 2.0, (double)H / 2.0, std::fabs(zd)};
+            double mv[3];
+            for (int r = 0; r < 3; ++r) mv[r] = std::fabs(M[r][0]) * vmax[0] + std::fabs(M[r][1]) * vmax[1] + std::fabs(M[r][2]) * vmax[2];
+            for (int r = 0; r < 3; ++r) {
+                for (int k = 0; k < 3; ++k) { a.n[3 * r + k] = N[r][k]; finite = finite && std::isfinite(N[r][k]); }
+                nrow = std::max(nrow, std::fabs(N[r][0]) + std::fabs(N[r][1]) + std::fabs(N[r][2]));
+                worst = std::max(worst, std::fabs(N[r][0]) * mv[0] + std::fabs(N[r][1]) * mv[1] + std::fabs(N[r][2]) * mv[2]);
+            }
+            if (!finite) {
+                refused |= RT_TILES_REFUSED_MATRIX;
+            } else if (g.z < 0.f) {
+                const double sigma = sigma_max3(N);
+                const double eps = 3.1 * 0x1p-24 * worst + 0x1p-140 * nrow;  // rt_grid.h: |v' - v|_inf
+                ti.eps = eps;
+                if (!std::isfinite(eps) || !std::isfinite(sigma) || eps >= std::fabs(zd) / 2.0) {
+                    refused |= RT_TILES_REFUSED_EPS;
+                } else {
+                    const double pad = eps * (1.0 + (double)std::max(W, H) / (2.0 * std::fabs(zd))) / (1.0 - eps / std::fabs(zd));
+                    ti.pad = pad;
+                    if (!(pad <= 1.0)) refused |= RT_TILES_REFUSED_EPS;
+                    a.sig1 = sigma * (1.0 + 0x1p-40);
+                    a.absk = 0x1p-40 * sigma;
+                    a.z = zd;
+                    a.zme = zd - eps;
+                    a.pad = pad;
+                }
+            }
+        }
+    }
+    if (refused) {
+        ti.refused = refused;
+        return RT_OK;
+    }
+    for (int k = 0; k < 3; ++k) a.o[k] = (double)g.origin[k];
+    a.o1 = (std::fabs(a.o[0]) + std::fabs(a.o[1])) + std::fabs(a.o[2]);
+    a.half_w = (double)((float)W / 2.0f);
+    a.top = (double)H - (double)((float)H / 2.0f);
+    a.width = W;
+    a.height = H;
+    a.tiles_x = ti.tiles_x;
+    a.tiles_y = ti.tiles_y;
+    a.n_objs = n;
+    a.budget = 256ull * n + 4096ull;
+    const uint32_t n_tiles = (uint32_t)n_tiles64;
+    rt::PoseTileBuffers& b = c->ptb;
+    if (!c->d_pose_spheres) {  // once per context: the spheres the grid registered its objects with, as doubles
+        RT_HIP(c, hipMalloc((void**)&c->d_pose_spheres, sizeof(double) * 4 * (size_t)n));
+        RT_HIP(c, hipMemcpy(c->d_pose_spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice));
+        b.spheres = c->d_pose_spheres;
+        RT_HIP(c, hipMalloc((void**)&b.rect, sizeof(uint4) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.key, sizeof(float) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.sums, sizeof(uint32_t) * 1024));
+        RT_HIP(c, hipMalloc((void**)&b.record, sizeof(rt::PoseTileRecord)));
+        RT_HIP(c, hipHostMalloc((void**)&c->h_pose_record, sizeof(rt::PoseTileRecord), hipHostMallocDefault));
+    }
+    for (hipEvent_t& ev : c->ev_tiles)
+        if (!ev) RT_HIP(c, hipEventCreate(&ev));
+    if (c->ptb_tiles < n_tiles) {
+        if (b.count) (void)hipFree(b.count);
+        if (b.cursor) (void)hipFree(b.cursor);
+        if (b.tile_start) (void)hipFree(b.tile_start);
+        b.count = b.cursor = b.tile_start = nullptr;
+        c->ptb_tiles = 0;
+        RT_HIP(c, hipMalloc((void**)&b.count, sizeof(uint32_t) * (size_t)n_tiles));
+        RT_HIP(c, hipMalloc((void**)&b.cursor, sizeof(uint32_t) * (size_t)n_tiles));
+        RT_HIP(c, hipMalloc((void**)&b.tile_start, sizeof(uint32_t) * ((size_t)n_tiles + 1)));
+        c->ptb_tiles = n_tiles;
+    }
+    RT_HIP(c, hipEventRecord(c->ev_tiles[0], stream));
+    hipError_t e = rt::launch_pose_tile_count(a, b, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "pose tile count launch");
+    RT_HIP(c, hipEventRecord(c->ev_tiles[1], stream));
+    RT_HIP(c, hipMemcpyAsync(c->h_pose_record, b.record, sizeof(rt::PoseTileRecord), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    const rt::PoseTileRecord rec = *c->h_pose_record;
+    ti.n_entries = rec.pairs;
+    ti.n_global = rec.n_global;
+    ti.max_list = rec.max_list;
+    if (rec.n_global > rt::kPoseMaxGlobal) refused |= RT_TILES_REFUSED_GLOBAL;
+    if (rec.pairs > a.budget || rec.pairs > 0xfffffff0ull) refused |= RT_TILES_REFUSED_BUDGET;
+    if (rec.max_list > rt::kPoseMaxList) refused |= RT_TILES_REFUSED_LIST;
+    float ms = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_tiles[0], c->ev_tiles[1]));
+    ti.build_device_ms = (double)ms;
+    if (refused) {
+        ti.refused = refused;
+        return RT_OK;
+    }
+    if ((unsigned long long)rec.total != rec.pairs) return fail(c, RT_ERR_STATE, "internal: the pose tiles' scan does not match their count");
+    const size_t need = (size_t)rec.total + rt::kPoseMaxGlobal + 1;
+    if (c->ptb_entries < need) {
+        if (b.scratch) (void)hipFree(b.scratch);
+        if (b.entries) (void)hipFree(b.entries);
+        b.scratch = nullptr;
+        b.entries = nullptr;
+        c->ptb_entries = 0;
+        const size_t cap = need + need / 4;  // grow-only, with headroom: a viewer's next pose has a few more or fewer pairs
+        RT_HIP(c, hipMalloc((void**)&b.scratch, sizeof(uint32_t) * cap));
+        RT_HIP(c, hipMalloc((void**)&b.entries, sizeof(uint2) * cap));
+        c->ptb_entries = cap;
+    }
+    RT_HIP(c, hipEventRecord(c->ev_tiles[2], stream));
+    e = rt::launch_pose_tile_fill(a, b, rec.total, rec.n_global, rec.max_list, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "pose tile fill launch");
+    RT_HIP(c, hipEventRecord(c->ev_tiles[3], stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_tiles[2], c->ev_tiles[3]));
+    ti.build_device_ms += (double)ms;
+    c->tiles.tile_start = b.tile_start;
+    c->tiles.entries = b.entries;
+    c->tiles.tiles_x = ti.tiles_x;
+    c->tiles.col_shift = 6u;
+    c->tiles.global_begin = rec.total;
+    c->tiles.n_global = rec.n_global;
+    c->tiles.width = W;
+    c->tiles.posed = 1u;
+    c->tiles.enabled = 1u;
+    ti.enabled = 1u;
+    ti.source = 2u;
     return RT_OK;
 }
 
@@ -2272,6 +2510,7 @@ static int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream,
     c->z = 0.f;
     c->pose_w = g.width;
     c->pose_h = g.height;
+    c->pose = g;
     c->dir_w_zero = true;
     c->primary_w_one = v.starts_ok;
     c->rays_out_of_domain = !v.in_domain;
@@ -2325,6 +2564,76 @@ int rt_get_rays_info(const rt_context* c, rt_rays_info_t* info) {
     info->grid_built = c->grid.enabled ? 1u : 0u;
     info->grid_in_use = (grid_in_use(c) && !(c->flags & RT_FLAG_LITERAL)) ? 1u : 0u;
     info->literal = (c->flags & RT_FLAG_LITERAL) ? 1u : 0u;
+    return RT_OK;
+}
+
+// ---- screen tiles (hip_raytracer.h) ----
+// the tile width (as a shift) do_launch would ask for: 8 x 8 when the work-items of a camera's frame walk 8 x 8 blocks, else 64 x 8
+static uint32_t primary_col_shift(const rt_context* c) {
+    if (!c->pinhole || !c->width) return 6u;
+    const bool row_tiles = c->world <= 1 || (c->tile_rays % c->width == 0 && (c->tile_rays / c->width) % 8 == 0);
+    if (!(row_tiles && c->n_local % c->width == 0 && c->n_local < 0x7fffffffull)) return 6u;
+    return (c->width % 8u == 0 && (uint32_t)(c->n_local / c->width) % 8u == 0) ? 3u : 6u;
+}
+
+// the table is a cache of the context's rays: building it on demand changes nothing a caller can observe but the answer
+static int tiles_current(rt_context* c) {
+    if (!use_wavefront(c) || (!c->pinhole && !c->have_rays)) {
+        c->tiles_info = rt_tiles_info_t{};
+        c->tiles_info.refused = RT_TILES_REFUSED_NO_GRID;
+        return RT_OK;
+    }
+    const uint32_t col_shift = primary_col_shift(c);
+    if (!c->tiles_dirty && c->tiles_built_for == col_shift) return RT_OK;
+    RT_DEVICE(c);
+    StopWatch sw;
+    const int rc = refresh_screen_tiles(c, c->stream, col_shift);
+    if (rc == RT_OK) c->setup.screen_tiles_ms += sw.lap_ms();
+    return rc;
+}
+
+int rt_get_tiles_info(const rt_context* cc, rt_tiles_info_t* info) {
+    if (!cc || !info) return RT_ERR_INVALID_ARGUMENT;
+    rt_context* c = const_cast<rt_context*>(cc);
+    const int rc = tiles_current(c);
+    if (rc) return rc;
+    *info = c->tiles_info;
+    if (!info->enabled || !(grid_in_use(c) && !(c->flags & RT_FLAG_LITERAL))) {  // (a camera's table of a frame the literal loops render)
+        info->enabled = 0;
+        info->source = 0;
+        if (!info->refused) info->refused = RT_TILES_REFUSED_NO_GRID;
+        return RT_OK;
+    }
+    if (info->source == 1u) {  // the host builder keeps no list lengths: read the offsets back
+        const size_t n_tiles = (size_t)info->tiles_x * info->tiles_y;
+        std::vector<uint32_t> start(n_tiles + 1);
+        RT_DEVICE(c);
+        RT_HIP(c, hipMemcpy(start.data(), c->tiles.tile_start, sizeof(uint32_t) * (n_tiles + 1), hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < n_tiles; ++t) info->max_list = std::max(info->max_list, start[t + 1] - start[t]);
+    }
+    return RT_OK;
+}
+
+int rt_read_tiles(rt_context* c, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries) {
+    if (!c || !tile_start || !entries) return RT_ERR_INVALID_ARGUMENT;
+    rt_tiles_info_t info;
+    const int rc = rt_get_tiles_info(c, &info);
+    if (rc) return rc;
+    if (!info.enabled) return fail(c, RT_ERR_STATE, "rt_read_tiles: the next frame uses no screen tiles (rt_get_tiles_info has the reason)");
+    const uint64_t n_tiles = (uint64_t)info.tiles_x * info.tiles_y, total = info.n_entries + info.n_global;
+    if (n_start < n_tiles + 1 || n_entries < total) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_read_tiles: an array is too small for the table");
+    RT_DEVICE(c);
+    RT_HIP(c, hipMemcpy(tile_start, c->tiles.tile_start, sizeof(uint32_t) * (size_t)(n_tiles + 1), hipMemcpyDeviceToHost));
+    if (total) RT_HIP(c, hipMemcpy(entries, c->tiles.entries, sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_read_grid_spheres(const rt_context* c, double* spheres, uint64_t n) {
+    if (!c || !spheres) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->grid.enabled || c->h_grid_spheres.size() != 4 * (size_t)c->n_objs)
+        return fail(const_cast<rt_context*>(c), RT_ERR_STATE, "rt_read_grid_spheres: the context has no grid");
+    if (n != c->n_objs) return fail(const_cast<rt_context*>(c), RT_ERR_INVALID_ARGUMENT, "rt_read_grid_spheres: n must be the object count");
+    std::memcpy(spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n);
     return RT_OK;
 }
 
@@ -2723,6 +3032,18 @@ void rt_destroy(rt_context* c) {
     if (c->d_grid_entry_sphere) (void)hipFree(c->d_grid_entry_sphere);
     if (c->d_tile_start) (void)hipFree(c->d_tile_start);
     if (c->d_tile_entries) (void)hipFree(c->d_tile_entries);
+    if (c->d_pose_spheres) (void)hipFree(c->d_pose_spheres);
+    if (c->ptb.rect) (void)hipFree(c->ptb.rect);
+    if (c->ptb.key) (void)hipFree(c->ptb.key);
+    if (c->ptb.count) (void)hipFree(c->ptb.count);
+    if (c->ptb.cursor) (void)hipFree(c->ptb.cursor);
+    if (c->ptb.sums) (void)hipFree(c->ptb.sums);
+    if (c->ptb.record) (void)hipFree(c->ptb.record);
+    if (c->ptb.scratch) (void)hipFree(c->ptb.scratch);
+    if (c->ptb.tile_start) (void)hipFree(c->ptb.tile_start);
+    if (c->ptb.entries) (void)hipFree(c->ptb.entries);
+    if (c->h_pose_record) (void)hipHostFree(c->h_pose_record);
+    for (hipEvent_t ev : c->ev_tiles) if (ev) (void)hipEventDestroy(ev);
     if (c->d_lt_range) (void)hipFree(c->d_lt_range);
     if (c->d_lt_records) (void)hipFree(c->d_lt_records);
     if (c->d_lt_blocks) (void)hipFree(c->d_lt_blocks);

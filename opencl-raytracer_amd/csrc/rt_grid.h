@@ -150,6 +150,40 @@ __device__ __forceinline__ T table_at(const T* __restrict__ base, uint32_t index
 // is ABOVE the T of every lane (strict: T < key): every object from there on has t >= key > T on every lane, so it can
 // neither win nor tie, and since closest_take is order-free the objects before it give the brute-force loop's result. A lane
 // without a hit (T = kMaxFloat) or with a NaN fails the comparison: its wave walks the whole list.
+//
+// Posed cameras (rt_set_pose; built on the device per pose, rt_tiles.hip; tiles.py: pose_screen_tiles is the executable
+// definition). The pose is (W, H, z, fp32 M, fp32 origin o); work-item j W + i has the grid direction v = (x, y, z) - exact
+// floats - and the traced direction d = fl(M v) in posed_rays' order: two roundings of products and sums per component plus the
+// product's own, |d_r - (M v)_r| <= gamma_3 sum_c |M_rc| |v_c| with gamma_3 = 3u / (1 - 3u) < 3.1 u, u = 2^-24 (a product that
+// underflows adds at most 2^-149; the builder carries 2^-140 |N|_inf for the three of them). With N = M^-1 (double, from M
+// converted exactly) a point p = o + t d of the traced ray has N (p - o) = t v', v' = N d = v + N delta, so
+//     |v' - v|_inf <= eps := 3.1 u max_r (|N| |M| v_max)_r,   v_max = (W/2, H/2, |z|) >= |v| componentwise.
+// In that CAMERA FRAME the ray is the pinhole ray of direction v' from the origin, and the camera's argument applies to it:
+//  * Sphere. x -> N (x - o) maps the registration sphere (c, R) into the ball (c', R'), c' = N (c - o), R' = R sigma_max(N)
+//    (closed-form largest eigenvalue of N N^T, as object_bound: padded by 1e-6 relative). The double arithmetic of c' - a
+//    difference that can cancel, then three products and two sums, each term at most |N|_max (|c|_1 + |o|_1) - errs by less than
+//    4 sqrt(3) 2^-53 sigma_max(N) (|c|_1 + |o|_1) in length; the builder adds 2^-40 sigma_max(N) (|c|_1 + |o|_1) to R' - 4000 times that -
+//    and 2^-40 R' for the product R sigma_max(N) and the sums that follow. The DEVICE evaluates this per object; its correctly
+//    rounded double + - * / sqrt without contraction give it the same error bound as the host's, and nothing below needs the
+//    two to agree: each side's result is inside the slack on its own.
+//  * Depth. A reported hit with t not above the current best has p inside (c, R), hence t v' inside (c', R'):
+//    c'_z - R' <= t v'_z <= c'_z + R', and v'_z is in [z - eps, z + eps], negative because the builder refuses eps >= |z| / 2.
+//    c'_z - R' >= 0 gives t <= 0 for every such hit: the object is in no list (screen_rect's "entirely behind" rule, in the
+//    camera frame). c'_z + R' >= 0: no bound, the whole screen. Otherwise t >= (c'_z + R') / v'_z >= (c'_z + R') / (z - eps) - a
+//    negative numerator over the negative denominator of largest magnitude - rounded down by the camera's rule.
+//  * Rectangle. v' passes through the ball (c', R'), so its central projection v'' = v' z / v'_z onto the plane of depth z lies
+//    within screen_rect's tangent-plane extents of that ball. The work-item sits at v, not v'': per image axis
+//        |v''_x - v_x| <= |v'_x - v_x| + |v'_x| |z / v'_z - 1| <= eps + (W/2 + eps) eps / (|z| - eps)
+//                       = eps (1 + W / (2 |z|)) / (1 - eps / |z|)  =:  pad   (max(W, H) for both axes),
+//    added on every side in direction units on top of screen_rect's own one pixel + 1e-6 relative, before the outward rounding
+//    to float. The builder refuses pad > 1 (and eps >= |z| / 2): a pose that ill-conditioned is traced through the grid walk.
+//    Typical: eps ~ 2e-5, pad ~ 5e-5 at 256 x 128; eps ~ 4e-4 at 4096^2.
+// Tiles are 64 x 8 (col_shift 6) - a posed frame's work-items are in linear order, a wave is 64 pixels of a row - and the kernel
+// takes row and column from `width`, the pose's grid; the ray itself still comes from the ray buffer. The table is refused -
+// the frame then goes through the grid walk as any buffer's - when the grid does not serve the rays, z is not < 0, M is not
+// finite or singular, eps >= |z| / 2 or pad > 1, W % 64 != 0, more than 64 whole-screen objects, more pairs than the camera
+// builder's budget, a list longer than 1024 entries (what one workgroup sorts in 8 KB of LDS), or more than 2^20 tiles.
+// No test can show these margins sufficient: they rest on the argument above.
 struct ScreenTiles {
     const uint32_t* __restrict__ tile_start;  // tiles_x * tiles_y + 1 offsets
     const uint2* __restrict__ entries;        // {object index, depth key (float bits)}, ascending key inside a tile
@@ -157,6 +191,8 @@ struct ScreenTiles {
     uint32_t col_shift;                       //   3 (8 x 8, exactly a wave's block when work-items walk 8 x 8 blocks) or 6 (64 x 8: a wave is 64 pixels of a row)
     uint32_t global_begin, n_global;          // entries[global_begin ..): objects whose projection is the whole screen
     uint32_t enabled;
+    uint32_t width;                           // posed tables: the pose's grid width (a buffer frame's RenderParams carry none)
+    uint32_t posed;                           // the table belongs to the pose the ray buffer was generated from
 };
 
 // Light tiles: shadow rays towards ONE positional light (the last light - the one shade_and_reflect's colour comes from)

@@ -1,0 +1,59 @@
+// rt_tiles.h - host-side launchers of the posed camera's screen-tile builder (rt_tiles.hip): the depth-ordered tile lists of
+// rt_grid.h's ScreenTiles for the rays of one pose, built on the device from the objects' registration spheres.
+// opencl-raytracer_amd/tiles.py (pose_screen_tiles) is the executable definition; rt_grid.h has the derivation.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace rt {
+
+constexpr uint32_t kPoseMaxGlobal = 64;        // whole-screen objects a table may hold (the camera builder's limit)
+constexpr uint32_t kPoseMaxList = 1024;        // entries of one tile: what one workgroup sorts in 8 KB of LDS
+constexpr uint32_t kPoseMaxTiles = 1u << 20;   // tiles of one table: the scan's top level is one workgroup of 1024 block sums
+
+// One pose, as the host computes it in double (tiles.py: pose_constants). Everything a lane needs besides its own sphere.
+struct PoseTileArgs {
+    double n[9];            // N = M^-1, row-major
+    double o[3];            // the origin, converted exactly
+    double o1;              // |o|_1
+    double sig1, absk;      // sigma_max(N) (1 + 2^-40) and 2^-40 sigma_max(N): R' = R sig1 + absk (|c|_1 + |o|_1)
+    double z, zme, pad;     // z, z - eps, and the rectangle's pad in direction units
+    double half_w, top;     // fl(W / 2) and H - fl(H / 2): column = x + half_w, row = top - y
+    uint32_t width, height, tiles_x, tiles_y;
+    uint32_t n_objs;
+    unsigned long long budget;  // (object, tile) pairs the table may hold
+};
+
+// What the host reads back after the count and the scan, with one synchronise.
+struct PoseTileRecord {
+    unsigned long long pairs;   // (object, tile) pairs of the listed objects
+    uint32_t n_global;          // whole-screen objects (all of them, also beyond kPoseMaxGlobal)
+    uint32_t max_list;          // longest tile list
+    uint32_t total;             // tile_start[tiles]
+    uint32_t reserved;
+    uint32_t global_ids[kPoseMaxGlobal];
+};
+
+// Device memory of the builder, owned by the context (grow-only).
+struct PoseTileBuffers {
+    const double* spheres;      // 4 doubles per object: centre, registration radius (inf: always-list, < 0: never hit)
+    uint4* rect;                // per object: tile rectangle x0, x1, y0, y1 inclusive (x1 < x0: in no list)
+    float* key;                 // per object: depth key
+    uint32_t* count;            // per tile
+    uint32_t* cursor;           // per tile: where the fill pass puts the next entry
+    uint32_t* sums;             // per scan block of 1024 tiles
+    PoseTileRecord* record;
+    uint32_t* scratch;          // the entries as the fill pass left them (object indices)
+    uint32_t* tile_start;       // tiles + 1
+    uint2* entries;             // total + n_global + 1
+};
+
+// Passes 1-3: rectangles, keys and classes; per-tile counts (skipped on the device when the pairs exceed the budget or there are
+// too many whole-screen objects); the exclusive scan into tile_start and cursor; record->total and max_list.
+hipError_t launch_pose_tile_count(const PoseTileArgs& a, const PoseTileBuffers& b, hipStream_t stream);
+// Passes 4-5: fill and per-tile sort into `entries`, the global list and one zeroed entry behind it. `total`, `n_global` and
+// `max_list` are the record's, already accepted by the host (scratch holds total, entries total + n_global + 1 elements).
+hipError_t launch_pose_tile_fill(const PoseTileArgs& a, const PoseTileBuffers& b, uint32_t total, uint32_t n_global, uint32_t max_list,
+                                 hipStream_t stream);
+
+}  // namespace rt

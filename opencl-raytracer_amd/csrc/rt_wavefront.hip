@@ -348,7 +348,8 @@ __device__ __forceinline__ void tile_candidate(const TileRecord& o, int k, const
     closest_update_unordered<AM>(o.type, sx, sy, sz, dx, dy, dz, k, T, idx, cur_sphere);
 }
 
-// First round of a pinhole frame: a wave holds 64 consecutive pixels of one row, i.e. one 64x8 screen tile, and
+// First round of a pinhole frame - the fixed camera's, or a posed camera's whose table was built for its pose (rt_tiles.hip; the
+// ray then comes from the buffer, row and column from the pose's grid): a wave holds 64 consecutive pixels of one row, i.e. one 64x8 screen tile, and
 // walks that tile's object list with wave-uniform scalar loads (plus the always-list). Waves that straddle tiles
 // (ragged ends) fall back to the per-lane grid walk. Order-free tie rules, so the result is the same either way.
 // The list is in depth order (rt_grid.h: ScreenTiles): the wave leaves it at the first entry whose key - the smallest t
@@ -364,7 +365,8 @@ __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk)
     const uint64_t i = w.identity_queue ? t : (w.q_prev_closest[t] & kQueuePixel);
     const uint64_t g = global_ray_of(p, i);
     const Ray ray = primary_ray(p, g);
-    const uint32_t row = (uint32_t)g / p.width, col = (uint32_t)g - row * p.width;
+    const uint32_t grid_w = p.pinhole ? p.width : w.tiles.width;  // (a posed frame is a buffer frame: the pose's grid is the table's)
+    const uint32_t row = (uint32_t)g / grid_w, col = (uint32_t)g - row * grid_w;
     const uint32_t tile = (row >> 3) * w.tiles.tiles_x + (col >> w.tiles.col_shift);
     const uint32_t first = __builtin_amdgcn_readfirstlane(tile);
     float T = kMaxFloat;
@@ -2363,7 +2365,7 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
             if ((e2 = hipEventRecord(buf.ev_join, any_stream)) != hipSuccess) return e2;
         }
         if (nc_max) {
-            if (use_grid && first && w.tiles.enabled && w.rp.pinhole) {
+            if (use_grid && first && w.tiles.enabled && (w.rp.pinhole || (w.tiles.posed && w.tiles.width))) {
                 hipLaunchKernelGGL((wf_trace_primary_tiles<AM>), grid_for(nc_max), dim3(256), 0, stream, w);
             } else if (use_grid) {
                 launch_persistent<AM, false>(w, nc_max, rs + kTicketBase, stream, side_by_side);  // (a grid implies direction.w = 0)

@@ -40,6 +40,7 @@ EXPORTS = [
     "rt_multi_frame_pixels",
     "rt_set_rays_device", "rt_set_rays", "rt_get_rays_info",
     "rt_set_pose", "rt_generate_rays_device", "rt_set_pose_multi",
+    "rt_get_tiles_info", "rt_read_tiles", "rt_read_grid_spheres",
 ]
 
 
@@ -82,6 +83,17 @@ class RTRaysInfo(ctypes.Structure):
             v = getattr(self, n)
             out[n] = int(v) if t is ctypes.c_uint32 else np.array(list(v), dtype=np.float32 if t._type_ is ctypes.c_float else np.float64)
         return out
+
+
+class RTTilesInfo(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_uint32), ("source", ctypes.c_uint32), ("tiles_x", ctypes.c_uint32), ("tiles_y", ctypes.c_uint32),
+        ("col_shift", ctypes.c_uint32), ("n_global", ctypes.c_uint32), ("max_list", ctypes.c_uint32), ("refused", ctypes.c_uint32),
+        ("n_entries", ctypes.c_uint64), ("build_device_ms", ctypes.c_double), ("eps", ctypes.c_double), ("pad", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
 
 
 _lib = None
@@ -190,6 +202,13 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_generate_rays_device.argtypes = [vp, u32, u32, ctypes.c_float, f9, f3, vp, vp]
         lib.rt_set_pose_multi.restype = i32
         lib.rt_set_pose_multi.argtypes = [vp, u32, u32, ctypes.c_float, f9, f3]
+    if hasattr(lib, "rt_get_tiles_info"):  # (the same: a build from before the posed camera's screen tiles)
+        lib.rt_get_tiles_info.restype = i32
+        lib.rt_get_tiles_info.argtypes = [vp, ctypes.POINTER(RTTilesInfo)]
+        lib.rt_read_tiles.restype = i32
+        lib.rt_read_tiles.argtypes = [vp, vp, u64, vp, u64]
+        lib.rt_read_grid_spheres.restype = i32
+        lib.rt_read_grid_spheres.argtypes = [vp, vp, u64]
     if path is None:
         _lib = lib
     return lib
@@ -274,6 +293,7 @@ class HIPRaytracer:
         if camera is not None:
             self._check(self._lib.rt_set_camera(self._ctx, int(camera[0]), int(camera[1]), float(camera[2])))
         self.n_rays = n_rays
+        self._n_objs = int(objects.shape[0])
         if supersample != 1:
             try:
                 self.set_supersampling(supersample)
@@ -472,6 +492,31 @@ class HIPRaytracer:
         info = RTRaysInfo()
         self._check(self._lib.rt_get_rays_info(self._ctx, ctypes.byref(info)))
         return info.as_dict()
+
+    def tiles_info(self) -> dict:
+        """rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use (built now if the rays
+        changed): enabled, source (0 none, 1 the camera's, 2 the pose's), tiles_x, tiles_y, col_shift, n_entries, n_global,
+        max_list, refused (tiles.REFUSED_* bits), build_device_ms, eps, pad."""
+        info = RTTilesInfo()
+        self._check(self._lib.rt_get_tiles_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
+
+    def read_tiles(self):
+        """rt_read_tiles: (tile_start uint32[tiles + 1], entries uint32[n_entries + n_global, 2] = {object index, key bits}) of
+        that table - a tile's entries ascending by (key, index), the whole-screen objects behind the last tile's."""
+        info = self.tiles_info()
+        start = np.zeros(info["tiles_x"] * info["tiles_y"] + 1, dtype=np.uint32)
+        entries = np.zeros((info["n_entries"] + info["n_global"], 2), dtype=np.uint32)
+        self._check(self._lib.rt_read_tiles(self._ctx, _ptr(start), start.size, _ptr(entries) if len(entries) else _ptr(start),
+                                            len(entries)))
+        return start, entries
+
+    def grid_spheres(self) -> np.ndarray:
+        """rt_read_grid_spheres: n x 4 float64, the spheres (centre, radius) the grid registered the objects with - what the
+        screen tiles are built from (inf: tested by every ray, negative: never hit)."""
+        out = np.zeros((self._n_objs, 4), dtype=np.float64)
+        self._check(self._lib.rt_read_grid_spheres(self._ctx, _ptr(out), self._n_objs))
+        return out
 
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))

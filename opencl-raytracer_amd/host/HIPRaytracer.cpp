@@ -131,6 +131,13 @@ size_t HIPRaytracer::Pixels() const {
     return (size_t)rt_local_pixels(ctx);
 }
 
+rt_tiles_info_t HIPRaytracer::TilesInfo() {
+    rt_tiles_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_tiles_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::TilesInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_stats_t HIPRaytracer::Stats() {
     rt_stats_t s;
     if (multi) {  // several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures

@@ -61,6 +61,9 @@ public:
     void SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream = nullptr);
 
     rt_stats_t Stats();
+    // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
+    // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.
+    rt_tiles_info_t TilesInfo();
     rt_context* Context() { return ctx; }
 
 private:

@@ -10,7 +10,16 @@ the same ray buffer alternating round by round:
 3. the host route: rays.posed_rays (numpy) + rt_set_rays (537 MB host-to-device, then the device route), fewer rounds;
 4. the kernel time of the cfg4 frame from the posed buffer (identity pose: the same rays) beside the rt_set_camera frame's on the
    same context - what the primary-tile kernel, which needs the fixed camera, is worth.
-Walls are host clocks around calls that end in a device synchronise. usage: python tools/ab/set_pose_timing.py cfg4 [repeats >= 5] [out.json]"""
+Walls are host clocks around calls that end in a device synchronise. usage: python tools/ab/set_pose_timing.py cfg4 [repeats >= 5] [out.json]
+
+With a fourth argument "tiles" (python tools/ab/set_pose_timing.py cfg4 7 profiles/pose_tiles_timing.json tiles) the script measures
+instead what a viewer pays per frame when the pose changes before EVERY frame, with and without the pose's screen tiles
+(csrc/rt_tiles.hip; RT_POSE_TILES=0 is the parent commit's route): the panned pose (its yaw moves a little every round) and the
+identity pose, the two settings of the knob alternating round by round in this one process, medians of >= 7 rounds after a warm-up
+round. Per frame: the wall of rt_set_pose, the tile build (device events: rt_tiles_info_t::build_device_ms; wall: the
+rt_get_tiles_info call that builds), the frame's kernel time, and their sum; the rt_set_camera frame beside them; the knob's 0
+position against profiles/set_pose_timing.json; and the verdict the default rests on (build + frame with tiles below the sum
+without, by more than the spread between the rounds of one setting)."""
 import json, os, re, statistics, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -87,6 +96,92 @@ desc, objs, lights, W, H, kernel, depth = bench.load_workload(wl)
 n = W * H
 z = float(camera.camera_z(H))
 M, origin = rotation(12, -7, 30), (0.0, 0.0, 0.0)
+
+
+def pose_tiles_timing(out_path):
+    rounds = max(7, repeats)
+    res = {"what": "a pose changed before every frame, with the pose's screen tiles built on the device (RT_POSE_TILES=1) and without "
+                   "(RT_POSE_TILES=0, the parent commit's route), alternating round by round in one process; per frame: rt_set_pose wall, "
+                   "tile build (device events and wall), frame kernel time, their sum",
+           "workload": desc, "frame": [W, H], "rays": n, "rounds": rounds, "library_sha16": bench.library_sha16(),
+           "measured_on": os.environ.get("RT_TIMING_WHERE", "not recorded")}
+    rt = HIPRaytracer(objs, lights, None, depth, kernel=kernel, camera=(W, H, z))
+    d_frame = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+    res["frame_kernel_ms_pinhole"] = frame_kernel_ms(rt, d_frame)
+    res["tiles_info_pinhole"] = rt.tiles_info()
+    rows = {(knob, pose): {"set_pose_wall_ms": [], "build_wall_ms": [], "build_device_ms": [], "frame_kernel_ms": [], "sum_ms": []}
+            for knob in "01" for pose in ("pan", "identity")}
+    infos = {}
+    for rnd in range(rounds + 1):   # round 0 warms up: buffers, the spheres' upload, code objects
+        for knob in "01":
+            os.environ["RT_POSE_TILES"] = knob
+            for pose in ("pan", "identity"):
+                Mp = rotation(12 + 0.05 * rnd, -7, 30) if pose == "pan" else np.eye(3)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                rt.set_pose(W, H, z, Mp, origin)
+                t1 = time.perf_counter()
+                info = rt.tiles_info()   # builds the table of the new pose (knob 0: refuses at once)
+                t2 = time.perf_counter()
+                rt.render_device(d_frame.data_ptr(), 0)
+                torch.cuda.synchronize()
+                k_ms = float(rt.stats().last_kernel_ms)
+                infos[(knob, pose)] = info
+                if rnd:
+                    r = rows[(knob, pose)]
+                    r["set_pose_wall_ms"].append((t1 - t0) * 1e3)
+                    r["build_wall_ms"].append((t2 - t1) * 1e3)
+                    r["build_device_ms"].append(info["build_device_ms"])
+                    r["frame_kernel_ms"].append(k_ms)
+                    r["sum_ms"].append((t2 - t0) * 1e3 + k_ms)
+    os.environ.pop("RT_POSE_TILES")
+    rt.set_camera(W, H, z)
+    res["frame_kernel_ms_pinhole_after"] = frame_kernel_ms(rt, d_frame)
+    rt.close()
+    before = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "set_pose_timing.json")) as f:
+            old = json.load(f)
+        before = {"pan": old["frame_kernel_ms_posed_pan"], "identity": old["frame_kernel_ms_posed_identity"], "pinhole": old["frame_kernel_ms_pinhole"]}
+    except (OSError, KeyError, ValueError):
+        pass
+    res["profiles_set_pose_timing_json"] = before
+    for pose in ("pan", "identity"):
+        off, on = rows[("0", pose)], rows[("1", pose)]
+        entry = {"without_tiles": {k: summary(v) for k, v in off.items()}, "with_tiles": {k: summary(v) for k, v in on.items()},
+                 "tiles_info_with": infos[("1", pose)], "tiles_info_without": infos[("0", pose)]}
+        spread = max(max(off["sum_ms"]) - min(off["sum_ms"]), max(on["sum_ms"]) - min(on["sum_ms"]))
+        gain = statistics.median(off["sum_ms"]) - statistics.median(on["sum_ms"])
+        entry["sum_gain_median_ms"] = gain
+        entry["sum_spread_between_rounds_ms"] = spread
+        entry["tiles_pay"] = bool(gain > spread)
+        pin = res["frame_kernel_ms_pinhole"]["median_ms"]
+        gap = statistics.median(off["frame_kernel_ms"]) - pin
+        entry["frame_gap_to_pinhole_without_ms"] = gap
+        entry["frame_gap_to_pinhole_with_ms"] = statistics.median(on["frame_kernel_ms"]) - pin
+        entry["gap_recovered_by_the_frame_ms"] = gap - entry["frame_gap_to_pinhole_with_ms"]
+        if pose in before:
+            lo, hi = before[pose]["best_ms"], before[pose]["max_ms"]
+            m0 = statistics.median(off["frame_kernel_ms"])
+            entry["knob_0_frame_matches_the_earlier_profile"] = bool(lo <= m0 <= hi)   # (inside that file's own best .. max)
+        res[pose] = entry
+        for label, r in (("without", off), ("with", on)):
+            print(f"{wl} {pose:8s} {label:7s} tiles: set_pose {statistics.median(r['set_pose_wall_ms']):7.3f}  build wall {statistics.median(r['build_wall_ms']):7.3f} "
+                  f"(device {statistics.median(r['build_device_ms']):6.3f})  frame {statistics.median(r['frame_kernel_ms']):7.3f}  sum {statistics.median(r['sum_ms']):7.3f} ms "
+                  f"[{min(r['sum_ms']):.3f} .. {max(r['sum_ms']):.3f}]", flush=True)
+        print(f"{wl} {pose:8s} gain of the sum {gain:.3f} ms, spread between rounds {spread:.3f} ms, tiles pay: {entry['tiles_pay']}; table "
+              f"{infos[('1', pose)]}", flush=True)
+    print(f"{wl} pinhole frame {res['frame_kernel_ms_pinhole']['median_ms']:.3f} ms (after: {res['frame_kernel_ms_pinhole_after']['median_ms']:.3f})", flush=True)
+    res["default_on"] = bool(res["pan"]["tiles_pay"] and res["identity"]["tiles_pay"])
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if len(sys.argv) > 4 and sys.argv[4] == "tiles":
+    pose_tiles_timing(sys.argv[3])
+    sys.exit(0)
+
 result = {"what": "rt_set_pose on a live context against the two routes to the same ray buffer without it (torch on the device + "
                   "rt_set_rays_device; numpy posed_rays + rt_set_rays); device time of the verdict and generation kernels; kernel time of the "
                   "frame from the posed buffer and from the pinhole camera",
