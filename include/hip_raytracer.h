@@ -61,7 +61,9 @@ extern "C" {
  *      Later addition, same version: replaceable rays - rt_set_rays_device, rt_set_rays, rt_get_rays_info. Additions only; a caller
  *      detects support by the symbol (dlsym of rt_set_rays_device).
  *      Later addition, same version: posed cameras - rt_set_pose, rt_generate_rays_device, rt_set_pose_multi; rt_rays_info_t::source
- *      may read 3. Additions only; a caller detects support by the symbol (dlsym of rt_set_pose). */
+ *      may read 3. Additions only; a caller detects support by the symbol (dlsym of rt_set_pose).
+ *      Later addition, same version: replaceable lights - rt_set_lights, rt_set_lights_multi, rt_get_light_tiles_info,
+ *      rt_read_light_tiles, rt_read_grid_pretest. Additions only; a caller detects support by the symbol (dlsym of rt_set_lights). */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -446,6 +448,79 @@ int rt_get_tiles_info(const rt_context* ctx, rt_tiles_info_t* info);
 int rt_read_tiles(rt_context* ctx, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries);
 int rt_read_grid_spheres(const rt_context* ctx, double* spheres, uint64_t n);
 
+/* ---- replaceable lights --------------------------------------------------------------------------------------------------------
+ * The last input of a frame that was frozen at rt_create: the lights. rt_set_lights replaces them on a live context - a viewer that
+ * drags a light, an animation that changes one per frame - without rt_destroy + rt_create.
+ *
+ * rt_set_lights: `lights` are n_lights HOST records in the layout rt_create takes. The count may differ from the creation's; 0 is
+ * allowed. Refused with RT_ERR_INVALID_ARGUMENT: n_lights >= 1 << 22 (rt_create's limit), n_lights != 0 with lights == NULL. A
+ * refused call leaves the context exactly as it was: lights, tables and flags. The call is synchronous like rt_set_pose: on return
+ * the array may be reused and the next render on any stream sees the new lights. Renders of this context still in flight on ANOTHER
+ * stream must be ordered by the caller (wait for them first), as for rt_set_pose and every other entry point: the call rewrites
+ * the light array and the light tiles those frames read.
+ *
+ * Contract. The next render is the frame a FRESH context renders that is created with the same objects and flags, the current rays /
+ * camera / pose / shard / supersampling factor, and these lights - bit for bit, with the same rays_reference and hit_pixels - for
+ * every kernel (hittest, shade, shade_and_reflect) and every path (small-scene kernel, round machine, literal loops, brute force,
+ * RT_FLAG_NO_GRID). What was set or rendered before does not matter.
+ *
+ * RT_FLAG_DEVICE_OPENCL: rt_create's predicate on the lights - a positional light on (within the padded bound of) an object, or a
+ * directional light whose direction is outside the walks' domain - is evaluated again for the new lights against the objects' bounds
+ * kept from creation; the frame goes literal, or stops being literal, as a fresh context's would. rt_get_rays_info().literal
+ * reports the result. (A literal frame forced by a degenerate instance, by RT_FLAG_LITERAL or by the rays in use is independent.)
+ *
+ * Light tiles. The shadow rays towards the LAST light are served by per-direction candidate lists (csrc/rt_grid.h: LightTiles).
+ * rt_create builds them on the host; rt_set_lights rebuilds them ON THE DEVICE from the objects' registration spheres
+ * (csrc/rt_light_tiles.hip; opencl-raytracer_amd/light_tiles.py is the executable definition), in the block form only. They are a
+ * culling structure - every candidate still goes through the pre-test and the exact test - so pixels do not depend on which side
+ * built them, or on whether they were built at all: a refused table (bits below) leaves the last light's shadow rays to the grid
+ * walk, same bits. RT_LIGHT_TILES_DEVICE=0 in the environment makes rt_set_lights build nothing (a measurement knob, as
+ * RT_POSE_TILES=0 is for poses); RT_NO_LIGHT_TILES and RT_NO_LT_BLOCKS keep their meaning. A context that never calls
+ * rt_set_lights renders through exactly the tables rt_create built (source 1).
+ *
+ * rt_get_light_tiles_info reports the table the next frame's shadow rays will use (valid for every context). rt_read_light_tiles
+ * copies the block table and its ids back and walks the chains on the host - what is read out is what the kernels read:
+ * tile_start[tiles_u * tiles_v + 1] offsets and, per entry in list order, three 32-bit words {object index, block word lo, block
+ * word hi} (lo = x16 | y16 << 16, hi = z16 | r8 << 16 | k8 << 24). n_start and n_entries are the arrays' capacities in elements /
+ * triples; too small: RT_ERR_INVALID_ARGUMENT. RT_ERR_STATE when no table, or only the record form (RT_NO_LT_BLOCKS), is in use. */
+#define RT_LTILES_REFUSED_NO_GRID 0x1u   /* no grid built, literal loops, kernel not shade_and_reflect, no lights, or objects on the
+                                            grid's always-list                                                                      */
+#define RT_LTILES_REFUSED_LIGHT   0x2u   /* the last light is directional or not finite                                           */
+#define RT_LTILES_REFUSED_PLANE   0x4u   /* no axis-aligned plane through the light with every object 0.05 in front of it         */
+#define RT_LTILES_REFUSED_TANGENT 0x8u   /* an object without a usable tangent (beyond 1.5533 rad of the axis)                     */
+#define RT_LTILES_REFUSED_BOUNDS  0x10u  /* the rectangles' bounds are empty or not finite                                        */
+#define RT_LTILES_REFUSED_BUDGET  0x20u  /* more than 64 n_objs + 4096 (object, tile) pairs, or 32-bit byte offsets exceeded       */
+#define RT_LTILES_REFUSED_LIST    0x40u  /* a tile's list is longer than 1024 entries (device builder)                            */
+#define RT_LTILES_REFUSED_BLOCKS  0x80u  /* block form impossible: lattice or steps not finite, 2^24 blocks, RT_NO_LT_BLOCKS       */
+#define RT_LTILES_REFUSED_KNOB    0x100u /* RT_NO_LIGHT_TILES, or RT_LIGHT_TILES_DEVICE=0 for a device build                       */
+typedef struct rt_light_tiles_info_t {
+    uint32_t enabled;               /* the next large-scene frame's shadow rays to `light` look up tile lists                  */
+    uint32_t source;                /* 0 none, 1 built by rt_create on the host, 2 built by rt_set_lights on the device        */
+    uint32_t light;                 /* index of the light the table serves (the last one)                                      */
+    uint32_t axis;                  /* projection axis 0 / 1 / 2: every object lies on the `sign` side of the light along it   */
+    int32_t  sign;                  /* +1 or -1                                                                                */
+    uint32_t tiles_u, tiles_v;
+    uint32_t n_blocks;              /* 32-byte blocks of the table: a head per tile + the chains (0: record form)              */
+    uint32_t max_list;              /* longest tile list                                                                       */
+    uint32_t refused;               /* RT_LTILES_REFUSED_* of the last build (0 when enabled)                                  */
+    uint64_t n_entries;             /* (object, tile) pairs                                                                    */
+    double   build_device_ms;       /* device time of the last build's passes (events; 0 for the host's)                       */
+    double   k_pad;                 /* the pad kPad every registration sphere gets                                             */
+    double   cut_pad;               /* absolute slack of the kernels' distance cut                                             */
+    double   box_diagonal;          /* the grid box's diagonal D used for the radius rounding                                  */
+    float    u0, v0, inv_du, inv_dv;/* tile (iu, iv) covers u0 + iu / inv_du ...                                               */
+    float    lat_lo[3], lat_step;   /* the 16-bit lattice of the centres: lat_lo + q lat_step                                  */
+    float    rstep, kstep;          /* the 8-bit steps of the radius (rounded up) and the key (rounded down)                   */
+    float    pretest_alpha;         /* the grid's pre-test distance term, part of the radius rounding                          */
+    uint32_t reserved;
+} rt_light_tiles_info_t;
+int rt_set_lights(rt_context* ctx, const void* lights, uint32_t n_lights);
+int rt_get_light_tiles_info(const rt_context* ctx, rt_light_tiles_info_t* info);
+int rt_read_light_tiles(rt_context* ctx, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries);
+/* The pre-test radii the block form's radii are rounded from, one float per object as the grid's entry spheres carry them (the
+ * sign is a flag of the kernels' pre-test; the radius is the magnitude): an accessor for tests, next to rt_read_grid_spheres. */
+int rt_read_grid_pretest(const rt_context* ctx, float* pre, uint64_t n);
+
 void rt_destroy(rt_context* ctx);
 
 /* ---- several GPUs from one process ------------------------------------------------------------------------------------
@@ -478,6 +553,8 @@ int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z);
 /* rt_set_pose ("posed cameras", above) on every context, all or none: every shard runs its verdict pass and its refusals, on its own
  * device, stream and host thread; only if none refuses, every shard generates the frame's rays in its own buffer. */
 int rt_set_pose_multi(rt_multi* m, uint32_t width, uint32_t height, float z, const float mat[9], const float origin[3]);
+/* rt_set_lights ("replaceable lights", above) on every context, all or none: the arguments are validated before any shard is touched. */
+int rt_set_lights_multi(rt_multi* m, const void* lights, uint32_t n_lights);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);
 int rt_render_multi_device(rt_multi* m, void* d_frame);

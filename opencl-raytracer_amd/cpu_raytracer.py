@@ -77,6 +77,11 @@ class CPURaytracer:
         self.pose = (int(width), int(height), float(np.float32(z)), np.ascontiguousarray(m.reshape(9)), np.ascontiguousarray(o))
         self.new_rays = None
 
+    def set_lights(self, lights):
+        """CPURaytracer::SetLights, the option HIPRaytracer.set_lights is on the GPU: the next Render() lights the scene with these
+        lights (any count) instead of the constructor's. Only the array is replaced."""
+        self.lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+
     def set_rays(self, rays):
         """CPURaytracer::SetRays, the option HIPRaytracer.set_rays is on the GPU: the next Render() traces these rays - as many as
         the object was constructed with - instead of the constructor's."""

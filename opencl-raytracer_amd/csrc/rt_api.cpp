@@ -10,6 +10,7 @@
 #include "rt_rays.h"
 #include "rt_raygen.h"
 #include "rt_tiles.h"
+#include "rt_light_tiles.h"
 
 #include <hip/hip_runtime.h>
 
@@ -147,6 +148,21 @@ struct rt_context {
     uint4* d_lt_blocks = nullptr;           // the light tiles' lists as blocks of three candidates (LightTiles::blocks)
     uint32_t* d_lt_block_ids = nullptr;
     rt::LightTiles light_tiles = {};
+    // Replaceable lights (rt_set_lights): what rt_get_light_tiles_info reports of the table in use; the device builder's memory
+    // (rt_light_tiles.hip; grow-only), its records' pinned mirrors and the events around its four stages; the flags rt_create was
+    // given and the two reasons it may have added RT_FLAG_LITERAL for, kept apart because only one of them follows the lights;
+    // and, under RT_FLAG_DEVICE_OPENCL, what object_bound gave per object (x, y, z, r) for the predicate on the new lights.
+    rt_light_tiles_info_t lt_info = {};
+    rt::LightTileBuffers ltb = {};
+    float* d_lt_pre = nullptr;
+    size_t ltb_tiles = 0, ltb_entries = 0, ltb_blocks = 0;
+    rt::LightTileRecord* h_lt_record = nullptr;
+    rt::PoseTileRecord* h_lt_lists = nullptr;   // [0] the lists', [1] the chains'
+    hipEvent_t ev_lt[8] = {};
+    uint32_t lights_capacity = 0;
+    uint32_t user_flags = 0;
+    bool degenerate_literal = false, lights_literal = false;
+    std::vector<double> h_obj_bounds;
     rt::BlockGrid blocks = {};              // the closest-hit walk's coarse grid of 32-byte blocks (rt_grid.h: BlockGrid)
     uint4* d_walk_blocks = nullptr;
     uint32_t* d_walk_ids = nullptr;
@@ -1041,7 +1057,9 @@ int build_pose_tiles(rt_context* c, hipStream_t stream) {
     if (!c->d_pose_spheres) {  // once per context: the spheres the grid registered its objects with, as doubles
         RT_HIP(c, hipMalloc((void**)&c->d_pose_spheres, sizeof(double) * 4 * (size_t)n));
         RT_HIP(c, hipMemcpy(c->d_pose_spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice));
-        b.spheres = c->d_pose_spheres;
+    }
+    b.spheres = c->d_pose_spheres;
+    if (!b.record) {  // (the spheres may be there already: the light tiles' builder shares them)
         RT_HIP(c, hipMalloc((void**)&b.rect, sizeof(uint4) * (size_t)n));
         RT_HIP(c, hipMalloc((void**)&b.key, sizeof(float) * (size_t)n));
         RT_HIP(c, hipMalloc((void**)&b.sums, sizeof(uint32_t) * 1024));
@@ -1736,6 +1754,29 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
     return RT_OK;
 }
 
+// RT_FLAG_DEVICE_OPENCL's predicate on the lights (rt_create has the reasons): a directional light whose direction is outside the
+// walks' domain, or a positional light within the padded bound of an object, makes the frame's outcome depend on the order of the
+// reference's loop, which only the literal loops follow. h_obj_bounds holds object_bound's x, y, z, r per object.
+bool lights_need_literal(const rt_context* c, const rt_light* L, uint32_t n_lights) {
+    if (!n_lights) return false;
+    for (uint32_t l = 0; l < n_lights; ++l)
+        if (L[l].position[3] == 0.f && !direction_in_domain(L[l].position[0], L[l].position[1], L[l].position[2])) return true;
+    std::atomic<bool> near{false};
+    parallel_for(c->n_objs, 8192, [&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1 && !near.load(std::memory_order_relaxed); ++i) {
+            const double bx = c->h_obj_bounds[4 * i], by = c->h_obj_bounds[4 * i + 1], bz = c->h_obj_bounds[4 * i + 2], br = c->h_obj_bounds[4 * i + 3];
+            if (!(br >= 0.0)) continue;  // never hit
+            const double reach = br * (1.0 + 1e-4) + 1e-4 * (std::fabs(bx) + std::fabs(by) + std::fabs(bz) + br);
+            for (uint32_t l = 0; l < n_lights; ++l) {
+                if (L[l].position[3] == 0.f) continue;
+                const double dx = (double)L[l].position[0] - bx, dy = (double)L[l].position[1] - by, dz = (double)L[l].position[2] - bz;
+                if (!(dx * dx + dy * dy + dz * dz > reach * reach)) { near.store(true, std::memory_order_relaxed); break; }
+            }
+        }
+    });
+    return near.load();
+}
+
 // Light tiles (rt_grid.h: LightTiles): the objects a shadow ray towards the LAST positional light can meet, binned by
 // direction as seen from that light. shade_and_reflect's colour comes from the last light (Q1), so outside literal
 // mode nearly every shadow ray goes there; rays towards other lights (stale-specular scans) keep using the grid walk.
@@ -1743,14 +1784,18 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
 // line of a shadow ray passes the light within ~1e-5), no always-tested objects, and an axis-aligned plane through the
 // light with every object strictly (by its radius + 0.05) on one side - else nothing is built and the grid walk serves.
 int build_light_tiles(rt_context* c, const rt_light* lights) {
+    // (rt_set_lights' builder for a live context is build_light_tiles_device below: the same rules on the device, block form only)
     c->light_tiles = rt::LightTiles{};
+    rt_light_tiles_info_t& info = c->lt_info;  // what rt_get_light_tiles_info reports of this build
+    info = rt_light_tiles_info_t{};
+    auto refuse = [&](uint32_t bit) { info.refused |= bit; return RT_OK; };
     if (!c->grid.enabled || c->grid.n_always != 0 || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->flags & RT_FLAG_LITERAL) ||
         c->n_lights == 0 || c->h_grid_spheres.empty() || c->h_grid_pre.size() != c->n_objs)
-        return RT_OK;
-    if (std::getenv("RT_NO_LIGHT_TILES")) return RT_OK;  // measurement knob
+        return refuse(RT_LTILES_REFUSED_NO_GRID);
+    if (std::getenv("RT_NO_LIGHT_TILES")) return refuse(RT_LTILES_REFUSED_KNOB);  // measurement knob
     const uint32_t li = c->n_lights - 1u;
     const float* lp = lights[li].position;
-    if (!(lp[3] != 0.f) || !std::isfinite(lp[0] + lp[1] + lp[2])) return RT_OK;  // directional (or garbage): no centre of projection
+    if (!(lp[3] != 0.f) || !std::isfinite(lp[0] + lp[1] + lp[2])) return refuse(RT_LTILES_REFUSED_LIGHT);  // directional (or garbage): no centre of projection
     const double L[3] = {lp[0], lp[1], lp[2]};
     SetupTrace lap("light tiles");
     const uint32_t n = c->n_objs;
@@ -1785,7 +1830,7 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
             }
             if (clear > kFront && clear != inf && clear > best_clear) { best_clear = clear; best_axis = a; best_sign = sg; }
         }
-    if (best_axis < 0) return RT_OK;
+    if (best_axis < 0) return refuse(RT_LTILES_REFUSED_PLANE);
     // light-local frame: z' = -sign * (p - L)[axis] (objects at z' < 0), x', y' = the other two components
     const uint32_t az = (uint32_t)best_axis, ax = (az + 1u) % 3u, ay = (az + 2u) % 3u;
     const double szn = -best_sign;
@@ -1818,13 +1863,13 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
             rect[i] = rc;
         }
     });
-    if (no_span.load()) return RT_OK;
+    if (no_span.load()) return refuse(RT_LTILES_REFUSED_TANGENT);
     for (uint32_t i = 0; i < n; ++i) {
         const Rect& rc = rect[i];
         if (!(rc.u1 >= rc.u0)) continue;
         U0 = std::min(U0, rc.u0); U1 = std::max(U1, rc.u1); V0 = std::min(V0, rc.v0); V1 = std::max(V1, rc.v1);
     }
-    if (!(U1 > U0) || !(V1 > V0) || !std::isfinite(U0 + U1 + V0 + V1)) return RT_OK;
+    if (!(U1 > U0) || !(V1 > V0) || !std::isfinite(U0 + U1 + V0 + V1)) return refuse(RT_LTILES_REFUSED_BOUNDS);
     lap("axis + rectangles");
     // tile count: ~1.6 sqrt(n) per axis, halved while the lists would hold more than 24 entries per object
     double tile_factor = 1.6;
@@ -1861,7 +1906,7 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
         if (total <= 24ull * n + 4096ull || T <= 16u) break;
         T /= 2u;
     }
-    if (total > 64ull * n + 4096ull || total * 32ull >= 0xffffffffull) return RT_OK;  // objects too wide as seen from the light / table beyond 32-bit byte offsets
+    if (total > 64ull * n + 4096ull || total * 32ull >= 0xffffffffull) return refuse(RT_LTILES_REFUSED_BUDGET);  // objects too wide as seen from the light / table beyond 32-bit byte offsets
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1) {
             for (size_t k = 0; k < (size_t)T * T; ++k) start[k + 1] += start[k];
@@ -1927,6 +1972,17 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
     lt.light = li;
     lt.cut_pad = (float)std::max(1e-4, 4e-7 * (2.0 * coord_max + reach_max));
     lt.enabled = 1u;
+    info.enabled = 1u;
+    info.source = 1u;
+    info.light = li;
+    info.axis = az;
+    info.sign = best_sign > 0 ? 1 : -1;
+    info.tiles_u = info.tiles_v = T;
+    info.n_entries = total;
+    for (const uint2& r : ranges) info.max_list = std::max(info.max_list, r.y);
+    info.k_pad = kPad;
+    info.cut_pad = (double)lt.cut_pad;
+    info.u0 = u0f; info.v0 = v0f; info.inv_du = inv_du; info.inv_dv = inv_dv;
     if ((!c->has_triangles || !std::getenv("RT_NO_TRI_BLOCKS")) && total && !std::getenv("RT_NO_LT_BLOCKS")) {
         // ... and as 32-byte blocks of three candidates (LightTiles::blocks). Lattice: 16 bits per axis over the grid box; every
         // sphere rounded outwards exactly as build_walk_blocks does it (the device's own fma for the centre, the known
@@ -2019,6 +2075,11 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
             lt.lat_lox = lof[0]; lt.lat_loy = lof[1]; lt.lat_loz = lof[2];
             lt.lat_step = stepf; lt.rstep = rstepf; lt.kstep = kstepf;
             lt.blocks_enabled = 1u;
+            info.n_blocks = (uint32_t)n_blocks;
+            info.box_diagonal = Dbox;
+            info.pretest_alpha = g.pretest_alpha;
+            for (int a = 0; a < 3; ++a) info.lat_lo[a] = lof[a];
+            info.lat_step = stepf; info.rstep = rstepf; info.kstep = kstepf;
             lap("blocks + uploads");
             if (std::getenv("RT_WALK_STATS"))
                 std::fprintf(stderr, "[light tiles] %u x %u tiles, %llu entries, %zu blocks (%zu behind the heads), lattice step %g, radius step %g, key step %g\n",
@@ -2043,6 +2104,260 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
             lt.walk_base = (uint32_t)base;
         }
     }
+    return RT_OK;
+}
+
+// A live context's light tiles, rebuilt on the device for new lights (rt_set_lights; rt_light_tiles.hip has the passes,
+// light_tiles.py the definition). The host keeps what build_light_tiles decides between its loops - kPad and the projection axis
+// from eight reduced numbers, the tile count T from the pair totals of every candidate of the halving rule, the tile origin and
+// the 8-bit steps from the reduced bounds, every refusal - and synchronises four times to read them. Block form only; refused:
+// c->light_tiles stays disabled and the last light's shadow rays go through the grid walk, same bits.
+int build_light_tiles_device(rt_context* c, const rt_light* lights) {
+    c->light_tiles = rt::LightTiles{};
+    rt_light_tiles_info_t& info = c->lt_info;
+    info = rt_light_tiles_info_t{};
+    auto refuse = [&](uint32_t bit) { info.enabled = 0; info.source = 0; info.refused |= bit; return RT_OK; };
+    const uint32_t n = c->n_objs;
+    if (!c->grid.enabled || c->grid.n_always != 0 || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->base_flags & RT_FLAG_LITERAL) ||
+        c->n_lights == 0 || n == 0 || c->h_grid_spheres.size() != 4 * (size_t)n || c->h_grid_pre.size() != n)
+        return refuse(RT_LTILES_REFUSED_NO_GRID);
+    if (std::getenv("RT_NO_LIGHT_TILES")) return refuse(RT_LTILES_REFUSED_KNOB);
+    if (const char* env = std::getenv("RT_LIGHT_TILES_DEVICE"))  // measurement knob: "0" leaves a replaced light to the grid walk
+        if (env[0] == '0') return refuse(RT_LTILES_REFUSED_KNOB);
+    const uint32_t li = c->n_lights - 1u;
+    const float* lp = lights[li].position;
+    if (!(lp[3] != 0.f) || !std::isfinite(lp[0] + lp[1] + lp[2])) return refuse(RT_LTILES_REFUSED_LIGHT);
+    if ((c->has_triangles && std::getenv("RT_NO_TRI_BLOCKS")) || std::getenv("RT_NO_LT_BLOCKS")) return refuse(RT_LTILES_REFUSED_BLOCKS);
+    const rt::GridDesc& g = c->grid;
+    const float lof[3] = {g.lox, g.loy, g.loz};
+    const double ext = (double)g.cell * std::max(g.nx, std::max(g.ny, g.nz));
+    const volatile float stepv = (float)(ext / 65535.0 * (1.0 + 1e-6));
+    const float stepf = stepv;
+    const double Dbox = std::sqrt((double)g.cell * g.nx * (double)g.cell * g.nx + (double)g.cell * g.ny * (double)g.cell * g.ny +
+                                  (double)g.cell * g.nz * (double)g.cell * g.nz);
+    if (!(stepf > 0.f) || !std::isfinite(stepf) || !std::isfinite(Dbox)) return refuse(RT_LTILES_REFUSED_BLOCKS);
+
+    hipStream_t stream = c->stream;
+    rt::LightTileBuffers& b = c->ltb;
+    if (!c->d_pose_spheres) {  // the registration spheres as doubles: shared with the pose tiles' builder
+        RT_HIP(c, hipMalloc((void**)&c->d_pose_spheres, sizeof(double) * 4 * (size_t)n));
+        RT_HIP(c, hipMemcpy(c->d_pose_spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice));
+    }
+    if (!b.record) {  // once per context: everything sized by the object count
+        RT_HIP(c, hipMalloc((void**)&c->d_lt_pre, sizeof(float) * (size_t)n));
+        RT_HIP(c, hipMemcpy(c->d_lt_pre, c->h_grid_pre.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+        RT_HIP(c, hipMalloc((void**)&b.span, sizeof(double4) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.wq, sizeof(double) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.packed, sizeof(uint2) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.lists.rect, sizeof(uint4) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.lists.key, sizeof(float) * (size_t)n));
+        RT_HIP(c, hipMalloc((void**)&b.lists.sums, sizeof(uint32_t) * 1024));
+        RT_HIP(c, hipMalloc((void**)&b.chains.sums, sizeof(uint32_t) * 1024));
+        RT_HIP(c, hipMalloc((void**)&b.lists.record, sizeof(rt::PoseTileRecord)));
+        RT_HIP(c, hipMalloc((void**)&b.chains.record, sizeof(rt::PoseTileRecord)));
+        RT_HIP(c, hipHostMalloc((void**)&c->h_lt_record, sizeof(rt::LightTileRecord), hipHostMallocDefault));
+        RT_HIP(c, hipHostMalloc((void**)&c->h_lt_lists, 2 * sizeof(rt::PoseTileRecord), hipHostMallocDefault));
+        RT_HIP(c, hipMalloc((void**)&b.record, sizeof(rt::LightTileRecord)));
+    }
+    b.spheres = c->d_pose_spheres;
+    b.pre = c->d_lt_pre;
+    for (hipEvent_t& ev : c->ev_lt)
+        if (!ev) RT_HIP(c, hipEventCreate(&ev));
+    double device_ms = 0.0;
+    auto stage_ms = [&](int k) -> int {
+        float ms = 0.f;
+        RT_HIP(c, hipEventElapsedTime(&ms, c->ev_lt[2 * k], c->ev_lt[2 * k + 1]));
+        device_ms += (double)ms;
+        info.build_device_ms = device_ms;
+        return RT_OK;
+    };
+
+    rt::LightTileArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.n_objs = n;
+    for (int k = 0; k < 3; ++k) { a.L[k] = (double)lp[k]; a.lat_lo[k] = lof[k]; }
+    a.lat_step = stepf;
+    a.Dbox = Dbox;
+    a.alpha = (double)g.pretest_alpha;
+    a.budget = 64ull * n + 4096ull;
+
+    // stage 1: the eight numbers kPad and the projection axis come from
+    {
+        rt::LightTileRecord& r = *c->h_lt_record;
+        std::memset(&r, 0, sizeof(r));
+        const unsigned long long lowest = rt::lt_key_of(-std::numeric_limits<double>::infinity()), highest = rt::lt_key_of(std::numeric_limits<double>::infinity());
+        r.coord_max = r.reach_max = r.U1 = r.V1 = r.rmax = r.kmax = lowest;
+        r.U0 = r.V0 = highest;
+        for (int k = 0; k < 6; ++k) r.clear[k] = highest;
+    }
+    RT_HIP(c, hipMemcpyAsync(b.record, c->h_lt_record, sizeof(rt::LightTileRecord), hipMemcpyHostToDevice, stream));
+    RT_HIP(c, hipEventRecord(c->ev_lt[0], stream));
+    hipError_t e = rt::launch_light_tile_reduce(a, b, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "light tile reduction launch");
+    RT_HIP(c, hipEventRecord(c->ev_lt[1], stream));
+    RT_HIP(c, hipMemcpyAsync(c->h_lt_record, b.record, sizeof(rt::LightTileRecord), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (int rc = stage_ms(0)) return rc;
+    const double inf = std::numeric_limits<double>::infinity();
+    double coord_max, reach_max, kPad;
+    int best_axis = -1;
+    double best_sign = 0, best_clear = 0;
+    {
+        const rt::LightTileRecord r = *c->h_lt_record;
+        coord_max = std::max(std::sqrt(a.L[0] * a.L[0] + a.L[1] * a.L[1] + a.L[2] * a.L[2]), rt::lt_unkey(r.coord_max));
+        reach_max = std::max(0.0, rt::lt_unkey(r.reach_max));
+        kPad = std::max(1e-3, 4e-7 * (2.0 * coord_max + reach_max));
+        const double kFront = 0.05;
+        for (int ax = 0; ax < 3; ++ax)
+            for (int s = 0; s < 2; ++s) {  // (the host builder's order: -1, then +1)
+                const double m = rt::lt_unkey(r.clear[2 * ax + s]);
+                const double clear = m - kPad;
+                if (m != inf && clear > kFront && clear != inf && clear > best_clear) { best_clear = clear; best_axis = ax; best_sign = s ? 1.0 : -1.0; }
+            }
+    }
+    info.k_pad = kPad;
+    info.cut_pad = (double)(float)std::max(1e-4, 4e-7 * (2.0 * coord_max + reach_max));
+    if (best_axis < 0) return refuse(RT_LTILES_REFUSED_PLANE);
+    const uint32_t az = (uint32_t)best_axis, ax = (az + 1u) % 3u, ay = (az + 2u) % 3u;
+    const double szn = -best_sign;
+
+    // stage 2: spans, keys, radii; the pair totals of every candidate T
+    a.kPad = kPad;
+    a.sz = szn;
+    a.ax = ax; a.ay = ay; a.az = az;
+    {
+        double tile_factor = 1.6;
+        if (const char* env = std::getenv("RT_LT_TILE_FACTOR")) {
+            const double v = std::atof(env);
+            if (v >= 0.1 && v <= 8.0) tile_factor = v;
+        }
+        uint32_t T = (uint32_t)std::min(1024.0, std::max(16.0, tile_factor * std::sqrt((double)n)));
+        for (;;) {
+            a.cand[a.n_cand++] = T;
+            if (T <= 16u || a.n_cand == rt::kLtMaxCandidates) break;
+            T /= 2u;
+        }
+    }
+    RT_HIP(c, hipEventRecord(c->ev_lt[2], stream));
+    e = rt::launch_light_tile_spans(a, b, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "light tile span launch");
+    RT_HIP(c, hipEventRecord(c->ev_lt[3], stream));
+    RT_HIP(c, hipMemcpyAsync(c->h_lt_record, b.record, sizeof(rt::LightTileRecord), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (int rc = stage_ms(1)) return rc;
+    const rt::LightTileRecord rec = *c->h_lt_record;
+    if (rec.flags & rt::kLtFlagNoTangent) return refuse(RT_LTILES_REFUSED_TANGENT);
+    const double U0 = rt::lt_unkey(rec.U0), U1 = rt::lt_unkey(rec.U1), V0 = rt::lt_unkey(rec.V0), V1 = rt::lt_unkey(rec.V1);
+    if (rec.n_listed == 0 || !(U1 > U0) || !(V1 > V0) || !std::isfinite(U0 + U1 + V0 + V1)) return refuse(RT_LTILES_REFUSED_BOUNDS);
+    uint32_t T = a.cand[a.n_cand - 1u];
+    unsigned long long pairs = rec.pairs[a.n_cand - 1u];
+    for (uint32_t k = 0; k < a.n_cand; ++k)
+        if (rec.pairs[k] <= 24ull * n + 4096ull || a.cand[k] <= 16u) { T = a.cand[k]; pairs = rec.pairs[k]; break; }
+    info.tiles_u = info.tiles_v = T;
+    info.n_entries = pairs;
+    if (pairs == 0 || pairs > a.budget || pairs * 32ull >= 0xffffffffull) return refuse(RT_LTILES_REFUSED_BUDGET);
+    {
+        const double du = (U1 - U0) / T * (1.0 + 1e-6), dv = (V1 - V0) / T * (1.0 + 1e-6);
+        a.T = T;
+        a.u0 = std::nextafter((float)U0, -std::numeric_limits<float>::infinity());
+        a.v0 = std::nextafter((float)V0, -std::numeric_limits<float>::infinity());
+        a.inv_du = (float)(1.0 / du);
+        a.inv_dv = (float)(1.0 / dv);
+        const double rmax = std::max(0.0, rt::lt_unkey(rec.rmax)), kmax = std::max(0.0, rt::lt_unkey(rec.kmax));
+        const volatile float rstepv = (float)(rmax / 255.0 * (1.0 + 1e-5)), kstepv = (float)(std::max(kmax, 1e-3) / 255.0 * (1.0 + 1e-5));
+        a.rstep = rstepv;
+        a.kstep = kstepv;
+    }
+    info.u0 = a.u0; info.v0 = a.v0; info.inv_du = a.inv_du; info.inv_dv = a.inv_dv;
+    if ((rec.flags & rt::kLtFlagOffLattice) || !(a.rstep > 0.f) || !std::isfinite(a.rstep) || !(a.kstep > 0.f) || !std::isfinite(a.kstep) ||
+        !std::isfinite(a.inv_du) || !std::isfinite(a.inv_dv))
+        return refuse(RT_LTILES_REFUSED_BLOCKS);
+
+    // stage 3: tile rectangles at T, count, scan, chain blocks
+    const uint32_t n_tiles = T * T;  // <= 2^20
+    if (c->ltb_tiles < n_tiles) {
+        uint32_t** arrays[6] = {&b.lists.count, &b.lists.cursor, &b.lists.tile_start, &b.chains.count, &b.chains.cursor, &b.chains.tile_start};
+        for (uint32_t** p : arrays) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        c->ltb_tiles = 0;
+        for (uint32_t** p : arrays) RT_HIP(c, hipMalloc((void**)p, sizeof(uint32_t) * ((size_t)n_tiles + 1)));
+        c->ltb_tiles = n_tiles;
+    }
+    RT_HIP(c, hipEventRecord(c->ev_lt[4], stream));
+    e = rt::launch_light_tile_count(a, b, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "light tile count launch");
+    RT_HIP(c, hipEventRecord(c->ev_lt[5], stream));
+    RT_HIP(c, hipMemcpyAsync(&c->h_lt_lists[0], b.lists.record, sizeof(rt::PoseTileRecord), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipMemcpyAsync(&c->h_lt_lists[1], b.chains.record, sizeof(rt::PoseTileRecord), hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (int rc = stage_ms(2)) return rc;
+    const rt::PoseTileRecord lists = c->h_lt_lists[0], chains = c->h_lt_lists[1];
+    info.n_entries = lists.pairs;
+    info.max_list = lists.max_list;
+    if (lists.pairs == 0 || lists.pairs > a.budget || lists.pairs * 32ull >= 0xffffffffull) return refuse(RT_LTILES_REFUSED_BUDGET);
+    if (lists.max_list > rt::kLtMaxList) return refuse(RT_LTILES_REFUSED_LIST);
+    if ((unsigned long long)lists.total != lists.pairs) return fail(c, RT_ERR_STATE, "internal: the light tiles' scan does not match their count");
+    const uint64_t n_blocks64 = (uint64_t)n_tiles + chains.total;
+    if (!rt::light_tile_blocks_fit(n_blocks64)) return refuse(RT_LTILES_REFUSED_BLOCKS);
+    const uint32_t n_blocks = (uint32_t)n_blocks64;
+
+    // stage 4: fill, rank sort, pack, heads and chains
+    const size_t need = (size_t)lists.total + 1;
+    if (c->ltb_entries < need) {
+        if (b.lists.scratch) (void)hipFree(b.lists.scratch);
+        if (b.lists.entries) (void)hipFree(b.lists.entries);
+        b.lists.scratch = nullptr;
+        b.lists.entries = nullptr;
+        c->ltb_entries = 0;
+        const size_t cap = need + need / 4;  // grow-only, with headroom: a dragged light's next table is about as large
+        RT_HIP(c, hipMalloc((void**)&b.lists.scratch, sizeof(uint32_t) * cap));
+        RT_HIP(c, hipMalloc((void**)&b.lists.entries, sizeof(uint2) * cap));
+        c->ltb_entries = cap;
+    }
+    if (c->ltb_blocks < n_blocks) {
+        if (b.blocks) (void)hipFree(b.blocks);
+        if (b.block_ids) (void)hipFree(b.block_ids);
+        b.blocks = nullptr;
+        b.block_ids = nullptr;
+        c->ltb_blocks = 0;
+        const size_t cap = (size_t)n_blocks + n_blocks / 4;
+        RT_HIP(c, hipMalloc((void**)&b.blocks, 2 * sizeof(uint4) * cap));
+        RT_HIP(c, hipMalloc((void**)&b.block_ids, 4 * sizeof(uint32_t) * cap));
+        c->ltb_blocks = cap;
+    }
+    RT_HIP(c, hipEventRecord(c->ev_lt[6], stream));
+    e = rt::launch_light_tile_fill(a, b, lists.total, lists.max_list, n_blocks, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "light tile fill launch");
+    RT_HIP(c, hipEventRecord(c->ev_lt[7], stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    if (int rc = stage_ms(3)) return rc;
+
+    rt::LightTiles& lt = c->light_tiles;
+    lt.lx = lp[0]; lt.ly = lp[1]; lt.lz = lp[2];
+    lt.u0 = a.u0; lt.v0 = a.v0; lt.inv_du = a.inv_du; lt.inv_dv = a.inv_dv;
+    lt.tiles_u = T; lt.tiles_v = T;
+    lt.ax = ax; lt.ay = ay; lt.az = az;
+    lt.sx = 1.f; lt.sy = 1.f; lt.sz = (float)szn;
+    lt.light = li;
+    lt.cut_pad = (float)std::max(1e-4, 4e-7 * (2.0 * coord_max + reach_max));
+    lt.enabled = 1u;
+    lt.blocks = b.blocks;
+    lt.block_ids = b.block_ids;
+    lt.lat_lox = lof[0]; lt.lat_loy = lof[1]; lt.lat_loz = lof[2];
+    lt.lat_step = stepf; lt.rstep = a.rstep; lt.kstep = a.kstep;
+    lt.blocks_enabled = 1u;
+    info.enabled = 1u;
+    info.source = 2u;
+    info.light = li;   // (light, axis and sign describe a table in use: a refused build leaves them 0, as the host's does)
+    info.axis = az;
+    info.sign = best_sign > 0 ? 1 : -1;
+    info.n_blocks = n_blocks;
+    info.box_diagonal = Dbox;
+    info.pretest_alpha = g.pretest_alpha;
+    for (int k = 0; k < 3; ++k) info.lat_lo[k] = lof[k];
+    info.lat_step = stepf; info.rstep = a.rstep; info.kstep = a.kstep;
     return RT_OK;
 }
 
@@ -2088,6 +2403,8 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     if (!c) return fail(nullptr, RT_ERR_OUT_OF_MEMORY, "host allocation failed");
     c->device = device;
     c->flags = flags;
+    c->user_flags = flags;
+    c->lights_capacity = n_lights;
     c->kernel = kernel;
     c->n_objs = n_objs;
     c->n_lights = n_lights;
@@ -2213,7 +2530,7 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
                 if (o.type <= 1u && !std::isfinite(object_bound(o).r)) degenerate.store(true, std::memory_order_relaxed);
             }
         });
-        if (degenerate.load()) { c->flags |= RT_FLAG_LITERAL; c->forced_literal = true; }
+        if (degenerate.load()) { c->flags |= RT_FLAG_LITERAL; c->forced_literal = true; c->degenerate_literal = true; }
     }
     // RT_FLAG_DEVICE_OPENCL: the device normalize(0) is 0, so the shadow ray of a light AT the hit point (or of a directional
     // light of direction 0) has a finite start and direction 0. Every sphere of the reference's loop then accepts it with a NaN
@@ -2222,25 +2539,20 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     // A directional light's shadow rays have the light's own direction, unnormalised: one of |d|^2 outside the walks' window
     // (direction_in_domain; a denormal direction, say) gives an object-space direction that can round to 0 and the same NaN
     // times, so it goes literal too.
-    if ((flags & RT_FLAG_DEVICE_OPENCL) && !(c->flags & RT_FLAG_LITERAL) && n_lights) {
-        const rt_light* L = static_cast<const rt_light*>(lights);
-        bool ordered = false;
-        for (uint32_t l = 0; l < n_lights && !ordered; ++l)
-            if (L[l].position[3] == 0.f && !direction_in_domain(L[l].position[0], L[l].position[1], L[l].position[2])) ordered = true;
-        std::atomic<bool> near{ordered};
+    // The predicate follows the lights (rt_set_lights evaluates it again), so what it needs of the objects is kept: lights_need_literal.
+    if ((flags & RT_FLAG_DEVICE_OPENCL) && !(c->flags & RT_FLAG_LITERAL)) {
+        c->h_obj_bounds.resize(4 * (size_t)n_objs);
         parallel_for(n_objs, 8192, [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1 && !near.load(std::memory_order_relaxed); ++i) {
+            for (size_t i = i0; i < i1; ++i) {
                 const Bound b = object_bound(static_cast<const rt_object_data*>(objs)[i]);
-                if (!(b.r >= 0.0)) continue;  // never hit
-                const double reach = b.r * (1.0 + 1e-4) + 1e-4 * (std::fabs(b.x) + std::fabs(b.y) + std::fabs(b.z) + b.r);
-                for (uint32_t l = 0; l < n_lights; ++l) {
-                    if (L[l].position[3] == 0.f) continue;
-                    const double dx = (double)L[l].position[0] - b.x, dy = (double)L[l].position[1] - b.y, dz = (double)L[l].position[2] - b.z;
-                    if (!(dx * dx + dy * dy + dz * dz > reach * reach)) { near.store(true, std::memory_order_relaxed); break; }
-                }
+                c->h_obj_bounds[4 * i] = b.x; c->h_obj_bounds[4 * i + 1] = b.y; c->h_obj_bounds[4 * i + 2] = b.z; c->h_obj_bounds[4 * i + 3] = b.r;
             }
         });
-        if (near.load()) { c->flags |= RT_FLAG_LITERAL; c->forced_literal = true; }
+        if (lights_need_literal(c, static_cast<const rt_light*>(lights), n_lights)) {
+            c->flags |= RT_FLAG_LITERAL;
+            c->forced_literal = true;
+            c->lights_literal = true;
+        }
     }
     lap("instance checks");
     c->base_flags = c->flags;
@@ -2634,6 +2946,94 @@ int rt_read_grid_spheres(const rt_context* c, double* spheres, uint64_t n) {
         return fail(const_cast<rt_context*>(c), RT_ERR_STATE, "rt_read_grid_spheres: the context has no grid");
     if (n != c->n_objs) return fail(const_cast<rt_context*>(c), RT_ERR_INVALID_ARGUMENT, "rt_read_grid_spheres: n must be the object count");
     std::memcpy(spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n);
+    return RT_OK;
+}
+
+// ---- replaceable lights (hip_raytracer.h) ----
+static int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
+    if (n_lights && !lights) return fail(c, RT_ERR_INVALID_ARGUMENT, "lights is NULL with a non-zero count");
+    if (n_lights >= (1u << 22)) return fail(c, RT_ERR_INVALID_ARGUMENT, "more than 4 194 303 lights");
+    return RT_OK;
+}
+
+int rt_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    const int refused = check_set_lights(c, lights, n_lights);
+    if (refused) return refused;
+    RT_DEVICE(c);
+    const rt_light* L = static_cast<const rt_light*>(lights);
+    if (n_lights > c->lights_capacity) {  // a larger array first: a failed allocation leaves the context as it was
+        rt::LightRec* d = nullptr;
+        RT_HIP(c, hipMalloc((void**)&d, sizeof(rt::LightRec) * ((size_t)n_lights + 1)));
+        if (c->d_lights) (void)hipFree(c->d_lights);
+        c->d_lights = d;
+        c->lights_capacity = n_lights;
+    }
+    if (n_lights) {
+        RT_HIP(c, hipMemcpyAsync(c->d_lights, lights, sizeof(rt::LightRec) * n_lights, hipMemcpyHostToDevice, c->stream));
+        RT_HIP(c, hipStreamSynchronize(c->stream));  // `lights` may be pageable and is the caller's again on return
+    }
+    c->n_lights = n_lights;
+    // RT_FLAG_DEVICE_OPENCL's predicate on the lights, for these lights (rt_create: lights_need_literal)
+    if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal) {
+        c->lights_literal = lights_need_literal(c, L, n_lights);
+        c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
+        c->forced_literal = c->lights_literal;
+        apply_ray_domain(c);
+    }
+    return build_light_tiles_device(c, L);
+}
+
+int rt_read_grid_pretest(const rt_context* c, float* pre, uint64_t n) {
+    if (!c || !pre) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->grid.enabled || c->h_grid_pre.size() != c->n_objs)
+        return fail(const_cast<rt_context*>(c), RT_ERR_STATE, "rt_read_grid_pretest: the context has no grid");
+    if (n != c->n_objs) return fail(const_cast<rt_context*>(c), RT_ERR_INVALID_ARGUMENT, "rt_read_grid_pretest: n must be the object count");
+    std::memcpy(pre, c->h_grid_pre.data(), sizeof(float) * (size_t)n);
+    return RT_OK;
+}
+
+int rt_get_light_tiles_info(const rt_context* c, rt_light_tiles_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    *info = c->lt_info;
+    return RT_OK;
+}
+
+int rt_read_light_tiles(rt_context* c, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries) {
+    if (!c || !tile_start || !entries) return RT_ERR_INVALID_ARGUMENT;
+    const rt_light_tiles_info_t& info = c->lt_info;
+    const rt::LightTiles& lt = c->light_tiles;
+    if (!info.enabled || !lt.blocks_enabled || !info.n_blocks)
+        return fail(c, RT_ERR_STATE, "rt_read_light_tiles: no light tiles in block form are in use (rt_get_light_tiles_info has the reason)");
+    const uint64_t n_tiles = (uint64_t)info.tiles_u * info.tiles_v;
+    if (n_start < n_tiles + 1 || n_entries < info.n_entries) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_read_light_tiles: an array is too small for the table");
+    RT_DEVICE(c);
+    std::vector<uint32_t> blk(8 * (size_t)info.n_blocks), ids(4 * (size_t)info.n_blocks);
+    RT_HIP(c, hipMemcpy(blk.data(), lt.blocks, sizeof(uint32_t) * blk.size(), hipMemcpyDeviceToHost));
+    RT_HIP(c, hipMemcpy(ids.data(), lt.block_ids, sizeof(uint32_t) * ids.size(), hipMemcpyDeviceToHost));
+    uint64_t at = 0;
+    for (uint64_t t = 0; t < n_tiles; ++t) {  // the chains as the kernels walk them; an empty slot (k8 = 255, r8 = 0) ends a list
+        tile_start[t] = (uint32_t)at;
+        uint64_t steps = 0;
+        for (uint32_t bl = (uint32_t)t;;) {
+            bool ended = false;
+            for (uint32_t e = 0; e < 3u; ++e) {
+                const uint32_t lo = blk[8 * (size_t)bl + 2 + 2 * e], hi = blk[8 * (size_t)bl + 3 + 2 * e];
+                if ((hi >> 16) == 0xff00u) { ended = true; break; }
+                if (at >= info.n_entries) return fail(c, RT_ERR_STATE, "internal: the light tiles' chains hold more entries than the table");
+                entries[3 * at] = ids[4 * (size_t)bl + e];
+                entries[3 * at + 1] = lo;
+                entries[3 * at + 2] = hi;
+                ++at;
+            }
+            const uint32_t next = blk[8 * (size_t)bl];
+            if (ended || next == 0u) break;
+            if (next >= info.n_blocks || ++steps > info.n_blocks) return fail(c, RT_ERR_STATE, "internal: a light tile's chain leaves the table");
+            bl = next;
+        }
+    }
+    tile_start[n_tiles] = (uint32_t)at;
+    if (at != info.n_entries) return fail(c, RT_ERR_STATE, "internal: the light tiles' chains do not hold the table's entries");
     return RT_OK;
 }
 
@@ -3052,6 +3452,18 @@ void rt_destroy(rt_context* c) {
     if (c->d_walk_blocks) (void)hipFree(c->d_walk_blocks);
     if (c->d_walk_ids) (void)hipFree(c->d_walk_ids);
     if (c->d_lights) (void)hipFree(c->d_lights);
+    {   // the light-tile builder's memory (rt_set_lights)
+        rt::LightTileBuffers& b = c->ltb;
+        void* arrays[] = {c->d_lt_pre, b.span, b.wq, b.packed, b.record, b.blocks, b.block_ids, b.lists.rect, b.lists.key, b.lists.sums,
+                          b.lists.record, b.lists.count, b.lists.cursor, b.lists.tile_start, b.lists.scratch, b.lists.entries,
+                          b.chains.sums, b.chains.record, b.chains.count, b.chains.cursor, b.chains.tile_start};
+        for (void* p : arrays)
+            if (p) (void)hipFree(p);
+        if (c->h_lt_record) (void)hipHostFree(c->h_lt_record);
+        if (c->h_lt_lists) (void)hipHostFree(c->h_lt_lists);
+        for (hipEvent_t ev : c->ev_lt)
+            if (ev) (void)hipEventDestroy(ev);
+    }
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->h_out) (void)hipHostFree(c->h_out);
@@ -3342,6 +3754,19 @@ int rt_set_pose_multi(rt_multi* m, uint32_t width, uint32_t height, float z, con
         for (std::thread& t : workers) t.join();
         for (size_t r = 0; r < n; ++r)
             if (rcs[r] != RT_OK) return multi_fail(m, rcs[r], "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
+    }
+    return RT_OK;
+}
+
+int rt_set_lights_multi(rt_multi* m, const void* lights, uint32_t n_lights) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    for (rt_context* c : m->ctx) {  // all or none: the arguments are all a shard can refuse
+        const int rc = check_set_lights(c, lights, n_lights);
+        if (rc != RT_OK) return multi_fail(m, rc, c->error);
+    }
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = rt_set_lights(m->ctx[r], lights, n_lights);
+        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
     }
     return RT_OK;
 }

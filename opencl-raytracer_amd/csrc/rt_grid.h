@@ -202,6 +202,14 @@ struct ScreenTiles {
 // at z' < 0), and a ray looks up the one tile its origin falls in - no cell walk. Built on the host (rt_api.cpp:
 // build_light_tiles) when every object lies strictly on one side of an axis-aligned plane through the light; every
 // candidate still goes through the pre-test and the reference's exact test, so the answer is the brute-force loop's.
+//
+// rt_set_lights rebuilds the table ON THE DEVICE (rt_light_tiles.hip; light_tiles.py is the executable definition), block
+// form only. The device's double atan2 / asin / tan differ from libm's in the last bits (a few ulp, relative 1e-15), so its
+// rectangles are not the host's to the last bit, and nothing needs them to be: each side's result is conservative on its own.
+// The margins that cover it: the span's 1e-5 (1 + |x|) padding (1e10 times the functions' error, there for the kernel's fp32
+// (u, v)), the 0.01 tile of slack in the tile range, and the 1.5533 rad limit, 0.0175 rad short of the pole where tan's
+// condition number would eat the padding (at the limit d tan = 1e-15 (1 + tan^2) ~ 3e-12). Keys and radii use only
+// + - * / sqrt, correctly rounded on both sides, and are rounded outwards by 1e-6 relative before they are quantised.
 struct LightTiles {
     const uint2* __restrict__ tile_range;      // tiles_u * tiles_v x {first entry, count}
     const float4* __restrict__ records;        // two float4 per entry, side by side (one or two cache lines per ray instead of three tables):

@@ -56,4 +56,14 @@ hipError_t launch_pose_tile_count(const PoseTileArgs& a, const PoseTileBuffers& 
 hipError_t launch_pose_tile_fill(const PoseTileArgs& a, const PoseTileBuffers& b, uint32_t total, uint32_t n_global, uint32_t max_list,
                                  hipStream_t stream);
 
+// The list passes on their own, shared with the light-tile builder (rt_light_tiles.hip), which has rectangles and keys of its
+// own: any builder that has filled b.rect (tile rectangles over a tiles_x x tiles_y table), b.key and record->pairs - and zeroed
+// b.count and the rest of the record - gets the same count / scan / fill / rank-sort. Of `a` only n_objs, tiles_x, tiles_y and
+// budget are read. launch_pose_tile_fill (n_global = 0) is the second half as it stands.
+//   launch_tile_list_count   the count expansion, then the scan below
+//   launch_tile_scan         exclusive scan of b.count[n_tiles] into b.tile_start[n_tiles + 1] and b.cursor, record->total and
+//                            record->max_list (n_tiles <= kPoseMaxTiles; b.sums holds 1024 block sums)
+hipError_t launch_tile_list_count(const PoseTileArgs& a, const PoseTileBuffers& b, hipStream_t stream);
+hipError_t launch_tile_scan(const PoseTileBuffers& b, uint32_t n_tiles, hipStream_t stream);
+
 }  // namespace rt

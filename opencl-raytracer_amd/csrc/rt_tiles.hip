@@ -277,9 +277,21 @@ hipError_t launch_pose_tile_count(const PoseTileArgs& a, const PoseTileBuffers& 
     hipError_t e;
     if ((e = hipMemsetAsync(b.record, 0, sizeof(PoseTileRecord), stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(b.count, 0, sizeof(uint32_t) * n_tiles, stream)) != hipSuccess) return e;
-    const uint32_t obj_blocks = (a.n_objs + kBlock - 1) / kBlock, scan_blocks = (n_tiles + kScanBlock - 1) / kScanBlock;
+    const uint32_t obj_blocks = (a.n_objs + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(tile_rects, dim3(obj_blocks), dim3(kBlock), 0, stream, a, b);
-    hipLaunchKernelGGL(tile_expand<false>, dim3(obj_blocks), dim3(kBlock), 0, stream, a, b, 0u);
+    return launch_tile_list_count(a, b, stream);
+}
+
+hipError_t launch_tile_list_count(const PoseTileArgs& a, const PoseTileBuffers& b, hipStream_t stream) {
+    const uint32_t n_tiles = a.tiles_x * a.tiles_y;
+    if (a.n_objs == 0 || n_tiles == 0 || n_tiles > kPoseMaxTiles) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tile_expand<false>, dim3((a.n_objs + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a, b, 0u);
+    return launch_tile_scan(b, n_tiles, stream);
+}
+
+hipError_t launch_tile_scan(const PoseTileBuffers& b, uint32_t n_tiles, hipStream_t stream) {
+    if (n_tiles == 0 || n_tiles > kPoseMaxTiles) return hipErrorInvalidValue;
+    const uint32_t scan_blocks = (n_tiles + kScanBlock - 1) / kScanBlock;
     hipLaunchKernelGGL(tile_scan_sums, dim3(scan_blocks), dim3(kBlock), 0, stream, b, n_tiles);
     hipLaunchKernelGGL(tile_scan_top, dim3(1), dim3(kBlock), 0, stream, b, scan_blocks);
     hipLaunchKernelGGL(tile_scan_add, dim3(scan_blocks), dim3(kBlock), 0, stream, b, n_tiles);

@@ -227,6 +227,13 @@ class ShardedHIPRaytracer:
         torch.cuda.synchronize(self.device)
         self.rt.set_pose(width, height, z, rotation3x3, origin)
 
+    def set_lights(self, lights):
+        """Replace the lights of this rank's context (HIPRaytracer.set_lights; every rank makes the same call): each rank uploads
+        the lights and rebuilds the last light's tiles on its own GPU, and keeps rendering its own tiles of the frame."""
+        self.gatherer.drain()   # (a pipelined frame still reads the lights in use)
+        torch.cuda.synchronize(self.device)
+        self.rt.set_lights(lights)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

@@ -41,6 +41,7 @@ EXPORTS = [
     "rt_set_rays_device", "rt_set_rays", "rt_get_rays_info",
     "rt_set_pose", "rt_generate_rays_device", "rt_set_pose_multi",
     "rt_get_tiles_info", "rt_read_tiles", "rt_read_grid_spheres",
+    "rt_set_lights", "rt_set_lights_multi", "rt_get_light_tiles_info", "rt_read_light_tiles", "rt_read_grid_pretest",
 ]
 
 
@@ -94,6 +95,34 @@ class RTTilesInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
+
+
+class RTLightTilesInfo(ctypes.Structure):
+    _fields_ = [
+        ("enabled", ctypes.c_uint32), ("source", ctypes.c_uint32), ("light", ctypes.c_uint32), ("axis", ctypes.c_uint32),
+        ("sign", ctypes.c_int32), ("tiles_u", ctypes.c_uint32), ("tiles_v", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32),
+        ("max_list", ctypes.c_uint32), ("refused", ctypes.c_uint32), ("n_entries", ctypes.c_uint64),
+        ("build_device_ms", ctypes.c_double), ("k_pad", ctypes.c_double), ("cut_pad", ctypes.c_double),
+        ("box_diagonal", ctypes.c_double), ("u0", ctypes.c_float), ("v0", ctypes.c_float), ("inv_du", ctypes.c_float),
+        ("inv_dv", ctypes.c_float), ("lat_lo", ctypes.c_float * 3), ("lat_step", ctypes.c_float), ("rstep", ctypes.c_float),
+        ("kstep", ctypes.c_float), ("pretest_alpha", ctypes.c_float), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        out = {}
+        for n, t in self._fields_:
+            if n == "reserved":
+                continue
+            v = getattr(self, n)
+            if n == "lat_lo":
+                out[n] = np.array(list(v), dtype=np.float32)
+            elif t in (ctypes.c_double,):
+                out[n] = float(v)
+            elif t is ctypes.c_float:
+                out[n] = np.float32(v)
+            else:
+                out[n] = int(v)
+        return out
 
 
 _lib = None
@@ -209,6 +238,17 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_read_tiles.argtypes = [vp, vp, u64, vp, u64]
         lib.rt_read_grid_spheres.restype = i32
         lib.rt_read_grid_spheres.argtypes = [vp, vp, u64]
+    if hasattr(lib, "rt_set_lights"):  # (the same: a build from before replaceable lights)
+        lib.rt_set_lights.restype = i32
+        lib.rt_set_lights.argtypes = [vp, vp, u32]
+        lib.rt_set_lights_multi.restype = i32
+        lib.rt_set_lights_multi.argtypes = [vp, vp, u32]
+        lib.rt_get_light_tiles_info.restype = i32
+        lib.rt_get_light_tiles_info.argtypes = [vp, ctypes.POINTER(RTLightTilesInfo)]
+        lib.rt_read_light_tiles.restype = i32
+        lib.rt_read_light_tiles.argtypes = [vp, vp, u64, vp, u64]
+        lib.rt_read_grid_pretest.restype = i32
+        lib.rt_read_grid_pretest.argtypes = [vp, vp, u64]
     if path is None:
         _lib = lib
     return lib
@@ -518,6 +558,36 @@ class HIPRaytracer:
         self._check(self._lib.rt_read_grid_spheres(self._ctx, _ptr(out), self._n_objs))
         return out
 
+    def grid_pretest(self) -> np.ndarray:
+        """rt_read_grid_pretest: n float32, the pre-test radii of the grid's entry spheres (magnitude; the sign is a kernel flag)."""
+        out = np.zeros(self._n_objs, dtype=np.float32)
+        self._check(self._lib.rt_read_grid_pretest(self._ctx, _ptr(out), self._n_objs))
+        return out
+
+    def set_lights(self, lights):
+        """rt_set_lights: replace the context's lights (any count below 1 << 22, 0 included). The next frame is the one a fresh
+        context created with these lights renders, bit for bit; the last light's tiles are rebuilt on the device."""
+        lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        self._check(self._lib.rt_set_lights(self._ctx, _ptr(lights), int(lights.shape[0])))
+
+    def light_tiles_info(self) -> dict:
+        """rt_get_light_tiles_info: the light tiles the next frame's shadow rays to the last light use: enabled, source (0 none,
+        1 host / rt_create, 2 device / rt_set_lights), light, axis, sign, tiles_u, tiles_v, n_entries, n_blocks, max_list,
+        refused (light_tiles.REFUSED_* bits), build_device_ms, k_pad, cut_pad, u0, v0, inv_du, inv_dv, lat_lo, lat_step,
+        rstep, kstep, pretest_alpha, box_diagonal."""
+        info = RTLightTilesInfo()
+        self._check(self._lib.rt_get_light_tiles_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
+
+    def read_light_tiles(self):
+        """rt_read_light_tiles: (tile_start uint32[tiles + 1], entries uint32[n_entries, 3] = {object index, block word lo,
+        block word hi}) read back from the block table the kernels walk, in list order."""
+        info = self.light_tiles_info()
+        start = np.zeros(info["tiles_u"] * info["tiles_v"] + 1, dtype=np.uint32)
+        entries = np.zeros((max(info["n_entries"], 1), 3), dtype=np.uint32)
+        self._check(self._lib.rt_read_light_tiles(self._ctx, _ptr(start), start.size, _ptr(entries), len(entries)))
+        return start, entries[:info["n_entries"]]
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -638,6 +708,11 @@ class MultiHIPRaytracer:
     def set_camera(self, width: int, height: int, z: float):
         """Re-aim every shard (rt_set_camera_multi). The tile size stays the one chosen at creation (in rays, not rows)."""
         self._check(self._lib.rt_set_camera_multi(self._m, int(width), int(height), float(z)))
+
+    def set_lights(self, lights):
+        """Replace every shard's lights (rt_set_lights_multi): all shards or none."""
+        lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        self._check(self._lib.rt_set_lights_multi(self._m, _ptr(lights), int(lights.shape[0])))
 
     def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
         """Turn or move every shard's camera (rt_set_pose_multi): all shards or none; each generates on its own device."""

@@ -338,6 +338,11 @@ void CPURaytracer::SetRays(const std::vector<Ray3D>& rays_) {
     replaced = true;
 }
 
+void CPURaytracer::SetLights(const std::vector<Light>& lights_) {
+    own_lights = lights_;
+    lights_replaced = true;
+}
+
 void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]) {
     if (!m || !origin) throw std::invalid_argument("SetPose: the matrix or the origin is null");
     if (width > 0x1000000u || height > 0x1000000u || width * height != rays.size())
@@ -369,7 +374,7 @@ cl_float4* CPURaytracer::Render() {
         if (kernel == kHittest) pixels[i] = cl_float4{{MAX_FLOAT, 0.f, 0.f, 0.f}};
         else pixels[i] = cl_float4{{0.f, 0.f, 0.f, 1.f}};
     }
-    const Scene sc{instances.data(), surfaces.data(), instances.size(), lights.data(), lights.size()};
+    const Scene sc{instances.data(), surfaces.data(), instances.size(), Lights().data(), Lights().size()};
     // row-tiles handed out from one counter: cost per tile varies with what the rays hit
     const size_t tile = std::max<size_t>(1, std::min<size_t>(256, n / ((size_t)n_threads * 8u)));
     std::atomic<size_t> next{0};

@@ -47,6 +47,10 @@ public:
     // number of rays the object was constructed with; std::invalid_argument otherwise.
     void SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]);
 
+    // Replaceable lights, the same option as HIPRaytracer's: the next Render() lights the scene with a copy of `lights` - any count -
+    // instead of the constructor's. Only the array is replaced.
+    void SetLights(const std::vector<Light>& lights);
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }
@@ -68,6 +72,9 @@ private:
     std::vector<Ray3D> own_rays;        // SetRays' copy; empty: the constructor's rays (IRaytracer holds them by reference)
     bool replaced = false;
     const std::vector<Ray3D>& Rays() const { return replaced ? own_rays : rays; }
+    std::vector<Light> own_lights;      // SetLights' copy (IRaytracer holds the constructor's by reference)
+    bool lights_replaced = false;
+    const std::vector<Light>& Lights() const { return lights_replaced ? own_lights : lights; }
 
 public:
     ~CPURaytracer() override;

@@ -118,6 +118,24 @@ void HIPRaytracer::SetPose(unsigned int width, unsigned int height, float z, con
     if (rt_set_pose(ctx, width, height, z, m, origin, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetPose: ") + rt_last_error(ctx));
 }
 
+void HIPRaytracer::SetLights(const std::vector<Light>& lights_) {
+    std::vector<rt_light> ls;
+    ls.reserve(lights_.size());
+    for (const Light& l : lights_) ls.push_back(to_device(l));
+    if (multi) {
+        if (rt_set_lights_multi(multi, ls.data(), (uint32_t)ls.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetLights: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_lights(ctx, ls.data(), (uint32_t)ls.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetLights: ") + rt_last_error(ctx));
+}
+
+rt_light_tiles_info_t HIPRaytracer::LightTilesInfo() {
+    rt_light_tiles_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_light_tiles_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::LightTilesInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 void HIPRaytracer::SetRaysDevice(const void* d_rays, size_t n, void* stream) {
     if (multi) throw std::runtime_error("HIPRaytracer::SetRaysDevice: not available on the several-GPU object");
     if (rt_set_rays_device(ctx, d_rays, n, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRaysDevice: ") + rt_last_error(ctx));

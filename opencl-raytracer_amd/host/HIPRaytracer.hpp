@@ -60,6 +60,15 @@ public:
     // Throws std::runtime_error with the library's message for what it refuses.
     void SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream = nullptr);
 
+    // Replaceable lights (hip_raytracer.h, "replaceable lights"): the next Render() lights the scene with these lights - any count,
+    // none included - instead of the constructor's (which are not touched). The last light's tiles are rebuilt on the GPU(s).
+    // Synchronous; the several-GPU object replaces them on every shard, all or none. Throws std::runtime_error with the library's
+    // message for what it refuses.
+    void SetLights(const std::vector<Light>& lights);
+    // rt_get_light_tiles_info: the light tiles the next frame's shadow rays to the last light use - rt_create's (host-built) or,
+    // after SetLights, the ones built on the GPU. The several-GPU object reports its first shard's.
+    rt_light_tiles_info_t LightTilesInfo();
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.
