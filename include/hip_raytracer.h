@@ -63,7 +63,9 @@ extern "C" {
  *      Later addition, same version: posed cameras - rt_set_pose, rt_generate_rays_device, rt_set_pose_multi; rt_rays_info_t::source
  *      may read 3. Additions only; a caller detects support by the symbol (dlsym of rt_set_pose).
  *      Later addition, same version: replaceable lights - rt_set_lights, rt_set_lights_multi, rt_get_light_tiles_info,
- *      rt_read_light_tiles, rt_read_grid_pretest. Additions only; a caller detects support by the symbol (dlsym of rt_set_lights). */
+ *      rt_read_light_tiles, rt_read_grid_pretest. Additions only; a caller detects support by the symbol (dlsym of rt_set_lights).
+ *      Later addition, same version: replaceable materials - rt_set_materials, rt_set_materials_device, rt_set_materials_multi,
+ *      rt_read_materials. Additions only; a caller detects support by the symbol (dlsym of rt_set_materials). */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -521,6 +523,42 @@ int rt_read_light_tiles(rt_context* ctx, uint32_t* tile_start, uint64_t n_start,
  * sign is a flag of the kernels' pre-test; the radius is the magnitude): an accessor for tests, next to rt_read_grid_spheres. */
 int rt_read_grid_pretest(const rt_context* ctx, float* pre, uint64_t n);
 
+/* ---- replaceable materials -----------------------------------------------------------------------------------------------------
+ * The colours of a live context's objects: a viewer that highlights the object under the mouse (rt_render_aux names it), a
+ * simulation that colours its particles by a scalar every step - without rt_destroy + rt_create. Geometry (mv, mvInverse, type, the
+ * object count) is NOT replaceable: the grid and the walks' tables are built from it.
+ *
+ * `materials` are `count` records of 64 bytes in rt_material's layout (rt_records.h), assigned to objects first .. first + count - 1.
+ *
+ * Contract. The next render is the frame a FRESH context renders that is created with the same object array except that those
+ * objects carry these materials (mv, mvInverse and type untouched), the same flags, and the current rays / camera / pose / shard /
+ * supersampling factor / lights - bit for bit, with the same rays_reference and hit_pixels - for every kernel (on an
+ * RT_KERNEL_HITTEST context the call is accepted and changes nothing visible), every path (small-scene kernel, round machine, literal
+ * loops, brute force, RT_FLAG_NO_GRID, triangles) and every arithmetic mode (default, RT_FLAG_UNFUSED, RT_FLAG_FAST_PHONG,
+ * RT_FLAG_DEVICE_OPENCL). What was set or rendered before does not matter. No table is rebuilt and no predicate re-evaluated -
+ * none depends on a material: rt_get_rays_info, rt_get_tiles_info and rt_get_light_tiles_info read exactly as before the call.
+ * Of a material the kernels read eleven floats (ambient, diffuse and specular rgb, absorption, shininess); reflection,
+ * transparency and the three pad words are accepted and ignored. NaN and infinite values are no error: they propagate exactly as
+ * in a fresh context.
+ *
+ * rt_set_materials: a HOST array of any alignment. It is staged in a context-owned device buffer (grow-only, allocated by the first
+ * call, freed by rt_destroy) and patched into the object records by the same kernel as the device form (csrc/rt_materials.hip).
+ * rt_set_materials_device: `d_materials` is device memory on the context's device, 16-byte aligned; the patch kernel is enqueued
+ * on `hip_stream` (NULL: the legacy default stream), behind the caller's kernels that produced the array.
+ * Both are synchronous like rt_set_lights: on return the array is the caller's again and the next render on any stream sees the
+ * materials. Renders of this context still in flight on ANOTHER stream must be ordered by the caller, as for every setter.
+ *
+ * Refused with RT_ERR_INVALID_ARGUMENT: first + count > n_objs (computed in 64 bits), a NULL array with count != 0, a misaligned
+ * device pointer. A refused call has touched nothing. count == 0 returns RT_OK and launches nothing.
+ *
+ * rt_read_materials: an accessor for tests and tools, next to rt_read_light_tiles. Copies the device records of objects first ..
+ * first + count - 1 back and reassembles rt_material records from what the kernels read: the eleven live floats, the five other
+ * words 0. The absorption is kept twice on the device (the shading records and the round machine's object records): the shading
+ * records' is returned, and RT_ERR_STATE with a message if the other copy holds other bits. Same refusals as above. */
+int rt_set_materials(rt_context* ctx, const void* materials, uint32_t first, uint32_t count);
+int rt_set_materials_device(rt_context* ctx, const void* d_materials, uint32_t first, uint32_t count, void* hip_stream);
+int rt_read_materials(rt_context* ctx, void* materials, uint32_t first, uint32_t count);
+
 void rt_destroy(rt_context* ctx);
 
 /* ---- several GPUs from one process ------------------------------------------------------------------------------------
@@ -555,6 +593,9 @@ int rt_set_camera_multi(rt_multi* m, uint32_t width, uint32_t height, float z);
 int rt_set_pose_multi(rt_multi* m, uint32_t width, uint32_t height, float z, const float mat[9], const float origin[3]);
 /* rt_set_lights ("replaceable lights", above) on every context, all or none: the arguments are validated before any shard is touched. */
 int rt_set_lights_multi(rt_multi* m, const void* lights, uint32_t n_lights);
+/* rt_set_materials ("replaceable materials", above; host arrays only) on every context, all or none: the arguments are validated
+ * before any shard is touched. */
+int rt_set_materials_multi(rt_multi* m, const void* materials, uint32_t first, uint32_t count);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);
 int rt_render_multi_device(rt_multi* m, void* d_frame);

@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE
+from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of
 
 LIB_PATH = Path(__file__).resolve().parent / "host" / "libcpu_raytracer.so"
 KERNELS = {"hittest": 0, "shade": 1, "shade_and_reflect": 2}
@@ -39,6 +39,10 @@ def load_library():
             fp = ctypes.POINTER(ctypes.c_float)
             lib.cpu_rt_render_set_pose.restype = ctypes.c_int
             lib.cpu_rt_render_set_pose.argtypes = lib.cpu_rt_render.argtypes + [u32, u32, ctypes.c_float, fp, fp]
+        if hasattr(lib, "cpu_rt_render_set_materials"):
+            fp = ctypes.POINTER(ctypes.c_float)
+            lib.cpu_rt_render_set_materials.restype = ctypes.c_int
+            lib.cpu_rt_render_set_materials.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
         _lib = lib
     return _lib
 
@@ -61,6 +65,19 @@ class CPURaytracer:
         self.threads_used = 0
         self.new_rays = None
         self.pose = None
+        self.materials = None
+
+    def set_materials(self, materials, first: int = 0):
+        """CPURaytracer::SetMaterials, the option HIPRaytracer.set_materials is on the GPU: the next Render() shades objects
+        first .. first + n - 1 with `materials` (a MATERIAL_DTYPE array, or an OBJECT_DTYPE array whose material fields are taken)
+        instead of the constructor's; geometry stays. Calls add up: a later one overrides an earlier one where they overlap."""
+        mats = materials_of(materials)
+        first = int(first)
+        if first < 0 or first + len(mats) > len(self.objects):
+            raise ValueError("set_materials: first + len(materials) exceeds the object count")
+        if self.materials is None:
+            self.materials = materials_of(self.objects)
+        self.materials[first:first + len(mats)] = mats
 
     def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
         """CPURaytracer::SetPose, the option HIPRaytracer.set_pose is on the GPU: the next Render() traces
@@ -102,7 +119,16 @@ class CPURaytracer:
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
         args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
                 ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
-        if self.pose is not None:
+        if self.materials is not None:
+            if self.supersample != 1:
+                raise ValueError("this front filters the constructor's scene only: set_materials and supersample exclude each other")
+            fp = ctypes.POINTER(ctypes.c_float)
+            w, h, z, m, o = self.pose if self.pose is not None else (0, 0, 0.0, None, None)
+            rc = self._lib.cpu_rt_render_set_materials(*args, ptr(self.materials), 0, len(self.materials),
+                                                       ptr(self.new_rays) if self.new_rays is not None else None, w, h, z,
+                                                       m.ctypes.data_as(fp) if m is not None else None,
+                                                       o.ctypes.data_as(fp) if o is not None else None)
+        elif self.pose is not None:
             if self.supersample != 1:
                 raise ValueError("this front filters the constructor's sample grid only: set_pose and supersample exclude each other")
             w, h, z, m, o = self.pose

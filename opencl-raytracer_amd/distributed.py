@@ -234,6 +234,13 @@ class ShardedHIPRaytracer:
         torch.cuda.synchronize(self.device)
         self.rt.set_lights(lights)
 
+    def set_materials(self, materials, first: int = 0):
+        """Replace the materials of objects first .. first + n - 1 of this rank's context (HIPRaytracer.set_materials; every rank
+        makes the same call): each rank patches its own copy of the object records, and keeps rendering its own tiles of the frame."""
+        self.gatherer.drain()   # (a pipelined frame still reads the materials in use)
+        torch.cuda.synchronize(self.device)
+        self.rt.set_materials(materials, first)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

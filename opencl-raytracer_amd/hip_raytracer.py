@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE
+from .records import LIGHT_DTYPE, MATERIAL_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libhip_raytracer.so"
 
@@ -42,6 +42,7 @@ EXPORTS = [
     "rt_set_pose", "rt_generate_rays_device", "rt_set_pose_multi",
     "rt_get_tiles_info", "rt_read_tiles", "rt_read_grid_spheres",
     "rt_set_lights", "rt_set_lights_multi", "rt_get_light_tiles_info", "rt_read_light_tiles", "rt_read_grid_pretest",
+    "rt_set_materials", "rt_set_materials_device", "rt_set_materials_multi", "rt_read_materials",
 ]
 
 
@@ -249,6 +250,15 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_read_light_tiles.argtypes = [vp, vp, u64, vp, u64]
         lib.rt_read_grid_pretest.restype = i32
         lib.rt_read_grid_pretest.argtypes = [vp, vp, u64]
+    if hasattr(lib, "rt_set_materials"):  # (the same: a build from before replaceable materials)
+        lib.rt_set_materials.restype = i32
+        lib.rt_set_materials.argtypes = [vp, vp, u32, u32]
+        lib.rt_set_materials_device.restype = i32
+        lib.rt_set_materials_device.argtypes = [vp, vp, u32, u32, vp]
+        lib.rt_set_materials_multi.restype = i32
+        lib.rt_set_materials_multi.argtypes = [vp, vp, u32, u32]
+        lib.rt_read_materials.restype = i32
+        lib.rt_read_materials.argtypes = [vp, vp, u32, u32]
     if path is None:
         _lib = lib
     return lib
@@ -588,6 +598,37 @@ class HIPRaytracer:
         self._check(self._lib.rt_read_light_tiles(self._ctx, _ptr(start), start.size, _ptr(entries), len(entries)))
         return start, entries[:info["n_entries"]]
 
+    # -- replaceable materials (hip_raytracer.h: the material words of the object records, patched on the device) ------------
+    def set_materials(self, materials, first: int = 0):
+        """Replace the materials of objects first .. first + n - 1 of a live context: the next frame is the one a fresh context
+        created with records.with_materials(objects, materials, first) renders, bit for bit. `materials` is a numpy
+        MATERIAL_DTYPE array, an OBJECT_DTYPE array whose material fields are taken (rt_set_materials), or a torch tensor on the
+        context's device - float32, contiguous, 16 elements per material in rt_material's layout - which is patched in on the
+        GPU, ordered behind the work of torch's current stream (rt_set_materials_device). Synchronous: on return the tensor may
+        be overwritten."""
+        if isinstance(materials, np.ndarray):
+            mats = materials_of(materials)
+            self._check(self._lib.rt_set_materials(self._ctx, _ptr(mats), int(first), int(mats.shape[0])))
+            return
+        import torch
+        if not isinstance(materials, torch.Tensor):
+            raise TypeError("set_materials takes a numpy material or object array, or a torch tensor on the context's device")
+        if not materials.is_cuda or materials.dtype != torch.float32 or not materials.is_contiguous() or materials.numel() % 16:
+            raise ValueError("a device material tensor is float32, contiguous, on the GPU, with 16 elements per material")
+        with torch.cuda.device(materials.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        self._check(self._lib.rt_set_materials_device(self._ctx, ctypes.c_void_p(materials.data_ptr()) if materials.numel() else None,
+                                                      int(first), materials.numel() // 16, ctypes.c_void_p(stream) if stream else None))
+
+    def read_materials(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """rt_read_materials: the MATERIAL_DTYPE records of objects first .. first + count - 1 (count None: up to the last object)
+        as the kernels read them - the eleven live floats; reflection, transparency and the pad lanes read 0."""
+        first = int(first)
+        count = self._n_objs - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=MATERIAL_DTYPE)
+        self._check(self._lib.rt_read_materials(self._ctx, _ptr(out), first, count))
+        return out
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -713,6 +754,12 @@ class MultiHIPRaytracer:
         """Replace every shard's lights (rt_set_lights_multi): all shards or none."""
         lights = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         self._check(self._lib.rt_set_lights_multi(self._m, _ptr(lights), int(lights.shape[0])))
+
+    def set_materials(self, materials, first: int = 0):
+        """Replace the materials of objects first .. first + n - 1 on every shard (rt_set_materials_multi): all shards or none.
+        `materials` is a numpy MATERIAL_DTYPE array or an OBJECT_DTYPE array whose material fields are taken."""
+        mats = materials_of(materials)
+        self._check(self._lib.rt_set_materials_multi(self._m, _ptr(mats), int(first), int(mats.shape[0])))
 
     def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
         """Turn or move every shard's camera (rt_set_pose_multi): all shards or none; each generates on its own device."""

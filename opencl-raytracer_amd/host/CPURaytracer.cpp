@@ -293,6 +293,14 @@ void render_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, 
     }
 }
 
+void set_material(CPURaytracer::Surface& d, const Material& m) {  // what the kernels read of a material
+    d.ambient[0] = m.ambient.x; d.ambient[1] = m.ambient.y; d.ambient[2] = m.ambient.z;
+    d.diffuse[0] = m.diffuse.x; d.diffuse[1] = m.diffuse.y; d.diffuse[2] = m.diffuse.z;
+    d.specular[0] = m.specular.x; d.specular[1] = m.specular.y; d.specular[2] = m.specular.z;
+    d.absorption = m.absorption;
+    d.shininess = m.shininess;
+}
+
 }  // namespace
 
 CPURaytracer::CPURaytracer(const std::vector<ObjectData>& objects_, const std::vector<Light>& lights_, const std::vector<Ray3D>& rays_,
@@ -306,11 +314,7 @@ CPURaytracer::CPURaytracer(const std::vector<ObjectData>& objects_, const std::v
         Surface& d = surfaces[i];
         std::memcpy(d.inv, o.mvInverse.data(), sizeof(d.inv));
         std::memcpy(d.mv, o.mv.data(), sizeof(d.mv));
-        d.ambient[0] = o.mat.ambient.x; d.ambient[1] = o.mat.ambient.y; d.ambient[2] = o.mat.ambient.z;
-        d.diffuse[0] = o.mat.diffuse.x; d.diffuse[1] = o.mat.diffuse.y; d.diffuse[2] = o.mat.diffuse.z;
-        d.specular[0] = o.mat.specular.x; d.specular[1] = o.mat.specular.y; d.specular[2] = o.mat.specular.z;
-        d.absorption = o.mat.absorption;
-        d.shininess = o.mat.shininess;
+        set_material(d, o.mat);
         Instance& h = instances[i];
         for (int r = 0; r < 3; ++r)
             for (int c = 0; c < 4; ++c) h.rows[r][c] = d.inv[4 * c + r];
@@ -341,6 +345,11 @@ void CPURaytracer::SetRays(const std::vector<Ray3D>& rays_) {
 void CPURaytracer::SetLights(const std::vector<Light>& lights_) {
     own_lights = lights_;
     lights_replaced = true;
+}
+
+void CPURaytracer::SetMaterials(uint32_t first, const std::vector<Material>& materials) {
+    if ((uint64_t)first + materials.size() > surfaces.size()) throw std::invalid_argument("SetMaterials: first + count exceeds the object count");
+    for (size_t i = 0; i < materials.size(); ++i) set_material(surfaces[first + i], materials[i]);
 }
 
 void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]) {

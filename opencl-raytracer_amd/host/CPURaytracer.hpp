@@ -51,6 +51,10 @@ public:
     // instead of the constructor's. Only the array is replaced.
     void SetLights(const std::vector<Light>& lights);
 
+    // Replaceable materials, the same option as HIPRaytracer's: the next Render() shades objects first .. first + n - 1 with
+    // `materials` instead of the constructor's; geometry stays. std::invalid_argument for a range beyond the objects.
+    void SetMaterials(uint32_t first, const std::vector<Material>& materials);
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

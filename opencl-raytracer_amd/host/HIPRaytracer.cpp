@@ -11,16 +11,23 @@ namespace {
 void put3(float* dst, const rtm::vec3& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = 0.f; }
 void put4(float* dst, const rtm::vec4& v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
 
+rt_material to_device(const Material& m) {
+    rt_material d;
+    std::memset(&d, 0, sizeof(d));
+    put3(d.ambient, m.ambient);
+    put3(d.diffuse, m.diffuse);
+    put3(d.specular, m.specular);
+    d.absorption = m.absorption;
+    d.reflection = m.reflection;
+    d.transparency = m.transparency;
+    d.shininess = m.shininess;
+    return d;
+}
+
 rt_object_data to_device(const ObjectData& o) {
     rt_object_data d;
     std::memset(&d, 0, sizeof(d));
-    put3(d.mat.ambient, o.mat.ambient);
-    put3(d.mat.diffuse, o.mat.diffuse);
-    put3(d.mat.specular, o.mat.specular);
-    d.mat.absorption = o.mat.absorption;
-    d.mat.reflection = o.mat.reflection;
-    d.mat.transparency = o.mat.transparency;
-    d.mat.shininess = o.mat.shininess;
+    d.mat = to_device(o.mat);
     std::memcpy(d.mv, o.mv.data(), sizeof(d.mv));
     std::memcpy(d.mvInverse, o.mvInverse.data(), sizeof(d.mvInverse));
     std::memcpy(d.mvInverseTranspose, o.mvInverseTranspose.data(), sizeof(d.mvInverseTranspose));
@@ -127,6 +134,17 @@ void HIPRaytracer::SetLights(const std::vector<Light>& lights_) {
         return;
     }
     if (rt_set_lights(ctx, ls.data(), (uint32_t)ls.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetLights: ") + rt_last_error(ctx));
+}
+
+void HIPRaytracer::SetMaterials(uint32_t first, const std::vector<Material>& materials) {
+    std::vector<rt_material> ms;
+    ms.reserve(materials.size());
+    for (const Material& m : materials) ms.push_back(to_device(m));
+    if (multi) {
+        if (rt_set_materials_multi(multi, ms.data(), first, (uint32_t)ms.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetMaterials: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_materials(ctx, ms.data(), first, (uint32_t)ms.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetMaterials: ") + rt_last_error(ctx));
 }
 
 rt_light_tiles_info_t HIPRaytracer::LightTilesInfo() {

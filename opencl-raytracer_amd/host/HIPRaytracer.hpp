@@ -69,6 +69,12 @@ public:
     // after SetLights, the ones built on the GPU. The several-GPU object reports its first shard's.
     rt_light_tiles_info_t LightTilesInfo();
 
+    // Replaceable materials (hip_raytracer.h, "replaceable materials"): the next Render() shades objects first .. first + n - 1
+    // with these materials instead of the constructor's (which are not touched); geometry stays. The object records are patched
+    // on the GPU(s), nothing is rebuilt. Synchronous; the several-GPU object patches every shard, all or none. Throws
+    // std::runtime_error with the library's message for what it refuses (a range beyond the objects).
+    void SetMaterials(uint32_t first, const std::vector<Material>& materials);
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

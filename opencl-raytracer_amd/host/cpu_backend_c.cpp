@@ -15,6 +15,17 @@ namespace {
 thread_local const rt_ray* g_new_rays = nullptr;  // cpu_rt_render_set_rays: the rays SetRays gets before Render()
 struct Pose { uint32_t width, height; float z; const float* m; const float* origin; };
 thread_local const Pose* g_pose = nullptr;        // cpu_rt_render_set_pose: what SetPose gets before Render()
+struct Materials { const rt_material* m; uint32_t first, count; };
+thread_local const Materials* g_materials = nullptr;  // cpu_rt_render_set_materials: what SetMaterials gets before Render()
+
+Material host_material(const rt_material& d) {
+    Material m;
+    m.ambient = rtm::vec3(d.ambient[0], d.ambient[1], d.ambient[2]);
+    m.diffuse = rtm::vec3(d.diffuse[0], d.diffuse[1], d.diffuse[2]);
+    m.specular = rtm::vec3(d.specular[0], d.specular[1], d.specular[2]);
+    m.absorption = d.absorption; m.reflection = d.reflection; m.transparency = d.transparency; m.shininess = d.shininess;
+    return m;
+}
 
 Ray3D host_ray(const rt_ray& r) {
     Ray3D h(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f));
@@ -53,11 +64,7 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
     for (uint32_t i = 0; i < n_objs; ++i) {
         const rt_object_data& d = objs[i];
         if (d.type == 2u) return -1;
-        Material m;
-        m.ambient = rtm::vec3(d.mat.ambient[0], d.mat.ambient[1], d.mat.ambient[2]);
-        m.diffuse = rtm::vec3(d.mat.diffuse[0], d.mat.diffuse[1], d.mat.diffuse[2]);
-        m.specular = rtm::vec3(d.mat.specular[0], d.mat.specular[1], d.mat.specular[2]);
-        m.absorption = d.mat.absorption; m.reflection = d.mat.reflection; m.transparency = d.mat.transparency; m.shininess = d.mat.shininess;
+        const Material m = host_material(d.mat);
         rtm::mat4 mv(1.f);
         std::memcpy(mv.data(), d.mv, sizeof(d.mv));
         ObjectData o(static_cast<ObjectData::PrimativeType>(d.type > 255u ? 255u : d.type), m, rtm::mat4(1.f));
@@ -93,6 +100,12 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
     }
     if (g_pose) {
         try { backend->SetPose(g_pose->width, g_pose->height, g_pose->z, g_pose->m, g_pose->origin); } catch (const std::exception&) { return -1; }
+    }
+    if (g_materials) {
+        std::vector<Material> ms;
+        ms.reserve(g_materials->count);
+        for (uint32_t i = 0; i < g_materials->count; ++i) ms.push_back(host_material(g_materials->m[i]));
+        try { backend->SetMaterials(g_materials->first, ms); } catch (const std::exception&) { return -1; }
     }
     const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
@@ -134,6 +147,29 @@ int cpu_rt_render_set_pose(int kernel, uint32_t max_bounces, const void* objs_, 
     g_pose = &pose;
     const int rc = cpu_rt_render_supersampled(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced,
                                               hit_pixels, seconds, threads_used, 1, 0);
+    g_pose = nullptr;
+    return rc;
+}
+
+// CPURaytracer::SetMaterials through the C entry: the backend is constructed with `objs_` and renders after
+// SetMaterials(first, materials_[0 .. count)) - rt_material records. new_rays_ (or NULL) and m / origin (or NULL: no pose) are
+// cpu_rt_render_set_rays' and cpu_rt_render_set_pose's arguments, so that the options combine. Same outputs and return value as
+// cpu_rt_render; -1 also for a range beyond the objects.
+int cpu_rt_render_set_materials(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                                const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                                uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, const void* materials_, uint32_t first,
+                                uint32_t count, const void* new_rays_, uint32_t width, uint32_t height, float z, const float* m,
+                                const float* origin) {
+    if (!materials_ && count) return -1;
+    const Materials mats{static_cast<const rt_material*>(materials_), first, count};
+    const Pose pose{width, height, z, m, origin};
+    g_materials = &mats;
+    g_new_rays = static_cast<const rt_ray*>(new_rays_);
+    g_pose = (m && origin) ? &pose : nullptr;
+    const int rc = cpu_rt_render_supersampled(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced,
+                                              hit_pixels, seconds, threads_used, 1, 0);
+    g_materials = nullptr;
+    g_new_rays = nullptr;
     g_pose = nullptr;
     return rc;
 }

@@ -32,8 +32,14 @@ LIGHT_DTYPE = np.dtype([
     ("ambient", "<f4", 4), ("diffuse", "<f4", 4), ("specular", "<f4", 4), ("position", "<f4", 4),
 ])
 RAY_DTYPE = np.dtype([("start", "<f4", 4), ("direction", "<f4", 4)])
+# rt_material (rt_records.h): the first 64 bytes of an ObjectData, what rt_set_materials replaces
+MATERIAL_FIELDS = ("ambient", "diffuse", "specular", "absorption", "reflection", "transparency", "shininess")
+MATERIAL_DTYPE = np.dtype([
+    ("ambient", "<f4", 4), ("diffuse", "<f4", 4), ("specular", "<f4", 4),
+    ("absorption", "<f4"), ("reflection", "<f4"), ("transparency", "<f4"), ("shininess", "<f4"),
+])
 
-assert OBJECT_DTYPE.itemsize == 320 and LIGHT_DTYPE.itemsize == 64 and RAY_DTYPE.itemsize == 32
+assert OBJECT_DTYPE.itemsize == 320 and LIGHT_DTYPE.itemsize == 64 and RAY_DTYPE.itemsize == 32 and MATERIAL_DTYPE.itemsize == 64
 
 SPHERE, BOX = 0, 1  # ObjectData::PrimativeType (ObjectData.hpp:9-12)
 MAX_FLOAT = np.float32(3.402823466e+38)
@@ -248,6 +254,33 @@ def objects_array(recs) -> np.ndarray:
     out = np.zeros(len(recs), dtype=OBJECT_DTYPE)
     for i, r in enumerate(recs):
         out[i] = r
+    return out
+
+
+def materials_of(objs) -> np.ndarray:
+    """The MATERIAL_DTYPE array an object array carries (a copy): its first 64 bytes per record. A MATERIAL_DTYPE array passes."""
+    objs = np.asarray(objs)
+    if objs.dtype == MATERIAL_DTYPE:
+        return np.ascontiguousarray(objs).copy()
+    objs = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE)
+    out = np.zeros(objs.shape[0], dtype=MATERIAL_DTYPE)
+    for name in MATERIAL_FIELDS:
+        out[name] = objs[name]
+    return out
+
+
+def with_materials(objs, materials, first: int = 0) -> np.ndarray:
+    """The object array a fresh context is created with for the frame rt_set_materials(materials, first) leaves a live one
+    with - its executable definition: a copy of `objs` whose records first .. first + len(materials) - 1 carry `materials`
+    (a MATERIAL_DTYPE array, or an OBJECT_DTYPE array whose material fields are taken), bit for bit; mv, mvInverse,
+    mvInverseTranspose, type and the padding are untouched."""
+    out = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE).copy()
+    mats = materials_of(materials)
+    first = int(first)
+    if first < 0 or first + mats.shape[0] > out.shape[0]:
+        raise ValueError("first + len(materials) exceeds the object count")
+    for name in MATERIAL_FIELDS:
+        out[name][first:first + mats.shape[0]] = mats[name]
     return out
 
 
