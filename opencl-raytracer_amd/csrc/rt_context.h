@@ -1,0 +1,361 @@
+// rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
+// points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
+// tiles) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in rt::host, apart from the launchers in rt::.
+#pragma once
+#include "hip_raytracer.h"
+#include "rt_records.h"
+#include "rt_kernels.h"
+#include "rt_pack.h"
+#include "rt_resolve.h"
+#include "rt_rays.h"
+#include "rt_raygen.h"
+#include "rt_tiles.h"
+#include "rt_light_tiles.h"
+#include "rt_materials.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <new>
+#include <string>
+#include <atomic>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+namespace rt::host {
+
+struct StopWatch {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double lap_ms() {
+        const auto t1 = std::chrono::steady_clock::now();
+        const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+        return ms;
+    }
+};
+
+// engineering aid (RT_SETUP_TRACE=1): where the one-time host work goes, lap by lap, on stderr
+struct SetupTrace {
+    const char* who;
+    bool on = std::getenv("RT_SETUP_TRACE") != nullptr;
+    StopWatch sw;
+    explicit SetupTrace(const char* w) : who(w) {}
+    void operator()(const char* what) { if (on) std::fprintf(stderr, "[%s] %-28s %8.2f ms\n", who, what, sw.lap_ms()); }
+};
+
+// One-time host work over independent items (per-tile sorts, per-tile block chains, ...) on several threads: f(begin, end) over
+// [0, n) in contiguous chunks, the calling thread taking the first one. RT_SETUP_THREADS=1 keeps it serial; the results do not
+// depend on the number of threads (every item writes its own outputs).
+template <class F>
+void parallel_for(size_t n, size_t grain, F&& f) {
+    size_t threads = std::thread::hardware_concurrency();
+    if (threads == 0) threads = 1;
+    threads = std::min<size_t>(threads, 16);
+    if (const char* env = std::getenv("RT_SETUP_THREADS")) threads = (size_t)std::max(1, std::atoi(env));
+    threads = std::min(threads, n / std::max<size_t>(grain, 1));
+    if (threads <= 1) { if (n) f((size_t)0, n); return; }
+    const size_t chunk = (n + threads - 1) / threads;
+    std::vector<std::thread> pool;
+    pool.reserve(threads - 1);
+    for (size_t t = 1; t < threads; ++t) {
+        const size_t lo = std::min(n, t * chunk), hi = std::min(n, lo + chunk);
+        if (lo == hi) continue;
+        try { pool.emplace_back([&f, lo, hi] { f(lo, hi); }); }
+        catch (...) { f(lo, hi); }  // (no thread to be had: this chunk on the calling thread)
+    }
+    f((size_t)0, std::min(n, chunk));
+    for (std::thread& th : pool) th.join();
+}
+
+constexpr uint32_t kTimingSlots = 256;
+constexpr uint32_t kMaxPasses = 4;  // of rt_render's frame (render_in_passes)
+
+// Path choice unless a flag says otherwise. Measured at 2048^2 (scratch sweep, depth 3, 4 lights): the small-scene
+// kernel wins up to 64 objects (per-bundle culling), the wavefront path with the grid from ~100 objects on
+// (N=128: 1.4 vs 0.9 ms, N=512: 7.4 vs 1.3 ms). Without a usable grid the wavefront path only pays once the
+// traversal loop dwarfs its per-round state traffic.
+constexpr uint32_t kWavefrontMinObjects = 512;      // brute-force wavefront
+constexpr uint32_t kWavefrontGridMinObjects = 96;   // wavefront when the conservative grid is available
+
+}  // namespace rt::host
+
+struct rt_context {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t flags = 0;
+    int kernel = 2;
+    uint32_t n_objs = 0, n_lights = 0, max_bounces = 0;
+    uint64_t n_rays = 0;
+
+    rt::HotPair* d_pairs = nullptr;
+    rt::HotPair* d_shadow_pairs = nullptr;  // the same objects sorted by decreasing size (shadow rays are order-free)
+    uint32_t n_pairs = 0;
+    rt::HotObject* d_hot = nullptr;
+    rt::ColdObject* d_cold = nullptr;
+    rt::ObjectRecord* d_objrec = nullptr;   // what materialise() reads of an object, in one 128-byte line
+    float4* d_bounds = nullptr;            // screen rectangles for the current camera
+    std::vector<double> h_spheres;         // per object: bounding sphere cx, cy, cz, R (R = +inf never cull, -inf never hit)
+    bool rects_dirty = true;
+
+    rt::LightRec* d_lights = nullptr;
+    float4* d_rays = nullptr;
+    bool have_rays = false;  // ray buffer uploaded
+    bool dir_w_zero = true;
+
+    bool pinhole = false;
+    uint32_t width = 0, height = 0;
+    float z = 0.f;
+
+    uint64_t tile_rays = 0;
+    uint32_t rank = 0, world = 1;
+    uint32_t span = 1;      // consecutive ranks one launch stands for (> 1 only inside render_in_passes)
+    uint64_t n_local = 0;
+
+    void* d_out = nullptr;  // context-owned device framebuffer
+    size_t d_out_bytes = 0;
+    void* h_out = nullptr;  // context-owned pinned host framebuffer (Render()'s return value)
+    size_t h_out_bytes = 0;
+    // 8-bit frames (rt_pack.hip): rt_render_packed's device and pinned byte frames, rt_render_device_packed's float scratch
+    void* d_pack = nullptr;
+    size_t d_pack_bytes = 0;
+    void* h_pack = nullptr;
+    size_t h_pack_bytes = 0;
+    void* d_scratch = nullptr;
+    size_t d_scratch_bytes = 0;
+    // supersampled frames (rt_resolve.hip): the factor, and the sample frame every render call with a factor > 1 filters from
+    uint32_t ss = 1;
+    void* d_samples = nullptr;
+    size_t d_samples_bytes = 0;
+    // rt_render in passes (render_in_passes): the stream the read-backs run on, an event per pass
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_pass[rt::host::kMaxPasses] = {};
+
+    float* aux_t = nullptr;  // caller-owned device buffers for the next render
+    int32_t* aux_index = nullptr;
+
+    rt::GridDesc grid = {};                 // device pointers owned by this context
+    uint2* d_grid_cell_range = nullptr;
+    float4* d_grid_cell_rec = nullptr;
+    uint32_t* d_grid_entries = nullptr;
+    uint32_t* d_grid_always = nullptr;
+    float4* d_grid_entry_sphere = nullptr;
+    std::vector<double> h_grid_spheres;     // per object: centre + grid radius (inf: always tested, < 0: never hit)
+    std::vector<float> h_grid_pre;          // per object: pre-test radius as the grid's entry spheres carry it
+    uint2* d_lt_range = nullptr;            // light tiles (rt_grid.h: LightTiles) for the last light's shadow rays
+    float4* d_lt_records = nullptr;
+    uint4* d_lt_blocks = nullptr;           // the light tiles' lists as blocks of three candidates (LightTiles::blocks)
+    uint32_t* d_lt_block_ids = nullptr;
+    rt::LightTiles light_tiles = {};
+    // Replaceable lights (rt_set_lights): what rt_get_light_tiles_info reports of the table in use; the device builder's memory
+    // (rt_light_tiles.hip; grow-only), its records' pinned mirrors and the events around its four stages; the flags rt_create was
+    // given and the two reasons it may have added RT_FLAG_LITERAL for, kept apart because only one of them follows the lights;
+    // and, under RT_FLAG_DEVICE_OPENCL, what object_bound gave per object (x, y, z, r) for the predicate on the new lights.
+    rt_light_tiles_info_t lt_info = {};
+    rt::LightTileBuffers ltb = {};
+    float* d_lt_pre = nullptr;
+    size_t ltb_tiles = 0, ltb_entries = 0, ltb_blocks = 0;
+    rt::LightTileRecord* h_lt_record = nullptr;
+    rt::PoseTileRecord* h_lt_lists = nullptr;   // [0] the lists', [1] the chains'
+    hipEvent_t ev_lt[8] = {};
+    uint32_t lights_capacity = 0;
+    uint32_t user_flags = 0;
+    bool degenerate_literal = false, lights_literal = false;
+    std::vector<double> h_obj_bounds;
+    rt::BlockGrid blocks = {};              // the closest-hit walk's coarse grid of 32-byte blocks (rt_grid.h: BlockGrid)
+    uint4* d_walk_blocks = nullptr;
+    uint32_t* d_walk_ids = nullptr;
+    std::vector<float4> h_walk;             // the unified walk's records while they are being put together (rt_grid.h: GridDesc::walk_rec)
+    float4* d_walk_rec = nullptr;
+    uint32_t* d_tile_start = nullptr;       // screen tiles (64 x 8 pixels) -> objects a pinhole primary ray can reach
+    uint2* d_tile_entries = nullptr;
+    rt::ScreenTiles tiles = {};
+    bool tiles_dirty = true;
+    uint32_t tiles_built_for = 0;           // the tile width (as a shift) the last build was asked for
+    // A posed camera's table (rt_tiles.hip): the pose the ray buffer in use was generated from, the registration spheres on the
+    // device (uploaded by the first posed build), the builder's device memory (grow-only), its record's pinned mirror, the
+    // events around its passes, and what rt_get_tiles_info reports of the last build of either kind.
+    rt::PoseGrid pose = {};
+    double* d_pose_spheres = nullptr;
+    rt::PoseTileBuffers ptb = {};
+    size_t ptb_tiles = 0, ptb_entries = 0;
+    rt::PoseTileRecord* h_pose_record = nullptr;
+    hipEvent_t ev_tiles[4] = {};
+    rt_tiles_info_t tiles_info = {};
+    bool has_triangles = false;             // type-2 records (extension): only the grid path knows them
+    int nan_winner = -1;                    // the last sphere / box of the scene decides what a NaN ray ends with (rt_device.h)
+    bool nan_winner_sphere = false;
+    bool forced_literal = false;            // a degenerate instance switched the context to RT_FLAG_LITERAL (rt_create)
+    // Primary directions the exact eliminations are not made for - |d|^2 == 0, below 1e-30 or above 1e30 (or not finite): the
+    // reference's tests then produce NaN times for every object (.cl:85-108), which only the literal loops reproduce. Such a
+    // frame is rendered the literal way as a whole (apply_ray_domain): `flags` = base_flags | LITERAL while the rays in use
+    // (the uploaded buffer, or the pinhole camera that replaced it) hold such a direction.
+    uint32_t base_flags = 0;                // `flags` after rt_create's instance checks
+    bool rays_out_of_domain = false, camera_out_of_domain = false;
+    bool affine_w = true;                   // every mv / mvInverse has bottom row (0,0,0,1) exactly
+    bool primary_w_one = true;              // every uploaded primary ray has start.w == 1
+    double origin_lo[3] = {0, 0, 0}, origin_hi[3] = {0, 0, 0};  // box of the primary ray origins
+    // Replaceable rays (rt_set_rays_device): the box build_grid's radii were derived for - the create-time origins united with the
+    // padded object bounds, before the one-cell padding - and whether the ray buffer in use may be served by
+    // the grid: direction.w = 0, start.w = 1, every origin inside that box. Off the grid a frame is rendered as RT_FLAG_NO_GRID
+    // renders it (grid_in_use); a camera's rays start at the origin, which the box always holds.
+    double grid_box_lo[3] = {0, 0, 0}, grid_box_hi[3] = {0, 0, 0};
+    bool rays_off_grid = false;
+    rt::RayScan* d_scan = nullptr;          // the ray scan's result (rt_rays.hip) and its pinned host mirror
+    rt::RayScan* h_scan = nullptr;
+    void* d_mat_stage = nullptr;            // rt_set_materials' staging buffer for a host array (grow-only) and its size in records
+    uint32_t mat_stage_capacity = 0;
+    // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
+    // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
+    uint32_t pose_w = 0, pose_h = 0;
+    rt::WavefrontBuffers wf;
+    bool last_wavefront = false;
+    uint32_t last_rounds = 0;
+
+    rt::Counters* d_counters = nullptr;
+    rt::Counters counters = {};
+
+    rt_setup_times_t setup = {};
+
+    hipEvent_t ev_begin[rt::host::kTimingSlots];
+    hipEvent_t ev_end[rt::host::kTimingSlots];
+    uint32_t ev_count = 0;   // launches recorded since the last rt_timing_reset
+    uint32_t ev_begin_made = 0, ev_end_made = 0;  // events created so far (rt_destroy frees a partial set too)
+    float last_ms = 0.f;
+
+    std::string error;
+};
+
+namespace rt::host {
+
+int fail(rt_context* ctx, int code, const std::string& msg);
+int fail_hip(rt_context* ctx, hipError_t e, const char* what);
+
+// The C ABI must not change the calling thread's current HIP device (the caller is usually a host framework with
+// its own idea of it): every entry point that needs the context's device switches to it through this guard, which
+// restores the caller's device on every exit path.
+struct DeviceGuard {
+    int saved = -1;
+    bool ok = true;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int device) {
+        if (hipGetDevice(&saved) != hipSuccess) saved = -1;
+        if (saved != device) {
+            err = hipSetDevice(device);
+            ok = (err == hipSuccess);
+        }
+    }
+    ~DeviceGuard() {
+        int now = -1;
+        if (saved >= 0 && hipGetDevice(&now) == hipSuccess && now != saved) (void)hipSetDevice(saved);
+    }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+#define RT_DEVICE(ctx)                                                       \
+    DeviceGuard device_guard_((ctx)->device);                                \
+    if (!device_guard_.ok) return fail_hip((ctx), device_guard_.err, "hipSetDevice")
+
+#define RT_HIP(ctx, call)                                           \
+    do {                                                            \
+        hipError_t e_ = (call);                                     \
+        if (e_ != hipSuccess) return fail_hip((ctx), e_, #call);    \
+    } while (0)
+
+// a context-owned buffer that only ever grows: device memory, or pinned host memory (rt_api.cpp)
+int grow_buffer(rt_context* c, void*& p, size_t& have, size_t need, bool pinned_host);
+// one array of a group that grows together: the group's capacity `have` (in elements) is the caller's to set once all of them have grown
+template <class T>
+int grow_array(rt_context* c, T*& p, size_t have, size_t need) {
+    void* q = p;
+    size_t bytes = sizeof(T) * have;
+    const int rc = grow_buffer(c, q, bytes, sizeof(T) * need, false);
+    p = static_cast<T*>(q);
+    return rc;
+}
+
+inline size_t packed_bytes(int format) { return format == RT_PIXEL_RGBA8 ? 4 : (format == RT_PIXEL_RGB8 ? 3 : 0); }
+
+// the sample grid a factor > 1 filters over: the pinhole camera's, or the pose's the ray buffer was generated from (0: neither)
+inline uint32_t sample_width(const rt_context* c) { return c->pinhole ? c->width : c->pose_w; }
+
+// |d|^2 exactly as the walks compute it (fp32, unfused, left to right) against their `tame` window
+inline bool direction_in_domain(float dx, float dy, float dz) {
+    const volatile float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    const volatile float s1 = xx + yy;
+    const float dd = s1 + zz;
+    return dd > 1.0e-30f && dd < 1.0e30f;
+}
+// the grid (fine grid, block grid, light tiles) serves the rays in use: always a camera's, a ray buffer's unless a scan said no
+inline bool grid_in_use(const rt_context* c) { return c->grid.enabled && (c->pinhole || !c->rays_off_grid); }
+
+// View-space bounding sphere of what the traversal tests for object o: { x : |A x + b| <= r0 } with A, b the
+// rows x,y,z of mvInverse (the kernels never consult mv for intersection) -> centre -A^-1 b, radius
+// r0 * sigma_max(A^-1) <= r0 * |A^-1|_F. Computed in double, then inflated:
+//   R_eff = R * (1 + 2^-9) + |c| * 2^-9
+// which covers (a) the reference's own rounding: its discriminant accepts rays that pass a sphere at up to
+// sqrt(1 + ~1e-6 (|c|/R)^2) radii, (b) the fp32 rounding of the bundle test. Anything doubtful (singular or
+// non-finite matrices) gets +inf = never culled; unknown primitive types can never be hit = -inf.
+struct Sphere { double x, y, z, r; };
+// Bounding sphere of an instanced unit sphere / unit box in view space, in double precision and WITHOUT safety
+// margins (callers add the ones their use needs): centre -A^-1 b, radius r0 * sigma_max(A^-1) (r0 = 1 or
+// sqrt(0.75)), plus an upper bound of the squared condition number kappa^2 = (sigma_max / sigma_min)^2.
+// r = +inf: no usable bound (test it for every ray); r = -inf: unknown type, can never be hit.
+struct Bound { double x, y, z, r, kappa2; };
+
+// The unified walk's record table (rt_grid.h: GridDesc::walk_rec), host side. build_grid puts down one head per cell of
+// the grid padded by two empty cells on every side, then the 2nd, 3rd ... entries of every cell; build_light_tiles appends
+// the light tiles' entries; upload_walk_records ships the table (or drops it when it would not fit 32-bit byte offsets).
+constexpr uint32_t kWalkBorder = 2;
+inline float4 walk_sphere(const float4& es) {
+    const volatile float w = es.w;
+    const volatile float w2 = w * w;  // the fp32 product the pre-test used to form per trip
+    return make_float4(es.x, es.y, es.z, w2);
+}
+inline float4 walk_link(uint32_t object, uint32_t next, float key) {
+    float4 r;
+    std::memcpy(&r.x, &object, 4);
+    std::memcpy(&r.y, &next, 4);
+    r.z = key;
+    r.w = 0.f;
+    return r;
+}
+
+struct PoseVerdict {
+    bool in_domain = false, starts_ok = false, on_grid = false;
+    double origin[3] = {0, 0, 0};
+    float verdict_ms = 0.f;
+};
+
+// rt_scene.cpp
+void pack_pairs(const rt_object_data* objs, const uint32_t* order, uint32_t n, std::vector<rt::HotPair>& pairs);
+void repack_objects(const rt_object_data* objs, uint32_t n, std::vector<rt::HotPair>& pairs,
+                    std::vector<rt::HotObject>& hot, std::vector<rt::ColdObject>& cold);
+Bound object_bound(const rt_object_data& o);
+Sphere bounding_sphere(const rt_object_data& o);
+double size_proxy(const rt_object_data& o);
+int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n);
+int upload_walk_records(rt_context* c);
+// rt_camera_tiles.cpp
+float4 screen_rect(const Sphere& s, double z);
+bool detect_pinhole(const rt_ray* rays, uint64_t n, uint32_t& W, uint32_t& H, float& z);
+int refresh_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift);
+// rt_light_setup.cpp
+bool lights_need_literal(const rt_context* c, const rt_light* L, uint32_t n_lights);
+int build_light_tiles(rt_context* c, const rt_light* lights);
+int build_light_tiles_device(rt_context* c, const rt_light* lights);
+// rt_api.cpp: what the rt_*_multi entry points share with the single-context ones
+int pose_grid(rt_context* c, uint32_t width, uint32_t height, float z, const float* m, const float* origin, rt::PoseGrid& g);
+int pose_check(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, PoseVerdict& v);
+int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const PoseVerdict& v);
+int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights);
+int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count);
+
+}  // namespace rt::host

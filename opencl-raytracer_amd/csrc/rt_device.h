@@ -31,7 +31,7 @@ namespace rt {
 
 constexpr float kMaxFloat = 3.402823466e+38F;  // shade_and_reflect_kernel.cl:31
 
-// ---- HBM layouts built by the upload path (rt_api.cpp) -------------------------------------------------
+// ---- HBM layouts built by the upload path (rt_api.cpp, rt_scene.cpp) -------------------------------------------------
 struct HotObject {   // 64 B, 64-B aligned: one s_load_dwordx16 per object per wave
     float4 row0;     // mvInverse row 0: (m[0], m[4], m[8],  m[12])
     float4 row1;     // mvInverse row 1: (m[1], m[5], m[9],  m[13])

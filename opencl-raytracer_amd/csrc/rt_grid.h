@@ -15,7 +15,7 @@
 //    |p_i| <= 0.5 + 2u(|o^_i| + 0.5), which is inside the same expression with r0^2 in place of 1;
 //  * back in view space (|o^| <= kappa dist / sigma_max(A^-1), distances scale by at most sigma_max(A^-1)):
 //        the line passes c within  sqrt(R^2 (1 + 8u) + 14 u kappa^2 dist^2) + 10.4 u kappa (|start| + |c|) + 9 u kappa^2 dist.
-// build_grid (rt_api.cpp) evaluates this with u_eff = 2e-7 (3.3 u; also covers the unfused flavour's extra
+// build_grid (rt_scene.cpp) evaluates this with u_eff = 2e-7 (3.3 u; also covers the unfused flavour's extra
 // roundings), in double precision, twice: with the farthest possible ray origin for the radius an object is
 // REGISTERED with (+ 0.01 cell for the walk's own fp32 arithmetic), and as a function of the ray's actual distance
 // for the PRE-TEST below. Objects whose bounds are not finite or as large as the scene sit in an "always" list that
@@ -90,7 +90,7 @@ struct GridDesc {
 //               its pre-test, its id is the never-hit dummy object)
 // and a parallel array of object ids (8 per block), read only for the few entries that pass the pre-test. The pre-test
 // is the one of misses_bounding_sphere, evaluated in lattice coordinates (a similarity transform: the ray origin is
-// moved there once per trip). The host (rt_api.cpp: build_walk_blocks) rounds every sphere OUTWARDS: it computes the
+// moved there once per trip). The host (rt_scene.cpp: build_walk_blocks) rounds every sphere OUTWARDS: it computes the
 // lattice the way the device does (same fp32 fma), knows each entry's exact quantisation error and adds it - plus the
 // transform's rounding and the cross term of the distance-dependent tolerance - to the radius; a sphere that does not
 // fit any scale becomes "the whole cell". Seven candidates per line instead of one: cells can be ~1.7x larger, a ray
@@ -134,7 +134,7 @@ __device__ __forceinline__ T table_at(const T* __restrict__ base, uint32_t index
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint32_t)(index * (uint32_t)sizeof(T)));
 }
 
-// screen tiles for pinhole primary rays (built on the host per camera, rt_api.cpp: build_screen_tiles)
+// screen tiles for pinhole primary rays (built on the host per camera, rt_camera_tiles.cpp: build_screen_tiles)
 //
 // Depth key of an entry: a lower bound on any t the exact test can report for that object on a pinhole primary ray. Such a
 // ray starts at the origin with direction (x, y, z), z < 0 the same for every pixel, so the point o + t d has view-space
@@ -199,7 +199,7 @@ struct ScreenTiles {
 // all lie on lines through that light, so "which objects can this ray meet" is a 2-D question in the light's own
 // perspective: objects are binned by the rectangle their registration sphere covers in gnomonic coordinates
 // (u, v) = (x', y') / -z' of the light-local frame (x', y', z' = a signed permutation of p - L in which every object lies
-// at z' < 0), and a ray looks up the one tile its origin falls in - no cell walk. Built on the host (rt_api.cpp:
+// at z' < 0), and a ray looks up the one tile its origin falls in - no cell walk. Built on the host (rt_light_setup.cpp:
 // build_light_tiles) when every object lies strictly on one side of an axis-aligned plane through the light; every
 // candidate still goes through the pre-test and the reference's exact test, so the answer is the brute-force loop's.
 //
@@ -278,7 +278,7 @@ __device__ __forceinline__ void closest_update_unordered(uint32_t type, float sx
 
 // Cheap conservative rejection of a grid candidate before its 52-byte matrix is fetched. s = (centre, w): the
 // reference's fp32 test can only accept a ray whose line passes the centre within sqrt(w^2 + 6e-6 K^2 |oc|^2)
-// (build_grid, rt_api.cpp: the bound is a function of the ray's ACTUAL distance |oc| from the object, which for
+// (build_grid, rt_scene.cpp: the bound is a function of the ray's ACTUAL distance |oc| from the object, which for
 // secondary rays is a small fraction of the scene size the cell registration has to assume). `alpha` adds 8e-6
 // for this test's own fp32 rounding (~1e-6 |oc|^2 A on the discriminant). A negative w marks an entry whose
 // radius already contains the worst-case distance term (it gets the same tolerance: more than it needs). Second test: the sphere is entirely behind the origin.

@@ -1,4 +1,4 @@
-// rt_kernels.h - launch interface between the C-ABI layer (rt_api.cpp) and the gfx950 kernels.
+// rt_kernels.h - launch interface between the C-ABI layer (rt_api.cpp and the host units beside it) and the gfx950 kernels.
 #pragma once
 
 #include "rt_device.h"

@@ -22,7 +22,7 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 // Which objects can any ray of this wave's 8x8 pixel bundle hit? Lane k compares the bundle's direction
 // rectangle [xl,xr] x [yb,yt] (pinhole rays: direction = (x, y, z), z fixed) with object k's screen rectangle,
 // i.e. the conservative projection of its inflated bounding sphere computed on the host in double precision
-// (rt_api.cpp: screen_rect). Four compares per object per wave.
+// (rt_camera_tiles.cpp: screen_rect). Four compares per object per wave.
 __device__ __forceinline__ uint64_t bundle_candidates(const float4* __restrict__ rects, uint32_t n, float xl, float xr,
                                                       float yb, float yt) {
     const uint32_t lane = threadIdx.x & 63u;

@@ -1,6 +1,6 @@
 // rt_light_tiles.h - host-side launchers of the light-tile builder (rt_light_tiles.hip): the per-direction candidate lists of
 // rt_grid.h's LightTiles for the shadow rays towards one positional light, built on the device from the objects' registration
-// spheres, in the block form. rt_api.cpp's build_light_tiles is the host builder it restates; opencl-raytracer_amd/light_tiles.py
+// spheres, in the block form. rt_light_setup.cpp's build_light_tiles is the host builder it restates; opencl-raytracer_amd/light_tiles.py
 // is the executable definition.
 #pragma once
 #include <hip/hip_runtime.h>

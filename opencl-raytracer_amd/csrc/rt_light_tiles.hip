@@ -1,4 +1,4 @@
-// rt_light_tiles.hip - the light tiles of rt_grid.h's LightTiles, built where the objects are: rt_api.cpp's build_light_tiles
+// rt_light_tiles.hip - the light tiles of rt_grid.h's LightTiles, built where the objects are: rt_light_setup.cpp's build_light_tiles
 // restated for the device, block form only (light_tiles.py is the executable definition, rt_grid.h has the margins).
 //
 // Passes on one stream, none of which waits on another workgroup (ordering is the stream's); the host synchronises four times:

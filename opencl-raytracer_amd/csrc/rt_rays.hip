@@ -3,7 +3,7 @@
 // rt_create decides from three predicates over the uploaded rays, and from the box of their origins, which path renders a
 // frame: the default path (grid, exact eliminations), the literal loops or brute force. Its host loops are single-threaded;
 // for rays that already live in device memory (rt_set_rays_device) the same predicates are a reduction here. Per ray, in
-// fp32, nothing contracted (the translation unit is built with -ffp-contract=off), left to right, as rt_api.cpp states them:
+// fp32, nothing contracted (the translation unit is built with -ffp-contract=off), left to right, as rt_api.cpp and rt_context.h state them:
 //   direction.w == 0.0f                                                          else kRayDirW
 //   dd = (dx*dx + dy*dy) + dz*dz;  dd > 1e-30f && dd < 1e30f  (a NaN fails)      else kRayDomain   (direction_in_domain)
 //   start.w == 1.0f && isfinite((sx + sy) + sz)                                  else kRayStart

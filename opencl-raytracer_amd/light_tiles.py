@@ -1,5 +1,5 @@
 """Light tiles - the executable definition (numpy, float64) of what csrc/rt_light_tiles.hip builds on the device for
-rt_set_lights, and csrc/rt_api.cpp's build_light_tiles on the host for rt_create (csrc/rt_grid.h: LightTiles).
+rt_set_lights, and csrc/rt_light_setup.cpp's build_light_tiles on the host for rt_create (csrc/rt_grid.h: LightTiles).
 
 Shadow rays towards one positional light L all lie on lines through L. In the light-local frame (x', y', z') - a signed
 permutation of p - L in which every object lies at z' < 0 - an object's registration sphere (c, r0), padded by kPad, covers a

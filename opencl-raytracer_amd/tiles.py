@@ -35,7 +35,7 @@ REFUSED_KNOB = 512        # RT_POSE_TILES said no
 
 
 def sigma_max(N: np.ndarray) -> float:
-    """sqrt of the largest eigenvalue of N N^T in closed form (object_bound's, csrc/rt_api.cpp): padded by 1e-6 relative,
+    """sqrt of the largest eigenvalue of N N^T in closed form (object_bound's, csrc/rt_scene.cpp): padded by 1e-6 relative,
     never above the Frobenius bound or below a third of it."""
     S = N @ N.T
     fro2 = float(np.sum(N * N))

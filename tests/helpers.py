@@ -219,7 +219,7 @@ def misc_fuzz_case(rng):
 # ---- RT_FLAG_DEVICE_OPENCL: where rt_create switches a scene to the literal loops --------------------------------------
 def object_reach(objs):
     """Per object, the float64 centre (n, 3) and radius (n,) of the ball in which a positional light makes rt_create render
-    an RT_FLAG_DEVICE_OPENCL scene with the literal loops: object_bound() of rt_api.cpp (bounding sphere of the instanced
+    an RT_FLAG_DEVICE_OPENCL scene with the literal loops: object_bound() of rt_scene.cpp (bounding sphere of the instanced
     unit sphere / box from rows x, y, z of mvInverse, sigma_max from the closed-form eigenvalue, padded by 1e-6), then
     R (1 + 1e-4) + 1e-4 (|cx| + |cy| + |cz| + R). The same expressions in the same order; radius +inf where rt_create has
     no usable bound (every light is near), -inf for a type that is never hit."""

@@ -1,4 +1,4 @@
-"""GPU: the closest-hit walk's coarse grid of 32-byte blocks (rt_grid.h: BlockGrid; rt_api.cpp: build_walk_blocks;
+"""GPU: the closest-hit walk's coarse grid of 32-byte blocks (rt_grid.h: BlockGrid; rt_scene.cpp: build_walk_blocks;
 rt_wavefront.hip: block_segment) at its edges - every case must give the brute-force loop's (t, index) bit for bit:
  * spheres far larger than a cell next to crowds of tiny ones (lattice scales 1-3 and the whole-cell fallback),
  * cells with many more than seven candidates (chained blocks),

@@ -161,10 +161,14 @@ def test_light_tile_block_indices_share_one_limit():
     import re
     from pathlib import Path
     src = Path(__file__).resolve().parent.parent / "opencl-raytracer_amd" / "csrc"
-    grid, api, wf = (src / "rt_grid.h").read_text(), (src / "rt_api.cpp").read_text(), (src / "rt_wavefront.hip").read_text()
+    grid, lights, wf = (src / "rt_grid.h").read_text(), (src / "rt_light_setup.cpp").read_text(), (src / "rt_wavefront.hip").read_text()
+    host_units = [src / "rt_context.h"] + sorted(src.glob("*.cpp"))   # every host unit of the C-ABI layer
+    assert {p.name for p in host_units} >= {"rt_api.cpp", "rt_scene.cpp", "rt_camera_tiles.cpp", "rt_light_setup.cpp", "rt_multi.cpp"}
     assert re.search(r"constexpr uint32_t kLtBlockIndexBits = 24;", grid)
     assert "static_assert(light_tile_blocks_fit((1ull << 24) - 1) && !light_tile_blocks_fit(1ull << 24)" in grid
-    assert "rt::light_tile_blocks_fit(n_lt_blocks)" in api and "1ull << 30" not in api
+    assert "rt::light_tile_blocks_fit(n_lt_blocks)" in lights
+    for p in host_units:
+        assert "1ull << 30" not in p.read_text(), p.name
     # every place that splits a light-tile cursor into (block, position) uses the shared mask / shift
     for m in re.finditer(r"const uint32_t b = (\w+) & (\w+), pos = \1 >> (\w+);", wf):
         if m.group(1) in ("e", "cursor"):   # the light-tile walks of trace_segment / walk_segment (the block GRID's cursors have their own 24-bit rule, checked by build_walk_blocks)

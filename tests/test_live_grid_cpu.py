@@ -37,7 +37,7 @@ AIM_OFFSETS = (0.0, 0.5, 1.0, 2.0, 0.5, 1.0, 2.0, 6.0)
 
 @functools.lru_cache(maxsize=None)
 def live_scene(name):
-    """s300 and tri of test_frame_shapes_cpu, and s608: the other side of kWavefrontMinObjects = 512 (rt_api.cpp), where an
+    """s300 and tri of test_frame_shapes_cpu, and s608: the other side of kWavefrontMinObjects = 512 (rt_context.h), where an
     off-grid frame stays on the large-scene kernels."""
     if name != "s608":
         return scene(name)
@@ -98,7 +98,7 @@ def inside_an_object(starts, objs):
 
 
 def cell_edges(lo, hi, n_objs):
-    """build_grid's cell edge (rt_api.cpp) and its refinements by 0.7: about three cells per object, at most 256 per axis."""
+    """build_grid's cell edge (rt_scene.cpp) and its refinements by 0.7: about three cells per object, at most 256 per axis."""
     ext = np.maximum(np.asarray(hi, np.float64) - np.asarray(lo, np.float64), 1e-6)
     cell = max(float(np.cbrt(ext.prod() / (3.0 * n_objs))), float(ext.max()) / 256.0)
     return [cell * 0.7 ** k for k in range(4)]

@@ -187,7 +187,7 @@ def test_spheres_behind_the_camera_and_without_a_bound_are_in_no_list():
 
 # ---- 4. the identity pose against the camera's rule ----------------------------------------------------------------------------
 def camera_memberships(spheres, W, H, z, col_shift=6):
-    """rt_api.cpp: screen_rect and build_screen_tiles' tile ranges, per object (x0, x1, y0, y1) or None."""
+    """rt_camera_tiles.cpp: screen_rect and build_screen_tiles' tile ranges, per object (x0, x1, y0, y1) or None."""
     out = []
     half_w, half_h = float(F(W) / F(2)), float(F(H) / F(2))
     for cx, cy, cz, r in spheres:

@@ -47,7 +47,7 @@ def pose_rays(name, W, H, pose, origin=None):
 
 
 def tri_box():
-    """build_grid's box for the mesh scene (rt_api.cpp): the origin united with every guard sphere padded by 1 %."""
+    """build_grid's box for the mesh scene (rt_scene.cpp): the origin united with every guard sphere padded by 1 %."""
     objs, _ = scene("tri")
     gs = objs["mvInverse"].reshape(len(objs), 16)[:, :4].astype(np.float64)
     return np.minimum(0.0, (gs[:, :3] - 1.01 * gs[:, 3:4]).min(0)), np.maximum(0.0, (gs[:, :3] + 1.01 * gs[:, 3:4]).max(0))
