@@ -65,7 +65,9 @@ extern "C" {
  *      Later addition, same version: replaceable lights - rt_set_lights, rt_set_lights_multi, rt_get_light_tiles_info,
  *      rt_read_light_tiles, rt_read_grid_pretest. Additions only; a caller detects support by the symbol (dlsym of rt_set_lights).
  *      Later addition, same version: replaceable materials - rt_set_materials, rt_set_materials_device, rt_set_materials_multi,
- *      rt_read_materials. Additions only; a caller detects support by the symbol (dlsym of rt_set_materials). */
+ *      rt_read_materials. Additions only; a caller detects support by the symbol (dlsym of rt_set_materials).
+ *      Later addition, same version: replaceable transforms - rt_set_transforms, rt_set_transforms_multi, rt_read_transforms,
+ *      rt_get_geometry_info. Additions only; detect by dlsym of rt_set_transforms. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -485,8 +487,8 @@ int rt_read_grid_spheres(const rt_context* ctx, double* spheres, uint64_t n);
  * tile_start[tiles_u * tiles_v + 1] offsets and, per entry in list order, three 32-bit words {object index, block word lo, block
  * word hi} (lo = x16 | y16 << 16, hi = z16 | r8 << 16 | k8 << 24). n_start and n_entries are the arrays' capacities in elements /
  * triples; too small: RT_ERR_INVALID_ARGUMENT. RT_ERR_STATE when no table, or only the record form (RT_NO_LT_BLOCKS), is in use. */
-#define RT_LTILES_REFUSED_NO_GRID 0x1u   /* no grid built, literal loops, kernel not shade_and_reflect, no lights, or objects on the
-                                            grid's always-list                                                                      */
+#define RT_LTILES_REFUSED_NO_GRID 0x1u   /* no grid built, literal loops, kernel not shade_and_reflect, no lights, or an object
+                                            without a finite registration radius (it is in no list)                               */
 #define RT_LTILES_REFUSED_LIGHT   0x2u   /* the last light is directional or not finite                                           */
 #define RT_LTILES_REFUSED_PLANE   0x4u   /* no axis-aligned plane through the light with every object 0.05 in front of it         */
 #define RT_LTILES_REFUSED_TANGENT 0x8u   /* an object without a usable tangent (beyond 1.5533 rad of the axis)                     */
@@ -525,8 +527,8 @@ int rt_read_grid_pretest(const rt_context* ctx, float* pre, uint64_t n);
 
 /* ---- replaceable materials -----------------------------------------------------------------------------------------------------
  * The colours of a live context's objects: a viewer that highlights the object under the mouse (rt_render_aux names it), a
- * simulation that colours its particles by a scalar every step - without rt_destroy + rt_create. Geometry (mv, mvInverse, type, the
- * object count) is NOT replaceable: the grid and the walks' tables are built from it.
+ * simulation that colours its particles by a scalar every step - without rt_destroy + rt_create. (The two matrices have a setter of
+ * their own, "replaceable transforms" below; type and the object count are NOT replaceable.)
  *
  * `materials` are `count` records of 64 bytes in rt_material's layout (rt_records.h), assigned to objects first .. first + count - 1.
  *
@@ -558,6 +560,76 @@ int rt_read_grid_pretest(const rt_context* ctx, float* pre, uint64_t n);
 int rt_set_materials(rt_context* ctx, const void* materials, uint32_t first, uint32_t count);
 int rt_set_materials_device(rt_context* ctx, const void* d_materials, uint32_t first, uint32_t count, void* hip_stream);
 int rt_read_materials(rt_context* ctx, void* materials, uint32_t first, uint32_t count);
+
+/* ---- replaceable transforms ----------------------------------------------------------------------------------------------------
+ * Where a live context's objects are: a viewer that drags the object under the mouse (rt_render_aux names it), an animation that
+ * moves a few bodies per frame - without rt_destroy + rt_create, which costs several frames' time for a large scene.
+ *
+ * `transforms` are `count` HOST records of 128 bytes in rt_transform's layout (rt_records.h: mv, then mvInverse, column-major like
+ * rt_object_data's), of any alignment, assigned to objects first .. first + count - 1. The caller supplies both matrices, as it
+ * does to rt_create; mvInverseTranspose is read by no kernel and is no part of the record.
+ *
+ * Contract. The next render is the frame a FRESH context renders that is created with the same object array except that those
+ * objects carry these two matrices (materials and type untouched), the same flags, and the current rays / camera / pose / shard /
+ * supersampling factor / lights / materials - bit for bit, with the same rays_reference and hit_pixels - for every kernel, every
+ * path (small-scene kernel, round machine, literal loops, brute force, RT_FLAG_NO_GRID) and every arithmetic mode. What was set or
+ * rendered before does not matter. The call is synchronous like rt_set_lights: on return the array is the caller's again and the
+ * next render on any stream sees the objects where they now are; renders of this context still in flight on ANOTHER stream must be
+ * ordered by the caller. count == 0 returns RT_OK and launches nothing.
+ *
+ * The records. One pass on the device (csrc/rt_transforms.hip) rewrites every copy of the two matrices the kernels read - the
+ * walks' records, the shading records, the round machine's records and the object's half of its pair in both pair streams - from
+ * the array, staged in a context-owned device buffer (grow-only, freed by rt_destroy). Values are moved, not computed with.
+ *
+ * Contexts with a grid (rt_get_rays_info().grid_built): the DYNAMIC set. The grid, the block grid and the current screen tiles list
+ * an object by where it was at rt_create, and rebuilding them on the device is not part of this call. Instead every object an
+ * accepted call names becomes dynamic and stays so until rt_destroy: it is appended to the list of "objects every ray must test"
+ * that the kernels loop over before they look at any table (the list rt_create uses for objects without a usable bound), and its old
+ * registrations stay where they are. That is sound because a table entry is only ever a CANDIDATE: a stale one can do no more than
+ * trigger one more exact test of an object the always-loop tests anyway, taking the closer of two hits is order-free and idempotent,
+ * and an any-hit answer does not depend on who asks - so pixels are those of a fresh context. The screen tiles' depth-order exit
+ * stays valid too: a stale entry keeps its place in the order, which still bounds every entry behind it. The list holds 64 entries,
+ * create-time ones included (rt_get_geometry_info: dynamic_capacity). A dynamic object gets registration spheres from the formula
+ * the grid was built with, evaluated for the box, cell and scene constant of THAT grid; they are what later screen tiles (a camera
+ * or pose change) and light tiles are built from, so those list the object where it is. The light tiles are the one table whose
+ * lists are all a ray consults: they ARE rebuilt by the call, on the device, as rt_set_lights does it
+ * (rt_get_light_tiles_info: source 2). The price is the always-loop: every ray tests every dynamic object (rt_get_stats:
+ * object_tests), and the rays of a frame's tail walk the fine grid instead of the block grid while the list is not empty.
+ * Contexts without a grid (at most 95 objects, RT_FLAG_NO_GRID, non-affine instances, literal contexts): no cap, no dynamic set;
+ * the records are patched and the small-scene kernel's culling rectangles follow.
+ * RT_FLAG_DEVICE_OPENCL: the predicate on the lights ("replaceable lights") is evaluated again with the objects' new bounds; the
+ * frame goes literal or stops being literal as a fresh context's would.
+ *
+ * Refusals are decided on the host, over the WHOLE range, before anything is touched; a refused call leaves the context exactly as
+ * it was. RT_ERR_INVALID_ARGUMENT: a NULL array with count != 0; first + count > n_objs (in 64 bits); an object in the range whose
+ * type is not 0 or 1 (a triangle's mv holds vertices); on a context whose instances are all affine, a matrix whose bottom row is
+ * not (0,0,0,1) exactly; on a context that is not already literal for a degenerate instance, a transform without a finite bound
+ * (singular or non-finite mvInverse); on a grid context, a new bound whose centre +- 1.01 R leaves box_lo .. box_hi of
+ * rt_get_rays_info on any axis (the grid's margins are derived for ray origins inside that box, and secondary rays start on object
+ * surfaces). RT_ERR_STATE: the dynamic set would exceed its capacity. A fresh context would render each of these by the literal
+ * loops, by brute force or with a bigger grid; this call never switches paths behind the caller's back.
+ *
+ * NOT part of this call (each would be its own addition): a device-memory form (the bounds and refusals are evaluated on the host);
+ * changing an object's type or the object count; triangles; folding dynamic objects back into the grid, hence moving more than 64
+ * objects of a grid context - that is the device rebuild of the fine grid and the block grid; poses outside the grid box.
+ *
+ * rt_read_transforms: an accessor for tests and tools, next to rt_read_materials. Reassembles rt_transform records of objects
+ * first .. first + count - 1 from the device records; RT_ERR_STATE with a message if two copies of a word disagree (HotObject /
+ * ObjectRecord / either pair stream for rows x, y, z of mvInverse; ColdObject / ObjectRecord for rows x, y, z of mv).
+ * rt_get_geometry_info: the dynamic set and what the last accepted rt_set_transforms did. */
+typedef struct rt_geometry_info_t {
+    uint32_t grid_built;            /* as rt_rays_info_t::grid_built: the context has a grid, moved objects become dynamic         */
+    uint32_t n_unbounded;           /* entries rt_create put on the always-list (objects without a usable bound)                  */
+    uint32_t n_dynamic;             /* objects rt_set_transforms has put there since                                              */
+    uint32_t dynamic_capacity;      /* how many it may put there in all: 64 - n_unbounded (0 without a grid: no dynamic set)      */
+    uint32_t dynamic_ids[64];       /* the first n_dynamic: object indices in the order they became dynamic                       */
+    uint32_t light_tiles_rebuilt;   /* the last accepted call ran the light tiles' device builder (rt_get_light_tiles_info)       */
+    uint32_t reserved;
+    double   patch_device_ms;       /* device time of the last accepted call's upload + patch pass (events)                       */
+} rt_geometry_info_t;
+int rt_set_transforms(rt_context* ctx, const void* transforms, uint32_t first, uint32_t count);
+int rt_read_transforms(rt_context* ctx, void* transforms, uint32_t first, uint32_t count);
+int rt_get_geometry_info(const rt_context* ctx, rt_geometry_info_t* info);
 
 void rt_destroy(rt_context* ctx);
 
@@ -596,6 +668,9 @@ int rt_set_lights_multi(rt_multi* m, const void* lights, uint32_t n_lights);
 /* rt_set_materials ("replaceable materials", above; host arrays only) on every context, all or none: the arguments are validated
  * before any shard is touched. */
 int rt_set_materials_multi(rt_multi* m, const void* materials, uint32_t first, uint32_t count);
+/* rt_set_transforms ("replaceable transforms", above) on every context, all or none: every refusal is evaluated on every shard
+ * before any shard is touched. */
+int rt_set_transforms_multi(rt_multi* m, const void* transforms, uint32_t first, uint32_t count);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);
 int rt_render_multi_device(rt_multi* m, void* d_frame);

@@ -12,6 +12,8 @@
  *   rt_light       64 B   +0 ambient  +16 diffuse  +32 specular  +48 position (w=1 positional, w=0 directional)
  *   rt_ray         32 B   +0 start (w=1)  +16 direction (w=0, not normalised)
  *   rt_pixel       16 B   float3 colour in a float4 slot (cl_float3 == cl_float4)
+ *   rt_transform   128 B  +0 mv  +64 mvInverse, column-major like rt_object_data's (rt_set_transforms; no reference struct:
+ *                         the two matrices of an ObjectData that a kernel reads)
  *
  * Alignment is the CALLER's business: the OpenCL types are 16- / 64-byte aligned (cl_float16 members), these plain C structs
  * ask for 4. The ABI only ever copies the arrays byte for byte (rt_create: "host buffers are copied"), so any alignment works;
@@ -46,6 +48,11 @@ typedef struct rt_object_data {
     uint8_t spacer[60];
 } rt_object_data;
 
+typedef struct rt_transform {
+    float mv[16];
+    float mvInverse[16];
+} rt_transform;
+
 typedef struct rt_light {
     float ambient[4];
     float diffuse[4];
@@ -64,6 +71,7 @@ typedef struct rt_pixel {
 
 RT_STATIC_ASSERT(sizeof(rt_material) == 64, "Material must be 64 bytes");
 RT_STATIC_ASSERT(sizeof(rt_object_data) == 320, "ObjectData must be 320 bytes");
+RT_STATIC_ASSERT(sizeof(rt_transform) == 128, "a transform record must be 128 bytes");
 RT_STATIC_ASSERT(sizeof(rt_light) == 64, "Light must be 64 bytes");
 RT_STATIC_ASSERT(sizeof(rt_ray) == 32, "Ray must be 32 bytes");
 RT_STATIC_ASSERT(sizeof(rt_pixel) == 16, "pixel must be 16 bytes");

@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of
+from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of, transforms_of
 
 LIB_PATH = Path(__file__).resolve().parent / "host" / "libcpu_raytracer.so"
 KERNELS = {"hittest": 0, "shade": 1, "shade_and_reflect": 2}
@@ -43,6 +43,10 @@ def load_library():
             fp = ctypes.POINTER(ctypes.c_float)
             lib.cpu_rt_render_set_materials.restype = ctypes.c_int
             lib.cpu_rt_render_set_materials.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
+        if hasattr(lib, "cpu_rt_render_set_transforms"):
+            fp = ctypes.POINTER(ctypes.c_float)
+            lib.cpu_rt_render_set_transforms.restype = ctypes.c_int
+            lib.cpu_rt_render_set_transforms.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
         _lib = lib
     return _lib
 
@@ -66,6 +70,19 @@ class CPURaytracer:
         self.new_rays = None
         self.pose = None
         self.materials = None
+        self.transforms = None
+
+    def set_transforms(self, transforms, first: int = 0):
+        """CPURaytracer::SetTransforms, the option HIPRaytracer.set_transforms is on the GPU: the next Render() has objects
+        first .. first + n - 1 where the mv / mvInverse of `transforms` put them (a TRANSFORM_DTYPE array, or an OBJECT_DTYPE array
+        whose matrices are taken); materials and type stay. Calls add up: a later one overrides an earlier one where they overlap."""
+        xf = transforms_of(transforms)
+        first = int(first)
+        if first < 0 or first + len(xf) > len(self.objects):
+            raise ValueError("set_transforms: first + len(transforms) exceeds the object count")
+        if self.transforms is None:
+            self.transforms = transforms_of(self.objects)
+        self.transforms[first:first + len(xf)] = xf
 
     def set_materials(self, materials, first: int = 0):
         """CPURaytracer::SetMaterials, the option HIPRaytracer.set_materials is on the GPU: the next Render() shades objects
@@ -119,7 +136,18 @@ class CPURaytracer:
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
         args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
                 ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
-        if self.materials is not None:
+        if self.transforms is not None:
+            if self.supersample != 1:
+                raise ValueError("this front filters the constructor's scene only: set_transforms and supersample exclude each other")
+            fp = ctypes.POINTER(ctypes.c_float)
+            w, h, z, m, o = self.pose if self.pose is not None else (0, 0, 0.0, None, None)
+            mats = self.materials
+            rc = self._lib.cpu_rt_render_set_transforms(*args, ptr(self.transforms), 0, len(self.transforms),
+                                                        ptr(mats) if mats is not None else None, 0, len(mats) if mats is not None else 0,
+                                                        ptr(self.new_rays) if self.new_rays is not None else None, w, h, z,
+                                                        m.ctypes.data_as(fp) if m is not None else None,
+                                                        o.ctypes.data_as(fp) if o is not None else None)
+        elif self.materials is not None:
             if self.supersample != 1:
                 raise ValueError("this front filters the constructor's scene only: set_materials and supersample exclude each other")
             fp = ctypes.POINTER(ctypes.c_float)

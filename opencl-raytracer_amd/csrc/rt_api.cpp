@@ -102,7 +102,7 @@ static bool camera_in_domain(uint32_t W, uint32_t H, float z) {
     const double hi = zz + 0.25 * (double)W * (double)W + 0.25 * (double)H * (double)H;
     return std::isfinite(zz) && lo > 1.0e-29 && hi < 1.0e29;  // (a decade inside the walks' window: fp32 rounding of the sum)
 }
-static void apply_ray_domain(rt_context* c) {
+void apply_ray_domain(rt_context* c) {
     const bool out = c->pinhole ? c->camera_out_of_domain : c->rays_out_of_domain;
     c->flags = c->base_flags | (out ? RT_FLAG_LITERAL : 0u);
 }
@@ -472,6 +472,8 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size[a] > size[b]; });
             std::vector<rt::HotPair> spairs;
             pack_pairs(od, order.data(), n_objs, spairs);
+            c->h_shadow_slot.resize(n_objs);  // (rt_set_transforms patches an object's half of its shadow pair where this order put it)
+            for (uint32_t i = 0; i < n_objs; ++i) c->h_shadow_slot[order[i]] = i;
             RT_TRY(hipMemcpy(c->d_shadow_pairs, spairs.data(), sizeof(rt::HotPair) * spairs.size(), hipMemcpyHostToDevice));
         }
         lap("pair streams (sort, upload)");
@@ -514,6 +516,8 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     lap("hot / cold / object records");
     RT_TRY(hipMalloc((void**)&c->d_lights, sizeof(rt::LightRec) * (size_t)(n_lights + 1)));
     if (n_lights) RT_TRY(hipMemcpy(c->d_lights, lights, sizeof(rt::LightRec) * n_lights, hipMemcpyHostToDevice));
+    c->h_lights.resize(n_lights);
+    if (n_lights) std::memcpy(static_cast<void*>(c->h_lights.data()), lights, sizeof(rt_light) * n_lights);
 
     for (uint32_t i = 0; i < n_objs; ++i)
         if (static_cast<const rt_object_data*>(objs)[i].type == 2u) { c->has_triangles = true; break; }
@@ -526,6 +530,22 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
         if (o.type == 2u) continue;  // vertices, not matrices
         c->affine_w = o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
                       o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f;
+    }
+    {   // per object, for rt_set_transforms: the type and whether both bottom rows are (0,0,0,1) - affine_w is "none is not"
+        c->h_kind.resize(n_objs);
+        std::atomic<uint32_t> not_affine{0};
+        parallel_for(n_objs, 16384, [&](size_t i0, size_t i1) {
+            uint32_t mine = 0;
+            for (size_t i = i0; i < i1; ++i) {
+                const rt_object_data& o = static_cast<const rt_object_data*>(objs)[i];
+                const bool affine = o.type == 2u || (o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
+                                                     o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f);
+                c->h_kind[i] = (uint8_t)(std::min(o.type, 3u) | (affine ? 0u : 0x80u));
+                mine += affine ? 0u : 1u;
+            }
+            not_affine.fetch_add(mine, std::memory_order_relaxed);
+        });
+        c->n_not_affine = not_affine.load();
     }
     // An instance that can produce a NaN hit time for a FINITE ray (non-finite or singular rows x,y,z of mvInverse:
     // a scale of 0, garbage) makes the reference's result depend on the ORDER its loop meets the objects in - a NaN
@@ -879,6 +899,7 @@ int rt_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
         RT_HIP(c, hipStreamSynchronize(c->stream));  // `lights` may be pageable and is the caller's again on return
     }
     c->n_lights = n_lights;
+    c->h_lights.assign(L, L + n_lights);  // (rt_set_transforms rebuilds the light tiles and evaluates the predicate below again)
     // RT_FLAG_DEVICE_OPENCL's predicate on the lights, for these lights (rt_create: lights_need_literal)
     if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal) {
         c->lights_literal = lights_need_literal(c, L, n_lights);
@@ -1477,6 +1498,8 @@ void rt_destroy(rt_context* c) {
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->h_scan) (void)hipHostFree(c->h_scan);
     if (c->d_mat_stage) (void)hipFree(c->d_mat_stage);
+    if (c->d_xf_stage) (void)hipFree(c->d_xf_stage);
+    for (hipEvent_t ev : c->ev_xf) if (ev) (void)hipEventDestroy(ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);
     if (c->d_counters) (void)hipFree(c->d_counters);

@@ -1,6 +1,7 @@
 // rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
 // points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
-// tiles) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in rt::host, apart from the launchers in rt::.
+// tiles), rt_geometry.cpp (replaceable transforms) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in
+// rt::host, apart from the launchers in rt::.
 #pragma once
 #include "hip_raytracer.h"
 #include "rt_records.h"
@@ -12,6 +13,7 @@
 #include "rt_tiles.h"
 #include "rt_light_tiles.h"
 #include "rt_materials.h"
+#include "rt_transforms.h"
 
 #include <hip/hip_runtime.h>
 
@@ -212,6 +214,23 @@ struct rt_context {
     rt::RayScan* h_scan = nullptr;
     void* d_mat_stage = nullptr;            // rt_set_materials' staging buffer for a host array (grow-only) and its size in records
     uint32_t mat_stage_capacity = 0;
+    // Replaceable transforms (rt_set_transforms, rt_geometry.cpp). Of the objects: type and "both bottom rows are (0,0,0,1)" per object
+    // (bits 0-1 and bit 7), how many are not affine, and the position rt_create's size order gave each in the shadow stream. Of the
+    // lights: a host copy (the light tiles are rebuilt, RT_FLAG_DEVICE_OPENCL's predicate is evaluated again). Of the grid: what
+    // build_grid's radii were evaluated with (GridRadii, below), the create-time always-list and behind it the DYNAMIC objects - every
+    // object an accepted call has named, tested by every ray from then on (the list the kernels read is d_grid_always, kMaxAlways
+    // entries). The staging buffer holds a call's records and, behind them, their shadow slots (grow-only, in records).
+    std::vector<uint8_t> h_kind;
+    uint32_t n_not_affine = 0;
+    std::vector<uint32_t> h_shadow_slot;
+    std::vector<rt_light> h_lights;
+    double grid_cell = 0.0, grid_diag = 0.0, grid_s_max = 0.0, grid_k2 = 1.0;
+    std::vector<uint32_t> h_always;
+    uint32_t n_unbounded = 0;
+    void* d_xf_stage = nullptr;
+    uint32_t xf_stage_capacity = 0;
+    hipEvent_t ev_xf[2] = {};
+    rt_geometry_info_t geo_info = {};
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -334,6 +353,22 @@ struct PoseVerdict {
     float verdict_ms = 0.f;
 };
 
+// The registration radius rg and the pre-test radius rpre of one object (rt_grid.h derives the bound; the comment is at the
+// function): what build_grid evaluates per object, and rt_set_transforms for a moved one with what the grid was built for.
+constexpr double kKappa2Tight = 4.0;
+constexpr uint32_t kMaxAlways = 64;   // build_grid's limit for its always-list; create-time entries + dynamic objects share it
+struct GridRadii {
+    double lo[3], hi[3];   // the box of the ray origins and the padded bounds (rt_context::grid_box_lo / hi)
+    double cell, diag;     // cell edge, the box's diagonal
+    double S_max;          // the largest |origin| the box allows
+};
+// rg: -1 never hit, +inf always tested (`always`). rpre: the tight form (>= 0, `tight`) while kappa^2 <= kKappa2Tight and <= K2_limit -
+// build_grid passes +inf and raises its K2 by the tight objects' kappa^2; a grid that is built already passes its K2 - else the full
+// registration radius, negative.
+struct ObjectRadii { double rg, rpre; bool tight, always; };
+ObjectRadii grid_radii(const GridRadii& g, const Bound& b, uint32_t type, double K2_limit);
+float pretest_as_stored(double rpre);  // rounded away from zero, as the grid's entry spheres carry it
+
 // rt_scene.cpp
 void pack_pairs(const rt_object_data* objs, const uint32_t* order, uint32_t n, std::vector<rt::HotPair>& pairs);
 void repack_objects(const rt_object_data* objs, uint32_t n, std::vector<rt::HotPair>& pairs,
@@ -357,5 +392,8 @@ int pose_check(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, PoseVer
 int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const PoseVerdict& v);
 int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights);
 int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count);
+void apply_ray_domain(rt_context* c);
+// rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched
+int check_set_transforms(rt_context* c, const void* transforms, uint32_t first, uint32_t count);
 
 }  // namespace rt::host

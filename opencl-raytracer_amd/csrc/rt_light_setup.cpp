@@ -126,13 +126,24 @@ void publish_light_tiles(rt_context* c, const float* lp, const LightTilePlan& p,
     info.lat_step = p.lat.step; info.rstep = p.rstep; info.kstep = p.kstep;
 }
 
+// The lists are all a shadow ray towards the last light consults (rt_wavefront.hip: last_light_blocked), so every object that can be
+// hit must be in them: one without a finite registration radius is in none. Such objects are on the grid's always-list - but so are
+// rt_set_transforms' dynamic objects, which have a sphere and are listed like any other: the list's length alone says nothing.
+bool has_unlisted_object(const rt_context* c) {
+    if (c->grid.n_always == 0) return false;  // (every object without a finite radius is on that list)
+    const double inf = std::numeric_limits<double>::infinity();
+    for (size_t i = 0; i < (size_t)c->n_objs; ++i)
+        if (c->h_grid_spheres[4 * i + 3] == inf) return true;
+    return false;
+}
+
 }  // namespace
 
 // Light tiles (rt_grid.h: LightTiles): the objects a shadow ray towards the LAST positional light can meet, binned by
 // direction as seen from that light. shade_and_reflect's colour comes from the last light (Q1), so outside literal
 // mode nearly every shadow ray goes there; rays towards other lights (stale-specular scans) keep using the grid walk.
 // Needs: the conservative grid (its registration radii are the ones used here, + 1e-3 for the ray's own rounding: the
-// line of a shadow ray passes the light within ~1e-5), no always-tested objects, and an axis-aligned plane through the
+// line of a shadow ray passes the light within ~1e-5), no object without a finite registration radius, and an axis-aligned plane through the
 // light with every object strictly (by its radius + 0.05) on one side - else nothing is built and the grid walk serves.
 int build_light_tiles(rt_context* c, const rt_light* lights) {
     // (rt_set_lights' builder for a live context is build_light_tiles_device below: the same rules on the device, block form only)
@@ -140,8 +151,8 @@ int build_light_tiles(rt_context* c, const rt_light* lights) {
     rt_light_tiles_info_t& info = c->lt_info;  // what rt_get_light_tiles_info reports of this build
     info = rt_light_tiles_info_t{};
     auto refuse = [&](uint32_t bit) { info.refused |= bit; return RT_OK; };
-    if (!c->grid.enabled || c->grid.n_always != 0 || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->flags & RT_FLAG_LITERAL) ||
-        c->n_lights == 0 || c->h_grid_spheres.empty() || c->h_grid_pre.size() != c->n_objs)
+    if (!c->grid.enabled || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->flags & RT_FLAG_LITERAL) ||
+        c->n_lights == 0 || c->h_grid_spheres.size() != 4 * (size_t)c->n_objs || c->h_grid_pre.size() != c->n_objs || has_unlisted_object(c))
         return refuse(RT_LTILES_REFUSED_NO_GRID);
     if (std::getenv("RT_NO_LIGHT_TILES")) return refuse(RT_LTILES_REFUSED_KNOB);  // measurement knob
     const uint32_t li = c->n_lights - 1u;
@@ -430,8 +441,8 @@ int build_light_tiles_device(rt_context* c, const rt_light* lights) {
     info = rt_light_tiles_info_t{};
     auto refuse = [&](uint32_t bit) { info.enabled = 0; info.source = 0; info.refused |= bit; return RT_OK; };
     const uint32_t n = c->n_objs;
-    if (!c->grid.enabled || c->grid.n_always != 0 || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->base_flags & RT_FLAG_LITERAL) ||
-        c->n_lights == 0 || n == 0 || c->h_grid_spheres.size() != 4 * (size_t)n || c->h_grid_pre.size() != n)
+    if (!c->grid.enabled || c->kernel != RT_KERNEL_SHADE_AND_REFLECT || (c->base_flags & RT_FLAG_LITERAL) ||
+        c->n_lights == 0 || n == 0 || c->h_grid_spheres.size() != 4 * (size_t)n || c->h_grid_pre.size() != n || has_unlisted_object(c))
         return refuse(RT_LTILES_REFUSED_NO_GRID);
     if (std::getenv("RT_NO_LIGHT_TILES")) return refuse(RT_LTILES_REFUSED_KNOB);
     if (const char* env = std::getenv("RT_LIGHT_TILES_DEVICE"))  // measurement knob: "0" leaves a replaced light to the grid walk

@@ -301,6 +301,19 @@ int rt_set_materials_multi(rt_multi* m, const void* materials, uint32_t first, u
     return RT_OK;
 }
 
+int rt_set_transforms_multi(rt_multi* m, const void* transforms, uint32_t first, uint32_t count) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    for (rt_context* c : m->ctx) {  // all or none: every refusal is the host's (bounds, the grid box, the dynamic set's room), per shard
+        const int rc = check_set_transforms(c, transforms, first, count);
+        if (rc != RT_OK) return multi_fail(m, rc, c->error);
+    }
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = rt_set_transforms(m->ctx[r], transforms, first, count);
+        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
+    }
+    return RT_OK;
+}
+
 uint64_t rt_multi_frame_elems(const rt_multi* m) { return m ? m->tiles * m->tile_rays : 0; }
 
 int rt_set_supersampling_multi(rt_multi* m, uint32_t s) {

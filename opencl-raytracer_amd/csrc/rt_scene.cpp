@@ -455,6 +455,49 @@ static int build_walk_blocks(rt_context* c, uint32_t n, const std::vector<Bound>
     return RT_OK;
 }
 
+// Radii (rt_grid.h derives the bound): with u = 2^-24, a ray that starts `dist` from the centre c of an object
+// with bounding radius R and condition number kappa can only be accepted by the reference's fp32 test if its
+// line passes c within
+//     sqrt(R^2 (1 + 8u) + 14 u kappa^2 dist^2) + 10.4 u kappa (|start| + |c|) + 9 u kappa^2 dist.
+// Everything below uses u_eff = 2e-7 (3.3 u):  a = R sqrt(1 + 2e-6),  L = 2.2e-6 kappa (S + |c|) + 2e-6 kappa^2 D,
+//   registration radius  sqrt(a^2 + 3e-6 kappa^2 D^2) + L   (D = farthest possible ray origin, S = largest |origin|)
+//   pre-test radius      a + 2L + 1e-6 |c|, used with the ACTUAL distance: r^2 = w^2 + alpha dist^2, alpha = 6e-6 K^2
+// (K^2 = largest kappa^2 among the objects that use the distance-dependent form, at most 4; more anisotropic
+// objects carry their full registration radius instead, flagged by a negative w).
+ObjectRadii grid_radii(const GridRadii& g, const Bound& b, uint32_t type, double K2_limit) {
+    const double inf = std::numeric_limits<double>::infinity();
+    ObjectRadii out{0.0, 0.0, false, false};
+    if (b.r == -inf) { out.rg = -1.0; return out; }
+    if (!std::isfinite(b.r)) { out.rg = inf; out.always = true; return out; }
+    double D2 = 0;
+    const double cc[3] = {b.x, b.y, b.z};
+    for (int a = 0; a < 3; ++a) {
+        const double d = std::max(std::fabs(cc[a] - g.lo[a]), std::fabs(g.hi[a] - cc[a]));
+        D2 += d * d;
+    }
+    const double k2 = b.kappa2, kap = std::sqrt(k2);
+    const double cl = std::sqrt(cc[0] * cc[0] + cc[1] * cc[1] + cc[2] * cc[2]);
+    const double a2 = b.r * b.r * (1.0 + 2e-6);
+    const double L = 2.2e-6 * kap * (g.S_max + cl) + 2e-6 * k2 * std::sqrt(D2);
+    double reg = std::sqrt(a2 + 3e-6 * k2 * D2) + L;
+    if (type == 2u) {
+        // triangle: the guard |(c - start) x d|^2 <= R^2 |d|^2 is computed with an error of ~10 u R |c - start| |d|^2
+        // (cross-product form), i.e. it can pass lines up to R + ~5 u D away; + the rounding of c - start itself
+        reg = b.r * (1.0 + 1e-6) + 2e-6 * std::sqrt(D2) + 1e-6 * (g.S_max + cl);
+    }
+    out.rg = reg * (1.0 + 1e-6) + 0.01 * g.cell;  // + slack for the kernels' fp32 cell arithmetic
+    if (type == 2u) out.rpre = -(reg * (1.0 + 1e-6) + 1e-6 * cl);  // no distance term: its guard has none to speak of
+    else if (k2 <= kKappa2Tight && k2 <= K2_limit) { out.rpre = std::sqrt(a2) + 2.0 * L + 1e-6 * cl; out.tight = true; }
+    else out.rpre = -(reg * (1.0 + 1e-6) + 1e-6 * cl);
+    if (!std::isfinite(out.rg) || out.rg > 0.25 * g.diag) { out.rg = inf; out.always = true; }  // as big as the scene: test it for every ray
+    return out;
+}
+
+float pretest_as_stored(double rpre) {
+    return rpre >= 0 ? std::nextafter((float)rpre, std::numeric_limits<float>::infinity())
+                     : std::nextafter((float)rpre, -std::numeric_limits<float>::infinity());
+}
+
 // Conservative uniform grid for the large-scene trace kernels (rt_grid.h explains the margins).
 int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
     SetupTrace lap("grid");
@@ -514,49 +557,26 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
         }
     }
     lap("bounds + cell size");
-    // Radii (rt_grid.h derives the bound): with u = 2^-24, a ray that starts `dist` from the centre c of an object
-    // with bounding radius R and condition number kappa can only be accepted by the reference's fp32 test if its
-    // line passes c within
-    //     sqrt(R^2 (1 + 8u) + 14 u kappa^2 dist^2) + 10.4 u kappa (|start| + |c|) + 9 u kappa^2 dist.
-    // Everything below uses u_eff = 2e-7 (3.3 u):  a = R sqrt(1 + 2e-6),  L = 2.2e-6 kappa (S + |c|) + 2e-6 kappa^2 D,
-    //   registration radius  sqrt(a^2 + 3e-6 kappa^2 D^2) + L   (D = farthest possible ray origin, S = largest |origin|)
-    //   pre-test radius      a + 2L + 1e-6 |c|, used with the ACTUAL distance: r^2 = w^2 + alpha dist^2, alpha = 6e-6 K^2
-    // (K^2 = largest kappa^2 among the objects that use the distance-dependent form, at most 4; more anisotropic
-    // objects carry their full registration radius instead, flagged by a negative w).
-    double S_max = 0;
+    // Radii: grid_radii, above, per object
+    GridRadii gr;
+    for (int a = 0; a < 3; ++a) { gr.lo[a] = lo[a]; gr.hi[a] = hi[a]; }
+    gr.cell = cell;
+    gr.diag = diag;
+    gr.S_max = 0;
     for (int k = 0; k < 8; ++k) {
         const double px = (k & 1) ? hi[0] : lo[0], py = (k & 2) ? hi[1] : lo[1], pz = (k & 4) ? hi[2] : lo[2];
-        S_max = std::max(S_max, std::sqrt(px * px + py * py + pz * pz));
+        gr.S_max = std::max(gr.S_max, std::sqrt(px * px + py * py + pz * pz));
     }
-    constexpr double kKappa2Tight = 4.0;
+    const double S_max = gr.S_max;
     double K2 = 1.0;
     std::vector<double> rg(n), rpre(n);
     std::vector<uint32_t> always;
     for (uint32_t i = 0; i < n; ++i) {
-        rpre[i] = 0;
-        if (sph[i].r == -inf) { rg[i] = -1.0; continue; }
-        if (!std::isfinite(sph[i].r)) { rg[i] = inf; always.push_back(i); continue; }
-        double D2 = 0;
-        const double cc[3] = {sph[i].x, sph[i].y, sph[i].z};
-        for (int a = 0; a < 3; ++a) {
-            const double d = std::max(std::fabs(cc[a] - lo[a]), std::fabs(hi[a] - cc[a]));
-            D2 += d * d;
-        }
-        const double k2 = sph[i].kappa2, kap = std::sqrt(k2);
-        const double cl = std::sqrt(cc[0] * cc[0] + cc[1] * cc[1] + cc[2] * cc[2]);
-        const double a2 = sph[i].r * sph[i].r * (1.0 + 2e-6);
-        const double L = 2.2e-6 * kap * (S_max + cl) + 2e-6 * k2 * std::sqrt(D2);
-        double reg = std::sqrt(a2 + 3e-6 * k2 * D2) + L;
-        if (objs[i].type == 2u) {
-            // triangle: the guard |(c - start) x d|^2 <= R^2 |d|^2 is computed with an error of ~10 u R |c - start| |d|^2
-            // (cross-product form), i.e. it can pass lines up to R + ~5 u D away; + the rounding of c - start itself
-            reg = sph[i].r * (1.0 + 1e-6) + 2e-6 * std::sqrt(D2) + 1e-6 * (S_max + cl);
-        }
-        rg[i] = reg * (1.0 + 1e-6) + 0.01 * cell;  // + slack for the kernels' fp32 cell arithmetic
-        if (objs[i].type == 2u) rpre[i] = -(reg * (1.0 + 1e-6) + 1e-6 * cl);  // no distance term: its guard has none to speak of
-        else if (k2 <= kKappa2Tight) { rpre[i] = std::sqrt(a2) + 2.0 * L + 1e-6 * cl; K2 = std::max(K2, k2); }
-        else rpre[i] = -(reg * (1.0 + 1e-6) + 1e-6 * cl);
-        if (!std::isfinite(rg[i]) || rg[i] > 0.25 * diag) { rg[i] = inf; always.push_back(i); }  // as big as the scene: test it for every ray
+        const ObjectRadii r = grid_radii(gr, sph[i], objs[i].type, inf);
+        rg[i] = r.rg;
+        rpre[i] = r.rpre;
+        if (r.tight) K2 = std::max(K2, sph[i].kappa2);
+        if (r.always) always.push_back(i);
     }
     // many scene-sized objects: a grid would not pay, stay with the brute-force stream - unless the scene holds
     // triangles, which only this path can trace (then every ray simply tests the whole always-list)
@@ -578,6 +598,12 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
     // the box D and S_max above were taken over: a later ray buffer (rt_set_rays_device) whose origins lie inside it is covered
     // by the radii as built
     for (int a = 0; a < 3; ++a) { c->grid_box_lo[a] = lo[a]; c->grid_box_hi[a] = hi[a]; }
+    c->grid_cell = cell;
+    c->grid_diag = diag;
+    c->grid_s_max = S_max;
+    c->grid_k2 = K2;
+    c->h_always = always;
+    c->n_unbounded = (uint32_t)always.size();
     const float cellf = (float)cell;
     const float lof[3] = {(float)glo[0], (float)glo[1], (float)glo[2]};
     // cell range of a sphere's box, computed with the SAME float origin / cell edge the kernels use (rg already
@@ -647,13 +673,12 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
         } else {
             lap("cell lists: fill");
             RT_HIP(c, hipMalloc((void**)&c->d_grid_entries, sizeof(uint32_t) * (total + 1)));
-            RT_HIP(c, hipMalloc((void**)&c->d_grid_always, sizeof(uint32_t) * (always.size() + 1)));
+            // (room for the dynamic objects of rt_set_transforms behind the create-time entries; a mesh may bring more of its own)
+            RT_HIP(c, hipMalloc((void**)&c->d_grid_always, sizeof(uint32_t) * (std::max<size_t>(always.size(), kMaxAlways) + 1)));
             {   // per entry: the sphere the object was registered with (rounded outwards), for the kernels' pre-test
                 // pre-test radius per object, rounded away from zero; negative = "already holds the worst-case distance term"
                 c->h_grid_pre.resize(n);
-                for (uint32_t i = 0; i < n; ++i)
-                    c->h_grid_pre[i] = rpre[i] >= 0 ? std::nextafter((float)rpre[i], std::numeric_limits<float>::infinity())
-                                                    : std::nextafter((float)rpre[i], -std::numeric_limits<float>::infinity());
+                for (uint32_t i = 0; i < n; ++i) c->h_grid_pre[i] = pretest_as_stored(rpre[i]);
                 std::vector<float4> es(total);
                 parallel_for(total, 1u << 16, [&](size_t k0, size_t k1) {
                     for (size_t k = k0; k < k1; ++k) {

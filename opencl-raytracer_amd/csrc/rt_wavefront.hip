@@ -1666,8 +1666,9 @@ __device__ __forceinline__ void finish_reflect(Ctx& c, int am, float abr, float 
 
 // Is the shadow ray towards the LAST light (the light of the light tiles) blocked? One thread, the whole list: the same
 // tile, the same cut, the same pre-test and the same exact tests as the light-tile mode of the persistent walk
-// (trace_segment, in_lt) - an any-hit answer does not depend on the order or on who asks. (Light tiles are only built for
-// scenes without always-tested objects: build_light_tiles.)
+// (trace_segment, in_lt) - an any-hit answer does not depend on the order or on who asks. (The tile's list is all that is consulted,
+// so light tiles are only built while every object that can be hit has a finite registration sphere and is therefore in the lists:
+// build_light_tiles. rt_set_transforms' dynamic objects are on the always-list AND in the lists, with the spheres of where they are.)
 template <int AM>
 __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, uint32_t& tests) {
     ray.sw = 1.0f; ray.dw = 0.0f;  // as the walk's hand-out (rt_create checks the preconditions of a grid-able frame)

@@ -241,6 +241,13 @@ class ShardedHIPRaytracer:
         torch.cuda.synchronize(self.device)
         self.rt.set_materials(materials, first)
 
+    def set_transforms(self, transforms, first: int = 0):
+        """Move objects first .. first + n - 1 of this rank's context (HIPRaytracer.set_transforms; every rank makes the same call):
+        each rank patches its own copy of the object records and rebuilds its own light tiles, and keeps rendering its own tiles."""
+        self.gatherer.drain()   # (a pipelined frame still reads the records in use)
+        torch.cuda.synchronize(self.device)
+        self.rt.set_transforms(transforms, first)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, MATERIAL_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of
+from .records import LIGHT_DTYPE, MATERIAL_DTYPE, OBJECT_DTYPE, RAY_DTYPE, TRANSFORM_DTYPE, materials_of, transforms_of
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libhip_raytracer.so"
 
@@ -43,6 +43,7 @@ EXPORTS = [
     "rt_get_tiles_info", "rt_read_tiles", "rt_read_grid_spheres",
     "rt_set_lights", "rt_set_lights_multi", "rt_get_light_tiles_info", "rt_read_light_tiles", "rt_read_grid_pretest",
     "rt_set_materials", "rt_set_materials_device", "rt_set_materials_multi", "rt_read_materials",
+    "rt_set_transforms", "rt_set_transforms_multi", "rt_read_transforms", "rt_get_geometry_info",
 ]
 
 
@@ -123,6 +124,20 @@ class RTLightTilesInfo(ctypes.Structure):
                 out[n] = np.float32(v)
             else:
                 out[n] = int(v)
+        return out
+
+
+class RTGeometryInfo(ctypes.Structure):
+    _fields_ = [
+        ("grid_built", ctypes.c_uint32), ("n_unbounded", ctypes.c_uint32), ("n_dynamic", ctypes.c_uint32),
+        ("dynamic_capacity", ctypes.c_uint32), ("dynamic_ids", ctypes.c_uint32 * 64), ("light_tiles_rebuilt", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32), ("patch_device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        out = {n: int(getattr(self, n)) for n in ("grid_built", "n_unbounded", "n_dynamic", "dynamic_capacity", "light_tiles_rebuilt")}
+        out["dynamic_ids"] = [int(v) for v in self.dynamic_ids[:out["n_dynamic"]]]
+        out["patch_device_ms"] = float(self.patch_device_ms)
         return out
 
 
@@ -259,6 +274,15 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_set_materials_multi.argtypes = [vp, vp, u32, u32]
         lib.rt_read_materials.restype = i32
         lib.rt_read_materials.argtypes = [vp, vp, u32, u32]
+    if hasattr(lib, "rt_set_transforms"):  # (the same: a build from before replaceable transforms)
+        lib.rt_set_transforms.restype = i32
+        lib.rt_set_transforms.argtypes = [vp, vp, u32, u32]
+        lib.rt_set_transforms_multi.restype = i32
+        lib.rt_set_transforms_multi.argtypes = [vp, vp, u32, u32]
+        lib.rt_read_transforms.restype = i32
+        lib.rt_read_transforms.argtypes = [vp, vp, u32, u32]
+        lib.rt_get_geometry_info.restype = i32
+        lib.rt_get_geometry_info.argtypes = [vp, ctypes.POINTER(RTGeometryInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -629,6 +653,32 @@ class HIPRaytracer:
         self._check(self._lib.rt_read_materials(self._ctx, _ptr(out), first, count))
         return out
 
+    # -- replaceable transforms (hip_raytracer.h: every copy of mv / mvInverse patched on the device; grid contexts: the dynamic set) --
+    def set_transforms(self, transforms, first: int = 0):
+        """Move objects first .. first + n - 1 of a live context (rt_set_transforms): the next frame is the one a fresh context
+        created with records.with_transforms(objects, transforms, first) renders, bit for bit. `transforms` is a numpy
+        TRANSFORM_DTYPE array, or an OBJECT_DTYPE array whose mv and mvInverse are taken. On a context with a grid the objects
+        become dynamic (geometry_info) - at most 64 of them; RTError with code RT_ERR_STATE beyond, RT_ERR_INVALID_ARGUMENT for a
+        transform the context cannot take (the header lists them). A refused call has changed nothing."""
+        xf = transforms_of(transforms)
+        self._check(self._lib.rt_set_transforms(self._ctx, _ptr(xf) if xf.shape[0] else None, int(first), int(xf.shape[0])))
+
+    def read_transforms(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """rt_read_transforms: the TRANSFORM_DTYPE records of objects first .. first + count - 1 (count None: up to the last
+        object), reassembled from the device records; RTError if two copies of a word disagree."""
+        first = int(first)
+        count = self._n_objs - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=TRANSFORM_DTYPE)
+        self._check(self._lib.rt_read_transforms(self._ctx, _ptr(out), first, count))
+        return out
+
+    def geometry_info(self) -> dict:
+        """rt_get_geometry_info: grid_built, n_unbounded, n_dynamic, dynamic_capacity, dynamic_ids (a list of n_dynamic object
+        indices), light_tiles_rebuilt and patch_device_ms of the last accepted set_transforms."""
+        info = RTGeometryInfo()
+        self._check(self._lib.rt_get_geometry_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -760,6 +810,12 @@ class MultiHIPRaytracer:
         `materials` is a numpy MATERIAL_DTYPE array or an OBJECT_DTYPE array whose material fields are taken."""
         mats = materials_of(materials)
         self._check(self._lib.rt_set_materials_multi(self._m, _ptr(mats), int(first), int(mats.shape[0])))
+
+    def set_transforms(self, transforms, first: int = 0):
+        """Move objects first .. first + n - 1 on every shard (rt_set_transforms_multi): all shards or none. `transforms` is a
+        numpy TRANSFORM_DTYPE array or an OBJECT_DTYPE array whose mv and mvInverse are taken."""
+        xf = transforms_of(transforms)
+        self._check(self._lib.rt_set_transforms_multi(self._m, _ptr(xf) if xf.shape[0] else None, int(first), int(xf.shape[0])))
 
     def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)):
         """Turn or move every shard's camera (rt_set_pose_multi): all shards or none; each generates on its own device."""

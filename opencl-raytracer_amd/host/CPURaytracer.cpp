@@ -293,6 +293,14 @@ void render_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, 
     }
 }
 
+// what the kernels read of an object's two matrices: the surface's copies, and rows x, y, z of mvInverse for the object loop
+void set_transform(CPURaytracer::Surface& d, CPURaytracer::Instance& h, const rtm::mat4& mv, const rtm::mat4& inv) {
+    std::memcpy(d.inv, inv.data(), sizeof(d.inv));
+    std::memcpy(d.mv, mv.data(), sizeof(d.mv));
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) h.rows[r][c] = d.inv[4 * c + r];
+}
+
 void set_material(CPURaytracer::Surface& d, const Material& m) {  // what the kernels read of a material
     d.ambient[0] = m.ambient.x; d.ambient[1] = m.ambient.y; d.ambient[2] = m.ambient.z;
     d.diffuse[0] = m.diffuse.x; d.diffuse[1] = m.diffuse.y; d.diffuse[2] = m.diffuse.z;
@@ -312,12 +320,9 @@ CPURaytracer::CPURaytracer(const std::vector<ObjectData>& objects_, const std::v
     for (size_t i = 0; i < objects.size(); ++i) {  // what the reference's ctor does for the device (OpenCLRaytracer.cpp:16-24)
         const ObjectData& o = objects[i];
         Surface& d = surfaces[i];
-        std::memcpy(d.inv, o.mvInverse.data(), sizeof(d.inv));
-        std::memcpy(d.mv, o.mv.data(), sizeof(d.mv));
-        set_material(d, o.mat);
         Instance& h = instances[i];
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c) h.rows[r][c] = d.inv[4 * c + r];
+        set_transform(d, h, o.mv, o.mvInverse);
+        set_material(d, o.mat);
         h.type = static_cast<int>(o.type);
     }
     pixels.resize(rays.size());
@@ -350,6 +355,11 @@ void CPURaytracer::SetLights(const std::vector<Light>& lights_) {
 void CPURaytracer::SetMaterials(uint32_t first, const std::vector<Material>& materials) {
     if ((uint64_t)first + materials.size() > surfaces.size()) throw std::invalid_argument("SetMaterials: first + count exceeds the object count");
     for (size_t i = 0; i < materials.size(); ++i) set_material(surfaces[first + i], materials[i]);
+}
+
+void CPURaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& transforms) {
+    if ((uint64_t)first + transforms.size() > surfaces.size()) throw std::invalid_argument("SetTransforms: first + count exceeds the object count");
+    for (size_t i = 0; i < transforms.size(); ++i) set_transform(surfaces[first + i], instances[first + i], transforms[i].mv, transforms[i].mvInverse);
 }
 
 void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]) {

@@ -55,6 +55,10 @@ public:
     // `materials` instead of the constructor's; geometry stays. std::invalid_argument for a range beyond the objects.
     void SetMaterials(uint32_t first, const std::vector<Material>& materials);
 
+    // Replaceable transforms, the same option as HIPRaytracer's: the next Render() has objects first .. first + n - 1 where these
+    // mv / mvInverse put them; materials and type stay. std::invalid_argument for a range beyond the objects.
+    void SetTransforms(uint32_t first, const std::vector<Transform>& transforms);
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

@@ -147,6 +147,26 @@ void HIPRaytracer::SetMaterials(uint32_t first, const std::vector<Material>& mat
     if (rt_set_materials(ctx, ms.data(), first, (uint32_t)ms.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetMaterials: ") + rt_last_error(ctx));
 }
 
+void HIPRaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& transforms) {
+    std::vector<rt_transform> ts(transforms.size());
+    for (size_t i = 0; i < transforms.size(); ++i) {
+        std::memcpy(ts[i].mv, transforms[i].mv.data(), sizeof(ts[i].mv));
+        std::memcpy(ts[i].mvInverse, transforms[i].mvInverse.data(), sizeof(ts[i].mvInverse));
+    }
+    if (multi) {
+        if (rt_set_transforms_multi(multi, ts.data(), first, (uint32_t)ts.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetTransforms: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_transforms(ctx, ts.data(), first, (uint32_t)ts.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetTransforms: ") + rt_last_error(ctx));
+}
+
+rt_geometry_info_t HIPRaytracer::GeometryInfo() {
+    rt_geometry_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_geometry_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::GeometryInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_light_tiles_info_t HIPRaytracer::LightTilesInfo() {
     rt_light_tiles_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

@@ -75,6 +75,14 @@ public:
     // std::runtime_error with the library's message for what it refuses (a range beyond the objects).
     void SetMaterials(uint32_t first, const std::vector<Material>& materials);
 
+    // Replaceable transforms (hip_raytracer.h, "replaceable transforms"): the next Render() has objects first .. first + n - 1
+    // where these mv / mvInverse put them; materials and type stay. The records are patched on the GPU(s); on a scene large
+    // enough for the grid the objects become dynamic (at most 64 of them, GeometryInfo()). Synchronous; the several-GPU object
+    // moves them on every shard, all or none. Throws std::runtime_error with the library's message for what it refuses.
+    void SetTransforms(uint32_t first, const std::vector<Transform>& transforms);
+    // rt_get_geometry_info: the dynamic set and what the last SetTransforms did. The several-GPU object reports its first shard's.
+    rt_geometry_info_t GeometryInfo();
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

@@ -192,3 +192,12 @@ public:
     rtm::mat4 mv, mvInverse, mvInverseTranspose;
     PrimativeType type;
 };
+
+// The two matrices of an ObjectData that the kernels read, what SetTransforms replaces (rt_records.h: rt_transform). The caller
+// supplies both, as it does through ObjectData; `Transform(mv)` takes the inverse the way ObjectData's constructor does.
+struct Transform {
+    Transform() : mv(1.f), mvInverse(1.f) {}
+    explicit Transform(const rtm::mat4& mv_) : mv(mv_), mvInverse(rtm::inverse(mv_)) {}
+    Transform(const rtm::mat4& mv_, const rtm::mat4& inv_) : mv(mv_), mvInverse(inv_) {}
+    rtm::mat4 mv, mvInverse;
+};

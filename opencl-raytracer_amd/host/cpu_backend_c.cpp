@@ -17,6 +17,8 @@ struct Pose { uint32_t width, height; float z; const float* m; const float* orig
 thread_local const Pose* g_pose = nullptr;        // cpu_rt_render_set_pose: what SetPose gets before Render()
 struct Materials { const rt_material* m; uint32_t first, count; };
 thread_local const Materials* g_materials = nullptr;  // cpu_rt_render_set_materials: what SetMaterials gets before Render()
+struct Transforms { const rt_transform* t; uint32_t first, count; };
+thread_local const Transforms* g_transforms = nullptr;  // cpu_rt_render_set_transforms: what SetTransforms gets before Render()
 
 Material host_material(const rt_material& d) {
     Material m;
@@ -107,6 +109,14 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
         for (uint32_t i = 0; i < g_materials->count; ++i) ms.push_back(host_material(g_materials->m[i]));
         try { backend->SetMaterials(g_materials->first, ms); } catch (const std::exception&) { return -1; }
     }
+    if (g_transforms) {
+        std::vector<Transform> ts(g_transforms->count);
+        for (uint32_t i = 0; i < g_transforms->count; ++i) {
+            std::memcpy(ts[i].mv.data(), g_transforms->t[i].mv, sizeof(g_transforms->t[i].mv));
+            std::memcpy(ts[i].mvInverse.data(), g_transforms->t[i].mvInverse, sizeof(g_transforms->t[i].mvInverse));
+        }
+        try { backend->SetTransforms(g_transforms->first, ts); } catch (const std::exception&) { return -1; }
+    }
     const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
     const auto t0 = std::chrono::steady_clock::now();
@@ -171,6 +181,24 @@ int cpu_rt_render_set_materials(int kernel, uint32_t max_bounces, const void* ob
     g_materials = nullptr;
     g_new_rays = nullptr;
     g_pose = nullptr;
+    return rc;
+}
+
+// CPURaytracer::SetTransforms through the C entry: the backend is constructed with `objs_` and renders after
+// SetTransforms(t_first, transforms_[0 .. t_count)) - rt_transform records. The arguments behind them are
+// cpu_rt_render_set_materials' (materials_ NULL with count 0: none), so that the options combine. Same outputs and return value
+// as cpu_rt_render; -1 also for a range beyond the objects.
+int cpu_rt_render_set_transforms(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                                 const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                                 uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, const void* transforms_, uint32_t t_first,
+                                 uint32_t t_count, const void* materials_, uint32_t first, uint32_t count, const void* new_rays_, uint32_t width,
+                                 uint32_t height, float z, const float* m, const float* origin) {
+    if (!transforms_ && t_count) return -1;
+    const Transforms ts{static_cast<const rt_transform*>(transforms_), t_first, t_count};
+    g_transforms = &ts;
+    const int rc = cpu_rt_render_set_materials(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced, hit_pixels,
+                                               seconds, threads_used, materials_, first, count, new_rays_, width, height, z, m, origin);
+    g_transforms = nullptr;
     return rc;
 }
 

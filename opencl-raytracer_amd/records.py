@@ -38,7 +38,10 @@ MATERIAL_DTYPE = np.dtype([
     ("ambient", "<f4", 4), ("diffuse", "<f4", 4), ("specular", "<f4", 4),
     ("absorption", "<f4"), ("reflection", "<f4"), ("transparency", "<f4"), ("shininess", "<f4"),
 ])
+# rt_transform (rt_records.h): the two matrices of an ObjectData that a kernel reads, what rt_set_transforms replaces
+TRANSFORM_DTYPE = np.dtype([("mv", "<f4", 16), ("mvInverse", "<f4", 16)])
 
+assert TRANSFORM_DTYPE.itemsize == 128
 assert OBJECT_DTYPE.itemsize == 320 and LIGHT_DTYPE.itemsize == 64 and RAY_DTYPE.itemsize == 32 and MATERIAL_DTYPE.itemsize == 64
 
 SPHERE, BOX = 0, 1  # ObjectData::PrimativeType (ObjectData.hpp:9-12)
@@ -281,6 +284,35 @@ def with_materials(objs, materials, first: int = 0) -> np.ndarray:
         raise ValueError("first + len(materials) exceeds the object count")
     for name in MATERIAL_FIELDS:
         out[name][first:first + mats.shape[0]] = mats[name]
+    return out
+
+
+def transforms_of(objs) -> np.ndarray:
+    """The TRANSFORM_DTYPE array an object array carries (a copy): mv and mvInverse per record. A TRANSFORM_DTYPE array passes."""
+    objs = np.asarray(objs)
+    if objs.dtype == TRANSFORM_DTYPE:
+        return np.ascontiguousarray(objs).copy()
+    objs = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE)
+    out = np.zeros(objs.shape[0], dtype=TRANSFORM_DTYPE)
+    out["mv"] = objs["mv"]
+    out["mvInverse"] = objs["mvInverse"]
+    return out
+
+
+def with_transforms(objs, transforms, first: int = 0) -> np.ndarray:
+    """The object array a fresh context is created with for the frame rt_set_transforms(transforms, first) leaves a live one
+    with - its executable definition: a copy of `objs` whose records first .. first + len(transforms) - 1 carry the mv and
+    mvInverse of `transforms` (a TRANSFORM_DTYPE array, or an OBJECT_DTYPE array whose matrices are taken), bit for bit, and as
+    mvInverseTranspose the transpose of that mvInverse (which no kernel reads); materials, type and the padding are untouched."""
+    out = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE).copy()
+    xf = transforms_of(transforms)
+    first = int(first)
+    n = xf.shape[0]
+    if first < 0 or first + n > out.shape[0]:
+        raise ValueError("first + len(transforms) exceeds the object count")
+    out["mv"][first:first + n] = xf["mv"]
+    out["mvInverse"][first:first + n] = xf["mvInverse"]
+    out["mvInverseTranspose"][first:first + n] = xf["mvInverse"].reshape(n, 4, 4).transpose(0, 2, 1).reshape(n, 16)
     return out
 
 
