@@ -67,7 +67,10 @@ extern "C" {
  *      Later addition, same version: replaceable materials - rt_set_materials, rt_set_materials_device, rt_set_materials_multi,
  *      rt_read_materials. Additions only; a caller detects support by the symbol (dlsym of rt_set_materials).
  *      Later addition, same version: replaceable transforms - rt_set_transforms, rt_set_transforms_multi, rt_read_transforms,
- *      rt_get_geometry_info. Additions only; detect by dlsym of rt_set_transforms. */
+ *      rt_get_geometry_info. Additions only; detect by dlsym of rt_set_transforms.
+ *      Later addition, same version: poses outside the grid's box keep the grid - RT_TILES_REFUSED_FAR, rt_tiles_info_t::source may
+ *      read 3, rt_rays_info_t::reserved became primary_outside_box, rt_read_pose_spheres, rt_read_object_bounds,
+ *      rt_get_grid_constants. Additions only; detect by dlsym of rt_read_pose_spheres. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -361,11 +364,15 @@ typedef struct rt_rays_info_t {
     uint32_t grid_built;            /* rt_create built a conservative grid                                                     */
     uint32_t grid_in_use;           /* ... and the next frame's rays are served by it (0 also while `literal`)                 */
     uint32_t literal;               /* the next frame renders with the literal loops                                           */
-    uint32_t reserved;
+    uint32_t primary_outside_box;   /* the next frame's primary rays start OUTSIDE box_lo .. box_hi (a pose's) and are served by its screen
+                                       tiles while the grid serves every later ray; grid_in_use then reads 1 ("posed cameras")  */
 } rt_rays_info_t;
 int rt_set_rays_device(rt_context* ctx, const void* d_rays, uint64_t n_rays, void* hip_stream);
 int rt_set_rays(rt_context* ctx, const void* rays, uint64_t n_rays);
-int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid for every context, also one that never called the setters */
+int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid for every context, also one that never called the setters.
+                                                                         After a pose outside the grid's box it builds that pose's screen tiles
+                                                                         first, as rt_get_tiles_info does: kernels on the context's stream, a
+                                                                         wait, possibly RT_ERR_HIP ("posed cameras", outside the box)          */
 
 /* ---- posed cameras -------------------------------------------------------------------------------------------------------------
  * A pinhole that turns or moves: the grid (width, height, z) of rt_set_camera seen through an fp32 3 x 3 matrix M (row-major,
@@ -386,7 +393,8 @@ int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid fo
  * call leaves the context exactly as it was. The verdict is the one the ray scan gives the same rays: dir_w_zero holds;
  * directions_in_domain is reduced over every direction's dd; starts_ok is isfinite((ox + oy) + oz); the origin box is the point.
  * A non-finite or degenerate M is no error: its directions leave the domain and the frame renders with the literal loops. An
- * origin outside box_lo .. box_hi renders by brute force, as for any ray buffer (no grid is rebuilt).
+ * origin outside box_lo .. box_hi keeps the grid when the pose's screen tiles are accepted (below: "outside the box"); otherwise it
+ * renders by brute force, as for any ray buffer. No grid is rebuilt either way.
  * Refused with RT_ERR_INVALID_ARGUMENT: a NULL m or origin; width * height != n_rays; for a scene with triangles a pose that needs
  * the literal loops or brute force; and, while the supersampling factor is > 1, what rt_set_camera is refused for (below).
  * rt_get_rays_info reports source 3; rt_stats_t::pinhole, width and height stay 0 as for any buffer. The RAYS of a posed frame are
@@ -397,6 +405,22 @@ int rt_get_rays_info(const rt_context* ctx, rt_rays_info_t* info);   /* valid fo
  * traced through the grid walk as before; RT_POSE_TILES=0 in the environment keeps every pose there (a measurement knob). A later
  * rt_set_camera or rt_set_rays* replaces the pose, and the other way round. Shards, rt_render's passes, aux buffers, 8-bit frames and rt_count_rays work as for a buffer; a
  * sharded context generates the whole frame's rays.
+ *
+ * Outside the box. A camera that orbits the scene or pulls back from it leaves box_lo .. box_hi at once. Only its PRIMARY rays start
+ * out there - every later ray starts on a surface, inside the box - and the tile lists need no grid: so such a pose gets registration
+ * spheres made for its own origin, on the device (csrc/rt_tiles.hip: pose_spheres; tiles.py: pose_registration_spheres - the grid's
+ * own expressions with the farthest origin and the largest |origin| taken over the box and the pose's origin), its table is built
+ * from them (rt_tiles_info_t::source 3), the primary round walks the lists and never the grid, and the grid, the block grid and the
+ * light tiles serve the rest as built. Accepted when the table is not refused and 3e-6 (|o| + far) <= 0.01 cell (far: the largest
+ * distance from the origin o to a corner of the box; cell: the fine grid's edge; else RT_TILES_REFUSED_FAR; DESIGN.md section 4.1 has
+ * the argument). rt_get_rays_info then reads grid_in_use = 1 and primary_outside_box = 1; both, like rt_get_tiles_info, build the
+ * table if the pose is new. (Both may therefore launch kernels on the context's stream, wait for them and return RT_ERR_HIP.) A frame
+ * of fewer than 16 tiles (128 x 64 pixels) of a scene of fewer than 512 objects is not served this way (RT_TILES_REFUSED_SMALL): it
+ * keeps the route it had before - the small-scene kernel - for callers and tests that rely on it; RT_POSE_OUTSIDE_MIN_TILES=0 in the
+ * environment serves such frames too (it is the faster route there as well: DESIGN.md section 6). A refused table of any kind - RT_POSE_TILES=0,
+ * width % 64 != 0, GLOBAL, FAR, SMALL, ... - reads RT_TILES_REFUSED_NO_GRID beside its own bit and leaves the frame where it was
+ * before this addition: the whole frame as RT_FLAG_NO_GRID renders it. Same pixels, bit for bit, on every route. rt_set_rays*
+ * buffers outside the box stay brute force (no common origin, no table), and scenes with triangles keep refusing such poses.
  *
  * Supersampling. The sample grid of a posed camera is defined, so a factor > 1 is open to it: the pose's (width, height, z) is the
  * SAMPLE grid, as rt_set_camera's is (camera.supersampled gives it for a picture's (W, H, z)); the context remembers the pose's
@@ -424,8 +448,8 @@ int rt_generate_rays_device(rt_context* ctx, uint32_t width, uint32_t height, fl
  * RT_ERR_INVALID_ARGUMENT / RT_ERR_STATE. rt_read_grid_spheres copies the registration spheres the tables are built from: 4
  * doubles per object (centre, radius; inf: tested by every ray, negative: never hit), n = the object count; RT_ERR_STATE for a
  * context without a grid. All three are accessors for tests and tools, as rt_get_rays_info is. */
-#define RT_TILES_REFUSED_NO_GRID 0x1u   /* the grid does not serve the rays in use (no grid, origin outside its box, literal loops,
-                                           small-scene path) or the rays are neither a camera's nor a pose's                      */
+#define RT_TILES_REFUSED_NO_GRID 0x1u   /* the grid does not serve the rays in use (no grid, literal loops, small-scene path, a buffer's
+                                           origins outside its box) or the rays are neither a camera's nor a pose's               */
 #define RT_TILES_REFUSED_Z       0x2u   /* z is not < 0                                                                          */
 #define RT_TILES_REFUSED_MATRIX  0x4u   /* the pose's matrix or origin is not finite, or the matrix is singular                  */
 #define RT_TILES_REFUSED_EPS     0x8u   /* eps >= |z| / 2 or pad > 1: the pose is too ill-conditioned for the table's margins    */
@@ -435,9 +459,12 @@ int rt_generate_rays_device(rt_context* ctx, uint32_t width, uint32_t height, fl
 #define RT_TILES_REFUSED_LIST    0x80u  /* a tile's list is longer than 1024 entries                                             */
 #define RT_TILES_REFUSED_TILES   0x100u /* more than 2^20 tiles                                                                  */
 #define RT_TILES_REFUSED_KNOB    0x200u /* RT_POSE_TILES=0                                                                       */
+#define RT_TILES_REFUSED_FAR     0x400u /* a pose outside the grid's box whose origin is too far: 3e-6 (|o| + far) > 0.01 cell         */
+#define RT_TILES_REFUSED_SMALL   0x800u /* a pose outside the grid's box, fewer than 512 objects and fewer than 16 tiles (128 x 64 pixels) */
 typedef struct rt_tiles_info_t {
     uint32_t enabled;               /* the next large-scene frame's primary round walks tile lists                             */
-    uint32_t source;                /* 0 none, 1 the fixed camera's (host), 2 the pose's (device)                              */
+    uint32_t source;                /* 0 none, 1 the fixed camera's (host), 2 the pose's (device), 3 a pose's outside the grid's box
+                                       (device, from spheres made for its origin: rt_read_pose_spheres)                        */
     uint32_t tiles_x, tiles_y;      /* tiles are 8 rows tall ...                                                               */
     uint32_t col_shift;             /* ... and 1 << col_shift pixels wide (3 or 6; a pose's: 6)                                */
     uint32_t n_global;              /* whole-screen objects, tested by every wave                                              */
@@ -451,6 +478,15 @@ typedef struct rt_tiles_info_t {
 int rt_get_tiles_info(const rt_context* ctx, rt_tiles_info_t* info);
 int rt_read_tiles(rt_context* ctx, uint32_t* tile_start, uint64_t n_start, uint32_t* entries, uint64_t n_entries);
 int rt_read_grid_spheres(const rt_context* ctx, double* spheres, uint64_t n);
+/* Accessors for tests and tools, next to rt_read_grid_spheres. rt_read_pose_spheres copies the per-pose registration spheres the
+ * current table was built from (4 doubles per object, as above; a sphere above a quarter of the box's diagonal is a whole-screen
+ * entry); RT_ERR_STATE when the current table was not built from such spheres (source != 3). rt_read_object_bounds copies what they
+ * are made from: 6 doubles per object - centre, radius, kappa^2 (squared condition number), type - kept from rt_create and replaced by
+ * rt_set_transforms; RT_ERR_STATE for a context without a grid or with triangles. rt_get_grid_constants: the fine grid's cell edge,
+ * the diagonal of box_lo .. box_hi, the largest |origin| that box allows, and the pre-test's K^2; RT_ERR_STATE without a grid. */
+int rt_read_pose_spheres(rt_context* ctx, double* spheres, uint64_t n);
+int rt_read_object_bounds(const rt_context* ctx, double* bounds, uint64_t n);
+int rt_get_grid_constants(const rt_context* ctx, double constants[4]);
 
 /* ---- replaceable lights --------------------------------------------------------------------------------------------------------
  * The last input of a frame that was frozen at rt_create: the lights. rt_set_lights replaces them on a live context - a viewer that

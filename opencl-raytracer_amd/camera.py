@@ -83,3 +83,15 @@ def grid_rays(width: int, height: int, z: float) -> np.ndarray:
     rays["direction"][..., 1] = y[:, None]
     rays["direction"][..., 2] = F(z)
     return rays.reshape(-1)
+
+
+def look_at(origin, target, up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """The fp32 3 x 3 matrix M of a pose (rt_set_pose, rays.posed_rays) at `origin` that looks at `target`: the grid's -z axis maps
+    onto the viewing direction, +x to the right, +y up. `up` must not be parallel to the viewing direction."""
+    o, t, u = (np.asarray(v, dtype=np.float64) for v in (origin, target, up))
+    f = (t - o) / np.linalg.norm(t - o)
+    r = np.cross(f, u)
+    if np.linalg.norm(r) < 1e-9:   # looking straight up or down: any horizontal axis serves as "right"
+        r = np.cross(f, np.array([1.0, 0.0, 0.0]))
+    r = r / np.linalg.norm(r)
+    return np.column_stack([r, np.cross(r, f), -f]).astype(np.float32)

@@ -226,6 +226,10 @@ static int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count)
         RT_HIP(c, hipStreamSynchronize(stream));  // `rects` is pageable host memory
         c->rects_dirty = false;
     }
+    {   // a pose outside the grid's box: its table decides whether the grid serves the frame, so it is built before the path is chosen
+        const int rc = settle_outside_pose(c, stream);
+        if (rc) return rc;
+    }
     c->last_wavefront = use_wavefront(c);
     c->last_rounds = 0;
     if (c->last_wavefront) {  // one-time host-side set-up (buffers, per-camera screen tiles) stays outside the timed region
@@ -234,12 +238,6 @@ static int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count)
         int rc = ensure_wavefront(c);
         if (rc) return rc;
         if (!had_buffers) c->setup.buffers_ms += sw.lap_ms();
-        {   // per frame: the grid's tables, or - for a ray buffer they were not built for - none, which is RT_FLAG_NO_GRID's frame
-            const bool on = grid_in_use(c);
-            c->wf.grid = on ? c->grid : rt::GridDesc{};
-            c->wf.light_tiles = on ? c->light_tiles : rt::LightTiles{};
-            c->wf.blocks = on ? c->blocks : rt::BlockGrid{};
-        }
         // a first-round wave is an 8 x 8 block of pixels (work-items in tile order) or 64 pixels of one row: the tile lists follow
         const uint32_t col_shift = p.wf_tile_order ? 3u : 6u;
         if (c->tiles_dirty || c->tiles_built_for != col_shift) {
@@ -248,6 +246,16 @@ static int do_launch(rt_context* c, void* d_out, hipStream_t stream, bool count)
             c->setup.screen_tiles_ms += sw.lap_ms();  // (wall: a posed build's device passes - rt_tiles_info_t::build_device_ms - are inside it)
         }
         c->wf.tiles = c->tiles;
+        {   // per frame: the grid's tables, or - for a ray buffer they were not built for - none, which is RT_FLAG_NO_GRID's frame
+            const bool on = grid_in_use(c);
+            c->wf.grid = on ? c->grid : rt::GridDesc{};
+            c->wf.light_tiles = on ? c->light_tiles : rt::LightTiles{};
+            c->wf.blocks = on ? c->blocks : rt::BlockGrid{};
+            // from outside the box the primary rays must never enter the grid walk: their table is there, or the frame is not rendered
+            c->wf.primary_outside = (on && !c->pinhole && c->rays_off_grid) ? 1u : 0u;
+            if (c->wf.primary_outside && !(c->tiles.enabled && c->tiles.posed && c->tiles.width && c->tiles.outside))
+                return fail(c, RT_ERR_STATE, "internal: a pose outside the grid's box without its screen tiles");
+        }
     }
     if (count) RT_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters), stream));
     const uint32_t slot = c->ev_count % kTimingSlots;
@@ -350,6 +358,8 @@ int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const 
     c->primary_w_one = v.starts_ok;
     c->rays_out_of_domain = !v.in_domain;
     c->rays_off_grid = !v.on_grid;
+    c->pose_outside = c->grid.enabled && v.starts_ok && !v.on_grid && !c->has_triangles;  // (its table decides: settle_outside_pose)
+    c->primary_outside = false;
     for (int a = 0; a < 3; ++a) c->origin_lo[a] = c->origin_hi[a] = v.origin[a];
     apply_ray_domain(c);
     c->rects_dirty = true;
@@ -663,6 +673,7 @@ int rt_set_camera(rt_context* c, uint32_t width, uint32_t height, float z) {
     c->camera_out_of_domain = out;
     c->pinhole = true;
     c->pose_w = c->pose_h = 0;
+    c->pose_outside = c->primary_outside = false;
     apply_ray_domain(c);
     c->width = width;
     c->height = height;
@@ -740,6 +751,7 @@ static int set_rays_from_device(rt_context* c, const void* d_src, uint64_t n_ray
     c->primary_w_one = starts_ok;
     c->rays_out_of_domain = !in_domain;
     c->rays_off_grid = !on_grid;
+    c->pose_outside = c->primary_outside = false;  // (a buffer has no common origin and no table: outside the box it stays brute force)
     for (int a = 0; a < 3; ++a) { c->origin_lo[a] = lo[a]; c->origin_hi[a] = hi[a]; }
     apply_ray_domain(c);
     c->rects_dirty = true;
@@ -790,8 +802,13 @@ int rt_generate_rays_device(rt_context* c, uint32_t width, uint32_t height, floa
     return e == hipSuccess ? RT_OK : fail_hip(c, e, "pose generation launch");
 }
 
-int rt_get_rays_info(const rt_context* c, rt_rays_info_t* info) {
-    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+int rt_get_rays_info(const rt_context* cc, rt_rays_info_t* info) {
+    if (!cc || !info) return RT_ERR_INVALID_ARGUMENT;
+    rt_context* c = const_cast<rt_context*>(cc);
+    {   // (a pose outside the box: whether the grid serves the next frame is its table's verdict - built now, as rt_get_tiles_info does)
+        const int rc = settle_outside_pose(c, c->stream);
+        if (rc) return rc;
+    }
     std::memset(info, 0, sizeof(*info));
     info->source = c->pinhole ? 1u : (c->have_rays ? (c->pose_w ? 3u : 2u) : 0u);
     const bool buffer = info->source >= 2u;
@@ -807,6 +824,7 @@ int rt_get_rays_info(const rt_context* c, rt_rays_info_t* info) {
     info->grid_built = c->grid.enabled ? 1u : 0u;
     info->grid_in_use = (grid_in_use(c) && !(c->flags & RT_FLAG_LITERAL)) ? 1u : 0u;
     info->literal = (c->flags & RT_FLAG_LITERAL) ? 1u : 0u;
+    info->primary_outside_box = (info->grid_in_use && !c->pinhole && c->rays_off_grid && c->primary_outside) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -821,9 +839,12 @@ static uint32_t primary_col_shift(const rt_context* c) {
 
 // the table is a cache of the context's rays: building it on demand changes nothing a caller can observe but the answer
 static int tiles_current(rt_context* c) {
+    if (const int rc = settle_outside_pose(c, c->stream)) return rc;
     if (!use_wavefront(c) || (!c->pinhole && !c->have_rays)) {
+        // (a pose outside the box whose table was refused, on a scene that takes the small-scene kernel without the grid: the reason stays)
+        const uint32_t why = (!c->pinhole && c->have_rays && c->pose_w && c->pose_outside && !c->tiles_dirty) ? c->tiles_info.refused : 0u;
         c->tiles_info = rt_tiles_info_t{};
-        c->tiles_info.refused = RT_TILES_REFUSED_NO_GRID;
+        c->tiles_info.refused = RT_TILES_REFUSED_NO_GRID | why;
         return RT_OK;
     }
     const uint32_t col_shift = primary_col_shift(c);
@@ -880,6 +901,38 @@ int rt_read_grid_spheres(const rt_context* c, double* spheres, uint64_t n) {
     return RT_OK;
 }
 
+int rt_read_pose_spheres(rt_context* c, double* spheres, uint64_t n) {
+    if (!c || !spheres) return RT_ERR_INVALID_ARGUMENT;
+    rt_tiles_info_t info;
+    const int rc = rt_get_tiles_info(c, &info);
+    if (rc) return rc;
+    if (!info.enabled || info.source != 3u || !c->d_outside_spheres)
+        return fail(c, RT_ERR_STATE, "rt_read_pose_spheres: the current screen tiles were not built from per-pose spheres (rt_tiles_info_t::source != 3)");
+    if (n != c->n_objs) return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_read_pose_spheres: n must be the object count");
+    RT_DEVICE(c);
+    RT_HIP(c, hipMemcpy(spheres, c->d_outside_spheres, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_read_object_bounds(const rt_context* c, double* bounds, uint64_t n) {
+    if (!c || !bounds) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->grid.enabled || c->h_obj_bound6.size() != rt::kBoundDoubles * (size_t)c->n_objs)
+        return fail(const_cast<rt_context*>(c), RT_ERR_STATE, "rt_read_object_bounds: the context keeps no bounds (no grid, or a scene with triangles)");
+    if (n != c->n_objs) return fail(const_cast<rt_context*>(c), RT_ERR_INVALID_ARGUMENT, "rt_read_object_bounds: n must be the object count");
+    std::memcpy(bounds, c->h_obj_bound6.data(), sizeof(double) * rt::kBoundDoubles * (size_t)n);
+    return RT_OK;
+}
+
+int rt_get_grid_constants(const rt_context* c, double constants[4]) {
+    if (!c || !constants) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->grid.enabled) return fail(const_cast<rt_context*>(c), RT_ERR_STATE, "rt_get_grid_constants: the context has no grid");
+    constants[0] = c->grid_cell;
+    constants[1] = c->grid_diag;
+    constants[2] = c->grid_s_max;
+    constants[3] = c->grid_k2;
+    return RT_OK;
+}
+
 // ---- replaceable lights (hip_raytracer.h) ----
 int rt_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
@@ -903,6 +956,7 @@ int rt_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
     // RT_FLAG_DEVICE_OPENCL's predicate on the lights, for these lights (rt_create: lights_need_literal)
     if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal) {
         c->lights_literal = lights_need_literal(c, L, n_lights);
+        if (c->base_flags != (c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u))) c->tiles_dirty = true;  // (a table's verdict depends on the literal flag)
         c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
         c->forced_literal = c->lights_literal;
         apply_ray_domain(c);
@@ -1457,6 +1511,8 @@ void rt_destroy(rt_context* c) {
     if (c->d_tile_start) (void)hipFree(c->d_tile_start);
     if (c->d_tile_entries) (void)hipFree(c->d_tile_entries);
     if (c->d_pose_spheres) (void)hipFree(c->d_pose_spheres);
+    if (c->d_obj_bound6) (void)hipFree(c->d_obj_bound6);
+    if (c->d_outside_spheres) (void)hipFree(c->d_outside_spheres);
     if (c->ptb.rect) (void)hipFree(c->ptb.rect);
     if (c->ptb.key) (void)hipFree(c->ptb.key);
     if (c->ptb.count) (void)hipFree(c->ptb.count);

@@ -76,6 +76,7 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream);
 static int build_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift) {
     c->tiles = rt::ScreenTiles{};
     c->tiles_dirty = false;
+    c->primary_outside = false;  // (only an accepted table of a pose outside the box sets it again: build_pose_tiles)
     if (!c->pinhole && c->have_rays && c->pose_w) return build_pose_tiles(c, stream);  // the rays in use come from a pose
     const uint32_t tile_w = 1u << col_shift;
     if (!c->grid.enabled || !c->pinhole || !(c->z < 0.f) || c->width % tile_w != 0 || c->h_grid_spheres.empty()) return RT_OK;
@@ -254,7 +255,22 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
     uint32_t refused = 0;
     if (const char* env = std::getenv("RT_POSE_TILES"))  // measurement knob: "0" keeps a posed frame on the grid walk
         if (env[0] == '0') refused |= RT_TILES_REFUSED_KNOB;
-    if (!grid_in_use(c) || (c->flags & RT_FLAG_LITERAL) || c->h_grid_spheres.size() != 4 * (size_t)n || n == 0) refused |= RT_TILES_REFUSED_NO_GRID;
+    // the grid serves the pose's rays - or, from outside its box, would serve every later ray if this table takes the primary ones
+    const bool outside = c->pose_outside && c->rays_off_grid;
+    const bool served = c->grid.enabled && (!c->rays_off_grid || (outside && !(c->flags & RT_FLAG_MONOLITHIC) &&
+                                                                  c->h_obj_bound6.size() == rt::kBoundDoubles * (size_t)n));
+    if (!served || (c->flags & RT_FLAG_LITERAL) || c->h_grid_spheres.size() != 4 * (size_t)n || n == 0) refused |= RT_TILES_REFUSED_NO_GRID;
+    const double origin_d[3] = {(double)g.origin[0], (double)g.origin[1], (double)g.origin[2]};
+    if (outside && served && !pose_within_reach(c, origin_d)) refused |= RT_TILES_REFUSED_FAR;
+    // Compatibility, not speed: a frame of fewer than kPoseOutsideMinTiles tiles of a scene of fewer than kWavefrontMinObjects objects
+    // keeps the route it had before poses outside the box were served - refused, the small-scene kernel - because the suite pins that
+    // route on a 64 x 48 frame of 300 objects. MEASURED: the tiles would be faster there too (0.26 against 0.58 ms); the
+    // knob RT_POSE_OUTSIDE_MIN_TILES=0 serves such frames. Larger scenes are served at every size.
+    {
+        uint64_t min_tiles = rt::kPoseOutsideMinTiles;
+        if (const char* env = std::getenv("RT_POSE_OUTSIDE_MIN_TILES")) min_tiles = (uint64_t)std::max(0, std::atoi(env));
+        if (outside && served && n < kWavefrontMinObjects && (uint64_t)ti.tiles_x * ti.tiles_y < min_tiles) refused |= RT_TILES_REFUSED_SMALL;
+    }
     if (W % 64u != 0 || W == 0) refused |= RT_TILES_REFUSED_WIDTH;
     if (!(g.z < 0.f)) refused |= RT_TILES_REFUSED_Z;
     const uint64_t n_tiles64 = (uint64_t)ti.tiles_x * ti.tiles_y;
@@ -316,7 +332,7 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
         }
     }
     if (refused) {
-        ti.refused = refused;
+        ti.refused = refused | (outside ? RT_TILES_REFUSED_NO_GRID : 0u);  // (refused from outside the box: the grid does not serve the frame)
         return RT_OK;
     }
     for (int k = 0; k < 3; ++k) a.o[k] = (double)g.origin[k];
@@ -329,6 +345,7 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
     a.tiles_y = ti.tiles_y;
     a.n_objs = n;
     a.budget = 256ull * n + 4096ull;
+    a.whole_r = outside ? 0.25 * c->grid_diag : std::numeric_limits<double>::infinity();
     const uint32_t n_tiles = (uint32_t)n_tiles64;
     rt::PoseTileBuffers& b = c->ptb;
     if (!c->d_pose_spheres) {  // once per context: the spheres the grid registered its objects with, as doubles
@@ -336,6 +353,14 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
         RT_HIP(c, hipMemcpy(c->d_pose_spheres, c->h_grid_spheres.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice));
     }
     b.spheres = c->d_pose_spheres;
+    if (outside) {  // spheres made for this pose's origin, from the objects' bounds (uploaded when first needed)
+        if (!c->d_obj_bound6) {
+            RT_HIP(c, hipMalloc((void**)&c->d_obj_bound6, sizeof(double) * rt::kBoundDoubles * (size_t)n));
+            RT_HIP(c, hipMemcpy(c->d_obj_bound6, c->h_obj_bound6.data(), sizeof(double) * rt::kBoundDoubles * (size_t)n, hipMemcpyHostToDevice));
+        }
+        if (!c->d_outside_spheres) RT_HIP(c, hipMalloc((void**)&c->d_outside_spheres, sizeof(double) * 4 * (size_t)n));
+        b.spheres = c->d_outside_spheres;
+    }
     if (!b.record) {  // (the spheres may be there already: the light tiles' builder shares them)
         RT_HIP(c, hipMalloc((void**)&b.rect, sizeof(uint4) * (size_t)n));
         RT_HIP(c, hipMalloc((void**)&b.key, sizeof(float) * (size_t)n));
@@ -354,7 +379,18 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
         c->ptb_tiles = n_tiles;
     }
     RT_HIP(c, hipEventRecord(c->ev_tiles[0], stream));
-    hipError_t e = rt::launch_pose_tile_count(a, b, stream);
+    hipError_t e = hipSuccess;
+    if (outside) {
+        rt::PoseSphereArgs sa;
+        std::memset(&sa, 0, sizeof(sa));
+        for (int k = 0; k < 3; ++k) { sa.lo[k] = c->grid_box_lo[k]; sa.hi[k] = c->grid_box_hi[k]; sa.o[k] = origin_d[k]; }
+        sa.cell = c->grid_cell;
+        sa.S_max = c->grid_s_max;
+        sa.n_objs = n;
+        e = rt::launch_pose_spheres(sa, c->d_obj_bound6, c->d_pose_spheres, c->d_outside_spheres, stream);
+        if (e != hipSuccess) return fail_hip(c, e, "pose spheres launch");
+    }
+    e = rt::launch_pose_tile_count(a, b, stream);
     if (e != hipSuccess) return fail_hip(c, e, "pose tile count launch");
     RT_HIP(c, hipEventRecord(c->ev_tiles[1], stream));
     RT_HIP(c, hipMemcpyAsync(c->h_pose_record, b.record, sizeof(rt::PoseTileRecord), hipMemcpyDeviceToHost, stream));
@@ -370,7 +406,7 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
     RT_HIP(c, hipEventElapsedTime(&ms, c->ev_tiles[0], c->ev_tiles[1]));
     ti.build_device_ms = (double)ms;
     if (refused) {
-        ti.refused = refused;
+        ti.refused = refused | (outside ? RT_TILES_REFUSED_NO_GRID : 0u);
         return RT_OK;
     }
     if ((unsigned long long)rec.total != rec.pairs) return fail(c, RT_ERR_STATE, "internal: the pose tiles' scan does not match their count");
@@ -397,10 +433,38 @@ static int build_pose_tiles(rt_context* c, hipStream_t stream) {
     c->tiles.n_global = rec.n_global;
     c->tiles.width = W;
     c->tiles.posed = 1u;
+    c->tiles.outside = outside ? 1u : 0u;
     c->tiles.enabled = 1u;
     ti.enabled = 1u;
-    ti.source = 2u;
+    ti.source = outside ? 3u : 2u;
+    c->primary_outside = outside;
     return RT_OK;
+}
+
+// The FAR condition of a pose outside the box: a primary hit point fl(o + t d) - where the secondary rays start - is off
+// its exact place by at most 3e-6 (|o| + far), far = the largest distance from o to a corner of the box (no hit lies farther); that
+// must stay within the 0.01 cell of slack every registration radius carries for the kernels' cell arithmetic.
+bool pose_within_reach(const rt_context* c, const double o[3]) {
+    double far2 = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double d = std::max(std::fabs(o[a] - c->grid_box_lo[a]), std::fabs(c->grid_box_hi[a] - o[a]));
+        far2 += d * d;
+    }
+    const double ol = std::sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]);
+    const double lhs = 3e-6 * (ol + std::sqrt(far2));
+    return std::isfinite(lhs) && lhs <= 0.01 * c->grid_cell;
+}
+
+// A pose outside the box renders through the grid only if its table is accepted, so the table is built BEFORE the path is chosen
+// (do_launch, rt_get_rays_info, rt_get_tiles_info): afterwards primary_outside - and with it grid_in_use - is settled for the frame.
+int settle_outside_pose(rt_context* c, hipStream_t stream) {
+    if (c->pinhole || !c->have_rays || !c->pose_w || !c->pose_outside || !c->rays_off_grid) return RT_OK;
+    if (!c->tiles_dirty && c->tiles_built_for == 6u) return RT_OK;
+    RT_DEVICE(c);
+    StopWatch sw;
+    const int rc = refresh_screen_tiles(c, stream, 6u);
+    if (rc == RT_OK) c->setup.screen_tiles_ms += sw.lap_ms();
+    return rc;
 }
 
 }  // namespace rt::host

@@ -11,6 +11,7 @@
 #include "rt_rays.h"
 #include "rt_raygen.h"
 #include "rt_tiles.h"
+#include "rt_grid_radii.h"
 #include "rt_light_tiles.h"
 #include "rt_materials.h"
 #include "rt_transforms.h"
@@ -191,6 +192,15 @@ struct rt_context {
     rt::PoseTileRecord* h_pose_record = nullptr;
     hipEvent_t ev_tiles[4] = {};
     rt_tiles_info_t tiles_info = {};
+    // A pose whose origin lies OUTSIDE the grid's box: `pose_outside` - the pose in use is such a one and the context
+    // could serve it (a grid, a finite origin, no triangles); `primary_outside` - its table was built and accepted, so the frame keeps
+    // the grid: tiles for the primary rays (registration spheres made for the pose's own origin, rt_tiles.hip: pose_spheres), the
+    // grid for every later ray. The objects' bounds (kBoundDoubles per object; host copy from build_grid, device copy uploaded by the
+    // first such pose, rt_set_transforms refreshes both) and the per-pose spheres on the device.
+    bool pose_outside = false, primary_outside = false;
+    std::vector<double> h_obj_bound6;
+    double* d_obj_bound6 = nullptr;
+    double* d_outside_spheres = nullptr;
     bool has_triangles = false;             // type-2 records (extension): only the grid path knows them
     int nan_winner = -1;                    // the last sphere / box of the scene decides what a NaN ray ends with (rt_device.h)
     bool nan_winner_sphere = false;
@@ -313,7 +323,8 @@ inline bool direction_in_domain(float dx, float dy, float dz) {
     return dd > 1.0e-30f && dd < 1.0e30f;
 }
 // the grid (fine grid, block grid, light tiles) serves the rays in use: always a camera's, a ray buffer's unless a scan said no
-inline bool grid_in_use(const rt_context* c) { return c->grid.enabled && (c->pinhole || !c->rays_off_grid); }
+// - or the rays are a pose's from outside the box whose screen tiles were accepted (primary_outside: tiles for them, the grid for the rest)
+inline bool grid_in_use(const rt_context* c) { return c->grid.enabled && (c->pinhole || !c->rays_off_grid || c->primary_outside); }
 
 // View-space bounding sphere of what the traversal tests for object o: { x : |A x + b| <= r0 } with A, b the
 // rows x,y,z of mvInverse (the kernels never consult mv for intersection) -> centre -A^-1 b, radius
@@ -382,6 +393,8 @@ int upload_walk_records(rt_context* c);
 float4 screen_rect(const Sphere& s, double z);
 bool detect_pinhole(const rt_ray* rays, uint64_t n, uint32_t& W, uint32_t& H, float& z);
 int refresh_screen_tiles(rt_context* c, hipStream_t stream, uint32_t col_shift);
+int settle_outside_pose(rt_context* c, hipStream_t stream);
+bool pose_within_reach(const rt_context* c, const double origin[3]);
 // rt_light_setup.cpp
 bool lights_need_literal(const rt_context* c, const rt_light* L, uint32_t n_lights);
 int build_light_tiles(rt_context* c, const rt_light* lights);

@@ -159,6 +159,7 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
     if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal &&
         c->h_obj_bounds.size() == 4 * (size_t)c->n_objs) {
         c->lights_literal = lights_need_literal(c, c->h_lights.data(), c->n_lights);
+        if (c->base_flags != (c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u))) c->tiles_dirty = true;  // (a table's verdict depends on the literal flag)
         c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
         c->forced_literal = c->lights_literal;
         apply_ray_domain(c);
@@ -179,7 +180,14 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
         s[0] = bounds[m].x; s[1] = bounds[m].y; s[2] = bounds[m].z; s[3] = r.rg;
         c->h_grid_pre[i] = pretest_as_stored(r.rpre);
         if (!on_always_list(c, i)) c->h_always.push_back(i);  // (plan_transforms made sure of the room)
+        if (c->h_obj_bound6.size() == rt::kBoundDoubles * (size_t)c->n_objs) {  // the bound a pose outside the box makes its sphere from
+            double* b = &c->h_obj_bound6[rt::kBoundDoubles * (size_t)i];
+            b[0] = bounds[m].x; b[1] = bounds[m].y; b[2] = bounds[m].z; b[3] = bounds[m].r; b[4] = bounds[m].kappa2;
+        }
     }
+    if (c->d_obj_bound6 && c->h_obj_bound6.size() == rt::kBoundDoubles * (size_t)c->n_objs)
+        RT_HIP(c, hipMemcpy(c->d_obj_bound6 + rt::kBoundDoubles * (size_t)first, &c->h_obj_bound6[rt::kBoundDoubles * (size_t)first],
+                            sizeof(double) * rt::kBoundDoubles * (size_t)count, hipMemcpyHostToDevice));
     if (c->d_pose_spheres)
         RT_HIP(c, hipMemcpy(c->d_pose_spheres + 4 * (size_t)first, &c->h_grid_spheres[4 * (size_t)first], sizeof(double) * 4 * (size_t)count, hipMemcpyHostToDevice));
     if (c->d_lt_pre)

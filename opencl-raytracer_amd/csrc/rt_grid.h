@@ -193,6 +193,9 @@ struct ScreenTiles {
     uint32_t enabled;
     uint32_t width;                           // posed tables: the pose's grid width (a buffer frame's RenderParams carry none)
     uint32_t posed;                           // the table belongs to the pose the ray buffer was generated from
+    uint32_t outside;                         // ... whose origin lies OUTSIDE the grid's box (lists from spheres made for that origin): the primary
+                                              // rays must never enter the grid walk - wf_trace_primary_tiles<AM, true> (in the struct's tail padding:
+                                              // its size, and with it the layout of the kernels' arguments, is what it was)
 };
 
 // Light tiles: shadow rays towards ONE positional light (the last light - the one shade_and_reflect's colour comes from)

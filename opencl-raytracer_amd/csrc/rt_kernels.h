@@ -43,6 +43,7 @@ struct WavefrontBuffers {
     const HotPair* shadow_pairs = nullptr;         // size-sorted pair stream (owned by the context)
     GridDesc grid = {};                            // conservative grid (owned by the context); enabled = 0 -> brute force
     ScreenTiles tiles = {};                        // per-screen-tile object lists for pinhole primary rays
+    uint32_t primary_outside = 0;                  // the primary rays start outside the grid's box: tiles serve them, never the grid walk
     LightTiles light_tiles = {};                   // per-direction object lists for the shadow rays of the last light
     BlockGrid blocks = {};                         // the closest-hit walk's coarse grid of 32-byte blocks (owned by the context)
     uint32_t* counts = nullptr;                    // device-side round state (queue lengths, hand-over flags) + run-ticket counters

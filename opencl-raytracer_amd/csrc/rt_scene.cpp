@@ -469,23 +469,12 @@ ObjectRadii grid_radii(const GridRadii& g, const Bound& b, uint32_t type, double
     ObjectRadii out{0.0, 0.0, false, false};
     if (b.r == -inf) { out.rg = -1.0; return out; }
     if (!std::isfinite(b.r)) { out.rg = inf; out.always = true; return out; }
-    double D2 = 0;
+    // (the expressions themselves: rt_grid_radii.h, shared with the per-pose spheres of rt_tiles.hip)
     const double cc[3] = {b.x, b.y, b.z};
-    for (int a = 0; a < 3; ++a) {
-        const double d = std::max(std::fabs(cc[a] - g.lo[a]), std::fabs(g.hi[a] - cc[a]));
-        D2 += d * d;
-    }
-    const double k2 = b.kappa2, kap = std::sqrt(k2);
-    const double cl = std::sqrt(cc[0] * cc[0] + cc[1] * cc[1] + cc[2] * cc[2]);
-    const double a2 = b.r * b.r * (1.0 + 2e-6);
-    const double L = 2.2e-6 * kap * (g.S_max + cl) + 2e-6 * k2 * std::sqrt(D2);
-    double reg = std::sqrt(a2 + 3e-6 * k2 * D2) + L;
-    if (type == 2u) {
-        // triangle: the guard |(c - start) x d|^2 <= R^2 |d|^2 is computed with an error of ~10 u R |c - start| |d|^2
-        // (cross-product form), i.e. it can pass lines up to R + ~5 u D away; + the rounding of c - start itself
-        reg = b.r * (1.0 + 1e-6) + 2e-6 * std::sqrt(D2) + 1e-6 * (g.S_max + cl);
-    }
-    out.rg = reg * (1.0 + 1e-6) + 0.01 * g.cell;  // + slack for the kernels' fp32 cell arithmetic
+    const double k2 = b.kappa2;
+    const rt::RadiusTerms rt_ = rt::registration_terms(cc, b.r, k2, type, rt::farthest_corner2(cc, g.lo, g.hi), g.S_max, g.cell);
+    const double cl = rt_.cl, a2 = rt_.a2, L = rt_.L, reg = rt_.reg;
+    out.rg = rt_.rg;
     if (type == 2u) out.rpre = -(reg * (1.0 + 1e-6) + 1e-6 * cl);  // no distance term: its guard has none to speak of
     else if (k2 <= kKappa2Tight && k2 <= K2_limit) { out.rpre = std::sqrt(a2) + 2.0 * L + 1e-6 * cl; out.tight = true; }
     else out.rpre = -(reg * (1.0 + 1e-6) + 1e-6 * cl);
@@ -789,6 +778,14 @@ int build_grid(rt_context* c, const rt_object_data* objs, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) {
         c->h_grid_spheres[4 * i] = sph[i].x; c->h_grid_spheres[4 * i + 1] = sph[i].y; c->h_grid_spheres[4 * i + 2] = sph[i].z;
         c->h_grid_spheres[4 * i + 3] = rg[i];
+    }
+    // the bounds themselves, for the spheres of a pose outside the box (rt_tiles.hip: pose_spheres; such poses are refused for meshes)
+    if (!c->has_triangles) {
+        c->h_obj_bound6.resize(rt::kBoundDoubles * (size_t)n);
+        for (uint32_t i = 0; i < n; ++i) {
+            double* b = &c->h_obj_bound6[rt::kBoundDoubles * (size_t)i];
+            b[0] = sph[i].x; b[1] = sph[i].y; b[2] = sph[i].z; b[3] = sph[i].r; b[4] = sph[i].kappa2; b[5] = (double)objs[i].type;
+        }
     }
     return RT_OK;
 }

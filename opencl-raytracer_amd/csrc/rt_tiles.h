@@ -9,6 +9,7 @@ namespace rt {
 
 constexpr uint32_t kPoseMaxGlobal = 64;        // whole-screen objects a table may hold (the camera builder's limit)
 constexpr uint32_t kPoseMaxList = 1024;        // entries of one tile: what one workgroup sorts in 8 KB of LDS
+constexpr uint32_t kPoseOutsideMinTiles = 16;  // tiles (128 x 64 pixels) below which a pose OUTSIDE the grid's box of a scene of fewer than 512 objects keeps its earlier route (rt_camera_tiles.cpp)
 constexpr uint32_t kPoseMaxTiles = 1u << 20;   // tiles of one table: the scan's top level is one workgroup of 1024 block sums
 
 // One pose, as the host computes it in double (tiles.py: pose_constants). Everything a lane needs besides its own sphere.
@@ -22,6 +23,17 @@ struct PoseTileArgs {
     uint32_t width, height, tiles_x, tiles_y;
     uint32_t n_objs;
     unsigned long long budget;  // (object, tile) pairs the table may hold
+    double whole_r;         // a registration radius above this makes the object a whole-screen entry (+inf: none - a pose inside the box)
+};
+
+// A pose outside the grid's box: what pose_spheres needs to evaluate every object's registration sphere for the pose's own origin
+// (rt_grid_radii.h; tiles.py: pose_registration_spheres is the definition). The grid's constants as the context keeps them.
+constexpr uint32_t kBoundDoubles = 6;  // an object's bound: centre, R, kappa^2, type
+struct PoseSphereArgs {
+    double lo[3], hi[3];    // the box the grid's radii were derived for
+    double cell, S_max;     // the fine grid's edge, the largest |origin| the box allows
+    double o[3];            // the pose's origin
+    uint32_t n_objs;
 };
 
 // What the host reads back after the count and the scan, with one synchronise.
@@ -51,6 +63,9 @@ struct PoseTileBuffers {
 // Passes 1-3: rectangles, keys and classes; per-tile counts (skipped on the device when the pairs exceed the budget or there are
 // too many whole-screen objects); the exclusive scan into tile_start and cursor; record->total and max_list.
 hipError_t launch_pose_tile_count(const PoseTileArgs& a, const PoseTileBuffers& b, hipStream_t stream);
+// In front of them for a pose outside the box: out[4 i ..] = (centre, rg') of object i from its bound (bounds[kBoundDoubles i ..]) and
+// the context's sphere (spheres[4 i ..]: an always-list or never-hit object stays what it is).
+hipError_t launch_pose_spheres(const PoseSphereArgs& a, const double* bounds, const double* spheres, double* out, hipStream_t stream);
 // Passes 4-5: fill and per-tile sort into `entries`, the global list and one zeroed entry behind it. `total`, `n_global` and
 // `max_list` are the record's, already accepted by the host (scratch holds total, entries total + n_global + 1 elements).
 hipError_t launch_pose_tile_fill(const PoseTileArgs& a, const PoseTileBuffers& b, uint32_t total, uint32_t n_global, uint32_t max_list,

@@ -17,6 +17,7 @@
 //                 by index, and the zeroed entry behind it.
 // Every loop is bounded by a rectangle's area or a list's length; every store is guarded by the size of its array.
 #include "rt_tiles.h"
+#include "rt_grid_radii.h"
 
 namespace rt {
 namespace {
@@ -48,6 +49,27 @@ __device__ __forceinline__ void extent(double cu, double cz, double R, double z,
     h = (h + (1.0 + 1e-6 * __builtin_fabs(h))) + pad;
     lo = (double)float_below((float)l);
     hi = (double)float_above((float)h);
+}
+
+// A pose outside the grid's box (in front of tile_rects): one lane per object, grid_radii's expressions with the farthest origin
+// and the largest |origin| taken over the box AND the pose's origin. rg' is finite for every finite origin (squares of fp32 values
+// in double); should it not be, the largest double stands for it, which tile_rects makes a whole-screen entry.
+__global__ __launch_bounds__(kBlock) void pose_spheres(const PoseSphereArgs a, const double* __restrict__ bounds,
+                                                       const double* __restrict__ spheres, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_objs) return;
+    const double* b = bounds + (unsigned long long)kBoundDoubles * i;
+    const double c[3] = {b[0], b[1], b[2]};
+    double rg = spheres[4ull * i + 3];
+    if (rg >= 0 && rg != __builtin_inf()) {  // else the always-list / never hit: what it is
+        const double D2 = pose_far2(c, a.o, farthest_corner2(c, a.lo, a.hi));
+        const RadiusTerms t = registration_terms(c, b[3], b[4], (uint32_t)b[5], D2, pose_reach(a.o, a.S_max), a.cell);
+        rg = (t.rg - t.rg) == 0.0 ? t.rg : 1.7976931348623157e308;
+    }
+    out[4ull * i] = spheres[4ull * i];
+    out[4ull * i + 1] = spheres[4ull * i + 1];
+    out[4ull * i + 2] = spheres[4ull * i + 2];
+    out[4ull * i + 3] = rg;
 }
 
 __global__ __launch_bounds__(kBlock) void tile_rects(const PoseTileArgs a, const PoseTileBuffers b) {
@@ -84,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void tile_rects(const PoseTileArgs a, const
                     kd = kd - __builtin_fabs(kd) * 0x1p-40;
                     if (kd == kd) key = float_below((float)kd);
                     const unsigned long long tiles = (unsigned long long)a.tiles_x * a.tiles_y;
-                    if (covered == tiles && tiles > 1ull) {  // the whole screen: the global list
+                    if ((covered == tiles && tiles > 1ull) || R > a.whole_r) {  // the whole screen (or, off the box, as big as the scene): the global list
                         global = true;
                         covered = 0ull;
                         rc = make_uint4(1u, 0u, 1u, 0u);
@@ -280,6 +302,12 @@ hipError_t launch_pose_tile_count(const PoseTileArgs& a, const PoseTileBuffers& 
     const uint32_t obj_blocks = (a.n_objs + kBlock - 1) / kBlock;
     hipLaunchKernelGGL(tile_rects, dim3(obj_blocks), dim3(kBlock), 0, stream, a, b);
     return launch_tile_list_count(a, b, stream);
+}
+
+hipError_t launch_pose_spheres(const PoseSphereArgs& a, const double* bounds, const double* spheres, double* out, hipStream_t stream) {
+    if (a.n_objs == 0 || !bounds || !spheres || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pose_spheres, dim3((a.n_objs + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a, bounds, spheres, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_tile_list_count(const PoseTileArgs& a, const PoseTileBuffers& b, hipStream_t stream) {

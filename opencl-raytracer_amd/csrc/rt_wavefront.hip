@@ -355,7 +355,10 @@ __device__ __forceinline__ void tile_candidate(const TileRecord& o, int k, const
 // The list is in depth order (rt_grid.h: ScreenTiles): the wave leaves it at the first entry whose key - the smallest t
 // that object can report - is above every lane's T. Entry e + 2 and the record of entry e + 1 are loaded while entry e is
 // tested; the look-ahead stops at the list's last entry, so nothing beyond the list is read.
-template <int AM>
+// OUTSIDE (WfParams::tiles.outside, wave-uniform): the rays start outside the grid's box, where the grid walk's t_enter = 0 does not hold - a
+// straddling wave runs the brute-force closest-hit loop over all objects instead (closest_hit: the loop of RT_FLAG_NO_GRID's frame,
+// whose result the order-free update reproduces). The instantiation for rays inside the box is the code it was.
+template <int AM, bool OUTSIDE>
 __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk) {
     WfParams w = wk;
     if (!resolve_round(w)) return;
@@ -402,6 +405,9 @@ __global__ __launch_bounds__(256) void wf_trace_primary_tiles(const WfParams wk)
                 cur = next; next = next2; rec = rec_next;
             }
         }
+    } else if (OUTSIDE) {
+        closest_hit<AM, true>(p.scene.pairs, p.scene.n_pairs, ray, T, idx);
+        tested = 2u * p.scene.n_pairs;
     } else {
         closest_hit_grid<AM, true>(w.grid, p.scene.hot, ray, T, idx, tested);
     }
@@ -2367,7 +2373,10 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
         }
         if (nc_max) {
             if (use_grid && first && w.tiles.enabled && (w.rp.pinhole || (w.tiles.posed && w.tiles.width))) {
-                hipLaunchKernelGGL((wf_trace_primary_tiles<AM>), grid_for(nc_max), dim3(256), 0, stream, w);
+                if (w.tiles.outside) hipLaunchKernelGGL((wf_trace_primary_tiles<AM, true>), grid_for(nc_max), dim3(256), 0, stream, w);
+                else hipLaunchKernelGGL((wf_trace_primary_tiles<AM, false>), grid_for(nc_max), dim3(256), 0, stream, w);
+            } else if (use_grid && first && buf.primary_outside) {
+                return hipErrorInvalidValue;  // (do_launch never asks for this: outside the box there is no grid walk for a primary ray)
             } else if (use_grid) {
                 launch_persistent<AM, false>(w, nc_max, rs + kTicketBase, stream, side_by_side);  // (a grid implies direction.w = 0)
             } else {

@@ -44,6 +44,7 @@ EXPORTS = [
     "rt_set_lights", "rt_set_lights_multi", "rt_get_light_tiles_info", "rt_read_light_tiles", "rt_read_grid_pretest",
     "rt_set_materials", "rt_set_materials_device", "rt_set_materials_multi", "rt_read_materials",
     "rt_set_transforms", "rt_set_transforms_multi", "rt_read_transforms", "rt_get_geometry_info",
+    "rt_read_pose_spheres", "rt_read_object_bounds", "rt_get_grid_constants",
 ]
 
 
@@ -75,14 +76,12 @@ class RTRaysInfo(ctypes.Structure):
         ("source", ctypes.c_uint32), ("dir_w_zero", ctypes.c_uint32), ("directions_in_domain", ctypes.c_uint32),
         ("starts_ok", ctypes.c_uint32), ("origin_lo", ctypes.c_float * 3), ("origin_hi", ctypes.c_float * 3),
         ("box_lo", ctypes.c_double * 3), ("box_hi", ctypes.c_double * 3), ("grid_built", ctypes.c_uint32),
-        ("grid_in_use", ctypes.c_uint32), ("literal", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("grid_in_use", ctypes.c_uint32), ("literal", ctypes.c_uint32), ("primary_outside_box", ctypes.c_uint32),
     ]
 
     def as_dict(self):
         out = {}
         for n, t in self._fields_:
-            if n == "reserved":
-                continue
             v = getattr(self, n)
             out[n] = int(v) if t is ctypes.c_uint32 else np.array(list(v), dtype=np.float32 if t._type_ is ctypes.c_float else np.float64)
         return out
@@ -254,6 +253,13 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_read_tiles.argtypes = [vp, vp, u64, vp, u64]
         lib.rt_read_grid_spheres.restype = i32
         lib.rt_read_grid_spheres.argtypes = [vp, vp, u64]
+    if hasattr(lib, "rt_read_pose_spheres"):  # (the same: a build from before poses outside the grid's box kept the grid)
+        lib.rt_read_pose_spheres.restype = i32
+        lib.rt_read_pose_spheres.argtypes = [vp, vp, u64]
+        lib.rt_read_object_bounds.restype = i32
+        lib.rt_read_object_bounds.argtypes = [vp, vp, u64]
+        lib.rt_get_grid_constants.restype = i32
+        lib.rt_get_grid_constants.argtypes = [vp, vp]
     if hasattr(lib, "rt_set_lights"):  # (the same: a build from before replaceable lights)
         lib.rt_set_lights.restype = i32
         lib.rt_set_lights.argtypes = [vp, vp, u32]
@@ -569,7 +575,7 @@ class HIPRaytracer:
 
     def tiles_info(self) -> dict:
         """rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use (built now if the rays
-        changed): enabled, source (0 none, 1 the camera's, 2 the pose's), tiles_x, tiles_y, col_shift, n_entries, n_global,
+        changed): enabled, source (0 none, 1 the camera's, 2 the pose's, 3 a pose's outside the grid's box), tiles_x, tiles_y, col_shift, n_entries, n_global,
         max_list, refused (tiles.REFUSED_* bits), build_device_ms, eps, pad."""
         info = RTTilesInfo()
         self._check(self._lib.rt_get_tiles_info(self._ctx, ctypes.byref(info)))
@@ -591,6 +597,26 @@ class HIPRaytracer:
         out = np.zeros((self._n_objs, 4), dtype=np.float64)
         self._check(self._lib.rt_read_grid_spheres(self._ctx, _ptr(out), self._n_objs))
         return out
+
+    def read_pose_spheres(self) -> np.ndarray:
+        """rt_read_pose_spheres: n x 4 float64, the registration spheres made for the origin of the pose in use, which lies outside
+        the grid's box (tiles_info()["source"] == 3; tiles.pose_registration_spheres is the definition). RTError otherwise."""
+        out = np.zeros((self._n_objs, 4), dtype=np.float64)
+        self._check(self._lib.rt_read_pose_spheres(self._ctx, _ptr(out), self._n_objs))
+        return out
+
+    def object_bounds(self) -> np.ndarray:
+        """rt_read_object_bounds: n x 6 float64 - centre, radius, kappa^2, type - the bounds the registration spheres are made from."""
+        out = np.zeros((self._n_objs, 6), dtype=np.float64)
+        self._check(self._lib.rt_read_object_bounds(self._ctx, _ptr(out), self._n_objs))
+        return out
+
+    def grid_constants(self) -> dict:
+        """rt_get_grid_constants with the box of rays_info(): what tiles.pose_registration_spheres takes as `grid_constants`."""
+        out = np.zeros(4, dtype=np.float64)
+        self._check(self._lib.rt_get_grid_constants(self._ctx, _ptr(out)))
+        info = self.rays_info()
+        return dict(box_lo=info["box_lo"], box_hi=info["box_hi"], cell=float(out[0]), diag=float(out[1]), S_max=float(out[2]), K2=float(out[3]))
 
     def grid_pretest(self) -> np.ndarray:
         """rt_read_grid_pretest: n float32, the pre-test radii of the grid's entry spheres (magnitude; the sign is a kernel flag)."""

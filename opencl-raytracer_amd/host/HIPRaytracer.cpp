@@ -194,6 +194,13 @@ rt_tiles_info_t HIPRaytracer::TilesInfo() {
     return info;
 }
 
+rt_rays_info_t HIPRaytracer::RaysInfo() {
+    rt_rays_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_rays_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::RaysInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_stats_t HIPRaytracer::Stats() {
     rt_stats_t s;
     if (multi) {  // several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures

@@ -86,7 +86,11 @@ public:
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.
+    // (source 3: the table of a pose outside the grid's box, from spheres made for its origin - hip_raytracer.h, "outside the box")
     rt_tiles_info_t TilesInfo();
+    // rt_get_rays_info: where the next frame's primary rays come from and whether the grid serves them - grid_in_use, and
+    // primary_outside_box for a pose outside the grid's box whose tiles were accepted. The several-GPU object reports its first shard's.
+    rt_rays_info_t RaysInfo();
     rt_context* Context() { return ctx; }
 
 private:

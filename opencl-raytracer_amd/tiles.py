@@ -5,6 +5,11 @@ pose_screen_tiles(spheres, width, height, z, M, origin)
     per 64 x 8 tile the objects whose registration sphere a ray of that tile can meet, each with a lower bound of the t it
     can report there, ascending by (key, index). csrc/rt_grid.h (ScreenTiles, "posed cameras") has the derivation; this file
     is the same arithmetic in numpy float64, in the order the device uses, and runs without a GPU.
+pose_registration_spheres(bounds, grid_constants, origin)
+    the registration spheres of a pose whose origin may lie OUTSIDE the grid's box (csrc/rt_tiles.hip: pose_spheres): the grid's
+    own expressions (csrc/rt_grid_radii.h) with the farthest origin and the largest |origin| taken over the box and the pose's
+    origin. pose_screen_tiles takes its output, with whole_r = 0.25 diag. grid_registration_spheres is the grid's own formula,
+    object_bounds / grid_constants stand in for a context's bounds and constants, pose_within_reach is the FAR condition.
 bounding_spheres(objects)
     bounding spheres of OBJECT_DTYPE records (centre -A^-1 b, radius r0 sigma_max(A^-1)), geometric or with rt_grid.h's
     registration bound, for callers that have no context to ask (HIPRaytracer.grid_spheres() returns the spheres a live
@@ -32,6 +37,9 @@ REFUSED_BUDGET = 64       # more (object, tile) pairs than 256 n + 4096
 REFUSED_LIST = 128        # a tile's list is longer than 1024 entries
 REFUSED_TILES = 256       # more than 2^20 tiles
 REFUSED_KNOB = 512        # RT_POSE_TILES said no
+REFUSED_FAR = 1024        # a pose outside the grid's box whose origin is too far: 3e-6 (|o| + far) > 0.01 cell
+REFUSED_SMALL = 2048      # a pose outside the grid's box on a frame of fewer than OUTSIDE_MIN_TILES tiles
+OUTSIDE_MIN_TILES = 16    # 128 x 64 pixels
 
 
 def sigma_max(N: np.ndarray) -> float:
@@ -110,9 +118,10 @@ def _next_above(x: np.ndarray) -> np.ndarray:
     return np.nextafter(x.astype(F), F(np.inf))
 
 
-def pose_rects(spheres: np.ndarray, width: int, height: int, k: dict) -> dict:
+def pose_rects(spheres: np.ndarray, width: int, height: int, k: dict, whole_r: float = np.inf) -> dict:
     """Per object: class (0 none, 1 listed, 2 whole screen), tile rectangle x0, x1, y0, y1 (inclusive) and depth key - the
-    device's tile_rects pass. `k` = pose_constants(...) of a pose that was not refused."""
+    device's tile_rects pass. `k` = pose_constants(...) of a pose that was not refused. A listed object whose radius is above
+    `whole_r` is a whole-screen entry (a pose outside the grid's box: 0.25 of the box's diagonal)."""
     s = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
     n = len(s)
     N, od, z = k["N"], k["origin"], k["z"]
@@ -171,16 +180,20 @@ def pose_rects(spheres: np.ndarray, width: int, height: int, k: dict) -> dict:
     cls = np.where(listed, 1, 0)
     if tiles_x * tiles_y > 1:
         cls = np.where(listed & (covered == tiles_x * tiles_y), 2, cls)
+    with np.errstate(invalid="ignore"):
+        cls = np.where(listed & (R > whole_r), 2, cls)
     edges = dict(c0=c0, c1=c1, r0=r0, r1=r1)
     return dict(cls=cls, x0=x0, x1=x1, y0=y0, y1=y1, key=key, covered=covered, edges=edges)
 
 
-def pose_screen_tiles(spheres, width: int, height: int, z: float, M, origin=(0.0, 0.0, 0.0), grid_in_use: bool = True) -> dict:
+def pose_screen_tiles(spheres, width: int, height: int, z: float, M, origin=(0.0, 0.0, 0.0), grid_in_use: bool = True,
+                      whole_r: float = np.inf) -> dict:
     """The table of one pose. `spheres`: n x 4 float64 registration spheres (centre, R; R = inf: always tested, R < 0 or NaN:
     never hit - neither is in any list). Returns enabled, refused (REFUSED_* bits), eps, pad, tiles_x, tiles_y, col_shift and -
     when enabled - tile_start (uint32[tiles + 1]), entries (uint32[n_entries + n_global + 1, 2]: {index, key bits}, a tile's
     ascending by (key, index), the global list behind the last tile's, one zeroed entry behind that), n_entries, n_global,
-    global_begin, max_list, and `rects` (pose_rects' per-object result)."""
+    global_begin, max_list, and `rects` (pose_rects' per-object result). For a pose outside the grid's box `spheres` are
+    pose_registration_spheres(...) and `whole_r` is 0.25 of the box's diagonal."""
     s = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
     n = len(s)
     k = pose_constants(width, height, z, M, origin)
@@ -191,7 +204,7 @@ def pose_screen_tiles(spheres, width: int, height: int, z: float, M, origin=(0.0
         out["refused"] |= REFUSED_NO_GRID
     if out["refused"]:
         return out
-    rects = pose_rects(s, width, height, k)
+    rects = pose_rects(s, width, height, k, whole_r)
     out["rects"] = rects
     cls = rects["cls"]
     glob = np.nonzero(cls == 2)[0]
@@ -263,3 +276,132 @@ def bounding_spheres(objects: np.ndarray, reach: float | None = None) -> np.ndar
         out[i, :3] = c
         out[i, 3] = R
     return out
+
+
+# ---- poses outside the grid's box ---------------------------------------------------------------------------------------------------
+def object_bounds(objects: np.ndarray) -> np.ndarray:
+    """n x 6 float64 - centre, radius, kappa^2, type - of OBJECT_DTYPE records, for callers without a context (a context's own:
+    HIPRaytracer.object_bounds()): bounding_spheres' centre and geometric radius, kappa = sigma_max / sigma_min of A^-1."""
+    out = np.zeros((len(objects), 6))
+    out[:, :4] = bounding_spheres(objects)
+    for i, o in enumerate(objects):
+        m = np.asarray(o["mvInverse"], dtype=np.float64).reshape(16)
+        A = np.array([[m[0], m[4], m[8]], [m[1], m[5], m[9]], [m[2], m[6], m[10]]])
+        out[i, 5] = int(o["type"])
+        if int(o["type"]) <= 1:
+            sv = np.linalg.svd(np.linalg.inv(A), compute_uv=False)
+            out[i, 4] = (sv[0] / sv[-1]) ** 2
+    return out
+
+
+def grid_constants(bounds, origin_lo=(0.0, 0.0, 0.0), origin_hi=(0.0, 0.0, 0.0), cells_per_object: float = 3.0) -> dict:
+    """A TEST STAND-IN for a context's constants (HIPRaytracer.grid_constants() returns the real ones; nothing in the library reads
+    this): build_grid's constants (csrc/rt_scene.cpp) for a scene of these bounds whose create-time origins fill origin_lo .. origin_hi,
+    WITHOUT the cell refinement of crowded scenes and with K2 = 1 as a placeholder:
+    the box - the origins united with the bounds padded by 1 % -, its diagonal, the largest |corner| S_max, and the cell edge before
+    the refinement build_grid applies to crowded scenes (a context's own: HIPRaytracer.grid_constants())."""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 6)
+    lo, hi = np.array(origin_lo, dtype=np.float64), np.array(origin_hi, dtype=np.float64)
+    ok = np.isfinite(b[:, 3])
+    pad = b[ok, 3] * 1.01
+    lo = np.minimum(lo, (b[ok, :3] - pad[:, None]).min(axis=0)) if ok.any() else lo
+    hi = np.maximum(hi, (b[ok, :3] + pad[:, None]).max(axis=0)) if ok.any() else hi
+    ext = hi - lo
+    diag = float(np.sqrt(ext[0] * ext[0] + ext[1] * ext[1] + ext[2] * ext[2]))
+    corners = np.array([[(hi if k & 1 else lo)[0], (hi if k & 2 else lo)[1], (hi if k & 4 else lo)[2]] for k in range(8)])
+    S_max = float(np.sqrt((corners * corners).sum(axis=1)).max())
+    e = np.maximum(ext, 1e-6)
+    cell = float(np.cbrt(e[0] * e[1] * e[2] / (cells_per_object * len(b))))
+    cell = max(cell, float(ext.max()) / 256.0)
+    return dict(box_lo=lo, box_hi=hi, cell=cell, diag=diag, S_max=S_max, K2=1.0)
+
+
+def _registration(b: np.ndarray, g: dict, D2: np.ndarray, S) -> np.ndarray:
+    """csrc/rt_grid_radii.h: registration_terms' rg, in its order of operations."""
+    c, r, k2, ty = b[:, :3], b[:, 3], b[:, 4], b[:, 5]
+    with np.errstate(all="ignore"):
+        kap = np.sqrt(k2)
+        cl = np.sqrt(c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1] + c[:, 2] * c[:, 2])
+        a2 = r * r * (1.0 + 2e-6)
+        L = 2.2e-6 * kap * (S + cl) + 2e-6 * k2 * np.sqrt(D2)
+        reg = np.sqrt(a2 + 3e-6 * k2 * D2) + L
+        tri = r * (1.0 + 1e-6) + 2e-6 * np.sqrt(D2) + 1e-6 * (S + cl)
+        reg = np.where(ty == 2, tri, reg)
+        return reg * (1.0 + 1e-6) + 0.01 * g["cell"]
+
+
+def _farthest_corner2(b: np.ndarray, g: dict) -> np.ndarray:
+    lo, hi = np.asarray(g["box_lo"], dtype=np.float64), np.asarray(g["box_hi"], dtype=np.float64)
+    D2 = np.zeros(len(b))
+    for a in range(3):
+        d = np.maximum(np.abs(b[:, a] - lo[a]), np.abs(hi[a] - b[:, a]))
+        D2 = D2 + d * d
+    return D2
+
+
+def _classes(b: np.ndarray, rg: np.ndarray, g: dict) -> np.ndarray:
+    """grid_radii's classes: a bound of -inf is never hit (-1), one without a finite radius - or a sphere above a quarter of the
+    box's diagonal - is tested by every ray (+inf: the always-list)."""
+    r = b[:, 3]
+    with np.errstate(invalid="ignore"):
+        rg = np.where(~np.isfinite(rg) | (rg > 0.25 * g["diag"]), np.inf, rg)
+    rg = np.where(~np.isfinite(r), np.inf, rg)
+    return np.where(r == -np.inf, -1.0, rg)
+
+
+def grid_registration_spheres(bounds, grid_constants: dict) -> np.ndarray:
+    """n x 4 float64: the spheres build_grid registers these bounds with (grid_radii, csrc/rt_scene.cpp): every ray origin inside
+    the box, i.e. at most D - the farthest corner - from the centre and S_max from the world's origin."""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 6)
+    rg = _registration(b, grid_constants, _farthest_corner2(b, grid_constants), grid_constants["S_max"])
+    return np.column_stack([b[:, :3], _classes(b, rg, grid_constants)])
+
+
+def pose_registration_spheres(bounds, grid_constants: dict, origin, grid_spheres=None) -> np.ndarray:
+    """n x 4 float64: (c, rg') for the rays of a pose at `origin` (fp32, converted exactly) - grid_radii's expressions with D^2
+    replaced by max(D^2, |o - c|^2) and S_max by max(S_max, |o|). An origin inside the box reproduces the grid's spheres bit for
+    bit. Objects the grid has in its always-list (+inf) or can never hit (negative) stay what they are: `grid_spheres`, a live
+    context's own (HIPRaytracer.grid_spheres()), decides where given, else grid_registration_spheres. An rg' that is not finite
+    becomes the largest double; pose_screen_tiles(..., whole_r = 0.25 diag) makes it, and every rg' above whole_r, a whole-screen
+    entry."""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 6)
+    g = grid_constants
+    o = np.asarray(origin, dtype=np.float64).astype(F).astype(np.float64)
+    base = grid_registration_spheres(b, g) if grid_spheres is None else np.asarray(grid_spheres, dtype=np.float64).reshape(-1, 4)
+    with np.errstate(all="ignore"):
+        d = o[None, :] - b[:, :3]
+        oc2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        D2 = _farthest_corner2(b, g)
+        D2 = np.where(D2 < oc2, oc2, D2)
+        ol = float(np.sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]))
+        S = ol if g["S_max"] < ol else g["S_max"]
+        rg = _registration(b, g, D2, S)
+        rg = np.where(np.isfinite(rg), rg, np.finfo(np.float64).max)
+        keep = ~((base[:, 3] >= 0) & (base[:, 3] != np.inf))
+    out = base.copy()
+    out[:, 3] = np.where(keep, base[:, 3], rg)
+    return out
+
+
+GROWTH_CELLS = 0.9        # (pose_growth_ok)
+
+
+def pose_growth_ok(bounds, grid_constants: dict, origin, grid_spheres=None) -> bool:
+    """Not enforced by the library (DESIGN.md 4.1 names the limit): does no listed object's rg' exceed its rg by more than GROWTH_CELLS
+    cells, so that every point a primary ray can report - inside (c, rg') - lies inside the grid's own box (padded by rg + one cell)?"""
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 6)
+    base = grid_registration_spheres(b, grid_constants) if grid_spheres is None else np.asarray(grid_spheres, dtype=np.float64).reshape(-1, 4)
+    mine = pose_registration_spheres(b, grid_constants, origin, grid_spheres=base)
+    listed = (base[:, 3] >= 0) & np.isfinite(base[:, 3])
+    return bool(np.all(mine[listed, 3] <= base[listed, 3] + GROWTH_CELLS * grid_constants["cell"]))
+
+
+def pose_within_reach(grid_constants: dict, origin) -> bool:
+    """The FAR condition: 3e-6 (|o| + far) <= 0.01 cell, far = the largest distance from o to a corner of the box."""
+    g = grid_constants
+    o = np.asarray(origin, dtype=np.float64).astype(F).astype(np.float64)
+    lo, hi = np.asarray(g["box_lo"], dtype=np.float64), np.asarray(g["box_hi"], dtype=np.float64)
+    with np.errstate(all="ignore"):
+        d = np.maximum(np.abs(o - lo), np.abs(hi - o))
+        lhs = 3e-6 * (float(np.sqrt((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2])) + float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])))
+    return bool(np.isfinite(lhs) and lhs <= 0.01 * g["cell"])
