@@ -70,7 +70,9 @@ extern "C" {
  *      rt_get_geometry_info. Additions only; detect by dlsym of rt_set_transforms.
  *      Later addition, same version: poses outside the grid's box keep the grid - RT_TILES_REFUSED_FAR, rt_tiles_info_t::source may
  *      read 3, rt_rays_info_t::reserved became primary_outside_box, rt_read_pose_spheres, rt_read_object_bounds,
- *      rt_get_grid_constants. Additions only; detect by dlsym of rt_read_pose_spheres. */
+ *      rt_get_grid_constants. Additions only; detect by dlsym of rt_read_pose_spheres.
+ *      Later addition, same version: replaceable visibility - rt_set_visibility, rt_set_visibility_device, rt_read_visibility,
+ *      rt_set_visibility_multi; RT_TYPE_HIDDEN in rt_records.h. Additions only; detect by dlsym of rt_set_visibility. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -564,7 +566,8 @@ int rt_read_grid_pretest(const rt_context* ctx, float* pre, uint64_t n);
 /* ---- replaceable materials -----------------------------------------------------------------------------------------------------
  * The colours of a live context's objects: a viewer that highlights the object under the mouse (rt_render_aux names it), a
  * simulation that colours its particles by a scalar every step - without rt_destroy + rt_create. (The two matrices have a setter of
- * their own, "replaceable transforms" below; type and the object count are NOT replaceable.)
+ * their own, "replaceable transforms" below, and an object can be hidden, "replaceable visibility"; sphere <-> box and the object
+ * count are NOT replaceable.)
  *
  * `materials` are `count` records of 64 bytes in rt_material's layout (rt_records.h), assigned to objects first .. first + count - 1.
  *
@@ -646,7 +649,7 @@ int rt_read_materials(rt_context* ctx, void* materials, uint32_t first, uint32_t
  * loops, by brute force or with a bigger grid; this call never switches paths behind the caller's back.
  *
  * NOT part of this call (each would be its own addition): a device-memory form (the bounds and refusals are evaluated on the host);
- * changing an object's type or the object count; triangles; folding dynamic objects back into the grid, hence moving more than 64
+ * changing an object between sphere and box, or the object count; triangles; folding dynamic objects back into the grid, hence moving more than 64
  * objects of a grid context - that is the device rebuild of the fine grid and the block grid; poses outside the grid box.
  *
  * rt_read_transforms: an accessor for tests and tools, next to rt_read_materials. Reassembles rt_transform records of objects
@@ -666,6 +669,62 @@ typedef struct rt_geometry_info_t {
 int rt_set_transforms(rt_context* ctx, const void* transforms, uint32_t first, uint32_t count);
 int rt_read_transforms(rt_context* ctx, void* transforms, uint32_t first, uint32_t count);
 int rt_get_geometry_info(const rt_context* ctx, rt_geometry_info_t* info);
+
+/* ---- replaceable visibility ----------------------------------------------------------------------------------------------------
+ * Which of a live context's objects are in the picture: a viewer that deletes the object under the mouse, switches a layer off or
+ * looks behind a wall, a simulation whose particles die and are born - without rt_destroy + rt_create.
+ *
+ * The hidden word. The reference's `raycast` switch has no default: an object whose type is none of 0, 1 (and 2, this backend's
+ * triangle) is never hit. RT_TYPE_HIDDEN (rt_records.h) is one such word, and not the pair streams' pad 0xffffffff. A hidden object
+ * is an object whose type word is RT_TYPE_HIDDEN in every record copy the kernels read.
+ *
+ * `visible` are `count` bytes for objects first .. first + count - 1: 0 hides the object, anything else gives it the type word
+ * rt_create was given. An object created with a type other than 0, 1, 2 can never be hit anyway: it is left alone and reads back
+ * as visible.
+ *
+ * Contract. The next render is the frame a FRESH context renders that is created with the same object array except that the hidden
+ * objects carry type = RT_TYPE_HIDDEN (records.with_visibility is the executable definition), the same flags, and the current rays /
+ * camera / pose / shard / supersampling factor / lights / materials / transforms - bit for bit, with the same rays_reference and
+ * hit_pixels - for every kernel (RT_KERNEL_HITTEST included: its times change), every path (small-scene kernel, round machine,
+ * literal loops, brute force, RT_FLAG_NO_GRID, triangles) and every arithmetic mode. What was set or rendered before does not
+ * matter: hide, then show, is the untouched context again. Object indices are stable: rt_render_aux keeps naming the same objects
+ * and never names a hidden one.
+ * rays_traced and object_tests are NOT part of the contract: no table is rebuilt, so a hidden object keeps its registrations in the
+ * grid, the block grid, the screen tiles and the light tiles (and its place on the always-list if it is dynamic), and each can still
+ * cost an exact test - which a never-hit type fails - but never a pixel: a table entry is only a candidate ("replaceable
+ * transforms"). rt_get_tiles_info, rt_get_light_tiles_info and rt_get_geometry_info read exactly as before the call. A frame that
+ * hides much of a scene is therefore slower than the fresh context's (README has the measured ratio).
+ *
+ * What follows the types, on the host, from a mirror of the mask: the NaN-ray winner (rt_set_aux_device: "the last sphere / box")
+ * is the last VISIBLE sphere or box; under RT_FLAG_DEVICE_OPENCL the predicate on the lights ("replaceable lights") skips hidden
+ * objects - a fresh context gives them no bound - here and in every later rt_set_lights / rt_set_transforms, so
+ * rt_get_rays_info().literal goes 0 or 1 as a fresh context's would. One exception, pixels unaffected: a context that rt_create made
+ * literal for a degenerate instance (singular or non-finite mvInverse) STAYS literal when that instance is hidden; `literal` reads 1
+ * where the fresh context's reads 0.
+ * rt_set_materials and rt_set_transforms go by the create-time type and keep working on hidden objects exactly as on visible ones
+ * (a moved hidden object becomes dynamic like any other); what they set is what shows when the object is shown again.
+ *
+ * rt_set_visibility: a HOST mask. It is staged in a context-owned device buffer (grow-only, freed by rt_destroy) and patched into
+ * the records by the same kernel as the device form (csrc/rt_visibility.hip: one pass, five 4-byte stores per object).
+ * rt_set_visibility_device: `d_visible` is device memory on the context's device, at ANY alignment (a torch bool or uint8 tensor
+ * qualifies); the kernel is enqueued on `hip_stream` (NULL: the legacy default stream) behind the caller's kernels that produced
+ * the mask, and the range is then copied back into the host mirror for the predicates above.
+ * Both are synchronous like rt_set_materials: on return the mask is the caller's again and the next render on any stream sees it.
+ * Renders of this context still in flight on ANOTHER stream must be ordered by the caller, as for every setter.
+ *
+ * Refused with RT_ERR_INVALID_ARGUMENT, before anything is touched: first + count > n_objs (computed in 64 bits), a NULL mask with
+ * count != 0. count == 0 returns RT_OK and launches nothing.
+ *
+ * NOT part of this call (each would be its own addition): sphere <-> box (the bounds change: that is the dynamic set's business);
+ * changing the object count; dropping hidden objects from the tables (the device rebuild of the grids); un-literalising a context
+ * whose degenerate instance is hidden; a scene_tool option.
+ *
+ * rt_read_visibility: an accessor for tests and tools, next to rt_read_transforms. Reads the type word of objects first .. first +
+ * count - 1 from EVERY device copy (walk records, round-machine records, shading records, both pair streams) and writes 1 or 0 per
+ * object; RT_ERR_STATE with a message if two copies disagree or a word is neither the create-time type nor RT_TYPE_HIDDEN. */
+int rt_set_visibility(rt_context* ctx, const uint8_t* visible, uint32_t first, uint32_t count);
+int rt_set_visibility_device(rt_context* ctx, const void* d_visible, uint32_t first, uint32_t count, void* hip_stream);
+int rt_read_visibility(rt_context* ctx, uint8_t* visible, uint32_t first, uint32_t count);
 
 void rt_destroy(rt_context* ctx);
 
@@ -707,6 +766,9 @@ int rt_set_materials_multi(rt_multi* m, const void* materials, uint32_t first, u
 /* rt_set_transforms ("replaceable transforms", above) on every context, all or none: every refusal is evaluated on every shard
  * before any shard is touched. */
 int rt_set_transforms_multi(rt_multi* m, const void* transforms, uint32_t first, uint32_t count);
+/* rt_set_visibility ("replaceable visibility", above; host masks only) on every context, all or none: the arguments are validated
+ * before any shard is touched. */
+int rt_set_visibility_multi(rt_multi* m, const uint8_t* visible, uint32_t first, uint32_t count);
 uint64_t rt_multi_frame_elems(const rt_multi* m);
 int rt_render_multi(rt_multi* m, const float** out);
 int rt_render_multi_device(rt_multi* m, void* d_frame);

@@ -78,6 +78,9 @@ RT_STATIC_ASSERT(sizeof(rt_pixel) == 16, "pixel must be 16 bytes");
 
 #define RT_TYPE_SPHERE 0u
 #define RT_TYPE_BOX 1u
+/* rt_set_visibility's word for a hidden object: none of 0, 1, 2 (never hit - the reference's switch has no default) and not the
+ * pair pad 0xffffffff; as float bits it is 2.0f, a number that survives any move through a float register */
+#define RT_TYPE_HIDDEN 0x40000000u
 #define RT_MAX_FLOAT 3.402823466e+38F /* shade_and_reflect_kernel.cl:31 */
 
 #endif /* RT_RECORDS_H */

@@ -47,6 +47,10 @@ def load_library():
             fp = ctypes.POINTER(ctypes.c_float)
             lib.cpu_rt_render_set_transforms.restype = ctypes.c_int
             lib.cpu_rt_render_set_transforms.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
+        if hasattr(lib, "cpu_rt_render_set_visibility"):
+            fp = ctypes.POINTER(ctypes.c_float)
+            lib.cpu_rt_render_set_visibility.restype = ctypes.c_int
+            lib.cpu_rt_render_set_visibility.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
         _lib = lib
     return _lib
 
@@ -71,6 +75,19 @@ class CPURaytracer:
         self.pose = None
         self.materials = None
         self.transforms = None
+        self.visible = None
+
+    def set_visibility(self, visible, first: int = 0):
+        """CPURaytracer::SetVisibility, the option HIPRaytracer.set_visibility is on the GPU: the next Render() does not hit the
+        objects first .. first + n - 1 whose entry of `visible` is 0, and hits the others as the constructor's type says.
+        Calls add up: a later one overrides an earlier one where they overlap."""
+        mask = (np.asarray(visible).reshape(-1) != 0).astype(np.uint8)
+        first = int(first)
+        if first < 0 or first + len(mask) > len(self.objects):
+            raise ValueError("set_visibility: first + len(visible) exceeds the object count")
+        if self.visible is None:
+            self.visible = np.ones(len(self.objects), dtype=np.uint8)
+        self.visible[first:first + len(mask)] = mask
 
     def set_transforms(self, transforms, first: int = 0):
         """CPURaytracer::SetTransforms, the option HIPRaytracer.set_transforms is on the GPU: the next Render() has objects
@@ -136,7 +153,19 @@ class CPURaytracer:
             return a.ctypes.data_as(ctypes.c_void_p) if a.size else None
         args = (self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights), len(self.lights),
                 ptr(self.rays), n, ptr(out), self.threads, ctypes.byref(traced), ctypes.byref(hits), ctypes.byref(secs), ctypes.byref(used))
-        if self.transforms is not None:
+        if self.visible is not None:
+            if self.supersample != 1:
+                raise ValueError("this front filters the constructor's scene only: set_visibility and supersample exclude each other")
+            fp = ctypes.POINTER(ctypes.c_float)
+            w, h, z, m, o = self.pose if self.pose is not None else (0, 0, 0.0, None, None)
+            mats, xf = self.materials, self.transforms
+            rc = self._lib.cpu_rt_render_set_visibility(*args, ptr(self.visible), 0, len(self.visible),
+                                                        ptr(xf) if xf is not None else None, 0, len(xf) if xf is not None else 0,
+                                                        ptr(mats) if mats is not None else None, 0, len(mats) if mats is not None else 0,
+                                                        ptr(self.new_rays) if self.new_rays is not None else None, w, h, z,
+                                                        m.ctypes.data_as(fp) if m is not None else None,
+                                                        o.ctypes.data_as(fp) if o is not None else None)
+        elif self.transforms is not None:
             if self.supersample != 1:
                 raise ValueError("this front filters the constructor's scene only: set_transforms and supersample exclude each other")
             fp = ctypes.POINTER(ctypes.c_float)

@@ -537,7 +537,7 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     }
     for (uint32_t i = 0; i < n_objs && c->affine_w; ++i) {
         const rt_object_data& o = static_cast<const rt_object_data*>(objs)[i];
-        if (o.type == 2u) continue;  // vertices, not matrices
+        if (o.type >= 2u) continue;  // vertices, not matrices - or a type that is never hit (RT_TYPE_HIDDEN among them): no kernel reads its rows
         c->affine_w = o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
                       o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f;
     }
@@ -548,7 +548,7 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             uint32_t mine = 0;
             for (size_t i = i0; i < i1; ++i) {
                 const rt_object_data& o = static_cast<const rt_object_data*>(objs)[i];
-                const bool affine = o.type == 2u || (o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
+                const bool affine = o.type >= 2u || (o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
                                                      o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f);
                 c->h_kind[i] = (uint8_t)(std::min(o.type, 3u) | (affine ? 0u : 0x80u));
                 mine += affine ? 0u : 1u;
@@ -1502,6 +1502,9 @@ void rt_destroy(rt_context* c) {
     if (c->d_hot) (void)hipFree(c->d_hot);
     if (c->d_cold) (void)hipFree(c->d_cold);
     if (c->d_objrec) (void)hipFree(c->d_objrec);
+    if (c->d_vis_types) (void)hipFree(c->d_vis_types);
+    if (c->d_vis_slots) (void)hipFree(c->d_vis_slots);
+    if (c->d_vis_stage) (void)hipFree(c->d_vis_stage);
     if (c->d_bounds) (void)hipFree(c->d_bounds);
     if (c->d_grid_cell_range) (void)hipFree(c->d_grid_cell_range);
     if (c->d_grid_cell_rec) (void)hipFree(c->d_grid_cell_rec);

@@ -1,6 +1,6 @@
 // rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
 // points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
-// tiles), rt_geometry.cpp (replaceable transforms) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in
+// tiles), rt_geometry.cpp (replaceable transforms), rt_visibility_host.cpp (replaceable visibility) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in
 // rt::host, apart from the launchers in rt::.
 #pragma once
 #include "hip_raytracer.h"
@@ -15,6 +15,7 @@
 #include "rt_light_tiles.h"
 #include "rt_materials.h"
 #include "rt_transforms.h"
+#include "rt_visibility.h"
 
 #include <hip/hip_runtime.h>
 
@@ -241,6 +242,15 @@ struct rt_context {
     uint32_t xf_stage_capacity = 0;
     hipEvent_t ev_xf[2] = {};
     rt_geometry_info_t geo_info = {};
+    // Replaceable visibility (rt_set_visibility, rt_visibility_host.cpp): the host mirror of the mask (1: hidden; empty until the first
+    // call - nothing is hidden), what the patch pass reads of rt_create on the device - the type word each object was created with
+    // (from h_kind; rt::kTypeKeep for a type other than 0, 1, 2) and its shadow slot, uploaded by the first call - and the staging
+    // buffer for a host mask (grow-only, in bytes).
+    std::vector<uint8_t> h_hidden;
+    uint32_t* d_vis_types = nullptr;
+    uint32_t* d_vis_slots = nullptr;
+    void* d_vis_stage = nullptr;
+    uint32_t vis_stage_capacity = 0;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -406,6 +416,8 @@ int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const 
 int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights);
 int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count);
 void apply_ray_domain(rt_context* c);
+// rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
+int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched
 int check_set_transforms(rt_context* c, const void* transforms, uint32_t first, uint32_t count);
 

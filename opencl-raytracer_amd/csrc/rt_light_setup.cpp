@@ -16,6 +16,7 @@ bool lights_need_literal(const rt_context* c, const rt_light* L, uint32_t n_ligh
         for (size_t i = i0; i < i1 && !near.load(std::memory_order_relaxed); ++i) {
             const double bx = c->h_obj_bounds[4 * i], by = c->h_obj_bounds[4 * i + 1], bz = c->h_obj_bounds[4 * i + 2], br = c->h_obj_bounds[4 * i + 3];
             if (!(br >= 0.0)) continue;  // never hit
+            if (!c->h_hidden.empty() && c->h_hidden[i]) continue;  // hidden (rt_set_visibility): a fresh context gives it no bound
             const double reach = br * (1.0 + 1e-4) + 1e-4 * (std::fabs(bx) + std::fabs(by) + std::fabs(bz) + br);
             for (uint32_t l = 0; l < n_lights; ++l) {
                 if (L[l].position[3] == 0.f) continue;

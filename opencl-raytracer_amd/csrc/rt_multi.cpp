@@ -314,6 +314,19 @@ int rt_set_transforms_multi(rt_multi* m, const void* transforms, uint32_t first,
     return RT_OK;
 }
 
+int rt_set_visibility_multi(rt_multi* m, const uint8_t* visible, uint32_t first, uint32_t count) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    for (rt_context* c : m->ctx) {  // all or none: the arguments are all a shard can refuse
+        const int rc = check_set_visibility(c, visible, first, count);
+        if (rc != RT_OK) return multi_fail(m, rc, c->error);
+    }
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = rt_set_visibility(m->ctx[r], visible, first, count);
+        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
+    }
+    return RT_OK;
+}
+
 uint64_t rt_multi_frame_elems(const rt_multi* m) { return m ? m->tiles * m->tile_rays : 0; }
 
 int rt_set_supersampling_multi(rt_multi* m, uint32_t s) {

@@ -241,6 +241,13 @@ class ShardedHIPRaytracer:
         torch.cuda.synchronize(self.device)
         self.rt.set_materials(materials, first)
 
+    def set_visibility(self, visible, first: int = 0):
+        """Hide or show objects first .. first + n - 1 of this rank's context (HIPRaytracer.set_visibility; every rank makes the
+        same call)."""
+        self.gatherer.drain()   # (a pipelined frame still reads the types in use)
+        torch.cuda.synchronize(self.device)
+        self.rt.set_visibility(visible, first)
+
     def set_transforms(self, transforms, first: int = 0):
         """Move objects first .. first + n - 1 of this rank's context (HIPRaytracer.set_transforms; every rank makes the same call):
         each rank patches its own copy of the object records and rebuilds its own light tiles, and keeps rendering its own tiles."""

@@ -45,6 +45,7 @@ EXPORTS = [
     "rt_set_materials", "rt_set_materials_device", "rt_set_materials_multi", "rt_read_materials",
     "rt_set_transforms", "rt_set_transforms_multi", "rt_read_transforms", "rt_get_geometry_info",
     "rt_read_pose_spheres", "rt_read_object_bounds", "rt_get_grid_constants",
+    "rt_set_visibility", "rt_set_visibility_device", "rt_set_visibility_multi", "rt_read_visibility",
 ]
 
 
@@ -280,6 +281,15 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_set_materials_multi.argtypes = [vp, vp, u32, u32]
         lib.rt_read_materials.restype = i32
         lib.rt_read_materials.argtypes = [vp, vp, u32, u32]
+    if hasattr(lib, "rt_set_visibility"):  # (the same: a build from before replaceable visibility)
+        lib.rt_set_visibility.restype = i32
+        lib.rt_set_visibility.argtypes = [vp, vp, u32, u32]
+        lib.rt_set_visibility_device.restype = i32
+        lib.rt_set_visibility_device.argtypes = [vp, vp, u32, u32, vp]
+        lib.rt_set_visibility_multi.restype = i32
+        lib.rt_set_visibility_multi.argtypes = [vp, vp, u32, u32]
+        lib.rt_read_visibility.restype = i32
+        lib.rt_read_visibility.argtypes = [vp, vp, u32, u32]
     if hasattr(lib, "rt_set_transforms"):  # (the same: a build from before replaceable transforms)
         lib.rt_set_transforms.restype = i32
         lib.rt_set_transforms.argtypes = [vp, vp, u32, u32]
@@ -705,6 +715,38 @@ class HIPRaytracer:
         self._check(self._lib.rt_get_geometry_info(self._ctx, ctypes.byref(info)))
         return info.as_dict()
 
+    # -- replaceable visibility (hip_raytracer.h: every copy of the type word patched on the device; no table is rebuilt) ----
+    def set_visibility(self, visible, first: int = 0):
+        """Hide (0) or show (non-zero) objects first .. first + n - 1 of a live context: the next frame is the one a fresh context
+        created with records.with_visibility(objects, visible, first) renders, bit for bit. `visible` is a numpy array (or a
+        sequence) of n entries (rt_set_visibility), or a torch bool / uint8 tensor on the context's device - contiguous, one byte
+        per object, at any alignment - which is patched in on the GPU, ordered behind the work of torch's current stream
+        (rt_set_visibility_device). Synchronous: on return the tensor may be overwritten."""
+        try:
+            import torch
+            is_tensor = isinstance(visible, torch.Tensor)
+        except ImportError:
+            is_tensor = False
+        if not is_tensor:
+            mask = np.ascontiguousarray(np.asarray(visible).reshape(-1) != 0, dtype=np.uint8)
+            self._check(self._lib.rt_set_visibility(self._ctx, _ptr(mask) if mask.shape[0] else None, int(first), int(mask.shape[0])))
+            return
+        if not visible.is_cuda or visible.dtype not in (torch.bool, torch.uint8) or not visible.is_contiguous():
+            raise ValueError("a device mask is a contiguous bool or uint8 tensor on the GPU, one element per object")
+        with torch.cuda.device(visible.device):
+            stream = torch.cuda.current_stream().cuda_stream
+        self._check(self._lib.rt_set_visibility_device(self._ctx, ctypes.c_void_p(visible.data_ptr()) if visible.numel() else None,
+                                                       int(first), visible.numel(), ctypes.c_void_p(stream) if stream else None))
+
+    def read_visibility(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """rt_read_visibility: one uint8 per object first .. first + count - 1 (count None: up to the last object), 1 visible,
+        0 hidden, read from every device copy of the type word; RTError if two copies disagree."""
+        first = int(first)
+        count = self._n_objs - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=np.uint8)
+        self._check(self._lib.rt_read_visibility(self._ctx, _ptr(out), first, count))
+        return out
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -836,6 +878,12 @@ class MultiHIPRaytracer:
         `materials` is a numpy MATERIAL_DTYPE array or an OBJECT_DTYPE array whose material fields are taken."""
         mats = materials_of(materials)
         self._check(self._lib.rt_set_materials_multi(self._m, _ptr(mats), int(first), int(mats.shape[0])))
+
+    def set_visibility(self, visible, first: int = 0):
+        """Hide (0) or show (non-zero) objects first .. first + n - 1 on every shard (rt_set_visibility_multi): all shards or
+        none. `visible` is a numpy array or a sequence."""
+        mask = np.ascontiguousarray(np.asarray(visible).reshape(-1) != 0, dtype=np.uint8)
+        self._check(self._lib.rt_set_visibility_multi(self._m, _ptr(mask) if mask.shape[0] else None, int(first), int(mask.shape[0])))
 
     def set_transforms(self, transforms, first: int = 0):
         """Move objects first .. first + n - 1 on every shard (rt_set_transforms_multi): all shards or none. `transforms` is a

@@ -362,6 +362,15 @@ void CPURaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& t
     for (size_t i = 0; i < transforms.size(); ++i) set_transform(surfaces[first + i], instances[first + i], transforms[i].mv, transforms[i].mvInverse);
 }
 
+void CPURaytracer::SetVisibility(uint32_t first, const std::vector<uint8_t>& visible) {
+    if ((uint64_t)first + visible.size() > instances.size()) throw std::invalid_argument("SetVisibility: first + count exceeds the object count");
+    for (size_t i = 0; i < visible.size(); ++i) {
+        const int created = static_cast<int>(objects[first + i].type);
+        if (created > 1) continue;  // never hit as it is: left alone
+        instances[first + i].type = visible[i] ? created : static_cast<int>(kTypeHidden);
+    }
+}
+
 void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9], const float origin[3]) {
     if (!m || !origin) throw std::invalid_argument("SetPose: the matrix or the origin is null");
     if (width > 0x1000000u || height > 0x1000000u || width * height != rays.size())

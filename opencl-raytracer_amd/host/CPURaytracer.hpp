@@ -59,6 +59,11 @@ public:
     // mv / mvInverse put them; materials and type stay. std::invalid_argument for a range beyond the objects.
     void SetTransforms(uint32_t first, const std::vector<Transform>& transforms);
 
+    // Replaceable visibility, the same option as HIPRaytracer's: the next Render() does not hit objects first .. first + n - 1 whose
+    // entry of `visible` is 0 (their type becomes kTypeHidden), and hits the others as the constructor's type says.
+    // std::invalid_argument for a range beyond the objects.
+    void SetVisibility(uint32_t first, const std::vector<uint8_t>& visible);
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

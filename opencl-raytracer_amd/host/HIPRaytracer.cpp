@@ -160,6 +160,21 @@ void HIPRaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& t
     if (rt_set_transforms(ctx, ts.data(), first, (uint32_t)ts.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetTransforms: ") + rt_last_error(ctx));
 }
 
+void HIPRaytracer::SetVisibility(uint32_t first, const std::vector<uint8_t>& visible) {
+    if (multi) {
+        if (rt_set_visibility_multi(multi, visible.data(), first, (uint32_t)visible.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetVisibility: ") + rt_multi_last_error(multi));
+        return;
+    }
+    if (rt_set_visibility(ctx, visible.data(), first, (uint32_t)visible.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetVisibility: ") + rt_last_error(ctx));
+}
+
+std::vector<uint8_t> HIPRaytracer::ReadVisibility(uint32_t first, uint32_t count) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    std::vector<uint8_t> out(count);
+    if (rt_read_visibility(c, out.data(), first, count) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::ReadVisibility: ") + rt_last_error(c));
+    return out;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

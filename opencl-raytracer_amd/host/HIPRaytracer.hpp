@@ -83,6 +83,15 @@ public:
     // rt_get_geometry_info: the dynamic set and what the last SetTransforms did. The several-GPU object reports its first shard's.
     rt_geometry_info_t GeometryInfo();
 
+    // Replaceable visibility (hip_raytracer.h, "replaceable visibility"): the next Render() does not hit objects first .. first + n - 1
+    // whose entry of `visible` is 0, and hits the others as the constructor's type says; indices, materials and matrices stay. Every
+    // copy of the type word is patched on the GPU(s), no table is rebuilt. Synchronous; the several-GPU object patches every shard,
+    // all or none. Throws std::runtime_error with the library's message for what it refuses (a range beyond the objects).
+    void SetVisibility(uint32_t first, const std::vector<uint8_t>& visible);
+    // rt_read_visibility: 1 / 0 per object first .. first + count - 1, read from every device copy of the type word. The several-GPU
+    // object reads its first shard's.
+    std::vector<uint8_t> ReadVisibility(uint32_t first, uint32_t count);
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

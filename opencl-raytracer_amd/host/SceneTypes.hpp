@@ -193,6 +193,9 @@ public:
     PrimativeType type;
 };
 
+// The type word of a hidden object, what SetVisibility writes (rt_records.h: RT_TYPE_HIDDEN): none of the kernels' cases - never hit.
+constexpr uint32_t kTypeHidden = 0x40000000u;
+
 // The two matrices of an ObjectData that the kernels read, what SetTransforms replaces (rt_records.h: rt_transform). The caller
 // supplies both, as it does through ObjectData; `Transform(mv)` takes the inverse the way ObjectData's constructor does.
 struct Transform {

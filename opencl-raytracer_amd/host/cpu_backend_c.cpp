@@ -19,6 +19,8 @@ struct Materials { const rt_material* m; uint32_t first, count; };
 thread_local const Materials* g_materials = nullptr;  // cpu_rt_render_set_materials: what SetMaterials gets before Render()
 struct Transforms { const rt_transform* t; uint32_t first, count; };
 thread_local const Transforms* g_transforms = nullptr;  // cpu_rt_render_set_transforms: what SetTransforms gets before Render()
+struct Visibility { const uint8_t* v; uint32_t first, count; };
+thread_local const Visibility* g_visibility = nullptr;  // cpu_rt_render_set_visibility: what SetVisibility gets before Render()
 
 Material host_material(const rt_material& d) {
     Material m;
@@ -117,6 +119,10 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
         }
         try { backend->SetTransforms(g_transforms->first, ts); } catch (const std::exception&) { return -1; }
     }
+    if (g_visibility) {
+        const std::vector<uint8_t> mask(g_visibility->v, g_visibility->v + g_visibility->count);
+        try { backend->SetVisibility(g_visibility->first, mask); } catch (const std::exception&) { return -1; }
+    }
     const uint64_t n_out = backend->Pixels();
     IRaytracer* raytracer = backend.get();  // everything below goes through the reference's interface
     const auto t0 = std::chrono::steady_clock::now();
@@ -199,6 +205,26 @@ int cpu_rt_render_set_transforms(int kernel, uint32_t max_bounces, const void* o
     const int rc = cpu_rt_render_set_materials(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced, hit_pixels,
                                                seconds, threads_used, materials_, first, count, new_rays_, width, height, z, m, origin);
     g_transforms = nullptr;
+    return rc;
+}
+
+// CPURaytracer::SetVisibility through the C entry: the backend is constructed with `objs_` and renders after
+// SetVisibility(v_first, visible_[0 .. v_count)) - one byte per object, 0 hidden. The arguments behind them are
+// cpu_rt_render_set_transforms' (transforms_ NULL with t_count 0: none), so that the options combine. Same outputs and return value
+// as cpu_rt_render; -1 also for a range beyond the objects.
+int cpu_rt_render_set_visibility(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                                 const void* rays_, uint64_t n_rays, float* out, unsigned int threads, uint64_t* rays_traced,
+                                 uint64_t* hit_pixels, double* seconds, unsigned int* threads_used, const void* visible_, uint32_t v_first,
+                                 uint32_t v_count, const void* transforms_, uint32_t t_first, uint32_t t_count, const void* materials_,
+                                 uint32_t first, uint32_t count, const void* new_rays_, uint32_t width, uint32_t height, float z, const float* m,
+                                 const float* origin) {
+    if (!visible_ && v_count) return -1;
+    const Visibility vis{static_cast<const uint8_t*>(visible_), v_first, v_count};
+    g_visibility = &vis;
+    const int rc = cpu_rt_render_set_transforms(kernel, max_bounces, objs_, n_objs, lights_, n_lights, rays_, n_rays, out, threads, rays_traced, hit_pixels,
+                                                seconds, threads_used, transforms_, t_first, t_count, materials_, first, count, new_rays_, width, height,
+                                                z, m, origin);
+    g_visibility = nullptr;
     return rc;
 }
 

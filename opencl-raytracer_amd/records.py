@@ -316,6 +316,31 @@ def with_transforms(objs, transforms, first: int = 0) -> np.ndarray:
     return out
 
 
+TYPE_HIDDEN = 0x40000000  # RT_TYPE_HIDDEN (rt_records.h): rt_set_visibility's type word for a hidden object - never hit
+
+
+def visibility_of(objs) -> np.ndarray:
+    """The mask an object array carries: one uint8 per record, 0 where its type is TYPE_HIDDEN, 1 elsewhere."""
+    objs = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE)
+    return (objs["type"] != TYPE_HIDDEN).astype(np.uint8)
+
+
+def with_visibility(objs, visible, first: int = 0) -> np.ndarray:
+    """The object array a fresh context is created with for the frame rt_set_visibility(visible, first) leaves a live one with -
+    its executable definition. `objs` is the array the context was created with; the copy returned has type = TYPE_HIDDEN on
+    the records first .. first + len(visible) - 1 whose mask entry is 0 and whose type is 0, 1 or 2 (any other type is never
+    hit anyway and is left alone); non-zero entries keep the type of `objs`. Everything else is untouched."""
+    out = np.ascontiguousarray(objs, dtype=OBJECT_DTYPE).copy()
+    mask = np.ascontiguousarray(visible).reshape(-1) != 0
+    first = int(first)
+    n = mask.shape[0]
+    if first < 0 or first + n > out.shape[0]:
+        raise ValueError("first + len(visible) exceeds the object count")
+    ty = out["type"][first:first + n]
+    out["type"][first:first + n] = np.where(~mask & (ty <= 2), np.uint32(TYPE_HIDDEN), ty)
+    return out
+
+
 def lights_array(recs) -> np.ndarray:
     recs = list(recs)
     out = np.zeros(len(recs), dtype=LIGHT_DTYPE)
