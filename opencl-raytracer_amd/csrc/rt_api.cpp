@@ -373,13 +373,6 @@ int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
     return RT_OK;
 }
 
-int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count) {
-    if ((uint64_t)first + (uint64_t)count > (uint64_t)c->n_objs)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "first + count exceeds the context's object count");
-    if (count && !materials) return fail(c, RT_ERR_INVALID_ARGUMENT, "materials is NULL with a non-zero count");
-    return RT_OK;
-}
-
 }  // namespace rt::host
 
 using namespace rt::host;
@@ -952,114 +945,9 @@ int rt_set_lights(rt_context* c, const void* lights, uint32_t n_lights) {
         RT_HIP(c, hipStreamSynchronize(c->stream));  // `lights` may be pageable and is the caller's again on return
     }
     c->n_lights = n_lights;
-    c->h_lights.assign(L, L + n_lights);  // (rt_set_transforms rebuilds the light tiles and evaluates the predicate below again)
-    // RT_FLAG_DEVICE_OPENCL's predicate on the lights, for these lights (rt_create: lights_need_literal)
-    if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal) {
-        c->lights_literal = lights_need_literal(c, L, n_lights);
-        if (c->base_flags != (c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u))) c->tiles_dirty = true;  // (a table's verdict depends on the literal flag)
-        c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
-        c->forced_literal = c->lights_literal;
-        apply_ray_domain(c);
-    }
+    c->h_lights.assign(L, L + n_lights);  // (rt_set_transforms and rt_set_visibility evaluate the predicate below again, the former rebuilds the light tiles)
+    refresh_lights_literal(c, L, n_lights);
     return build_light_tiles_device(c, L);
-}
-
-// ---- replaceable materials (hip_raytracer.h) ----
-// Nothing of a context is derived from a material but the words repack_objects and the ObjectRecord fill copy out of it, so new
-// materials are one patch pass over those two arrays (rt_materials.hip). The host form stages its array in device memory and
-// takes the same pass.
-// d_src: `count` records in device memory, valid behind what `stream` holds already. Enqueues the patch there and waits for it.
-// ev (or null): three events, [0] recorded by the caller before its upload, if any.
-static int patch_materials_on(rt_context* c, const void* d_src, uint32_t first, uint32_t count, hipStream_t stream, hipEvent_t* ev) {
-    if (ev) RT_HIP(c, hipEventRecord(ev[1], stream));
-    const hipError_t e = rt::launch_patch_materials(static_cast<const float4*>(d_src), first, count, c->d_cold, c->d_objrec, c->n_objs, stream);
-    if (e != hipSuccess) return fail_hip(c, e, "material patch launch");
-    if (ev) RT_HIP(c, hipEventRecord(ev[2], stream));
-    RT_HIP(c, hipStreamSynchronize(stream));  // synchronous like rt_set_lights: the array is the caller's again, any stream's next frame sees it
-    if (ev) {  // engineering aid (RT_MATERIALS_TRACE=1, tools/ab/set_materials_timing.py): device time of the upload and of the patch
-        float copy_ms = 0.f, patch_ms = 0.f;
-        RT_HIP(c, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-        RT_HIP(c, hipEventElapsedTime(&patch_ms, ev[1], ev[2]));
-        std::fprintf(stderr, "[rt_set_materials] copy %.4f ms patch %.4f ms materials %u\n", (double)copy_ms, (double)patch_ms, count);
-    }
-    return RT_OK;
-}
-
-namespace {
-struct MaterialTrace {  // three events when RT_MATERIALS_TRACE is set, destroyed on every exit path
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool on = false;
-    ~MaterialTrace() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-}  // namespace
-
-int rt_set_materials_device(rt_context* c, const void* d_materials, uint32_t first, uint32_t count, void* hip_stream) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int refused = check_set_materials(c, d_materials, first, count);
-    if (refused) return refused;
-    if (reinterpret_cast<uintptr_t>(d_materials) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the material array must be 16-byte aligned");
-    if (count == 0) return RT_OK;
-    RT_DEVICE(c);
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);  // NULL: the legacy default stream, as for rt_set_rays_device
-    MaterialTrace trace;
-    if (std::getenv("RT_MATERIALS_TRACE")) {
-        for (hipEvent_t& e : trace.ev) RT_HIP(c, hipEventCreate(&e));
-        trace.on = true;
-        RT_HIP(c, hipEventRecord(trace.ev[0], stream));
-    }
-    return patch_materials_on(c, d_materials, first, count, stream, trace.on ? trace.ev : nullptr);
-}
-
-int rt_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int refused = check_set_materials(c, materials, first, count);
-    if (refused) return refused;
-    if (count == 0) return RT_OK;
-    RT_DEVICE(c);
-    if (count > c->mat_stage_capacity) {  // grow-only; a failed allocation leaves the context as it was
-        void* d = nullptr;
-        RT_HIP(c, hipMalloc(&d, sizeof(rt_material) * (size_t)count));
-        if (c->d_mat_stage) (void)hipFree(c->d_mat_stage);
-        c->d_mat_stage = d;
-        c->mat_stage_capacity = count;
-    }
-    MaterialTrace trace;
-    if (std::getenv("RT_MATERIALS_TRACE")) {
-        for (hipEvent_t& e : trace.ev) RT_HIP(c, hipEventCreate(&e));
-        trace.on = true;
-        RT_HIP(c, hipEventRecord(trace.ev[0], c->stream));
-    }
-    // (the copy takes the bytes as they are: `materials` may have any alignment)
-    RT_HIP(c, hipMemcpyAsync(c->d_mat_stage, materials, sizeof(rt_material) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    return patch_materials_on(c, c->d_mat_stage, first, count, c->stream, trace.on ? trace.ev : nullptr);
-}
-
-int rt_read_materials(rt_context* c, void* materials, uint32_t first, uint32_t count) {
-    if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int refused = check_set_materials(c, materials, first, count);
-    if (refused) return refused;
-    if (count == 0) return RT_OK;
-    RT_DEVICE(c);
-    std::vector<rt::ColdObject> cold(count);
-    std::vector<rt::ObjectRecord> rec(count);
-    RT_HIP(c, hipMemcpy(cold.data(), c->d_cold + first, sizeof(rt::ColdObject) * (size_t)count, hipMemcpyDeviceToHost));
-    RT_HIP(c, hipMemcpy(rec.data(), c->d_objrec + first, sizeof(rt::ObjectRecord) * (size_t)count, hipMemcpyDeviceToHost));
-    uint8_t* out = static_cast<uint8_t*>(materials);  // (any alignment: the records are assembled here and copied out)
-    for (uint32_t i = 0; i < count; ++i) {
-        const rt::ColdObject& k = cold[i];
-        if (std::memcmp(&k.amb_absorb.w, &rec[i].absorption, 4) != 0)
-            return fail(c, RT_ERR_STATE, "rt_read_materials: object " + std::to_string((uint64_t)first + i) +
-                                             ": ObjectRecord::absorption does not hold the bits of ColdObject::amb_absorb.w");
-        rt_material m;
-        std::memset(&m, 0, sizeof(m));  // the five words no kernel reads: 0
-        std::memcpy(m.ambient, &k.amb_absorb, 12);
-        std::memcpy(m.diffuse, &k.dif_shine, 12);
-        std::memcpy(m.specular, &k.spec_type, 12);
-        std::memcpy(&m.absorption, &k.amb_absorb.w, 4);
-        std::memcpy(&m.shininess, &k.dif_shine.w, 4);
-        std::memcpy(out + sizeof(rt_material) * (size_t)i, &m, sizeof(m));
-    }
-    return RT_OK;
 }
 
 int rt_read_grid_pretest(const rt_context* c, float* pre, uint64_t n) {
@@ -1504,7 +1392,6 @@ void rt_destroy(rt_context* c) {
     if (c->d_objrec) (void)hipFree(c->d_objrec);
     if (c->d_vis_types) (void)hipFree(c->d_vis_types);
     if (c->d_vis_slots) (void)hipFree(c->d_vis_slots);
-    if (c->d_vis_stage) (void)hipFree(c->d_vis_stage);
     if (c->d_bounds) (void)hipFree(c->d_bounds);
     if (c->d_grid_cell_range) (void)hipFree(c->d_grid_cell_range);
     if (c->d_grid_cell_rec) (void)hipFree(c->d_grid_cell_rec);
@@ -1556,8 +1443,7 @@ void rt_destroy(rt_context* c) {
     if (c->d_samples) (void)hipFree(c->d_samples);
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->h_scan) (void)hipHostFree(c->h_scan);
-    if (c->d_mat_stage) (void)hipFree(c->d_mat_stage);
-    if (c->d_xf_stage) (void)hipFree(c->d_xf_stage);
+    if (c->d_patch_stage) (void)hipFree(c->d_patch_stage);
     for (hipEvent_t ev : c->ev_xf) if (ev) (void)hipEventDestroy(ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);

@@ -1,7 +1,8 @@
 // rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
 // points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
-// tiles), rt_geometry.cpp (replaceable transforms), rt_visibility_host.cpp (replaceable visibility) and rt_multi.cpp (several GPUs). Everything with external linkage here lives in
-// rt::host, apart from the launchers in rt::.
+// tiles), rt_object_patch.cpp (what the calls that patch a range of objects share; replaceable materials), rt_geometry.cpp (replaceable
+// transforms), rt_visibility_host.cpp (replaceable visibility) and rt_multi.cpp (several GPUs). Everything with external linkage here
+// lives in rt::host, apart from the launchers in rt::.
 #pragma once
 #include "hip_raytracer.h"
 #include "rt_records.h"
@@ -223,14 +224,16 @@ struct rt_context {
     bool rays_off_grid = false;
     rt::RayScan* d_scan = nullptr;          // the ray scan's result (rt_rays.hip) and its pinned host mirror
     rt::RayScan* h_scan = nullptr;
-    void* d_mat_stage = nullptr;            // rt_set_materials' staging buffer for a host array (grow-only) and its size in records
-    uint32_t mat_stage_capacity = 0;
+    // The staging buffer of the calls that patch a range of objects from a host array (rt_set_materials, rt_set_transforms,
+    // rt_set_visibility; rt_object_patch.cpp: ensure_patch_stage): one, grow-only, as large as the largest call so far needed.
+    void* d_patch_stage = nullptr;
+    size_t patch_stage_bytes = 0;
     // Replaceable transforms (rt_set_transforms, rt_geometry.cpp). Of the objects: type and "both bottom rows are (0,0,0,1)" per object
     // (bits 0-1 and bit 7), how many are not affine, and the position rt_create's size order gave each in the shadow stream. Of the
     // lights: a host copy (the light tiles are rebuilt, RT_FLAG_DEVICE_OPENCL's predicate is evaluated again). Of the grid: what
     // build_grid's radii were evaluated with (GridRadii, below), the create-time always-list and behind it the DYNAMIC objects - every
     // object an accepted call has named, tested by every ray from then on (the list the kernels read is d_grid_always, kMaxAlways
-    // entries). The staging buffer holds a call's records and, behind them, their shadow slots (grow-only, in records).
+    // entries). A call stages its records in d_patch_stage and, behind them (at sizeof(rt_transform) * count of that call), their shadow slots.
     std::vector<uint8_t> h_kind;
     uint32_t n_not_affine = 0;
     std::vector<uint32_t> h_shadow_slot;
@@ -238,19 +241,15 @@ struct rt_context {
     double grid_cell = 0.0, grid_diag = 0.0, grid_s_max = 0.0, grid_k2 = 1.0;
     std::vector<uint32_t> h_always;
     uint32_t n_unbounded = 0;
-    void* d_xf_stage = nullptr;
-    uint32_t xf_stage_capacity = 0;
     hipEvent_t ev_xf[2] = {};
     rt_geometry_info_t geo_info = {};
     // Replaceable visibility (rt_set_visibility, rt_visibility_host.cpp): the host mirror of the mask (1: hidden; empty until the first
     // call - nothing is hidden), what the patch pass reads of rt_create on the device - the type word each object was created with
-    // (from h_kind; rt::kTypeKeep for a type other than 0, 1, 2) and its shadow slot, uploaded by the first call - and the staging
-    // buffer for a host mask (grow-only, in bytes).
+    // (from h_kind; rt::kTypeKeep for a type other than 0, 1, 2) and its shadow slot, uploaded by the first call. A host mask is
+    // staged in d_patch_stage.
     std::vector<uint8_t> h_hidden;
     uint32_t* d_vis_types = nullptr;
     uint32_t* d_vis_slots = nullptr;
-    void* d_vis_stage = nullptr;
-    uint32_t vis_stage_capacity = 0;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -414,8 +413,32 @@ int pose_grid(rt_context* c, uint32_t width, uint32_t height, float z, const flo
 int pose_check(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, PoseVerdict& v);
 int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const PoseVerdict& v);
 int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights);
-int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count);
 void apply_ray_domain(rt_context* c);
+// rt_object_patch.cpp: what the calls that patch a range [first, first + count) of a live context's objects share.
+// The two refusals of a range and its array `p`, named `what` in the message; nothing is touched. Both at once: the range's, unless null_first.
+int check_object_range(rt_context* c, const void* p, uint32_t first, uint32_t count, const char* what, bool null_first = false);
+int check_set_materials(rt_context* c, const void* materials, uint32_t first, uint32_t count);
+int ensure_patch_stage(rt_context* c, size_t bytes);  // c->d_patch_stage holds `bytes`; a failed call leaves the context as it was
+void refresh_lights_literal(rt_context* c, const rt_light* L, uint32_t n_lights);
+// Engineering aid: device time of a patch call's upload and of its pass, on stderr as "[label] copy .. ms patch .. ms unit count"
+// (tools/ab/*_timing.py). Three events, created only when the variable `env` is set and destroyed on every exit path.
+struct PatchTrace {
+    rt_context* c;
+    const char *env, *label, *unit;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    bool on = false;
+    PatchTrace(rt_context* ctx, const char* env_name, const char* bracket_label, const char* unit_word)
+        : c(ctx), env(env_name), label(bracket_label), unit(unit_word) {}
+    ~PatchTrace();
+    PatchTrace(const PatchTrace&) = delete;
+    PatchTrace& operator=(const PatchTrace&) = delete;
+    int begin(hipStream_t stream);                               // before the upload, if any
+    int uploaded(hipStream_t stream) { return mark(1, stream); }  // before the pass
+    int patched(hipStream_t stream) { return mark(2, stream); }   // behind the pass
+    int report(uint32_t count);                                  // once the stream is synchronised
+private:
+    int mark(int k, hipStream_t stream);
+};
 // rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched

@@ -38,10 +38,8 @@ uint32_t dynamic_capacity(const rt_context* c) { return c->grid.enabled && c->n_
 
 // Every refusal, over the whole range; the bounds of the accepted transforms for the caller that goes on (or null).
 int plan_transforms(rt_context* c, const void* transforms, uint32_t first, uint32_t count, std::vector<Bound>* bounds_out) {
-    if (count && !transforms) return fail(c, RT_ERR_INVALID_ARGUMENT, "transforms is NULL with a non-zero count");
-    if ((uint64_t)first + (uint64_t)count > (uint64_t)c->n_objs)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "first + count exceeds the context's object count");
-    if (count == 0) return RT_OK;
+    const int refused = check_object_range(c, transforms, first, count, "transforms", true);
+    if (refused || count == 0) return refused;
     for (uint32_t m = 0; m < count; ++m)
         if ((c->h_kind[first + m] & 0x7fu) > 1u)
             return fail(c, RT_ERR_INVALID_ARGUMENT, "object " + std::to_string((uint64_t)first + m) +
@@ -107,18 +105,13 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
     if (count == 0) return RT_OK;
     RT_DEVICE(c);
     // ---- the records ----
-    const size_t slots_at = sizeof(rt_transform) * (size_t)count;  // the shadow slots behind the records (a multiple of 128)
-    if (count > c->xf_stage_capacity) {  // grow-only; a failed allocation leaves the context as it was
-        void* d = nullptr;
-        RT_HIP(c, hipMalloc(&d, slots_at + sizeof(uint32_t) * (size_t)count));
-        if (c->d_xf_stage) (void)hipFree(c->d_xf_stage);
-        c->d_xf_stage = d;
-        c->xf_stage_capacity = count;
-    }
+    const size_t slots_at = sizeof(rt_transform) * (size_t)count;  // the shadow slots behind THIS call's records (a multiple of 128)
+    const int staged = ensure_patch_stage(c, slots_at + sizeof(uint32_t) * (size_t)count);
+    if (staged != RT_OK) return staged;
     for (hipEvent_t& e : c->ev_xf)
         if (!e) RT_HIP(c, hipEventCreate(&e));
     std::vector<uint32_t> slots(c->h_shadow_slot.begin() + first, c->h_shadow_slot.begin() + first + count);
-    uint8_t* stage = static_cast<uint8_t*>(c->d_xf_stage);
+    uint8_t* stage = static_cast<uint8_t*>(c->d_patch_stage);
     RT_HIP(c, hipEventRecord(c->ev_xf[0], c->stream));
     // (the copies take the bytes as they are: `transforms` may have any alignment)
     RT_HIP(c, hipMemcpyAsync(stage, transforms, slots_at, hipMemcpyHostToDevice, c->stream));
@@ -155,15 +148,7 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
     }
     c->affine_w = c->n_not_affine == 0;
     c->rects_dirty = true;
-    // RT_FLAG_DEVICE_OPENCL's predicate on the lights, for the objects where they now are (as rt_set_lights evaluates it for new lights)
-    if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal &&
-        c->h_obj_bounds.size() == 4 * (size_t)c->n_objs) {
-        c->lights_literal = lights_need_literal(c, c->h_lights.data(), c->n_lights);
-        if (c->base_flags != (c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u))) c->tiles_dirty = true;  // (a table's verdict depends on the literal flag)
-        c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
-        c->forced_literal = c->lights_literal;
-        apply_ray_domain(c);
-    }
+    refresh_lights_literal(c, c->h_lights.data(), c->n_lights);  // (the predicate on the lights, for the objects where they now are)
     if (!c->grid.enabled) return RT_OK;
 
     // ---- the grid: registration spheres for where the objects are, the dynamic set, the light tiles ----
@@ -206,10 +191,8 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
 
 int rt_read_transforms(rt_context* c, void* transforms, uint32_t first, uint32_t count) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (count && !transforms) return fail(c, RT_ERR_INVALID_ARGUMENT, "transforms is NULL with a non-zero count");
-    if ((uint64_t)first + (uint64_t)count > (uint64_t)c->n_objs)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "first + count exceeds the context's object count");
-    if (count == 0) return RT_OK;
+    const int refused = check_object_range(c, transforms, first, count, "transforms", true);
+    if (refused || count == 0) return refused;
     for (uint32_t m = 0; m < count; ++m)
         if ((c->h_kind[first + m] & 0x7fu) > 1u)
             return fail(c, RT_ERR_INVALID_ARGUMENT, "rt_read_transforms: object " + std::to_string((uint64_t)first + m) + " is neither a sphere nor a box");

@@ -135,6 +135,21 @@ int multi_run_frame(rt_multi* m, void* target, bool to_host, int format = 0) {
     return RT_OK;
 }
 
+// A call every context takes, all or none: `check` (every refusal, nothing touched) on every context, then `apply` on every context.
+template <class Check, class Apply>
+int multi_all_or_none(rt_multi* m, Check check, Apply apply) {
+    if (!m) return RT_ERR_INVALID_ARGUMENT;
+    for (rt_context* c : m->ctx) {
+        const int rc = check(c);
+        if (rc != RT_OK) return multi_fail(m, rc, c->error);
+    }
+    for (size_t r = 0; r < m->ctx.size(); ++r) {
+        const int rc = apply(m->ctx[r]);
+        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,56 +290,26 @@ int rt_set_pose_multi(rt_multi* m, uint32_t width, uint32_t height, float z, con
     return RT_OK;
 }
 
+// All or none: what a shard can refuse of such a call it refuses on the host, before anything is touched (check_set_*).
 int rt_set_lights_multi(rt_multi* m, const void* lights, uint32_t n_lights) {
-    if (!m) return RT_ERR_INVALID_ARGUMENT;
-    for (rt_context* c : m->ctx) {  // all or none: the arguments are all a shard can refuse
-        const int rc = check_set_lights(c, lights, n_lights);
-        if (rc != RT_OK) return multi_fail(m, rc, c->error);
-    }
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        const int rc = rt_set_lights(m->ctx[r], lights, n_lights);
-        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
-    }
-    return RT_OK;
+    return multi_all_or_none(m, [&](rt_context* c) { return check_set_lights(c, lights, n_lights); },
+                             [&](rt_context* c) { return rt_set_lights(c, lights, n_lights); });
 }
 
 int rt_set_materials_multi(rt_multi* m, const void* materials, uint32_t first, uint32_t count) {
-    if (!m) return RT_ERR_INVALID_ARGUMENT;
-    for (rt_context* c : m->ctx) {  // all or none: the arguments are all a shard can refuse
-        const int rc = check_set_materials(c, materials, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, c->error);
-    }
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        const int rc = rt_set_materials(m->ctx[r], materials, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
-    }
-    return RT_OK;
+    return multi_all_or_none(m, [&](rt_context* c) { return check_set_materials(c, materials, first, count); },
+                             [&](rt_context* c) { return rt_set_materials(c, materials, first, count); });
 }
 
+// (every refusal is the host's: bounds, the grid box, the dynamic set's room, per shard)
 int rt_set_transforms_multi(rt_multi* m, const void* transforms, uint32_t first, uint32_t count) {
-    if (!m) return RT_ERR_INVALID_ARGUMENT;
-    for (rt_context* c : m->ctx) {  // all or none: every refusal is the host's (bounds, the grid box, the dynamic set's room), per shard
-        const int rc = check_set_transforms(c, transforms, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, c->error);
-    }
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        const int rc = rt_set_transforms(m->ctx[r], transforms, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
-    }
-    return RT_OK;
+    return multi_all_or_none(m, [&](rt_context* c) { return check_set_transforms(c, transforms, first, count); },
+                             [&](rt_context* c) { return rt_set_transforms(c, transforms, first, count); });
 }
 
 int rt_set_visibility_multi(rt_multi* m, const uint8_t* visible, uint32_t first, uint32_t count) {
-    if (!m) return RT_ERR_INVALID_ARGUMENT;
-    for (rt_context* c : m->ctx) {  // all or none: the arguments are all a shard can refuse
-        const int rc = check_set_visibility(c, visible, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, c->error);
-    }
-    for (size_t r = 0; r < m->ctx.size(); ++r) {
-        const int rc = rt_set_visibility(m->ctx[r], visible, first, count);
-        if (rc != RT_OK) return multi_fail(m, rc, "shard " + std::to_string(r) + ": " + m->ctx[r]->error);
-    }
-    return RT_OK;
+    return multi_all_or_none(m, [&](rt_context* c) { return check_set_visibility(c, visible, first, count); },
+                             [&](rt_context* c) { return rt_set_visibility(c, visible, first, count); });
 }
 
 uint64_t rt_multi_frame_elems(const rt_multi* m) { return m ? m->tiles * m->tile_rays : 0; }

@@ -9,10 +9,7 @@
 namespace rt::host {
 
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count) {
-    if ((uint64_t)first + (uint64_t)count > (uint64_t)c->n_objs)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "first + count exceeds the context's object count");
-    if (count && !visible) return fail(c, RT_ERR_INVALID_ARGUMENT, "visible is NULL with a non-zero count");
-    return RT_OK;
+    return check_object_range(c, visible, first, count, "visible");
 }
 
 namespace {
@@ -44,8 +41,10 @@ int ensure_support(rt_context* c) {
 // the host's side of an accepted call: `mask` is the `count` bytes the pass has read
 void follow_the_types(rt_context* c, const uint8_t* mask, uint32_t first, uint32_t count) {
     if (c->h_hidden.empty()) c->h_hidden.assign(c->n_objs, 0);
-    for (uint32_t m = 0; m < count; ++m)
-        c->h_hidden[first + m] = (mask[m] == 0 && created_word(c->h_kind[first + m]) != rt::kTypeKeep) ? 1 : 0;
+    // (all of the call that grows with count: locals, since a byte store may alias the context, and no branch on the mask's bytes)
+    uint8_t* const hidden = c->h_hidden.data() + first;
+    const uint8_t* const kind = c->h_kind.data() + first;
+    for (uint32_t m = 0; m < count; ++m) hidden[m] = (uint8_t)((mask[m] == 0) & (created_word(kind[m]) != rt::kTypeKeep));
     // the last sphere / box of the scene decides what a NaN ray ends with (rt_create): the last VISIBLE one
     c->nan_winner = -1;
     c->nan_winner_sphere = false;
@@ -53,40 +52,38 @@ void follow_the_types(rt_context* c, const uint8_t* mask, uint32_t first, uint32
         const uint32_t ty = c->h_kind[i] & 0x7fu;
         if (ty <= 1u && !c->h_hidden[i]) { c->nan_winner = (int)i; c->nan_winner_sphere = (ty == 0u); break; }
     }
-    // RT_FLAG_DEVICE_OPENCL's predicate on the lights, without the hidden objects (as rt_set_lights evaluates it for new lights)
-    if ((c->user_flags & RT_FLAG_DEVICE_OPENCL) && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal &&
-        c->h_obj_bounds.size() == 4 * (size_t)c->n_objs) {
-        c->lights_literal = lights_need_literal(c, c->h_lights.data(), c->n_lights);
-        if (c->base_flags != (c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u))) c->tiles_dirty = true;  // (a table's verdict depends on the literal flag)
-        c->base_flags = c->user_flags | (c->lights_literal ? RT_FLAG_LITERAL : 0u);
-        c->forced_literal = c->lights_literal;
-        apply_ray_domain(c);
-    }
+    refresh_lights_literal(c, c->h_lights.data(), c->n_lights);  // (the predicate on the lights, without the hidden objects)
 }
 
-struct VisibilityTrace {  // three events when RT_VISIBILITY_TRACE is set, destroyed on every exit path
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool on = false;
-    ~VisibilityTrace() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
-// d_src: `count` bytes in device memory, valid behind what `stream` holds already. Enqueues the patch there and waits for it.
-// ev (or null): three events, [0] recorded by the caller before its upload, if any.
-int patch_visibility_on(rt_context* c, const uint8_t* d_src, uint32_t first, uint32_t count, hipStream_t stream, hipEvent_t* ev) {
-    if (ev) RT_HIP(c, hipEventRecord(ev[1], stream));
+// Both forms of the call. d_src: `count` bytes in device memory, valid behind what `stream` holds already - or, with the caller's host
+// mask h_mask, null: the mask is staged and uploaded on `stream`. Enqueues the patch there and waits for it; the host's mirror follows
+// the bytes the pass read, which the device form copies back behind the pass on the same stream (the caller's kernels have written them).
+int set_visibility_from(rt_context* c, const uint8_t* d_src, hipStream_t stream, const uint8_t* h_mask, uint32_t first, uint32_t count) {
+    const int refused = check_set_visibility(c, h_mask ? h_mask : d_src, first, count);
+    if (refused || count == 0) return refused;
+    RT_DEVICE(c);
+    if (const int rc = ensure_support(c)) return rc;
+    if (h_mask) {
+        if (const int rc = ensure_patch_stage(c, (size_t)count)) return rc;
+        d_src = static_cast<const uint8_t*>(c->d_patch_stage);
+    }
+    PatchTrace trace(c, "RT_VISIBILITY_TRACE", "rt_set_visibility", "objects");  // (tools/ab/set_visibility_timing.py)
+    if (const int rc = trace.begin(stream)) return rc;
+    if (h_mask) RT_HIP(c, hipMemcpyAsync(c->d_patch_stage, h_mask, (size_t)count, hipMemcpyHostToDevice, stream));
+    if (const int rc = trace.uploaded(stream)) return rc;
     const rt::VisibilityTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->d_vis_types, c->d_vis_slots, c->n_objs};
     const hipError_t e = rt::launch_patch_visibility(d_src, first, count, to, stream);
     if (e != hipSuccess) return fail_hip(c, e, "visibility patch launch");
-    if (ev) RT_HIP(c, hipEventRecord(ev[2], stream));
-    return RT_OK;
-}
-
-int report(rt_context* c, hipEvent_t* ev, uint32_t count) {  // engineering aid (RT_VISIBILITY_TRACE=1, tools/ab/set_visibility_timing.py)
-    float copy_ms = 0.f, patch_ms = 0.f;
-    RT_HIP(c, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    RT_HIP(c, hipEventElapsedTime(&patch_ms, ev[1], ev[2]));
-    std::fprintf(stderr, "[rt_set_visibility] copy %.4f ms patch %.4f ms objects %u\n", (double)copy_ms, (double)patch_ms, count);
-    return RT_OK;
+    if (const int rc = trace.patched(stream)) return rc;
+    std::vector<uint8_t> read_back;
+    if (!h_mask) {
+        read_back.resize(count);
+        RT_HIP(c, hipMemcpyAsync(read_back.data(), d_src, (size_t)count, hipMemcpyDeviceToHost, stream));
+        h_mask = read_back.data();
+    }
+    RT_HIP(c, hipStreamSynchronize(stream));  // synchronous like rt_set_materials: the mask is the caller's again, any stream's next frame sees it
+    follow_the_types(c, h_mask, first, count);
+    return trace.report(count);
 }
 
 }  // namespace
@@ -98,56 +95,13 @@ extern "C" {
 
 int rt_set_visibility_device(rt_context* c, const void* d_visible, uint32_t first, uint32_t count, void* hip_stream) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int refused = check_set_visibility(c, d_visible, first, count);
-    if (refused) return refused;
-    if (count == 0) return RT_OK;
-    RT_DEVICE(c);
-    const int rc = ensure_support(c);
-    if (rc != RT_OK) return rc;
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);  // NULL: the legacy default stream, as for rt_set_materials_device
-    std::vector<uint8_t> mask(count);
-    VisibilityTrace trace;
-    if (std::getenv("RT_VISIBILITY_TRACE")) {
-        for (hipEvent_t& e : trace.ev) RT_HIP(c, hipEventCreate(&e));
-        trace.on = true;
-        RT_HIP(c, hipEventRecord(trace.ev[0], stream));
-    }
-    const int launched = patch_visibility_on(c, static_cast<const uint8_t*>(d_visible), first, count, stream, trace.on ? trace.ev : nullptr);
-    if (launched != RT_OK) return launched;
-    // the bytes the pass read, for the host's mirror (behind the pass on the same stream: the caller's kernels have written them)
-    RT_HIP(c, hipMemcpyAsync(mask.data(), d_visible, (size_t)count, hipMemcpyDeviceToHost, stream));
-    RT_HIP(c, hipStreamSynchronize(stream));  // synchronous like rt_set_materials: the mask is the caller's again, any stream's next frame sees it
-    follow_the_types(c, mask.data(), first, count);
-    return trace.on ? report(c, trace.ev, count) : RT_OK;
+    // (a NULL stream: the legacy default stream, as for rt_set_materials_device)
+    return set_visibility_from(c, static_cast<const uint8_t*>(d_visible), static_cast<hipStream_t>(hip_stream), nullptr, first, count);
 }
 
 int rt_set_visibility(rt_context* c, const uint8_t* visible, uint32_t first, uint32_t count) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    const int refused = check_set_visibility(c, visible, first, count);
-    if (refused) return refused;
-    if (count == 0) return RT_OK;
-    RT_DEVICE(c);
-    const int rc = ensure_support(c);
-    if (rc != RT_OK) return rc;
-    if (count > c->vis_stage_capacity) {  // grow-only; a failed allocation leaves the context as it was
-        void* d = nullptr;
-        RT_HIP(c, hipMalloc(&d, (size_t)count));
-        if (c->d_vis_stage) (void)hipFree(c->d_vis_stage);
-        c->d_vis_stage = d;
-        c->vis_stage_capacity = count;
-    }
-    VisibilityTrace trace;
-    if (std::getenv("RT_VISIBILITY_TRACE")) {
-        for (hipEvent_t& e : trace.ev) RT_HIP(c, hipEventCreate(&e));
-        trace.on = true;
-        RT_HIP(c, hipEventRecord(trace.ev[0], c->stream));
-    }
-    RT_HIP(c, hipMemcpyAsync(c->d_vis_stage, visible, (size_t)count, hipMemcpyHostToDevice, c->stream));
-    const int launched = patch_visibility_on(c, static_cast<const uint8_t*>(c->d_vis_stage), first, count, c->stream, trace.on ? trace.ev : nullptr);
-    if (launched != RT_OK) return launched;
-    RT_HIP(c, hipStreamSynchronize(c->stream));  // synchronous like rt_set_materials
-    follow_the_types(c, visible, first, count);
-    return trace.on ? report(c, trace.ev, count) : RT_OK;
+    return set_visibility_from(c, nullptr, c->stream, visible, first, count);
 }
 
 int rt_read_visibility(rt_context* c, uint8_t* visible, uint32_t first, uint32_t count) {

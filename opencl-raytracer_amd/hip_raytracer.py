@@ -340,6 +340,13 @@ def _ptr(a: np.ndarray | None):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _current_stream_of(tensor) -> int:
+    """The raw handle of torch's current stream on the tensor's device (0: the legacy default stream)."""
+    import torch
+    with torch.cuda.device(tensor.device):
+        return torch.cuda.current_stream().cuda_stream
+
+
 class HIPRaytracer:
     """IRaytracer backend for one MI355X."""
 
@@ -531,8 +538,7 @@ class HIPRaytracer:
             raise TypeError("set_rays takes a numpy ray array or a torch tensor on the context's device")
         if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
             raise ValueError("a device ray tensor is float32, contiguous, on the GPU, with 8 elements per ray")
-        with torch.cuda.device(rays.device):
-            stream = torch.cuda.current_stream().cuda_stream
+        stream = _current_stream_of(rays)
         self._check(self._lib.rt_set_rays_device(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.numel() // 8,
                                                  ctypes.c_void_p(stream) if stream else None))
 
@@ -567,8 +573,7 @@ class HIPRaytracer:
                 raise ValueError("a device ray tensor is float32, contiguous, on the GPU, with 8 elements per ray")
             tensor = out
             if stream is None:
-                with torch.cuda.device(out.device):
-                    stream = torch.cuda.current_stream().cuda_stream
+                stream = _current_stream_of(out)
             ptr = out.data_ptr()
         else:
             ptr = out
@@ -658,6 +663,15 @@ class HIPRaytracer:
         self._check(self._lib.rt_read_light_tiles(self._ctx, _ptr(start), start.size, _ptr(entries), len(entries)))
         return start, entries[:info["n_entries"]]
 
+    def _read_range(self, fn, dtype, first, count) -> np.ndarray:
+        """What read_materials, read_transforms and read_visibility share: fn(ctx, out, first, count) into a new array of `dtype`,
+        one element per object first .. first + count - 1 (count None: up to the last object)."""
+        first = int(first)
+        count = self._n_objs - first if count is None else int(count)
+        out = np.zeros(max(count, 0), dtype=dtype)
+        self._check(fn(self._ctx, _ptr(out), first, count))
+        return out
+
     # -- replaceable materials (hip_raytracer.h: the material words of the object records, patched on the device) ------------
     def set_materials(self, materials, first: int = 0):
         """Replace the materials of objects first .. first + n - 1 of a live context: the next frame is the one a fresh context
@@ -675,19 +689,14 @@ class HIPRaytracer:
             raise TypeError("set_materials takes a numpy material or object array, or a torch tensor on the context's device")
         if not materials.is_cuda or materials.dtype != torch.float32 or not materials.is_contiguous() or materials.numel() % 16:
             raise ValueError("a device material tensor is float32, contiguous, on the GPU, with 16 elements per material")
-        with torch.cuda.device(materials.device):
-            stream = torch.cuda.current_stream().cuda_stream
+        stream = _current_stream_of(materials)
         self._check(self._lib.rt_set_materials_device(self._ctx, ctypes.c_void_p(materials.data_ptr()) if materials.numel() else None,
                                                       int(first), materials.numel() // 16, ctypes.c_void_p(stream) if stream else None))
 
     def read_materials(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """rt_read_materials: the MATERIAL_DTYPE records of objects first .. first + count - 1 (count None: up to the last object)
         as the kernels read them - the eleven live floats; reflection, transparency and the pad lanes read 0."""
-        first = int(first)
-        count = self._n_objs - first if count is None else int(count)
-        out = np.zeros(max(count, 0), dtype=MATERIAL_DTYPE)
-        self._check(self._lib.rt_read_materials(self._ctx, _ptr(out), first, count))
-        return out
+        return self._read_range(self._lib.rt_read_materials, MATERIAL_DTYPE, first, count)
 
     # -- replaceable transforms (hip_raytracer.h: every copy of mv / mvInverse patched on the device; grid contexts: the dynamic set) --
     def set_transforms(self, transforms, first: int = 0):
@@ -702,11 +711,7 @@ class HIPRaytracer:
     def read_transforms(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """rt_read_transforms: the TRANSFORM_DTYPE records of objects first .. first + count - 1 (count None: up to the last
         object), reassembled from the device records; RTError if two copies of a word disagree."""
-        first = int(first)
-        count = self._n_objs - first if count is None else int(count)
-        out = np.zeros(max(count, 0), dtype=TRANSFORM_DTYPE)
-        self._check(self._lib.rt_read_transforms(self._ctx, _ptr(out), first, count))
-        return out
+        return self._read_range(self._lib.rt_read_transforms, TRANSFORM_DTYPE, first, count)
 
     def geometry_info(self) -> dict:
         """rt_get_geometry_info: grid_built, n_unbounded, n_dynamic, dynamic_capacity, dynamic_ids (a list of n_dynamic object
@@ -733,19 +738,14 @@ class HIPRaytracer:
             return
         if not visible.is_cuda or visible.dtype not in (torch.bool, torch.uint8) or not visible.is_contiguous():
             raise ValueError("a device mask is a contiguous bool or uint8 tensor on the GPU, one element per object")
-        with torch.cuda.device(visible.device):
-            stream = torch.cuda.current_stream().cuda_stream
+        stream = _current_stream_of(visible)
         self._check(self._lib.rt_set_visibility_device(self._ctx, ctypes.c_void_p(visible.data_ptr()) if visible.numel() else None,
                                                        int(first), visible.numel(), ctypes.c_void_p(stream) if stream else None))
 
     def read_visibility(self, first: int = 0, count: int | None = None) -> np.ndarray:
         """rt_read_visibility: one uint8 per object first .. first + count - 1 (count None: up to the last object), 1 visible,
         0 hidden, read from every device copy of the type word; RTError if two copies disagree."""
-        first = int(first)
-        count = self._n_objs - first if count is None else int(count)
-        out = np.zeros(max(count, 0), dtype=np.uint8)
-        self._check(self._lib.rt_read_visibility(self._ctx, _ptr(out), first, count))
-        return out
+        return self._read_range(self._lib.rt_read_visibility, np.uint8, first, count)
 
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))

@@ -83,33 +83,25 @@ HIPRaytracer::~HIPRaytracer() {
     rt_destroy_multi(multi);
 }
 
+// what a call of the one-GPU or of the several-GPU object returned: anything but RT_OK throws the library's message for that object
+void HIPRaytracer::Check(int rc, const char* method) const {
+    if (rc != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::") + method + ": " + (multi ? rt_multi_last_error(multi) : rt_last_error(ctx)));
+}
+
 cl_float4* HIPRaytracer::Render() {
     const float* out = nullptr;
-    if (multi) {
-        if (rt_render_multi(multi, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::Render: ") + rt_multi_last_error(multi));
-        return reinterpret_cast<cl_float4*>(const_cast<float*>(out));
-    }
-    if (rt_render(ctx, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::Render: ") + rt_last_error(ctx));
+    Check(multi ? rt_render_multi(multi, &out) : rt_render(ctx, &out), "Render");
     return reinterpret_cast<cl_float4*>(const_cast<float*>(out));
 }
 
 const uint8_t* HIPRaytracer::RenderPacked(rt_pixel_format format) {
     const uint8_t* out = nullptr;
-    if (multi) {
-        if (rt_render_multi_packed(multi, format, &out) != RT_OK)
-            throw std::runtime_error(std::string("HIPRaytracer::RenderPacked: ") + rt_multi_last_error(multi));
-        return out;
-    }
-    if (rt_render_packed(ctx, format, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::RenderPacked: ") + rt_last_error(ctx));
+    Check(multi ? rt_render_multi_packed(multi, format, &out) : rt_render_packed(ctx, format, &out), "RenderPacked");
     return out;
 }
 
 void HIPRaytracer::SetSupersampling(unsigned int s) {
-    if (multi) {
-        if (rt_set_supersampling_multi(multi, s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetSupersampling: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_supersampling(ctx, s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetSupersampling: ") + rt_last_error(ctx));
+    Check(multi ? rt_set_supersampling_multi(multi, s) : rt_set_supersampling(ctx, s), "SetSupersampling");
 }
 
 void HIPRaytracer::SetRays(const std::vector<Ray3D>& rays_) {
@@ -118,33 +110,22 @@ void HIPRaytracer::SetRays(const std::vector<Ray3D>& rays_) {
 }
 
 void HIPRaytracer::SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream) {
-    if (multi) {
-        if (rt_set_pose_multi(multi, width, height, z, m, origin) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetPose: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_pose(ctx, width, height, z, m, origin, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetPose: ") + rt_last_error(ctx));
+    Check(multi ? rt_set_pose_multi(multi, width, height, z, m, origin) : rt_set_pose(ctx, width, height, z, m, origin, stream), "SetPose");
 }
 
 void HIPRaytracer::SetLights(const std::vector<Light>& lights_) {
     std::vector<rt_light> ls;
     ls.reserve(lights_.size());
     for (const Light& l : lights_) ls.push_back(to_device(l));
-    if (multi) {
-        if (rt_set_lights_multi(multi, ls.data(), (uint32_t)ls.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetLights: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_lights(ctx, ls.data(), (uint32_t)ls.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetLights: ") + rt_last_error(ctx));
+    Check(multi ? rt_set_lights_multi(multi, ls.data(), (uint32_t)ls.size()) : rt_set_lights(ctx, ls.data(), (uint32_t)ls.size()), "SetLights");
 }
 
 void HIPRaytracer::SetMaterials(uint32_t first, const std::vector<Material>& materials) {
     std::vector<rt_material> ms;
     ms.reserve(materials.size());
     for (const Material& m : materials) ms.push_back(to_device(m));
-    if (multi) {
-        if (rt_set_materials_multi(multi, ms.data(), first, (uint32_t)ms.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetMaterials: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_materials(ctx, ms.data(), first, (uint32_t)ms.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetMaterials: ") + rt_last_error(ctx));
+    const uint32_t n = (uint32_t)ms.size();
+    Check(multi ? rt_set_materials_multi(multi, ms.data(), first, n) : rt_set_materials(ctx, ms.data(), first, n), "SetMaterials");
 }
 
 void HIPRaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& transforms) {
@@ -153,19 +134,13 @@ void HIPRaytracer::SetTransforms(uint32_t first, const std::vector<Transform>& t
         std::memcpy(ts[i].mv, transforms[i].mv.data(), sizeof(ts[i].mv));
         std::memcpy(ts[i].mvInverse, transforms[i].mvInverse.data(), sizeof(ts[i].mvInverse));
     }
-    if (multi) {
-        if (rt_set_transforms_multi(multi, ts.data(), first, (uint32_t)ts.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetTransforms: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_transforms(ctx, ts.data(), first, (uint32_t)ts.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetTransforms: ") + rt_last_error(ctx));
+    const uint32_t n = (uint32_t)ts.size();
+    Check(multi ? rt_set_transforms_multi(multi, ts.data(), first, n) : rt_set_transforms(ctx, ts.data(), first, n), "SetTransforms");
 }
 
 void HIPRaytracer::SetVisibility(uint32_t first, const std::vector<uint8_t>& visible) {
-    if (multi) {
-        if (rt_set_visibility_multi(multi, visible.data(), first, (uint32_t)visible.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetVisibility: ") + rt_multi_last_error(multi));
-        return;
-    }
-    if (rt_set_visibility(ctx, visible.data(), first, (uint32_t)visible.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetVisibility: ") + rt_last_error(ctx));
+    const uint32_t n = (uint32_t)visible.size();
+    Check(multi ? rt_set_visibility_multi(multi, visible.data(), first, n) : rt_set_visibility(ctx, visible.data(), first, n), "SetVisibility");
 }
 
 std::vector<uint8_t> HIPRaytracer::ReadVisibility(uint32_t first, uint32_t count) {
@@ -218,10 +193,7 @@ rt_rays_info_t HIPRaytracer::RaysInfo() {
 
 rt_stats_t HIPRaytracer::Stats() {
     rt_stats_t s;
-    if (multi) {  // several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures
-        if (rt_get_stats_multi(multi, &s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::Stats: ") + rt_multi_last_error(multi));
-        return s;
-    }
-    if (rt_get_stats(ctx, &s) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::Stats: ") + rt_last_error(ctx));
+    // (several GPUs: the counters summed over the shards, the slowest shard's kernel time - the whole frame's figures)
+    Check(multi ? rt_get_stats_multi(multi, &s) : rt_get_stats(ctx, &s), "Stats");
     return s;
 }

@@ -103,6 +103,7 @@ public:
     rt_context* Context() { return ctx; }
 
 private:
+    void Check(int rc, const char* method) const;  // throws "HIPRaytracer::<method>: " + the last error of ctx or of multi
     rt_context* ctx = nullptr;
     rt_multi* multi = nullptr;   // set instead of ctx by the several-GPU constructor
 };
