@@ -18,6 +18,7 @@
 // at the traversal calls; tests require both paths to agree bit for bit.
 #include "rt_kernels.h"
 #include "rt_grid.h"
+#include "rt_walk_stash.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1135,6 +1136,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WA
 #ifndef RT_WALK3_REFILL_MIN
 #define RT_WALK3_REFILL_MIN RT_WALK2_REFILL_MIN
 #endif
+#ifndef RT_WALK3_TAKE_MIN
+#define RT_WALK3_TAKE_MIN RT_WALK3_REFILL_MIN  // idle lanes that make a prepare / take worth its round, where rays come from the stash. A take is
+#endif                             // a copy, and 4 / 8 / 12 are faster than 16 by ~0.15 ms per cfg4 frame - but 8 against 16 missed "every run faster
+                                   // than every run" in seven alternated runs by one pair (docs/LOG.md, first section): not kept
 #ifndef RT_WALK3_DEFER_PENDING
 #define RT_WALK3_DEFER_PENDING 16  // exact tests of the block walk once this many lanes hold a candidate (a trip is ~300 instructions here, the
 #endif                             // test ~150): cfg4 frame with 8 / 12 / 16 / 24: 12.07 / 11.93 / 11.99 / 12.06 ms, 16 with half the lanes stuck: 11.92
@@ -1200,6 +1205,10 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                                               uint32_t wave, uint32_t n_waves, uint32_t* __restrict__ run_ctr,
                                               unsigned long long& tested) {
     const uint32_t lane = threadIdx.x & 63u;
+    // (The wave's number comes from threadIdx: uniform, but not to the compiler. Left as it is, `next`, `seg_end` and with them
+    // the stash's head and count live in vector registers, and every pass of the loop pays some ten vector instructions of
+    // compares and exec-mask branches for decisions that are scalar. The mesh instances keep the parent's code.)
+    if constexpr (!TRI) wave = __builtin_amdgcn_readfirstlane(wave);
     RunCursor rc;   // runs of queue entries and their tickets (wave-uniform)
     if (!rc.begin(n_queue, wave, n_waves, run_ctr, lane)) return;
     uint32_t& next = rc.next;
@@ -1226,13 +1235,41 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
     uint32_t cur = 0;                         // block to look at next (bits 0-23) and the entry to resume it at (bits 24-26)
     float fx = 0.f, fy = 0.f, fz = 0.f;       // current cell, padded coordinates (whole numbers)
     float tx = 0.f, ty = 0.f, tz = 0.f, dtx = 0.f, dty = 0.f, dtz = 0.f;
-    float T = kMaxFloat, limit = 0.f, t_stop = 0.f, slack = 0.f;
+    float T = kMaxFloat, limit = 0.f, t_stop = 0.f;
     int idx = -1;
     uint32_t pend_k = 0, done_k = 0xffffffffu;
+    // How far past a hit at T the walk goes on (limit = min(T + slack, t_stop)). Kept per lane only by the mesh instances; the
+    // others need the register for the prepare and make it anew when a hit is taken - that is when it is wanted - which costs
+    // a reciprocal square root there. (bg.cell through an empty asm: see the prepare.)
+    float slack = 0.f;
+    auto slack_of = [&](float dd_) -> float {
+        if constexpr (TRI) return slack;
+        float cell = bg.cell;
+        asm volatile("" : "+s"(cell));
+        return dd_ > 0.f ? kWalkSlackCells * cell * __builtin_amdgcn_rsqf(dd_) * 1.0001f : 3.0e38f;
+    };
+
+    // Prepared rays (rt_walk_stash.h): a ray's set-up depends on nothing but its queue entry, so the wave does it for up to 64
+    // consecutive entries at once, with all lanes, and idle lanes later copy their next ray from here. Wave-private - the four
+    // waves of a workgroup run independent loops and never wait for each other - and field-major, one 64-word row per field:
+    // the prepare (lane j writes word j of every row) and the take (consecutive idle lanes read consecutive words) meet no
+    // bank conflict. 4 x 19 x 64 words = 19 456 B per workgroup: six workgroups fit a CU's 160 KiB, one wave each per SIMD.
+    enum : uint32_t { SF_CUR, SF_PIX, SF_SX, SF_SY, SF_SZ, SF_DX, SF_DY, SF_DZ, SF_FX, SF_FY, SF_FZ, SF_TX, SF_TY, SF_TZ, SF_DTX, SF_DTY, SF_DTZ,
+                      SF_TSTOP, SF_DONE, kStashFields };
+    // SF_CUR: the first block (bits 0-23) and what the taking lane does with the slot
+    constexpr uint32_t kStashCell = 0xffffffu;
+    constexpr uint32_t kStashStart = 0x80000000u;  // the ray starts a walk (else: the lane stores its result and stays idle)
+    constexpr uint32_t kStashBrute = 0x40000000u;  // not this walk's kind of ray: every object is tested one by one
+    static_assert(4u * kStashFields * kStashSlots * sizeof(uint32_t) <= 24576u, "the stash must leave room for six workgroups per CU");
+    __shared__ uint32_t stash_mem[4][kStashFields][kStashSlots];
+    uint32_t (*const stash)[kStashSlots] = stash_mem[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3u];  // (uniform: a scalar register)
+    WalkStash sh;  // wave-uniform
 
     for (;;) {
-        // ---- hand out rays to idle lanes ----
         const unsigned long long idle = __ballot((fl & kAlive) == 0u);
+        if constexpr (TRI) {
+        // ---- meshes: rays are set up by the lanes that fall idle, at the moment they do. (With the triangle test the kernel wants
+        // ~95 registers and lives with 17 spilled; the prepare below, run beside every lane's walk, made that 24.) ----
         if (next < seg_end && ((uint32_t)__popcll(idle) >= (uint32_t)RT_WALK3_REFILL_MIN || idle == ~0ull)) {
             const uint32_t mine = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
             if (STATS && lane == 0u) ++s_refill;
@@ -1251,11 +1288,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                 slack = dd > 0.f ? kWalkSlackCells * bg.cell * __builtin_amdgcn_rsqf(dd) * 1.0001f : 3.0e38f;
                 bool start = false, brute = false;
                 const Walk w0 = walk_begin(bg, ray, 3.0e38f);  // (a ray with a NaN in it: not alive)
-                if (w0.alive) {
-                    // (walk_segment: the rays this walk is made for; anything else tests every object here and now. Since round 4 a
-                    // frame whose PRIMARY directions fail this window is rendered by the literal loops as a whole - rt_create's ray scan,
-                    // rt_set_camera - and every origin lies in the grid box, so what is left for this branch are secondary rays with
-                    // |d|^2 outside (1e-30, 1e30): a light within 1e-15 of a hit point. Rare, slow, and the same result.)
+                if (w0.alive) {  // (the prepare below says which rays are `tame`)
                     const float dmin = __builtin_fminf(__builtin_fminf(w0.dtx, w0.dty), w0.dtz);
                     const bool tame = dd > 1.0e-30f && dd < 1.0e30f && w0.t_enter <= 4096.f * dmin;
                     brute = !tame;
@@ -1275,7 +1308,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                         if (STATS) ++tested;
                         if (cand) closest_take(t, k, sphere, T, idx, cur_sphere);
                     }
-                    limit = __builtin_fminf(T + slack, t_stop);
+                    limit = __builtin_fminf(T + slack_of(dd), t_stop);
                 }
                 if (!start) store_closest_result(w, pix, T, idx);  // no cell to look at, or everything tested already
                 fl = start ? (kAlive | (cur_sphere ? kSphere : 0u)) : 0u;
@@ -1283,9 +1316,130 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
             next += (uint32_t)__popcll(idle);
             if (next >= seg_end && more) more = grab();  // on to another run, if any is left
         }
+        } else {
+        const uint32_t n_idle = (uint32_t)__popcll(idle);
+        // ---- prepare: the next (up to) 64 queue entries, by all lanes, whatever they are walking ----
+        const uint32_t n_prep = sh.to_prepare(n_idle, (uint32_t)RT_WALK3_TAKE_MIN, next, seg_end);
+        if (n_prep != 0u) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the loads of earlier takes come before these stores)
+            __builtin_amdgcn_wave_barrier();
+            if (lane < n_prep) {
+                uint32_t sl = lane;  // this lane's slot (through an empty asm: its LDS address is made here, not kept across the loop)
+                asm volatile("" : "+v"(sl));
+                const uint32_t mine = next + lane;
+                const uint32_t entry = w.identity_queue ? mine : queue[mine];
+                const uint32_t p_pix = w.identity_queue ? mine : (entry & kQueuePixel);
+                Ray ray;
+                if (w.first_round != 0u) {
+                    // (closest_ray's primary branch, with its divisors through an empty asm: their reciprocals, computed once per
+                    // wave, would otherwise sit in vector registers across the whole loop - see the grid box below)
+                    RenderParams rp = w.rp;
+                    asm volatile("" : "+s"(rp.width), "+s"(rp.bundles_x), "+s"(rp.run_rays));
+                    ray = primary_ray(rp, global_ray_of(rp, p_pix));
+                } else {
+                    ray = load_ray(w, p_pix, kSlotClosest);
+                }
+                const uint32_t note = __float_as_uint(ray.dw);  // begin_shade_lit's note: the object a reflection ray leaves
+                ray.sw = 1.0f; ray.dw = 0.0f;  // what every ray of a grid-able frame carries (rt_create checks the preconditions)
+                const float p_dd = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
+                bool start = false, brute = false;
+                // (The grid box as walk_begin sees it goes through an empty asm: otherwise the box's far corner and the like are
+                // computed once per wave and kept in vector registers across the whole loop, which the trip cannot spare.)
+                struct { float lox, loy, loz, cell, inv_cell; int nx, ny, nz; } pg = {bg.lox, bg.loy, bg.loz, bg.cell, bg.inv_cell, bg.nx, bg.ny, bg.nz};
+                asm volatile("" : "+s"(pg.cell), "+s"(pg.nx), "+s"(pg.ny), "+s"(pg.nz));
+                const Walk w0 = walk_begin(pg, ray, 3.0e38f);  // (a ray with a NaN in it: not alive)
+                if (w0.alive) {
+                    // (walk_segment: the rays this walk is made for; anything else tests every object when its slot is taken. Since round 4 a
+                    // frame whose PRIMARY directions fail this window is rendered by the literal loops as a whole - rt_create's ray scan,
+                    // rt_set_camera - and every origin lies in the grid box, so what is left for this branch are secondary rays with
+                    // |d|^2 outside (1e-30, 1e30): a light within 1e-15 of a hit point. Rare, slow, and the same result.)
+                    const float dmin = __builtin_fminf(__builtin_fminf(w0.dtx, w0.dty), w0.dtz);
+                    const bool tame = p_dd > 1.0e-30f && p_dd < 1.0e30f && w0.t_enter <= 4096.f * dmin;
+                    brute = !tame;
+                    start = tame;
+                }
+                // A ray that starts no walk (a NaN in it, a miss of the grid box, a ray the walk is not made for) and the always-list
+                // (usually empty) have objects tested one by one and a result stored. The lane that takes the slot does that: an
+                // idle lane's walk registers are free, while here every lane still holds the walk it is in, and the exact test
+                // on top of that does not fit the kernel's 80 registers.
+                // (walk_begin leaves the cell of a ray that is not alive unset: it is read only for a ray that starts, and masked,
+                // so that nothing but a cell can reach the word's flag bits)
+                uint32_t word = brute ? kStashBrute : 0u;
+                if (start) {
+                    const uint32_t cell0 = ((uint32_t)(w0.iz + (int)kBlockBorder) * bg.wny + (uint32_t)(w0.iy + (int)kBlockBorder)) * bg.wnx + (uint32_t)(w0.ix + (int)kBlockBorder);
+                    word = kStashStart | (cell0 & kStashCell);
+                }
+                stash[SF_CUR][sl] = word;
+                stash[SF_PIX][sl] = p_pix;
+                stash[SF_SX][sl] = __float_as_uint(ray.sx); stash[SF_SY][sl] = __float_as_uint(ray.sy); stash[SF_SZ][sl] = __float_as_uint(ray.sz);
+                stash[SF_DX][sl] = __float_as_uint(ray.dx); stash[SF_DY][sl] = __float_as_uint(ray.dy); stash[SF_DZ][sl] = __float_as_uint(ray.dz);
+                if (start) {
+                    const float dmin = __builtin_fminf(__builtin_fminf(w0.dtx, w0.dty), w0.dtz);
+                    stash[SF_FX][sl] = __float_as_uint((float)(w0.ix + (int)kBlockBorder));
+                    stash[SF_FY][sl] = __float_as_uint((float)(w0.iy + (int)kBlockBorder));
+                    stash[SF_FZ][sl] = __float_as_uint((float)(w0.iz + (int)kBlockBorder));
+                    stash[SF_TX][sl] = __float_as_uint(w0.tx); stash[SF_TY][sl] = __float_as_uint(w0.ty); stash[SF_TZ][sl] = __float_as_uint(w0.tz);
+                    stash[SF_DTX][sl] = __float_as_uint(w0.dtx); stash[SF_DTY][sl] = __float_as_uint(w0.dty); stash[SF_DTZ][sl] = __float_as_uint(w0.dtz);
+                    stash[SF_TSTOP][sl] = __float_as_uint(__builtin_fminf(w0.t_exit + 0.25f * dmin, 3.0e38f));
+                    stash[SF_DONE][sl] = (w.first_round == 0u) ? note : 0xffffffffu;
+                }
+            }
+            next = sh.prepared(n_prep, next);
+            if (WalkStash::run_used_up(next, seg_end, more)) more = grab();  // on to another run, if any is left
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the slots are written before any lane of this wave reads them)
+            __builtin_amdgcn_wave_barrier();
+        }
+        // ---- take: idle lanes copy their next ray from the stash, in slot order ----
+        const uint32_t n_take = sh.to_take(n_idle, (uint32_t)RT_WALK3_TAKE_MIN);
+        if (n_take != 0u) {
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+            if (STATS && lane == 0u) ++s_refill;
+            if ((fl & kAlive) == 0u && rank < n_take) {
+                const uint32_t slot = (sh.take_from() + rank) & (kStashSlots - 1u);  // (head + rank < head + count <= 64)
+                const uint32_t c = stash[SF_CUR][slot];
+                if (STATS) ++s_rays;  // (the per-ray counters start at the take, for a ray that starts no walk too)
+                {
+                    pix = stash[SF_PIX][slot];
+                    rsx = __uint_as_float(stash[SF_SX][slot]); rsy = __uint_as_float(stash[SF_SY][slot]); rsz = __uint_as_float(stash[SF_SZ][slot]);
+                    rdx = __uint_as_float(stash[SF_DX][slot]); rdy = __uint_as_float(stash[SF_DY][slot]); rdz = __uint_as_float(stash[SF_DZ][slot]);
+                    T = kMaxFloat; idx = -1;
+                    bool cur_sphere = false;
+                    const bool brute = (c & kStashBrute) != 0u;
+                    const bool start = (c & kStashStart) != 0u;
+                    if (brute || g.n_always != 0u) {
+                        // objects every ray must test (usually none); a ray the walk is not made for tests them all
+                        const Ray ray = {rsx, rsy, rsz, 1.0f, rdx, rdy, rdz, 0.0f};
+                        const uint32_t n_loop = brute ? w.rp.scene.n_objs : g.n_always;
+                        for (uint32_t a = 0; a < n_loop; ++a) {
+                            const int k = brute ? (int)a : (int)g.always[a];
+                            float t;
+                            bool sphere;
+                            const bool cand = lane_candidate<AM, true, TRI>(hot + k, ray, t, sphere);
+                            if (STATS) ++tested;
+                            if (cand) closest_take(t, k, sphere, T, idx, cur_sphere);
+                        }
+                    }
+                    if (!start) store_closest_result(w, pix, T, idx);  // no cell to look at, or everything tested already: the lane stays idle
+                    if (start) {
+                        if (STATS) my_trips = 0;
+                        cur = c & kStashCell;
+                        fx = __uint_as_float(stash[SF_FX][slot]); fy = __uint_as_float(stash[SF_FY][slot]); fz = __uint_as_float(stash[SF_FZ][slot]);
+                        tx = __uint_as_float(stash[SF_TX][slot]); ty = __uint_as_float(stash[SF_TY][slot]); tz = __uint_as_float(stash[SF_TZ][slot]);
+                        dtx = __uint_as_float(stash[SF_DTX][slot]); dty = __uint_as_float(stash[SF_DTY][slot]); dtz = __uint_as_float(stash[SF_DTZ][slot]);
+                        t_stop = __uint_as_float(stash[SF_TSTOP][slot]);
+                        done_k = stash[SF_DONE][slot];
+                        dd = rdx * rdx + rdy * rdy + rdz * rdz;
+                        limit = idx < 0 ? t_stop : __builtin_fminf(T + slack_of(dd), t_stop);  // (no hit yet, T = kMaxFloat: min(T + slack, t_stop) is t_stop)
+                        fl = kAlive | (cur_sphere ? kSphere : 0u);
+                    }
+                }
+            }
+            sh.taken(n_take);
+        }
+        }
         const unsigned long long live = __ballot((fl & kAlive) != 0u);
         if (live == 0ull) {
-            if (next >= seg_end) break;
+            if (TRI ? next >= seg_end : sh.finished(next, seg_end)) break;
             continue;
         }
         // ---- one trip: the block under the cursor ----
@@ -1375,7 +1529,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                     bool cur_sphere = (fl & kSphere) != 0u;
                     if (cand) {
                         closest_take(t, (int)pend_k, sphere, T, idx, cur_sphere);
-                        limit = __builtin_fminf(T + slack, t_stop);
+                        limit = __builtin_fminf(T + slack_of(dd), t_stop);
                     }
                     fl = (fl & ~(kPend | kSphere)) | (cur_sphere ? kSphere : 0u);
                 }
