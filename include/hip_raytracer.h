@@ -72,7 +72,9 @@ extern "C" {
  *      read 3, rt_rays_info_t::reserved became primary_outside_box, rt_read_pose_spheres, rt_read_object_bounds,
  *      rt_get_grid_constants. Additions only; detect by dlsym of rt_read_pose_spheres.
  *      Later addition, same version: replaceable visibility - rt_set_visibility, rt_set_visibility_device, rt_read_visibility,
- *      rt_set_visibility_multi; RT_TYPE_HIDDEN in rt_records.h. Additions only; detect by dlsym of rt_set_visibility. */
+ *      rt_set_visibility_multi; RT_TYPE_HIDDEN in rt_records.h. Additions only; detect by dlsym of rt_set_visibility.
+ *      Later addition, same version: ray queries - rt_query_closest_device, rt_query_occluded_device, rt_query_closest,
+ *      rt_query_occluded, rt_query_primary, rt_get_query_info. Additions only; detect by dlsym of rt_query_closest_device. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -725,6 +727,75 @@ int rt_get_geometry_info(const rt_context* ctx, rt_geometry_info_t* info);
 int rt_set_visibility(rt_context* ctx, const uint8_t* visible, uint32_t first, uint32_t count);
 int rt_set_visibility_device(rt_context* ctx, const void* d_visible, uint32_t first, uint32_t count, void* hip_stream);
 int rt_read_visibility(rt_context* ctx, uint8_t* visible, uint32_t first, uint32_t count);
+
+/* ---- ray queries ----------------------------------------------------------------------------------------------------------------
+ * Closest hit and occlusion for a few rays of the caller's own, on a live context: the object under the mouse, line of sight between
+ * particles, collision and depth probes - without a frame (rt_render_aux traces every ray of the frame for one answer) and without a
+ * second RT_KERNEL_HITTEST context (a second grid, a second copy of the records, which sees none of this context's rt_set_transforms /
+ * rt_set_visibility). "intersect" / "occluded" of every library of this kind.
+ *
+ * `rays` are n 32-byte rt_ray records; n is ANY count, independent of the context's ray count. A query reads the context's object
+ * records and grid as the setters have left them and writes only the caller's outputs and a context-owned counter block. The frame's
+ * rays, camera, pose, shard, supersampling factor, aux buffers and state buffers are untouched: a render before and after a query is
+ * the same frame. It works on a context of any rt_kernel; max_bounces, lights and materials do not enter.
+ *
+ * Closest hit. (t[i], index[i]) is what rt_render_aux returns for work-item i of a FRESH RT_KERNEL_HITTEST context created with the
+ * context's current objects (the create-time array through records.with_transforms / with_visibility as set so far), the same
+ * arithmetic flags (RT_FLAG_UNFUSED, RT_FLAG_DEVICE_OPENCL), these rays and RT_FLAG_NO_RAYGEN - bit for bit. t is the loop's value:
+ * 3.402823466e+38f on a miss, NaN where the loop ends with NaN; index follows the hittest rule of rt_set_aux_device: the winner where
+ * t < MAX_FLOAT, else -1. Either output may be NULL, not both.
+ * Occlusion. occluded[i] = !(T >= 1.f || T < 0) ? 1 : 0 with T that closest-hit time: the reference's shadow predicate
+ * (shade_and_reflect_kernel.cl:229) - something lies on the segment start .. start + direction. A NaN T reads occluded.
+ *
+ * Route, decided in the kernel by each lane for its own ray (csrc/rt_query.hip; rays.query_route is the executable definition). The
+ * grid serves a ray iff the context has a grid (rt_rays_info_t::grid_built) and is not literal by its objects or by the caller - it
+ * was not created with RT_FLAG_LITERAL and holds no degenerate instance (a singular or non-finite mvInverse, for which rt_create
+ * renders literally: NaN times for finite rays make the result depend on the order of the loop) -, every component of the ray is finite, start.w == 1.0f,
+ * direction.w == 0.0f, dd = (dx*dx + dy*dy) + dz*dz lies in (1e-30, 1e30), and the origin lies inside box_lo .. box_hi of
+ * rt_get_rays_info - compared in fp32 against the box rounded INWARDS (lo up, hi down), so that a ray the double box excludes is never
+ * admitted. Every other ray runs the ordered brute-force loop over all objects: the reference's loop in the reference's order, NaN and
+ * zero-direction rays included (no closed form is consulted). Such a ray costs n_objs tests in one lane and keeps its wave until it is
+ * done (the brute-force lanes of a wave share one pass): the price of never refusing a ray and never approximating one. The
+ * frame-level predicates - directions_in_domain, `literal`, a pose outside the box - play no part: a query's domain is per ray.
+ *
+ * rt_query_closest_device / rt_query_occluded_device: d_rays and the outputs are device memory on the context's device, d_rays
+ * 16-BYTE ALIGNED, d_t / d_index 4-byte aligned. ASYNCHRONOUS on hip_stream (NULL: the legacy default stream), behind the caller's
+ * kernels that made the rays: no host synchronisation, and no allocation after the first call - a one-ray pick costs a launch. The
+ * rays and outputs must stay valid until the stream has passed the query. Queries, setters and renders of one context on different
+ * streams are ordered by the caller, as for every entry point (the setters themselves are synchronous as ever).
+ * rt_query_closest / rt_query_occluded: the host twins, synchronous; rays and results are staged in the context's grow-only patch
+ * buffer ("replaceable visibility") on the context's stream.
+ * rt_query_primary: the viewer's pick. Traces the context's OWN primary rays of the given frame work-items j * width + i (regardless
+ * of shard; each below the context's ray count) and returns host results synchronously: with the in-kernel pinhole camera the ray is
+ * generated as rt_set_camera defines it, with a pose or a ray buffer it is read from the context's ray buffer. The result is
+ * rt_render_aux's for that work-item on an unsharded RT_KERNEL_HITTEST context. A primary ray of a pose OUTSIDE the box takes the
+ * brute-force route like any ray whose origin is outside the box (the frame's screen tiles are not consulted). RT_ERR_STATE while the
+ * context has no rays yet (rt_rays_info_t::source == 0).
+ * rt_get_query_info: the LAST query's counters. The block is zeroed on the query's stream before the kernel, which adds to it once
+ * per wave; the call waits for that query and reads it. n_grid + n_brute == n_rays; object_tests counts exact ray-object tests (a
+ * brute-force ray: 2 per pair record); device_ms is an event pair around the kernel. RT_ERR_STATE before the first query.
+ *
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: a NULL ray (work-item) array with n != 0; a misaligned device pointer; all
+ * outputs NULL; a work-item >= the context's ray count. RT_ERR_STATE: a context with triangles (the ordered loop over the pair stream
+ * does not know type 2, so no ray could be guaranteed a route). n == 0 returns RT_OK with nothing launched.
+ *
+ * There are no _multi forms: every shard of an rt_multi holds the whole scene, so rt_multi_context(m, 0) answers queries.
+ *
+ * NOT part of this call (each would be its own addition): contexts with triangles; a batched multi-GPU split of one query; queries
+ * that return normals or hit points; refilling a wave's idle lanes from a segment as the frame's persistent walk does. */
+typedef struct rt_query_info_t {
+    uint64_t n_rays;        /* rays of the last query */
+    uint64_t n_grid;        /* ... served by the grid */
+    uint64_t n_brute;       /* ... by the ordered loop over all objects */
+    uint64_t object_tests;
+    double device_ms;
+} rt_query_info_t;
+int rt_query_closest_device(rt_context* ctx, const void* d_rays, uint64_t n, float* d_t, int32_t* d_index, void* hip_stream);
+int rt_query_occluded_device(rt_context* ctx, const void* d_rays, uint64_t n, uint8_t* d_occluded, void* hip_stream);
+int rt_query_closest(rt_context* ctx, const void* rays, uint64_t n, float* t, int32_t* index);
+int rt_query_occluded(rt_context* ctx, const void* rays, uint64_t n, uint8_t* occluded);
+int rt_query_primary(rt_context* ctx, const uint64_t* work_items, uint64_t n, float* t, int32_t* index);
+int rt_get_query_info(rt_context* ctx, rt_query_info_t* info);
 
 void rt_destroy(rt_context* ctx);
 

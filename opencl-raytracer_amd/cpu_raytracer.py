@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of, transforms_of
+from .records import LIGHT_DTYPE, OBJECT_DTYPE, RAY_DTYPE, materials_of, rays_of, transforms_of
 
 LIB_PATH = Path(__file__).resolve().parent / "host" / "libcpu_raytracer.so"
 KERNELS = {"hittest": 0, "shade": 1, "shade_and_reflect": 2}
@@ -51,6 +51,9 @@ def load_library():
             fp = ctypes.POINTER(ctypes.c_float)
             lib.cpu_rt_render_set_visibility.restype = ctypes.c_int
             lib.cpu_rt_render_set_visibility.argtypes = lib.cpu_rt_render.argtypes + [vp, u32, u32, vp, u32, u32, vp, u32, u32, vp, u32, u32, ctypes.c_float, fp, fp]
+        if hasattr(lib, "cpu_rt_query"):
+            lib.cpu_rt_query.restype = ctypes.c_int
+            lib.cpu_rt_query.argtypes = [vp, u32, vp, u64, vp, vp, vp, ctypes.c_uint, vp, u32, u32, vp, u32, u32]
         _lib = lib
     return _lib
 
@@ -141,6 +144,37 @@ class CPURaytracer:
             raise ValueError("set_rays: as many rays as the object was constructed with")
         self.new_rays = rays
         self.pose = None
+
+    # -- ray queries: CPURaytracer::QueryClosest / QueryOccluded, the option HIPRaytracer.query_closest / query_occluded is on the GPU --
+    def _query(self, rays, want_closest: bool):
+        rays = rays_of(rays)
+        n = len(rays)
+        t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+        occluded = np.empty(n, dtype=np.uint8)
+
+        def ptr(a):
+            return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+        vis, xf = self.visible, self.transforms
+        rc = self._lib.cpu_rt_query(ptr(self.objects), len(self.objects), ptr(rays), n,
+                                    ptr(t) if want_closest else None, ptr(index) if want_closest else None,
+                                    None if want_closest else ptr(occluded), self.threads,
+                                    ptr(vis), 0, len(vis) if vis is not None else 0, ptr(xf), 0, len(xf) if xf is not None else 0)
+        if rc != 0:
+            raise ValueError("cpu_rt_query: unsupported arguments (triangle records are a HIP-backend extension)")
+        return (t, index) if want_closest else occluded
+
+    def query_closest(self, rays):
+        """(t, index) of the reference's object loop for `rays` - any number of rays of the caller's own, a RAY_DTYPE array or an
+        (n, 8) float32 array (records.rays_of) - over the
+        CURRENT objects (set_transforms / set_visibility as set so far): t float32, MAX_FLOAT on a miss and NaN where the loop ends
+        with NaN; index int32, the winner where t < MAX_FLOAT, else -1. The executable definition of HIPRaytracer.query_closest.
+        Lights, materials and the frame's rays do not enter."""
+        return self._query(rays, True)
+
+    def query_occluded(self, rays):
+        """uint8 per ray: !(t >= 1 or t < 0) with t of query_closest - something lies on start .. start + direction (a NaN t reads
+        occluded): the kernels' shadow predicate."""
+        return self._query(rays, False)
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)

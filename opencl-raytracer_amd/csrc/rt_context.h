@@ -1,7 +1,7 @@
 // rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
 // points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
 // tiles), rt_object_patch.cpp (what the calls that patch a range of objects share; replaceable materials), rt_geometry.cpp (replaceable
-// transforms), rt_visibility_host.cpp (replaceable visibility) and rt_multi.cpp (several GPUs). Everything with external linkage here
+// transforms), rt_visibility_host.cpp (replaceable visibility), rt_query_host.cpp (ray queries) and rt_multi.cpp (several GPUs). Everything with external linkage here
 // lives in rt::host, apart from the launchers in rt::.
 #pragma once
 #include "hip_raytracer.h"
@@ -17,6 +17,7 @@
 #include "rt_materials.h"
 #include "rt_transforms.h"
 #include "rt_visibility.h"
+#include "rt_query.h"
 
 #include <hip/hip_runtime.h>
 
@@ -250,6 +251,11 @@ struct rt_context {
     std::vector<uint8_t> h_hidden;
     uint32_t* d_vis_types = nullptr;
     uint32_t* d_vis_slots = nullptr;
+    // Ray queries (rt_query_*, rt_query_host.cpp): the counter block the query kernels add to, the event pair around the last query
+    // (both made by the first query), and whether there has been one. The host twins stage rays and results in d_patch_stage.
+    rt::QueryCounters* d_query_counters = nullptr;
+    hipEvent_t ev_query[2] = {};
+    bool query_made = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;

@@ -1,0 +1,46 @@
+// rt_query.h - launch interface of the ray queries (rt_query.hip): closest hit and occlusion for rays that are NOT the frame's, on a
+// live context's object records and grid (hip_raytracer.h, "ray queries").
+#pragma once
+
+#include "rt_device.h"
+#include "rt_grid.h"
+
+namespace rt {
+
+// The box a query ray's origin must lie in to be served by the grid: rt_context::grid_box_lo / hi rounded INWARDS to fp32 on the
+// host (lo up, hi down), so that the kernel's fp32 comparison never admits an origin the double box excludes. grid = 0: the context
+// has no grid, or is literal by RT_FLAG_LITERAL or for a degenerate instance (rt_query_host.cpp: grid_serves_queries): every ray
+// takes the ordered loop.
+struct QueryBox {
+    float lox, loy, loz;
+    float hix, hiy, hiz;
+    uint32_t grid;
+};
+
+// What a query adds up, once per wave (vector atomics): rays, rays per route, exact ray-object tests (2 per pair for a brute-force ray,
+// as Counters::tests counts them). Zeroed on the query's stream before the kernel.
+struct QueryCounters {
+    unsigned long long n_rays, n_grid, n_brute, tests;
+};
+
+// Where rt_query_primary's rays come from: the context's pinhole camera (rt_kernels.h: RenderParams' fields of the same names) or its
+// ray buffer.
+struct QueryCamera {
+    const float4* __restrict__ rays;  // null in pinhole mode
+    uint32_t pinhole;
+    uint32_t width;
+    float half_w, half_h, height_f, z;
+};
+
+// One thread per ray, 256 per workgroup; any n (a workgroup loops when n exceeds the launch). `arith`: kUnfused / kFused / kDeviceCL.
+// d_rays: n x {start, direction}, 16-byte aligned. d_t / d_index: either may be null. n == 0 launches nothing.
+hipError_t launch_query_closest(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays,
+                                uint64_t n, float* d_t, int32_t* d_index, QueryCounters* d_counters, hipStream_t stream);
+hipError_t launch_query_occluded(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays,
+                                 uint64_t n, uint8_t* d_occluded, QueryCounters* d_counters, hipStream_t stream);
+// ... of the primary rays of the work-items d_items[0 .. n) (each below the camera's / the buffer's ray count: the caller checks)
+hipError_t launch_query_primary(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
+                                const uint64_t* d_items, uint64_t n, float* d_t, int32_t* d_index, QueryCounters* d_counters,
+                                hipStream_t stream);
+
+}  // namespace rt

@@ -1,0 +1,224 @@
+// rt_query_host.cpp - ray queries (hip_raytracer.h): rt_query_closest_device, rt_query_occluded_device, their host twins
+// rt_query_closest / rt_query_occluded, rt_query_primary and rt_get_query_info. A query reads the context's object records and grid as
+// the setters have left them and writes the caller's outputs and the context's counter block - nothing of the frame: not its rays,
+// camera, pose, shard, supersampling factor, aux buffers or state buffers. The device forms enqueue a memset, two event records and one
+// kernel (rt_query.hip) and return; after the first call, which makes the counter block and the events, nothing is allocated.
+#include "rt_context.h"
+
+namespace rt::host {
+namespace {
+
+// rt_context::grid_box_lo / hi as floats that lie INSIDE the double box: lo rounded up, hi rounded down
+float round_up(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = std::nextafterf(f, std::numeric_limits<float>::infinity());
+    return f;
+}
+float round_down(double v) {
+    float f = (float)v;
+    if ((double)f > v) f = std::nextafterf(f, -std::numeric_limits<float>::infinity());
+    return f;
+}
+
+// The grid serves queries unless the context is literal by its OBJECTS or by the caller's wish: a degenerate instance (singular or
+// non-finite mvInverse: NaN times for finite rays, so the result depends on the order of the loop - rt_create, "instance checks")
+// or RT_FLAG_LITERAL itself. build_grid builds a grid for such a context all the same (the frames leave it alone: use_grid =
+// grid.enabled && !literal); the order-free walks must not answer there. The frame-level reasons for RT_FLAG_LITERAL - the rays in
+// use left the domain, RT_FLAG_DEVICE_OPENCL's predicate on the lights - concern the frame's rays and zero-direction shadow rays, not
+// a query's: they play no part.
+bool grid_serves_queries(const rt_context* c) {
+    return c->grid.enabled && !(c->user_flags & RT_FLAG_LITERAL) && !c->degenerate_literal;
+}
+
+rt::QueryBox query_box(const rt_context* c) {
+    rt::QueryBox b = {};
+    b.grid = grid_serves_queries(c) ? 1u : 0u;
+    if (!b.grid) return b;
+    b.lox = round_up(c->grid_box_lo[0]); b.loy = round_up(c->grid_box_lo[1]); b.loz = round_up(c->grid_box_lo[2]);
+    b.hix = round_down(c->grid_box_hi[0]); b.hiy = round_down(c->grid_box_hi[1]); b.hiz = round_down(c->grid_box_hi[2]);
+    return b;
+}
+
+// the records as do_launch hands them to a frame (rt_api.cpp); a query reads the traversal's part of them
+rt::Scene query_scene(const rt_context* c) {
+    rt::Scene s = {};
+    s.pairs = c->d_pairs;
+    s.n_pairs = c->n_pairs;
+    s.hot = c->d_hot;
+    s.bounds = c->d_bounds;
+    s.cold = c->d_cold;
+    s.objrec = c->d_objrec;
+    s.lights = c->d_lights;
+    s.n_objs = c->n_objs;
+    s.n_lights = c->n_lights;
+    s.affine = (c->affine_w && !c->has_triangles) ? 1u : 0u;
+    s.nan_winner = c->nan_winner;
+    s.nan_winner_sphere = c->nan_winner_sphere ? 1u : 0u;
+    return s;
+}
+
+// RT_FLAG_FAST_PHONG does not touch t: the mode is the two arithmetic flags'
+int query_arith(const rt_context* c) {
+    return (c->flags & RT_FLAG_DEVICE_OPENCL) ? rt::kDeviceCL : ((c->flags & RT_FLAG_UNFUSED) ? rt::kUnfused : rt::kFused);
+}
+
+int refuse_triangles(rt_context* c) {
+    if (c->has_triangles)
+        return fail(c, RT_ERR_STATE, "ray queries on a context with triangle records: the ordered loop over the pair stream does not know type 2, "
+                                     "so no ray could be guaranteed a route");
+    return RT_OK;
+}
+
+// what the device forms and the host twins refuse of (rays, n); nothing is touched
+int check_query_rays(rt_context* c, const void* rays, uint64_t n, bool device) {
+    if (n != 0 && !rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "the ray array is NULL with a non-zero count");
+    if (device && (reinterpret_cast<uintptr_t>(rays) & 15u)) return fail(c, RT_ERR_INVALID_ARGUMENT, "the ray array must be 16-byte aligned");
+    if (n > (std::numeric_limits<uint64_t>::max)() / sizeof(rt_ray)) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many rays");
+    return RT_OK;
+}
+
+// the counter block and the event pair: made by the first query
+int ensure_query_support(rt_context* c) {
+    if (!c->d_query_counters) RT_HIP(c, hipMalloc((void**)&c->d_query_counters, sizeof(rt::QueryCounters)));
+    for (hipEvent_t& e : c->ev_query)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    return RT_OK;
+}
+
+enum class Kind { Closest, Occluded, Primary };
+
+// One query on `stream`: counters zeroed, event, kernel, event. All pointers are device memory; `d_in` the rays or, for Kind::Primary, the
+// work-items. Asynchronous.
+int enqueue_query(rt_context* c, Kind kind, const void* d_in, uint64_t n, float* d_t, int32_t* d_index, uint8_t* d_occluded, hipStream_t stream) {
+    if (const int rc = ensure_query_support(c)) return rc;
+    const rt::Scene scene = query_scene(c);
+    const rt::QueryBox box = query_box(c);
+    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
+    const int arith = query_arith(c);
+    RT_HIP(c, hipMemsetAsync(c->d_query_counters, 0, sizeof(rt::QueryCounters), stream));
+    RT_HIP(c, hipEventRecord(c->ev_query[0], stream));
+    hipError_t e = hipSuccess;
+    if (kind == Kind::Closest) {
+        e = rt::launch_query_closest(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
+    } else if (kind == Kind::Occluded) {
+        e = rt::launch_query_occluded(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_occluded, c->d_query_counters, stream);
+    } else {
+        rt::QueryCamera cam = {};
+        cam.rays = c->pinhole ? nullptr : c->d_rays;
+        cam.pinhole = c->pinhole ? 1u : 0u;
+        cam.width = c->width ? c->width : 1;
+        cam.half_w = (float)c->width / 2.0f;
+        cam.half_h = (float)c->height / 2.0f;
+        cam.height_f = (float)c->height;
+        cam.z = c->z;
+        e = rt::launch_query_primary(scene, grid, box, arith, cam, static_cast<const uint64_t*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
+    }
+    if (e != hipSuccess) return fail_hip(c, e, "query launch");
+    RT_HIP(c, hipEventRecord(c->ev_query[1], stream));
+    c->query_made = true;
+    return RT_OK;
+}
+
+size_t align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+// The host twins and rt_query_primary: input and results staged in the context's patch buffer (rt_object_patch.cpp), on the context's
+// stream; synchronous. `in_bytes` bytes of input per element.
+int query_from_host(rt_context* c, Kind kind, const void* in, size_t in_bytes, uint64_t n, float* t, int32_t* index, uint8_t* occluded) {
+    RT_DEVICE(c);
+    const size_t off_t = align16(in_bytes * (size_t)n);
+    const size_t off_index = off_t + align16(sizeof(float) * (size_t)n);
+    const size_t off_occ = off_index + align16(sizeof(int32_t) * (size_t)n);
+    if (const int rc = ensure_patch_stage(c, off_occ + align16((size_t)n))) return rc;
+    char* const stage = static_cast<char*>(c->d_patch_stage);
+    float* const d_t = t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
+    int32_t* const d_index = index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
+    uint8_t* const d_occ = occluded ? reinterpret_cast<uint8_t*>(stage + off_occ) : nullptr;
+    hipStream_t stream = c->stream;
+    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * (size_t)n, hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_query(c, kind, stage, n, d_t, d_index, d_occ, stream)) return rc;
+    if (t) RT_HIP(c, hipMemcpyAsync(t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    if (index) RT_HIP(c, hipMemcpyAsync(index, d_index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    if (occluded) RT_HIP(c, hipMemcpyAsync(occluded, d_occ, (size_t)n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+}  // namespace
+}  // namespace rt::host
+
+using namespace rt::host;
+
+extern "C" {
+
+int rt_query_closest_device(rt_context* c, const void* d_rays, uint64_t n, float* d_t, int32_t* d_index, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, d_rays, n, true)) return rc;
+    if (!d_t && !d_index) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    if ((reinterpret_cast<uintptr_t>(d_t) | reinterpret_cast<uintptr_t>(d_index)) & 3u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "the outputs must be 4-byte aligned");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_query(c, Kind::Closest, d_rays, n, d_t, d_index, nullptr, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_occluded_device(rt_context* c, const void* d_rays, uint64_t n, uint8_t* d_occluded, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, d_rays, n, true)) return rc;
+    if (!d_occluded) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output is NULL");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_query(c, Kind::Occluded, d_rays, n, nullptr, nullptr, d_occluded, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_closest(rt_context* c, const void* rays, uint64_t n, float* t, int32_t* index) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, rays, n, false)) return rc;
+    if (!t && !index) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    return query_from_host(c, Kind::Closest, rays, sizeof(rt_ray), n, t, index, nullptr);
+}
+
+int rt_query_occluded(rt_context* c, const void* rays, uint64_t n, uint8_t* occluded) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, rays, n, false)) return rc;
+    if (!occluded) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output is NULL");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    return query_from_host(c, Kind::Occluded, rays, sizeof(rt_ray), n, nullptr, nullptr, occluded);
+}
+
+int rt_query_primary(rt_context* c, const uint64_t* work_items, uint64_t n, float* t, int32_t* index) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
+    if (n > (std::numeric_limits<uint64_t>::max)() / sizeof(rt_ray)) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many work-items");
+    if (!t && !index) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    for (uint64_t k = 0; k < n; ++k)
+        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (!c->pinhole && !c->have_rays)
+        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    if (n == 0) return RT_OK;
+    return query_from_host(c, Kind::Primary, work_items, sizeof(uint64_t), n, t, index, nullptr);
+}
+
+int rt_get_query_info(rt_context* c, rt_query_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->query_made) return fail(c, RT_ERR_STATE, "rt_get_query_info: no query has been made on this context");
+    RT_DEVICE(c);
+    RT_HIP(c, hipEventSynchronize(c->ev_query[1]));  // the last query's stream, up to the query
+    rt::QueryCounters ctr = {};
+    RT_HIP(c, hipMemcpy(&ctr, c->d_query_counters, sizeof(ctr), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_query[0], c->ev_query[1]));
+    info->n_rays = ctr.n_rays;
+    info->n_grid = ctr.n_grid;
+    info->n_brute = ctr.n_brute;
+    info->object_tests = ctr.tests;
+    info->device_ms = (double)ms;
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -18,7 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .records import LIGHT_DTYPE, MATERIAL_DTYPE, OBJECT_DTYPE, RAY_DTYPE, TRANSFORM_DTYPE, materials_of, transforms_of
+from .records import LIGHT_DTYPE, MATERIAL_DTYPE, OBJECT_DTYPE, RAY_DTYPE, TRANSFORM_DTYPE, materials_of, rays_of, transforms_of
 
 LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libhip_raytracer.so"
 
@@ -46,6 +46,8 @@ EXPORTS = [
     "rt_set_transforms", "rt_set_transforms_multi", "rt_read_transforms", "rt_get_geometry_info",
     "rt_read_pose_spheres", "rt_read_object_bounds", "rt_get_grid_constants",
     "rt_set_visibility", "rt_set_visibility_device", "rt_set_visibility_multi", "rt_read_visibility",
+    "rt_query_closest_device", "rt_query_occluded_device", "rt_query_closest", "rt_query_occluded", "rt_query_primary",
+    "rt_get_query_info",
 ]
 
 
@@ -139,6 +141,16 @@ class RTGeometryInfo(ctypes.Structure):
         out["dynamic_ids"] = [int(v) for v in self.dynamic_ids[:out["n_dynamic"]]]
         out["patch_device_ms"] = float(self.patch_device_ms)
         return out
+
+
+class RTQueryInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_rays", ctypes.c_uint64), ("n_grid", ctypes.c_uint64), ("n_brute", ctypes.c_uint64), ("object_tests", ctypes.c_uint64),
+        ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
 
 
 _lib = None
@@ -299,6 +311,19 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_read_transforms.argtypes = [vp, vp, u32, u32]
         lib.rt_get_geometry_info.restype = i32
         lib.rt_get_geometry_info.argtypes = [vp, ctypes.POINTER(RTGeometryInfo)]
+    if hasattr(lib, "rt_query_closest_device"):  # (the same: a build from before ray queries)
+        lib.rt_query_closest_device.restype = i32
+        lib.rt_query_closest_device.argtypes = [vp, vp, u64, vp, vp, vp]
+        lib.rt_query_occluded_device.restype = i32
+        lib.rt_query_occluded_device.argtypes = [vp, vp, u64, vp, vp]
+        lib.rt_query_closest.restype = i32
+        lib.rt_query_closest.argtypes = [vp, vp, u64, vp, vp]
+        lib.rt_query_occluded.restype = i32
+        lib.rt_query_occluded.argtypes = [vp, vp, u64, vp]
+        lib.rt_query_primary.restype = i32
+        lib.rt_query_primary.argtypes = [vp, vp, u64, vp, vp]
+        lib.rt_get_query_info.restype = i32
+        lib.rt_get_query_info.argtypes = [vp, ctypes.POINTER(RTQueryInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -338,6 +363,82 @@ def _ptr(a: np.ndarray | None):
         return None
     assert a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _is_tensor(x) -> bool:
+    """A torch tensor? numpy arrays and sequences are answered without importing torch."""
+    if isinstance(x, (np.ndarray, list, tuple)):
+        return False
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(x, torch.Tensor)
+
+
+def _check_rc(lib, ctx, rc: int):
+    if rc != 0:
+        msg = lib.rt_last_error(ctx)
+        raise RTError(rc, msg.decode() if msg else "")
+
+
+def _device_rays(rays, device: int):
+    """(pointer or None, n, stream or None) of a device ray tensor for the rt_query_*_device calls; `device`: the context's."""
+    import torch
+    if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8:
+        raise ValueError("a device ray tensor is float32, contiguous, on the GPU, with 8 elements per ray")
+    if rays.device.index is not None and rays.device.index != device:
+        raise ValueError(f"the ray tensor lives on device {rays.device.index}, the context on device {device}")
+    stream = _current_stream_of(rays)
+    return (ctypes.c_void_p(rays.data_ptr()) if rays.numel() else None), rays.numel() // 8, (ctypes.c_void_p(stream) if stream else None)
+
+
+def _query_closest(lib, ctx, rays, device: int):
+    """What HIPRaytracer.query_closest and MultiHIPRaytracer.query_closest (through its shard 0) share."""
+    if _is_tensor(rays):
+        import torch
+        ptr, n, stream = _device_rays(rays, device)
+        t = torch.empty(n, dtype=torch.float32, device=rays.device)
+        index = torch.empty(n, dtype=torch.int32, device=rays.device)
+        if n:
+            _check_rc(lib, ctx, lib.rt_query_closest_device(ctx, ptr, n, ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(index.data_ptr()), stream))
+        return t, index
+    rays = rays_of(rays)
+    n = int(rays.shape[0])
+    t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+    if n:
+        _check_rc(lib, ctx, lib.rt_query_closest(ctx, _ptr(rays), n, _ptr(t), _ptr(index)))
+    return t, index
+
+
+def _query_occluded(lib, ctx, rays, device: int):
+    if _is_tensor(rays):
+        import torch
+        ptr, n, stream = _device_rays(rays, device)
+        occluded = torch.empty(n, dtype=torch.uint8, device=rays.device)
+        if n:
+            _check_rc(lib, ctx, lib.rt_query_occluded_device(ctx, ptr, n, ctypes.c_void_p(occluded.data_ptr()), stream))
+        return occluded
+    rays = rays_of(rays)
+    n = int(rays.shape[0])
+    occluded = np.empty(n, dtype=np.uint8)
+    if n:
+        _check_rc(lib, ctx, lib.rt_query_occluded(ctx, _ptr(rays), n, _ptr(occluded)))
+    return occluded
+
+
+def _pick(lib, ctx, work_items):
+    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
+    n = int(items.shape[0])
+    t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+    _check_rc(lib, ctx, lib.rt_query_primary(ctx, _ptr(items), n, _ptr(t), _ptr(index)))
+    return t, index
+
+
+def _query_info(lib, ctx) -> dict:
+    info = RTQueryInfo()
+    _check_rc(lib, ctx, lib.rt_get_query_info(ctx, ctypes.byref(info)))
+    return info.as_dict()
 
 
 def _current_stream_of(tensor) -> int:
@@ -391,6 +492,8 @@ class HIPRaytracer:
             self._check(self._lib.rt_set_camera(self._ctx, int(camera[0]), int(camera[1]), float(camera[2])))
         self.n_rays = n_rays
         self._n_objs = int(objects.shape[0])
+        self._device = int(device)   # (ray queries: a device tensor must live here)
+        self._pose_width = 0         # (pick(i, j): the grid width of the last set_pose through this object; 0: none)
         if supersample != 1:
             try:
                 self.set_supersampling(supersample)
@@ -532,6 +635,7 @@ class HIPRaytracer:
         if isinstance(rays, np.ndarray):
             rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
             self._check(self._lib.rt_set_rays(self._ctx, _ptr(rays), int(rays.shape[0])))
+            self._pose_width = 0
             return
         import torch
         if not isinstance(rays, torch.Tensor):
@@ -541,6 +645,7 @@ class HIPRaytracer:
         stream = _current_stream_of(rays)
         self._check(self._lib.rt_set_rays_device(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.numel() // 8,
                                                  ctypes.c_void_p(stream) if stream else None))
+        self._pose_width = 0
 
     # -- posed cameras (hip_raytracer.h: the rays of rays.posed_rays, generated on the device) -----------------------------
     def set_pose(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0), stream=None):
@@ -551,6 +656,7 @@ class HIPRaytracer:
         m, o = pose_arguments(rotation3x3, origin)
         self._check(self._lib.rt_set_pose(self._ctx, int(width), int(height), float(z), m, o,
                                           ctypes.c_void_p(int(stream)) if stream else None))
+        self._pose_width = int(width)  # (pick(i, j))
 
     def generate_rays(self, width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0), out=None, stream=None):
         """The generator alone (rt_generate_rays_device): rays.posed_rays(...) written to device memory, asynchronously on a HIP
@@ -747,6 +853,42 @@ class HIPRaytracer:
         0 hidden, read from every device copy of the type word; RTError if two copies disagree."""
         return self._read_range(self._lib.rt_read_visibility, np.uint8, first, count)
 
+    # -- ray queries (hip_raytracer.h: closest hit and occlusion for rays that are not the frame's; the frame is untouched) --------
+    def query_closest(self, rays):
+        """(t, index) per ray of `rays` - ANY number of rays of the caller's own - on the context's current objects: what render_aux()
+        returns on a fresh hittest context created with these rays, bit for bit (t: MAX_FLOAT on a miss; index: -1). A numpy ray
+        array - RAY_DTYPE records, or float32 of shape (n, 8): start.xyzw, direction.xyzw, as a device tensor's .cpu().numpy()
+        (records.rays_of) - goes through rt_query_closest (synchronous, numpy results). A torch tensor on the context's device - float32,
+        contiguous, 8 elements per ray - goes through rt_query_closest_device on torch's current stream: the results are torch
+        tensors on the same device, enqueued behind the kernels that made the rays, with no host synchronisation."""
+        return _query_closest(self._lib, self._ctx, rays, self._device)
+
+    def query_occluded(self, rays):
+        """uint8 per ray (numpy array or torch tensor, as query_closest): 1 where an object lies on the segment start .. start +
+        direction - !(t >= 1 or t < 0) of the closest-hit time, the reference's shadow predicate."""
+        return _query_occluded(self._lib, self._ctx, rays, self._device)
+
+    def pick(self, i, j=None):
+        """The object under the mouse (rt_query_primary): (t, index) of the context's OWN primary rays. pick(i, j): column i, row j of
+        the pinhole / posed grid -> (float, int). pick(work_items): an array of frame work-items j * width + i (regardless of the
+        shard) -> (t float32[n], index int32[n]) - render_aux()'s entries of an unsharded hittest context with the same rays."""
+        if j is not None:
+            width = self._grid_width()
+            if not width:
+                raise ValueError("pick(i, j) needs a camera or a pose; with a plain ray buffer use pick(work_items)")
+            t, index = _pick(self._lib, self._ctx, [int(j) * width + int(i)])
+            return float(t[0]), int(index[0])
+        return _pick(self._lib, self._ctx, i)
+
+    def _grid_width(self) -> int:
+        """The width of the grid the rays in use were generated for: the camera's, or the last set_pose's (0: a plain ray buffer)."""
+        st = self.stats()
+        return int(st.width) if st.pinhole else self._pose_width
+
+    def query_info(self) -> dict:
+        """rt_get_query_info: n_rays, n_grid, n_brute (rays per route), object_tests and device_ms of the last query; waits for it."""
+        return _query_info(self._lib, self._ctx)
+
     def set_shard(self, tile_rays: int, rank: int, world: int):
         self._check(self._lib.rt_set_shard(self._ctx, int(tile_rays), int(rank), int(world)))
 
@@ -828,6 +970,7 @@ class MultiHIPRaytracer:
             self._check(self._lib.rt_set_camera_multi(self._m, int(camera[0]), int(camera[1]), float(camera[2])))
         self.n_rays = n_rays
         self.n_devices = len(devices)
+        self._device0 = int(devices[0])   # (ray queries go through shard 0)
         self.supersample = 1
         if supersample != 1:
             try:
@@ -895,6 +1038,25 @@ class MultiHIPRaytracer:
         """Turn or move every shard's camera (rt_set_pose_multi): all shards or none; each generates on its own device."""
         m, o = pose_arguments(rotation3x3, origin)
         self._check(self._lib.rt_set_pose_multi(self._m, int(width), int(height), float(z), m, o))
+
+    # -- ray queries: every shard holds the whole scene, so shard 0 answers (hip_raytracer.h, "ray queries": no _multi forms) -----
+    def _shard0(self):
+        return ctypes.c_void_p(self._lib.rt_multi_context(self._m, 0))
+
+    def query_closest(self, rays):
+        """HIPRaytracer.query_closest through shard 0 (a device tensor lives on devices[0])."""
+        return _query_closest(self._lib, self._shard0(), rays, self._device0)
+
+    def query_occluded(self, rays):
+        """HIPRaytracer.query_occluded through shard 0."""
+        return _query_occluded(self._lib, self._shard0(), rays, self._device0)
+
+    def pick(self, work_items):
+        """HIPRaytracer.pick(work_items) through shard 0: frame work-items, regardless of the shards' tiles."""
+        return _pick(self._lib, self._shard0(), work_items)
+
+    def query_info(self) -> dict:
+        return _query_info(self._lib, self._shard0())
 
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()

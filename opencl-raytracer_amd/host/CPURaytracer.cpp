@@ -293,6 +293,21 @@ void render_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, 
     }
 }
 
+// the object loop alone for a tile of the caller's rays (CPURaytracer::QueryClosest); the clones as render_tile's
+__attribute__((target_clones("fma", "default")))
+void query_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, float* t, int32_t* index) {
+    for (size_t i = first; i < last; ++i) {
+        Ray ray;
+        ray.start = F4{rays[i].start.x, rays[i].start.y, rays[i].start.z, rays[i].start.w};
+        ray.direction = F4{rays[i].direction.x, rays[i].direction.y, rays[i].direction.z, rays[i].direction.w};
+        float time = MAX_FLOAT;
+        int k = -1;
+        closest(sc, ray, time, k);
+        t[i] = time;
+        index[i] = (time < MAX_FLOAT) ? k : -1;  // hittest's verdict (hittest_kernel.cl:149): a NaN time names nothing
+    }
+}
+
 // what the kernels read of an object's two matrices: the surface's copies, and rows x, y, z of mvInverse for the object loop
 void set_transform(CPURaytracer::Surface& d, CPURaytracer::Instance& h, const rtm::mat4& mv, const rtm::mat4& inv) {
     std::memcpy(d.inv, inv.data(), sizeof(d.inv));
@@ -393,6 +408,35 @@ void CPURaytracer::SetPose(size_t width, size_t height, float z, const float m[9
         }
     }
     SetRays(posed);
+}
+
+void CPURaytracer::QueryClosest(const std::vector<Ray3D>& q, std::vector<float>& t, std::vector<int32_t>& index) const {
+    const size_t n = q.size();
+    t.assign(n, MAX_FLOAT);
+    index.assign(n, -1);
+    const Scene sc{instances.data(), surfaces.data(), instances.size(), nullptr, 0};
+    const size_t tile = 256;
+    std::atomic<size_t> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const size_t first = next.fetch_add(tile);
+            if (first >= n) break;
+            query_tile(sc, q.data(), first, std::min(n, first + tile), t.data(), index.data());
+        }
+    };
+    const unsigned int nt = (unsigned int)std::min<size_t>(n_threads, std::max<size_t>(1, (n + tile - 1) / tile));
+    std::vector<std::thread> pool;
+    for (unsigned int k = 1; k < nt; ++k) pool.emplace_back(worker);
+    worker();
+    for (std::thread& th : pool) th.join();
+}
+
+void CPURaytracer::QueryOccluded(const std::vector<Ray3D>& q, std::vector<uint8_t>& occluded) const {
+    std::vector<float> t;
+    std::vector<int32_t> index;
+    QueryClosest(q, t, index);
+    occluded.resize(q.size());
+    for (size_t i = 0; i < q.size(); ++i) occluded[i] = (t[i] >= 1.f || t[i] < 0) ? 0 : 1;  // (.cl:229; a NaN reads occluded)
 }
 
 cl_float4* CPURaytracer::Render() {

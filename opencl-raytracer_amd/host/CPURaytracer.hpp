@@ -64,6 +64,14 @@ public:
     // std::invalid_argument for a range beyond the objects.
     void SetVisibility(uint32_t first, const std::vector<uint8_t>& visible);
 
+    // Ray queries, the same option as HIPRaytracer's (hip_raytracer.h, "ray queries"), and its executable definition without a GPU:
+    // the reference's object loop over the CURRENT objects (SetTransforms and SetVisibility as set so far) for rays of the caller's
+    // own, any number of them. t[i] is the loop's time - MAX_FLOAT on a miss, NaN where the loop ends with NaN - and index[i] the
+    // winner where t[i] < MAX_FLOAT, else -1; occluded[i] = !(t >= 1 || t < 0), the kernels' shadow predicate (.cl:229). Lights,
+    // materials, MAX_BOUNCES and the frame's rays do not enter; Render() is not disturbed.
+    void QueryClosest(const std::vector<Ray3D>& rays, std::vector<float>& t, std::vector<int32_t>& index) const;
+    void QueryOccluded(const std::vector<Ray3D>& rays, std::vector<uint8_t>& occluded) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

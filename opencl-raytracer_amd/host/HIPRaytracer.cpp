@@ -150,6 +150,36 @@ std::vector<uint8_t> HIPRaytracer::ReadVisibility(uint32_t first, uint32_t count
     return out;
 }
 
+void HIPRaytracer::QueryClosest(const std::vector<Ray3D>& q, std::vector<float>& t, std::vector<int32_t>& index) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    t.assign(q.size(), 0.f);
+    index.assign(q.size(), -1);
+    if (!c || rt_query_closest(c, q.data(), q.size(), t.data(), index.data()) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::QueryClosest: ") + (c ? rt_last_error(c) : "no context"));
+}
+
+void HIPRaytracer::QueryOccluded(const std::vector<Ray3D>& q, std::vector<uint8_t>& occluded) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    occluded.assign(q.size(), 0);
+    if (!c || rt_query_occluded(c, q.data(), q.size(), occluded.data()) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::QueryOccluded: ") + (c ? rt_last_error(c) : "no context"));
+}
+
+void HIPRaytracer::Pick(const std::vector<uint64_t>& work_items, std::vector<float>& t, std::vector<int32_t>& index) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    t.assign(work_items.size(), 0.f);
+    index.assign(work_items.size(), -1);
+    if (!c || rt_query_primary(c, work_items.data(), work_items.size(), t.data(), index.data()) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::Pick: ") + (c ? rt_last_error(c) : "no context"));
+}
+
+rt_query_info_t HIPRaytracer::QueryInfo() {
+    rt_query_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_query_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::QueryInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

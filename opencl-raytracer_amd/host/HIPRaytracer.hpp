@@ -92,6 +92,17 @@ public:
     // object reads its first shard's.
     std::vector<uint8_t> ReadVisibility(uint32_t first, uint32_t count);
 
+    // Ray queries (hip_raytracer.h, "ray queries"): closest hit and occlusion for rays of the caller's own - any number, whatever the
+    // frame's - on the objects as SetTransforms / SetVisibility have left them; the frame is untouched. t[i]: the nearest time
+    // (MAX_FLOAT on a miss), index[i]: the object or -1; occluded[i]: something lies on start .. start + direction. Pick: the same for
+    // the frame's OWN primary rays of the work-items j * width + i - the object under the mouse. Synchronous (rt_query_closest,
+    // rt_query_occluded, rt_query_primary); the several-GPU object asks its first shard, which holds the whole scene. Throws
+    // std::runtime_error with the library's message for what it refuses.
+    void QueryClosest(const std::vector<Ray3D>& rays, std::vector<float>& t, std::vector<int32_t>& index);
+    void QueryOccluded(const std::vector<Ray3D>& rays, std::vector<uint8_t>& occluded);
+    void Pick(const std::vector<uint64_t>& work_items, std::vector<float>& t, std::vector<int32_t>& index);
+    rt_query_info_t QueryInfo();
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

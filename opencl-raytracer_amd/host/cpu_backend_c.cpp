@@ -228,4 +228,61 @@ int cpu_rt_render_set_visibility(int kernel, uint32_t max_bounces, const void* o
     return rc;
 }
 
+// CPURaytracer::QueryClosest / QueryOccluded through the C entry: the backend is constructed with `objs_` (no lights, no frame rays),
+// SetTransforms(t_first, transforms_[0 .. t_count)) and SetVisibility(v_first, visible_[0 .. v_count)) are applied (NULL with a count
+// of 0: none), then the `n_rays` rt_ray records of `rays_` are queried. t, index (n_rays each) and occluded (n_rays bytes) may each be
+// NULL. Returns 0, or -1 for arguments it cannot serve (triangle records, a range beyond the objects, a NULL array with a count).
+int cpu_rt_query(const void* objs_, uint32_t n_objs, const void* rays_, uint64_t n_rays, float* t, int32_t* index, uint8_t* occluded,
+                 unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count, const void* transforms_, uint32_t t_first,
+                 uint32_t t_count) {
+    if ((!rays_ && n_rays) || (!objs_ && n_objs) || (!visible_ && v_count) || (!transforms_ && t_count)) return -1;
+    const rt_object_data* objs = static_cast<const rt_object_data*>(objs_);
+    const rt_ray* rays = static_cast<const rt_ray*>(rays_);
+    std::vector<ObjectData> objects;
+    objects.reserve(n_objs);
+    for (uint32_t i = 0; i < n_objs; ++i) {
+        const rt_object_data& d = objs[i];
+        if (d.type == 2u) return -1;
+        ObjectData o(static_cast<ObjectData::PrimativeType>(d.type > 255u ? 255u : d.type), host_material(d.mat), rtm::mat4(1.f));
+        std::memcpy(o.mv.data(), d.mv, sizeof(d.mv));
+        std::memcpy(o.mvInverse.data(), d.mvInverse, sizeof(d.mvInverse));
+        std::memcpy(o.mvInverseTranspose.data(), d.mvInverseTranspose, sizeof(d.mvInverseTranspose));
+        objects.push_back(o);
+    }
+    const std::vector<Light> no_lights;
+    const std::vector<Ray3D> no_rays;
+    CPURaytracer backend(objects, no_lights, no_rays, 0, CPURaytracer::kHittest, threads);
+    try {
+        if (t_count) {
+            const rt_transform* src = static_cast<const rt_transform*>(transforms_);
+            std::vector<Transform> ts(t_count);
+            for (uint32_t i = 0; i < t_count; ++i) {
+                std::memcpy(ts[i].mv.data(), src[i].mv, sizeof(src[i].mv));
+                std::memcpy(ts[i].mvInverse.data(), src[i].mvInverse, sizeof(src[i].mvInverse));
+            }
+            backend.SetTransforms(t_first, ts);
+        }
+        if (v_count) {
+            const uint8_t* v = static_cast<const uint8_t*>(visible_);
+            backend.SetVisibility(v_first, std::vector<uint8_t>(v, v + v_count));
+        }
+    } catch (const std::exception&) { return -1; }
+    std::vector<Ray3D> q;
+    q.reserve(n_rays);
+    for (uint64_t i = 0; i < n_rays; ++i) q.push_back(host_ray(rays[i]));
+    if (t || index) {
+        std::vector<float> qt;
+        std::vector<int32_t> qi;
+        backend.QueryClosest(q, qt, qi);
+        if (t && n_rays) std::memcpy(t, qt.data(), sizeof(float) * n_rays);
+        if (index && n_rays) std::memcpy(index, qi.data(), sizeof(int32_t) * n_rays);
+    }
+    if (occluded) {
+        std::vector<uint8_t> occ;
+        backend.QueryOccluded(q, occ);
+        if (n_rays) std::memcpy(occluded, occ.data(), n_rays);
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -10,6 +10,10 @@
 //                       backend (SetSupersampling). The picture stays W x H; the sample grid is S W x S H at S z.
 //   render and render8 take `--pose m00,m01,m02,m10,m11,m12,m20,m21,m22,ox,oy,oz` likewise: the camera seen through the 3 x 3
 //                       matrix (row-major) from the origin (ox, oy, oz) - the backend's SetPose on the (sample) grid; also with --ss.
+//   scene_tool pick    <scene.txt> <W> <H> <i> <j> [hip|cpu] [z-bits|-]
+//                       the object under pixel (column i, row j) of the W x H picture: prints "pick <object index or -1> <t>
+//                       <backend>". HIPRaytracer::Pick on the GPU; with `cpu`, or where no GPU backend can be made,
+//                       CPURaytracer::QueryClosest of that pixel's ray - the same answer; z-bits as for render
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -85,6 +89,39 @@ int main(int argc, char** argv) {
         loader.Load(argv[2], objects, lights);
         std::printf("Scene file loaded without any errors.\n");
         if (std::strcmp(argv[1], "records") == 0) { dump_records(objects, lights, argv[3]); return 0; }
+        if (std::strcmp(argv[1], "pick") == 0) {
+            if (argc < 7) { std::fprintf(stderr, "usage: scene_tool pick <scene.txt> <W> <H> <i> <j>\n"); return 1; }
+            const int pw = std::atoi(argv[3]), ph = std::atoi(argv[4]), pi = std::atoi(argv[5]), pj = std::atoi(argv[6]);
+            if (pw <= 0 || ph <= 0 || pi < 0 || pj < 0 || pi >= pw || pj >= ph) { std::fprintf(stderr, "pick: 0 <= i < W, 0 <= j < H\n"); return 1; }
+            float pfov = rtm::radians(60.f);
+            pfov *= 0.5f;
+            float pz = -((ph / 2.0f) / tanf(pfov));
+            if (argc > 8 && std::strcmp(argv[8], "-") != 0) { const uint32_t bits = (uint32_t)std::strtoul(argv[8], nullptr, 16); std::memcpy(&pz, &bits, 4); }
+            std::vector<Ray3D> grid;
+            grid.reserve((size_t)pw * ph);
+            for (int jj = 0; jj < ph; ++jj)
+                for (int ii = 0; ii < pw; ++ii)
+                    grid.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - pw / 2.0f, (float)(ph - jj) - ph / 2.0f, pz));
+            const uint64_t item = (uint64_t)pj * (uint64_t)pw + (uint64_t)pi;
+            std::vector<float> t;
+            std::vector<int32_t> index;
+            const char* backend_name = (argc > 7 && std::strcmp(argv[7], "cpu") == 0) ? "cpu" : "hip";
+            if (std::strcmp(backend_name, "hip") == 0) {
+                try {
+                    HIPRaytracer backend(objects, lights, grid, 0);
+                    backend.Pick(std::vector<uint64_t>(1, item), t, index);
+                } catch (const std::exception& e) {  // (no GPU: the CPU backend's loop over the same ray - said on stderr and in the line)
+                    std::fprintf(stderr, "pick: %s; using the CPU backend\n", e.what());
+                    backend_name = "cpu";
+                }
+            }
+            if (std::strcmp(backend_name, "cpu") == 0) {
+                CPURaytracer backend(objects, lights, grid, 0);
+                backend.QueryClosest(std::vector<Ray3D>(1, grid[item]), t, index);
+            }
+            std::printf("pick %d %.9g %s\n", (int)index[0], (double)t[0], backend_name);
+            return 0;
+        }
         if (argc < 7) return 1;
         const int width = std::atoi(argv[3]), height = std::atoi(argv[4]);
         const unsigned depth = (unsigned)std::atoi(argv[5]);

@@ -2,6 +2,8 @@
 
 ray_verdict(rays)  what the ray scan (csrc/rt_rays.hip) reports about a ray array: the predicates of rt_create's host loops,
                    in float32 with the same order of operations, and the box of the origins.
+query_route(...)   which of a ray query's rays (hip_raytracer.h, "ray queries"; csrc/rt_query.hip) the grid serves and which run the
+                   ordered loop over all objects: the kernel's per-ray predicate, in float32 with the same order of operations.
 posed_rays(...)    a pinhole grid seen through a rotation, from a common origin: the rays of a panned, tilted, rolled or
                    moved camera, in a stated float32 order, so that a caller who computes them elsewhere (on the GPU) can
                    reproduce them bit for bit. rt_set_pose / rt_generate_rays_device (hip_raytracer.h, "posed cameras";
@@ -40,6 +42,44 @@ def ray_verdict(rays: np.ndarray) -> dict:
         out["origin_lo"] = s[:, :3].min(axis=0).astype(F)
         out["origin_hi"] = s[:, :3].max(axis=0).astype(F)
     return out
+
+
+def inward_box(box_lo, box_hi):
+    """The float64 box box_lo .. box_hi (rays_info()) as float32 numbers that lie INSIDE it: lo rounded up, hi rounded down - what
+    the query kernels compare origins with, so that an origin the double box excludes is never admitted."""
+    lo64, hi64 = np.asarray(box_lo, dtype=np.float64), np.asarray(box_hi, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        lo, hi = lo64.astype(F), hi64.astype(F)
+        lo = np.where(lo.astype(np.float64) < lo64, np.nextafter(lo, F(np.inf)), lo).astype(F)
+        hi = np.where(hi.astype(np.float64) > hi64, np.nextafter(hi, F(-np.inf)), hi).astype(F)
+    return lo, hi
+
+
+def query_route(rays: np.ndarray, box_lo, box_hi) -> np.ndarray:
+    """bool per ray: True - the grid serves the ray of a query, False - it runs the ordered brute-force loop over all objects.
+
+    box_lo / box_hi are rays_info()'s (float64[3]); None for a context whose grid serves no query: every ray is False. That is a
+    context without a grid (grid_built == 0), one created with literal=True (RT_FLAG_LITERAL), and one that holds a degenerate
+    instance (a singular or non-finite mvInverse) - there the result depends on the order of the loop, which only the ordered loop
+    follows.
+    Per ray, float32, every operation rounded, left to right - True iff all of
+        every one of the eight components is finite
+        start.w == 1 and direction.w == 0
+        dd = (dx*dx + dy*dy) + dz*dz;  dd > 1e-30 and dd < 1e30
+        lo[a] <= start[a] <= hi[a] for a = x, y, z, with (lo, hi) = inward_box(box_lo, box_hi)."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    if box_lo is None or box_hi is None:
+        return np.zeros(len(rays), dtype=bool)
+    lo, hi = inward_box(box_lo, box_hi)
+    d = rays["direction"].astype(F, copy=False)
+    s = rays["start"].astype(F, copy=False)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(s).all(axis=1) & np.isfinite(d).all(axis=1)
+        dd = ((d[:, 0] * d[:, 0]).astype(F) + (d[:, 1] * d[:, 1]).astype(F)).astype(F)
+        dd = (dd + (d[:, 2] * d[:, 2]).astype(F)).astype(F)
+        in_domain = (dd > F(1.0e-30)) & (dd < F(1.0e30))
+        inside = ((s[:, :3] >= lo) & (s[:, :3] <= hi)).all(axis=1)
+    return finite & (s[:, 3] == F(1.0)) & (d[:, 3] == F(0.0)) & in_domain & inside
 
 
 def posed_rays(width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)) -> np.ndarray:

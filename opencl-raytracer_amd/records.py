@@ -341,6 +341,21 @@ def with_visibility(objs, visible, first: int = 0) -> np.ndarray:
     return out
 
 
+def rays_of(rays) -> np.ndarray:
+    """A 1-D contiguous RAY_DTYPE array from what a caller may hold of n rays: a RAY_DTYPE array (taken as it is), or a plain
+    float32 array whose last dimension is 8 - start.xyzw, direction.xyzw per ray, the layout of a device ray tensor, e.g.
+    tensor.cpu().numpy() - which is REINTERPRETED, not converted (numpy's own conversion of an (n, 8) array to a record dtype
+    broadcasts every scalar into a whole record). Any other plain array raises ValueError."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.dtype.fields is not None:   # another record layout with the same field names: numpy converts field by field
+        return np.ascontiguousarray(a, dtype=RAY_DTYPE).reshape(-1)
+    if a.dtype != np.float32 or a.ndim < 1 or a.shape[-1] != 8:
+        raise ValueError("rays are a RAY_DTYPE array or a float32 array whose last dimension is 8 (start.xyzw, direction.xyzw)")
+    return np.ascontiguousarray(a).reshape(-1, 8).view(RAY_DTYPE).reshape(-1)
+
+
 def lights_array(recs) -> np.ndarray:
     recs = list(recs)
     out = np.zeros(len(recs), dtype=LIGHT_DTYPE)
