@@ -1,6 +1,7 @@
-// rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (entry
-// points, do_launch), rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light
-// tiles), rt_object_patch.cpp (what the calls that patch a range of objects share; replaceable materials), rt_geometry.cpp (replaceable
+// rt_context.h - internal to the C-ABI layer (not installed): struct rt_context and what the host units share - rt_api.cpp (life
+// cycle, rays / camera / pose, the setters and readers), rt_render.cpp (do_launch, the frame pipeline, the render entry points),
+// rt_scene.cpp (re-pack, bounds, grid, walk blocks), rt_camera_tiles.cpp (screen tiles), rt_light_setup.cpp (light tiles),
+// rt_object_patch.cpp (what the calls that patch a range of objects share; replaceable materials), rt_geometry.cpp (replaceable
 // transforms), rt_visibility_host.cpp (replaceable visibility), rt_query_host.cpp (ray queries) and rt_multi.cpp (several GPUs). Everything with external linkage here
 // lives in rt::host, apart from the launchers in rt::.
 #pragma once
@@ -91,6 +92,28 @@ constexpr uint32_t kMaxPasses = 4;  // of rt_render's frame (render_in_passes)
 constexpr uint32_t kWavefrontMinObjects = 512;      // brute-force wavefront
 constexpr uint32_t kWavefrontGridMinObjects = 96;   // wavefront when the conservative grid is available
 
+// The work-items one launch renders: tiles of `tile_rays` rays dealt round-robin to `world` ranks, of which this launch stands for
+// ranks rank .. rank + span - 1. The context's own is what rt_set_shard set (span 1); a pass of render_in_passes makes its own.
+struct Shard {
+    uint64_t tile_rays = 0;
+    uint32_t rank = 0, world = 1, span = 1;
+    uint64_t n_local = 0;
+};
+
+// a context-owned buffer that only ever grows: device memory, or pinned host memory (rt_api.cpp)
+int grow_buffer(rt_context* c, void*& p, size_t& have, size_t need, bool pinned_host);
+// One such buffer that knows its kind and frees itself with the context. A failed grow() leaves it empty.
+struct Buffer {
+    void* p = nullptr;
+    size_t bytes = 0;
+    const bool pinned_host;
+    explicit Buffer(bool pinned = false) : pinned_host(pinned) {}
+    ~Buffer() { if (p) (void)(pinned_host ? hipHostFree(p) : hipFree(p)); }
+    Buffer(const Buffer&) = delete;
+    Buffer& operator=(const Buffer&) = delete;
+    int grow(rt_context* c, size_t need) { return grow_buffer(c, p, bytes, need, pinned_host); }
+};
+
 }  // namespace rt::host
 
 struct rt_context {
@@ -120,26 +143,15 @@ struct rt_context {
     uint32_t width = 0, height = 0;
     float z = 0.f;
 
-    uint64_t tile_rays = 0;
-    uint32_t rank = 0, world = 1;
-    uint32_t span = 1;      // consecutive ranks one launch stands for (> 1 only inside render_in_passes)
-    uint64_t n_local = 0;
+    rt::host::Shard shard;  // rt_set_shard's
 
-    void* d_out = nullptr;  // context-owned device framebuffer
-    size_t d_out_bytes = 0;
-    void* h_out = nullptr;  // context-owned pinned host framebuffer (Render()'s return value)
-    size_t h_out_bytes = 0;
+    rt::host::Buffer d_out;        // context-owned device framebuffer
+    rt::host::Buffer h_out{true};  // context-owned pinned host framebuffer (Render()'s return value)
     // 8-bit frames (rt_pack.hip): rt_render_packed's device and pinned byte frames, rt_render_device_packed's float scratch
-    void* d_pack = nullptr;
-    size_t d_pack_bytes = 0;
-    void* h_pack = nullptr;
-    size_t h_pack_bytes = 0;
-    void* d_scratch = nullptr;
-    size_t d_scratch_bytes = 0;
+    rt::host::Buffer d_pack, h_pack{true}, d_scratch;
     // supersampled frames (rt_resolve.hip): the factor, and the sample frame every render call with a factor > 1 filters from
     uint32_t ss = 1;
-    void* d_samples = nullptr;
-    size_t d_samples_bytes = 0;
+    rt::host::Buffer d_samples;
     // rt_render in passes (render_in_passes): the stream the read-backs run on, an event per pass
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_pass[rt::host::kMaxPasses] = {};
@@ -227,8 +239,7 @@ struct rt_context {
     rt::RayScan* h_scan = nullptr;
     // The staging buffer of the calls that patch a range of objects from a host array (rt_set_materials, rt_set_transforms,
     // rt_set_visibility; rt_object_patch.cpp: ensure_patch_stage): one, grow-only, as large as the largest call so far needed.
-    void* d_patch_stage = nullptr;
-    size_t patch_stage_bytes = 0;
+    rt::host::Buffer d_patch_stage;
     // Replaceable transforms (rt_set_transforms, rt_geometry.cpp). Of the objects: type and "both bottom rows are (0,0,0,1)" per object
     // (bits 0-1 and bit 7), how many are not affine, and the position rt_create's size order gave each in the shadow stream. Of the
     // lights: a host copy (the light tiles are rebuilt, RT_FLAG_DEVICE_OPENCL's predicate is evaluated again). Of the grid: what
@@ -313,8 +324,6 @@ struct DeviceGuard {
         if (e_ != hipSuccess) return fail_hip((ctx), e_, #call);    \
     } while (0)
 
-// a context-owned buffer that only ever grows: device memory, or pinned host memory (rt_api.cpp)
-int grow_buffer(rt_context* c, void*& p, size_t& have, size_t need, bool pinned_host);
 // one array of a group that grows together: the group's capacity `have` (in elements) is the caller's to set once all of them have grown
 template <class T>
 int grow_array(rt_context* c, T*& p, size_t have, size_t need) {
@@ -329,6 +338,10 @@ inline size_t packed_bytes(int format) { return format == RT_PIXEL_RGBA8 ? 4 : (
 
 // the sample grid a factor > 1 filters over: the pinhole camera's, or the pose's the ray buffer was generated from (0: neither)
 inline uint32_t sample_width(const rt_context* c) { return c->pinhole ? c->width : c->pose_w; }
+inline uint32_t sample_height(const rt_context* c) { return c->pinhole ? c->height : c->pose_h; }
+inline bool has_sample_grid(const rt_context* c) { return c->pinhole || c->pose_w != 0; }
+inline size_t elem_bytes(const rt_context* c) { return c->kernel == RT_KERNEL_HITTEST ? sizeof(float) : 4 * sizeof(float); }
+inline uint64_t local_pixels(const rt_context* c) { return c->shard.n_local / ((uint64_t)c->ss * c->ss); }  // what a render call delivers
 
 // |d|^2 exactly as the walks compute it (fp32, unfused, left to right) against their `tame` window
 inline bool direction_in_domain(float dx, float dy, float dz) {
@@ -420,6 +433,10 @@ int pose_check(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, PoseVer
 int pose_commit(rt_context* c, const rt::PoseGrid& g, hipStream_t stream, const PoseVerdict& v);
 int check_set_lights(rt_context* c, const void* lights, uint32_t n_lights);
 void apply_ray_domain(rt_context* c);
+// rt_render.cpp: the work-items of ranks rank .. rank + span - 1 (whole tiles; 1 rank: everything); the path a frame takes; rt_destroy's part of it
+uint64_t local_count(uint64_t n_rays, uint64_t tile_rays, uint32_t rank, uint32_t world, uint32_t span = 1);
+bool use_wavefront(const rt_context* c);
+void free_wavefront(rt_context* c);
 // rt_object_patch.cpp: what the calls that patch a range [first, first + count) of a live context's objects share.
 // The two refusals of a range and its array `p`, named `what` in the message; nothing is touched. Both at once: the range's, unless null_first.
 int check_object_range(rt_context* c, const void* p, uint32_t first, uint32_t count, const char* what, bool null_first = false);

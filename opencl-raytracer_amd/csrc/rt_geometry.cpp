@@ -111,7 +111,7 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
     for (hipEvent_t& e : c->ev_xf)
         if (!e) RT_HIP(c, hipEventCreate(&e));
     std::vector<uint32_t> slots(c->h_shadow_slot.begin() + first, c->h_shadow_slot.begin() + first + count);
-    uint8_t* stage = static_cast<uint8_t*>(c->d_patch_stage);
+    uint8_t* stage = static_cast<uint8_t*>(c->d_patch_stage.p);
     RT_HIP(c, hipEventRecord(c->ev_xf[0], c->stream));
     // (the copies take the bytes as they are: `transforms` may have any alignment)
     RT_HIP(c, hipMemcpyAsync(stage, transforms, slots_at, hipMemcpyHostToDevice, c->stream));

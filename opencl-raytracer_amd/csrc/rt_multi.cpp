@@ -58,12 +58,12 @@ int multi_render_shard(rt_multi* m, uint32_t r, void* frame, bool to_host, int f
     void* local = m->d_local[r];  // what travels: the float tiles, or their bytes
     if (format) {
         if (!m->d_bytes[r]) {
-            e = hipMalloc(&m->d_bytes[r], c->n_local ? (size_t)c->n_local * 4 : 16);
+            e = hipMalloc(&m->d_bytes[r], c->shard.n_local ? (size_t)c->shard.n_local * 4 : 16);
             if (e != hipSuccess) { err = std::string("byte tiles: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP; }
         }
         local = m->d_bytes[r];
         if (fused) rc = rt_render_device_packed(c, format, local, c->stream);
-        else rc = rt_pack_device(c, m->d_local[r], c->n_local, format, local, c->stream);
+        else rc = rt_pack_device(c, m->d_local[r], c->shard.n_local, format, local, c->stream);
         if (rc != RT_OK) { err = c->error; return rc; }
     }
     if (mine) {
@@ -230,7 +230,7 @@ int rt_create_multi(rt_multi** out, const void* objs, uint32_t n_objs, const voi
         hipError_t e = hipSuccess;
         if (rc == RT_OK) {
             DeviceGuard guard(c->device);
-            const size_t bytes = (size_t)c->n_local * m->elem;
+            const size_t bytes = (size_t)c->shard.n_local * m->elem;
             e = hipMalloc(&m->d_local[r], bytes ? bytes : 16);
             if (e == hipSuccess && c->device != m->devices[0]) {  // both directions; "already enabled" is fine
                 int can = 0;

@@ -18,16 +18,16 @@ int check_set_materials(rt_context* c, const void* materials, uint32_t first, ui
     return check_object_range(c, materials, first, count, "materials");
 }
 
-// Grow-only. The larger buffer first, then the old one freed: a failed allocation leaves the context as it was (grow_buffer frees
+// Grow-only. The larger buffer first, then the old one freed: a failed allocation leaves the context as it was (Buffer::grow frees
 // first). One buffer serves every patch call because each of them synchronises its stream before it returns and a context is
 // driven by one thread at a time: no call finds another's bytes still in flight.
 int ensure_patch_stage(rt_context* c, size_t bytes) {
-    if (bytes <= c->patch_stage_bytes) return RT_OK;
-    void* d = nullptr;
-    RT_HIP(c, hipMalloc(&d, bytes));
-    if (c->d_patch_stage) (void)hipFree(c->d_patch_stage);
-    c->d_patch_stage = d;
-    c->patch_stage_bytes = bytes;
+    Buffer& stage = c->d_patch_stage;
+    if (bytes <= stage.bytes) return RT_OK;
+    Buffer larger;
+    if (const int rc = larger.grow(c, bytes)) return rc;
+    std::swap(stage.p, larger.p);  // (the old one goes with `larger`)
+    std::swap(stage.bytes, larger.bytes);
     return RT_OK;
 }
 
@@ -121,8 +121,8 @@ int rt_set_materials(rt_context* c, const void* materials, uint32_t first, uint3
     PatchTrace trace(c, "RT_MATERIALS_TRACE", "rt_set_materials", "materials");
     if (const int rc = trace.begin(c->stream)) return rc;
     // (the copy takes the bytes as they are: `materials` may have any alignment)
-    RT_HIP(c, hipMemcpyAsync(c->d_patch_stage, materials, bytes, hipMemcpyHostToDevice, c->stream));
-    return patch_materials_on(c, c->d_patch_stage, first, count, c->stream, trace);
+    RT_HIP(c, hipMemcpyAsync(c->d_patch_stage.p, materials, bytes, hipMemcpyHostToDevice, c->stream));
+    return patch_materials_on(c, c->d_patch_stage.p, first, count, c->stream, trace);
 }
 
 int rt_read_materials(rt_context* c, void* materials, uint32_t first, uint32_t count) {

@@ -129,7 +129,7 @@ int query_from_host(rt_context* c, Kind kind, const void* in, size_t in_bytes, u
     const size_t off_index = off_t + align16(sizeof(float) * (size_t)n);
     const size_t off_occ = off_index + align16(sizeof(int32_t) * (size_t)n);
     if (const int rc = ensure_patch_stage(c, off_occ + align16((size_t)n))) return rc;
-    char* const stage = static_cast<char*>(c->d_patch_stage);
+    char* const stage = static_cast<char*>(c->d_patch_stage.p);
     float* const d_t = t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
     int32_t* const d_index = index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
     uint8_t* const d_occ = occluded ? reinterpret_cast<uint8_t*>(stage + off_occ) : nullptr;

@@ -65,11 +65,11 @@ int set_visibility_from(rt_context* c, const uint8_t* d_src, hipStream_t stream,
     if (const int rc = ensure_support(c)) return rc;
     if (h_mask) {
         if (const int rc = ensure_patch_stage(c, (size_t)count)) return rc;
-        d_src = static_cast<const uint8_t*>(c->d_patch_stage);
+        d_src = static_cast<const uint8_t*>(c->d_patch_stage.p);
     }
     PatchTrace trace(c, "RT_VISIBILITY_TRACE", "rt_set_visibility", "objects");  // (tools/ab/set_visibility_timing.py)
     if (const int rc = trace.begin(stream)) return rc;
-    if (h_mask) RT_HIP(c, hipMemcpyAsync(c->d_patch_stage, h_mask, (size_t)count, hipMemcpyHostToDevice, stream));
+    if (h_mask) RT_HIP(c, hipMemcpyAsync(c->d_patch_stage.p, h_mask, (size_t)count, hipMemcpyHostToDevice, stream));
     if (const int rc = trace.uploaded(stream)) return rc;
     const rt::VisibilityTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->d_vis_types, c->d_vis_slots, c->n_objs};
     const hipError_t e = rt::launch_patch_visibility(d_src, first, count, to, stream);

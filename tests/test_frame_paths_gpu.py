@@ -95,7 +95,7 @@ def test_a_shard_is_its_tiles_of_the_whole_frame():
                                           ("camera", 200, "5,2,1"), ("camera", 312, "2,1,1,3"), ("ray_buffer", 1000, "2,1")])
 def test_render_in_two_passes_is_the_one_pass_frame(monkeypatch, mode, H, split):
     """rt_render of a large frame renders three row-tiles of every four, then the fourth, and copies the first pass to the host
-    while the second renders (rt_api.cpp: render_in_passes; frames of >= 4 M rays, forced here with RT_RENDER_PASSES=2; other
+    while the second renders (rt_render.cpp: render_in_passes; frames of >= 4 M rays, forced here with RT_RENDER_PASSES=2; other
     splits through RT_RENDER_SPLIT): same pixels as the one-pass Render(), short last group of tiles and ragged last tile
     included, call after call."""
     from opencl_raytracer_amd import synthetic

@@ -96,7 +96,7 @@ SCENES = ("s40", "s80", "s300", "tri")
 
 # ---- the predicates -----------------------------------------------------------------------------------------------------
 def local_count(n_rays, tile_rays, rank, world, span=1):
-    """rt_api.cpp: local_tiles / local_count - work-items of ranks rank .. rank + span - 1 (whole tiles)."""
+    """rt_render.cpp: local_count -work-items of ranks rank .. rank + span - 1 (whole tiles)."""
     if world <= 1:
         return n_rays
     tiles = -(-n_rays // tile_rays)
@@ -105,7 +105,7 @@ def local_count(n_rays, tile_rays, rank, world, span=1):
 
 
 def launch_form(W, H, z, n_objs, tile_rays=0, rank=0, world=1, span=1, literal=False, triangles=False):
-    """The form do_launch gives a pinhole frame, as a pure function. Mirrors csrc/rt_api.cpp: do_launch (row_tiles, tile2d,
+    """The form do_launch gives a pinhole frame, as a pure function. Mirrors csrc/rt_render.cpp: do_launch (row_tiles, tile2d,
     local_rows, wf_tile_order, tile_cull, bundles_x; the col_shift of the screen tiles and build_screen_tiles' own conditions),
     use_wavefront, local_count; csrc/rt_wavefront.hip: run_wavefront (`padded`, finish_threshold = max(2048, n / 128)) and
     wf_trace_primary_tiles (a wave of 64 work-items in one screen tile, or not). Two things are NOT restated because they
@@ -148,7 +148,7 @@ def form_key(form, n_objs):
 
 
 def pass_forms(W, H, z, n_objs, split, packed=False):
-    """render_in_passes (rt_api.cpp): per pass its launch form and how its tiles travel - (form, strided copy, short last run)."""
+    """render_in_passes (rt_render.cpp): per pass its launch form and how its tiles travel - (form, strided copy, short last run)."""
     spans = [int(s) for s in split.split(",")] if split else ([7, 1] if packed else [3, 1])
     world, tile_rays = sum(spans), 16 * W
     tiles = -(-(W * H) // tile_rays)

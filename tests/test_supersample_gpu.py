@@ -317,7 +317,8 @@ def test_shards_assemble_to_the_unsharded_filtered_frame(s, world, tile_rows):
 
 @pytest.mark.parametrize("s", [2, 3])
 def test_passes_do_not_change_the_frame(monkeypatch, s):
-    """RT_RENDER_PASSES=2 against =1 on the large-scene path, float and RGBA8, the default split and a split of three passes"""
+    """RT_RENDER_PASSES=2 against =1 on the large-scene path, float, RGBA8 and RGB8 (the 3-byte element is the one a pass's tile-byte
+    arithmetic can get wrong while 4- and 16-byte elements pass), the default split and a split of three passes"""
     from opencl_raytracer_amd import synthetic
     objs, lights = synthetic.spheres_and_lights(900, 4)
     w, h = 168, 156            # 9.75 tiles of 16 rows, 3.25 of 48
@@ -326,9 +327,9 @@ def test_passes_do_not_change_the_frame(monkeypatch, s):
     with hip(objs, lights, None, 3, camera=cam) as rt:
         samples = rt.Render()
         rt.set_supersampling(s)
-        one, one8 = rt.Render(), rt.render_packed("rgba8")
+        one, one8, one3 = rt.Render(), rt.render_packed("rgba8"), rt.render_packed("rgb8")
         assert rt.stats().wavefront == 1
-    assert same_floats(one, box(samples, w, s)) and np.array_equal(one8, qbytes(one, 4))
+    assert same_floats(one, box(samples, w, s)) and np.array_equal(one8, qbytes(one, 4)) and np.array_equal(one3, one8[:, :3])
     monkeypatch.setenv("RT_RENDER_PASSES", "2")
     with hip(objs, lights, None, 3, camera=cam) as rt:
         rt.set_supersampling(s)
@@ -337,6 +338,7 @@ def test_passes_do_not_change_the_frame(monkeypatch, s):
             for _ in range(2):
                 assert np.array_equal(bits(rt.Render()), bits(one)), split
                 assert np.array_equal(rt.render_packed("rgba8"), one8), split
+                assert np.array_equal(rt.render_packed("rgb8"), one3), split
         monkeypatch.delenv("RT_RENDER_SPLIT")
         assert rt.local_rays == w * h and rt.local_pixels == w * h // (s * s)
         rt.set_supersampling(1)
