@@ -74,7 +74,9 @@ extern "C" {
  *      Later addition, same version: replaceable visibility - rt_set_visibility, rt_set_visibility_device, rt_read_visibility,
  *      rt_set_visibility_multi; RT_TYPE_HIDDEN in rt_records.h. Additions only; detect by dlsym of rt_set_visibility.
  *      Later addition, same version: ray queries - rt_query_closest_device, rt_query_occluded_device, rt_query_closest,
- *      rt_query_occluded, rt_query_primary, rt_get_query_info. Additions only; detect by dlsym of rt_query_closest_device. */
+ *      rt_query_occluded, rt_query_primary, rt_get_query_info. Additions only; detect by dlsym of rt_query_closest_device.
+ *      Later addition, same version: hit-record queries - rt_hits_t, rt_query_hits_device, rt_query_hits, rt_query_primary_hits.
+ *      Additions only; detect by dlsym of rt_query_hits_device. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -781,8 +783,9 @@ int rt_read_visibility(rt_context* ctx, uint8_t* visible, uint32_t first, uint32
  *
  * There are no _multi forms: every shard of an rt_multi holds the whole scene, so rt_multi_context(m, 0) answers queries.
  *
- * NOT part of this call (each would be its own addition): contexts with triangles; a batched multi-GPU split of one query; queries
- * that return normals or hit points; refilling a wave's idle lanes from a segment as the frame's persistent walk does. */
+ * NOT part of this call (each would be its own addition): contexts with triangles; a batched multi-GPU split of one query;
+ * refilling a wave's idle lanes from a segment as the frame's persistent walk does. (Normals and hit points: "hit-record
+ * queries" below.) */
 typedef struct rt_query_info_t {
     uint64_t n_rays;        /* rays of the last query */
     uint64_t n_grid;        /* ... served by the grid */
@@ -796,6 +799,61 @@ int rt_query_closest(rt_context* ctx, const void* rays, uint64_t n, float* t, in
 int rt_query_occluded(rt_context* ctx, const void* rays, uint64_t n, uint8_t* occluded);
 int rt_query_primary(rt_context* ctx, const uint64_t* work_items, uint64_t n, float* t, int32_t* index);
 int rt_get_query_info(rt_context* ctx, rt_query_info_t* info);
+
+/* ---- hit-record queries -----------------------------------------------------------------------------------------------------------
+ * WHERE a ray meets the scene and how the surface faces there: the closest-hit query with what the reference's raycast() leaves in its
+ * HitRecord for the winner (shade_kernel.cl:106-112 sphere, :143-159 box) and the next ray of the reflection chain
+ * (shade_and_reflect_kernel.cl:175, :260-263). For dropping an object onto the surface under the mouse, bouncing particles off the
+ * scene from a device tensor, following a mirror / laser / acoustic chain, or a depth-and-normal buffer - without reading 320-byte
+ * object records back and redoing the reference's arithmetic by hand. The kernels compute all of this for every frame; this call
+ * hands it out.
+ *
+ * (t, index) are EXACTLY rt_query_closest's: the route per ray, the domain, the arithmetic flags, literal contexts, the refusal of
+ * triangle contexts and the counter block are those of "ray queries" above, unchanged. Where index >= 0:
+ *   point      float4: HitRecord.intersection = mv * (s' + t d') in view space, w as the reference carries it (1 for a ray with
+ *              start.w == 1, direction.w == 0 on affine instances);
+ *   normal     float4: HitRecord.normal = normalize((mv * (n, 0)).xyz) in xyz, w = 0; n the object-space point (sphere) or the sum of
+ *              the +-1 face normals whose slab the point lies within 0.0002 of (box);
+ *   reflected  rt_ray: start = intersection + 0.001 * normalize(reflection), direction = (reflection, 0), with
+ *              reflection = d - 2 dot(d, normal) normal, d the ray's UN-normalised direction: the next ray of the chain, ready to be
+ *              queried;
+ * in the context's arithmetic mode, as the frames compute them for that winner at that time (the kernels' own functions, with the
+ * scene's affine flag; a ray with an inf or a NaN among start / direction x, y, z is taken through the matrices' bottom rows like the
+ * reference's, so that its w is the reference's NaN). RT_FLAG_FAST_PHONG plays no part: it never touches a vector a ray is built from.
+ * Where index == -1 - a miss, a NaN time, or a masked ray - every requested record is all-zero bytes and t is as rt_query_closest
+ * gives it (MAX_FLOAT for a masked ray).
+ * The zero box normal follows its mode, as the frames' does: a box hit whose object-space point lies on no face within the 0.0002
+ * margin (a far or tiny box, where fp32 rounding of the point exceeds the margin) has n = 0. Under the default and RT_FLAG_UNFUSED
+ * arithmetic normalize(0) = 0 / 0: a NaN normal and a NaN reflected ray (direction and start). Under RT_FLAG_DEVICE_OPENCL
+ * normalize(0) = 0: a zero normal and the reflection along d.
+ *
+ * Mask. d_mask is NULL or n int32: a ray with mask[i] < 0 is not traced and reads as a miss. This is what makes chains safe: the zero
+ * record of a miss has start.w == 0 and would take the ordered brute-force loop if fed back, so the next bounce passes the previous
+ * bounce's index array as its mask. rt_query_info_t::n_rays counts TRACED rays only (n_grid + n_brute == n_rays keeps holding).
+ * Aliasing. A lane reads ray i and mask[i] before it writes anything of element i and touches no other element, so
+ * out->reflected == d_rays (an in-place chain) and out->index == d_mask are allowed. Any other overlap is the caller's error.
+ *
+ * rt_query_hits_device: `d_out` points to a HOST struct, read during the call, whose members are device pointers on the context's
+ * device (each may be NULL, not all). d_rays, point, normal and reflected 16-BYTE ALIGNED; t, index and d_mask 4-byte aligned.
+ * ASYNCHRONOUS on hip_stream like rt_query_closest_device: no host synchronisation, no allocation after the first query.
+ * rt_query_hits: the host twin, synchronous, staged through the context's grow-only patch buffer; members of `out` are host arrays.
+ * rt_query_primary_hits: the pick with its record - rt_query_primary's work-items and rules (RT_ERR_STATE without rays), host results.
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: what rt_query_closest_device refuses, a NULL struct, all members NULL, a
+ * misaligned device member. RT_ERR_STATE: a context with triangles. n == 0 returns RT_OK with nothing launched.
+ *
+ * NOT part of this call: contexts with triangles; a multi-GPU split of one query; refilling idle lanes; a whole-frame G-buffer entry
+ * point (rt_generate_rays_device + rt_query_hits_device give one; a pose outside the box would send every primary ray down the
+ * brute-force route); materials in the record (rt_read_materials by index has them). */
+typedef struct rt_hits_t {      /* every member may be NULL, not all of them */
+    float*   t;          /* n floats      - as rt_query_closest                                   */
+    int32_t* index;      /* n int32       - as rt_query_closest (the hittest rule)                */
+    float*   point;      /* n x float4    - HitRecord.intersection, view space, w as the reference carries it */
+    float*   normal;     /* n x float4    - HitRecord.normal in xyz, w = 0                        */
+    void*    reflected;  /* n x 32-byte rt_ray - the next ray of the reflection chain             */
+} rt_hits_t;
+int rt_query_hits_device(rt_context* ctx, const void* d_rays, uint64_t n, const int32_t* d_mask, const rt_hits_t* d_out, void* hip_stream);
+int rt_query_hits(rt_context* ctx, const void* rays, uint64_t n, const int32_t* mask, const rt_hits_t* out);
+int rt_query_primary_hits(rt_context* ctx, const uint64_t* work_items, uint64_t n, const rt_hits_t* out);
 
 void rt_destroy(rt_context* ctx);
 

@@ -54,6 +54,9 @@ def load_library():
         if hasattr(lib, "cpu_rt_query"):
             lib.cpu_rt_query.restype = ctypes.c_int
             lib.cpu_rt_query.argtypes = [vp, u32, vp, u64, vp, vp, vp, ctypes.c_uint, vp, u32, u32, vp, u32, u32]
+        if hasattr(lib, "cpu_rt_query_hits"):
+            lib.cpu_rt_query_hits.restype = ctypes.c_int
+            lib.cpu_rt_query_hits.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_uint, vp, u32, u32, vp, u32, u32]
         _lib = lib
     return _lib
 
@@ -175,6 +178,46 @@ class CPURaytracer:
         """uint8 per ray: !(t >= 1 or t < 0) with t of query_closest - something lies on start .. start + direction (a NaN t reads
         occluded): the kernels' shadow predicate."""
         return self._query(rays, False)
+
+    # -- hit-record queries: CPURaytracer::QueryHits / HitRecords, the option HIPRaytracer.query_hits is on the GPU ---------------
+    def _hits(self, rays, mask, t, index):
+        rays = rays_of(rays)
+        n = len(rays)
+        records_only = t is not None
+        if records_only:
+            t = np.ascontiguousarray(np.asarray(t).reshape(-1), dtype=np.float32).copy()
+            index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32).copy()
+            if len(t) != n or len(index) != n:
+                raise ValueError("hit_records: t and index have one entry per ray")
+        else:
+            t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
+            if len(mask) != n:
+                raise ValueError("query_hits: the mask has one int32 entry per ray")
+        point, normal = np.zeros((n, 4), dtype=np.float32), np.zeros((n, 4), dtype=np.float32)
+        reflected = np.zeros(n, dtype=RAY_DTYPE)
+
+        def ptr(a):
+            return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+        vis, xf = self.visible, self.transforms
+        rc = self._lib.cpu_rt_query_hits(ptr(self.objects), len(self.objects), ptr(rays), n, ptr(mask), ptr(t), ptr(index), ptr(point),
+                                         ptr(normal), ptr(reflected), int(records_only), self.threads,
+                                         ptr(vis), 0, len(vis) if vis is not None else 0, ptr(xf), 0, len(xf) if xf is not None else 0)
+        if rc != 0:
+            raise ValueError("cpu_rt_query_hits: unsupported arguments (triangle records are a HIP-backend extension)")
+        return {"t": t, "index": index, "point": point, "normal": normal, "reflected": reflected}
+
+    def query_hits(self, rays, mask=None):
+        """query_closest with the hit record, the executable definition of HIPRaytracer.query_hits in the default arithmetic: a dict of
+        "t", "index" (query_closest's), "point" float32[n, 4] (HitRecord.intersection), "normal" float32[n, 4] (HitRecord.normal,
+        w = 0) and "reflected" RAY_DTYPE[n] (the next ray of the reflection chain) - finish_hit and reflection_ray of the winner, the
+        functions Render() uses. Zero records where index is -1; a ray whose `mask` entry is negative reads as a miss."""
+        return self._hits(rays, mask, None, None)
+
+    def hit_records(self, rays, t, index):
+        """The record stage alone: point / normal / reflected for the given winner and time per ray (index < 0: zero records)."""
+        return self._hits(rays, None, t, index)
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)

@@ -43,4 +43,21 @@ hipError_t launch_query_primary(const Scene& scene, const GridDesc& grid, const 
                                 const uint64_t* d_items, uint64_t n, float* d_t, int32_t* d_index, QueryCounters* d_counters,
                                 hipStream_t stream);
 
+// Hit-record queries (hip_raytracer.h: rt_hits_t with device pointers). Every member may be null, not all of them; point / normal /
+// reflected 16-byte aligned (reflected: two float4 per ray, start then direction), t / index 4-byte aligned.
+struct QueryHits {
+    float* t;
+    int32_t* index;
+    float4* point;
+    float4* normal;
+    float4* reflected;
+};
+// (t, index) as launch_query_closest's, and for the winner what materialise() and reflection_ray() give in mode `arith`; all-zero
+// records where index == -1. d_mask: null, or n int32 - a ray whose entry is negative is not traced (nor counted) and reads as a
+// miss. out.reflected may be d_rays and out.index may be d_mask: a lane reads element i of both before it writes element i.
+hipError_t launch_query_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays, uint64_t n,
+                             const int32_t* d_mask, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream);
+hipError_t launch_query_primary_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
+                                     const uint64_t* d_items, uint64_t n, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream);
+
 }  // namespace rt

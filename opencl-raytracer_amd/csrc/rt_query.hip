@@ -20,6 +20,10 @@ constexpr uint64_t kQueryMaxBlocks = 1ull << 20;  // 2^28 rays per trip of the w
 
 __device__ __forceinline__ bool finite_(float x) { return __builtin_fabsf(x) < __builtin_inff(); }  // (NaN: false)
 
+__device__ __forceinline__ bool finite3(const Ray& r) {  // start.xyz and direction.xyz
+    return finite_(r.sx) && finite_(r.sy) && finite_(r.sz) && finite_(r.dx) && finite_(r.dy) && finite_(r.dz);
+}
+
 // the per-ray route (hip_raytracer.h; rays.py: query_route is the executable definition)
 __device__ __forceinline__ bool query_on_grid(const QueryBox& b, const Ray& r) {
     if (!b.grid) return false;
@@ -163,6 +167,83 @@ __global__ __launch_bounds__(kQueryBlock) void query_occluded(const Scene S, con
     query_body<AM, true>(S, g, box, BufferRays{rays}, n, nullptr, nullptr, occluded, counters);
 }
 
+// ---- hit records (hip_raytracer.h, "hit-record queries") -------------------------------------------------------------------------
+// The closest-hit query with what raycast() leaves in the HitRecord of the winner: the same route decision and the same walks, then -
+// where T < MAX_FLOAT - materialise<AM>() and reflection_ray<AM>() as the frames call them (but for the affine shortcut of a ray with
+// an inf or a NaN in it, below). A ray whose mask entry is negative is not
+// traced and reads as a miss (T = MAX_FLOAT, index -1): it enters no counter. A miss's records are all-zero bytes. Each record leaves
+// as one 16-byte store per lane (two for the reflected ray). A lane reads ray i and mask[i] before it writes anything of element i
+// and touches no other element, so `reflected` may be the ray array and `index` the mask: the caller's rays are loaded through
+// AliasedRays, and no pointer on the way from the kernel's parameters to a load or store of rays, mask or outputs is __restrict__.
+struct AliasedRays {  // BufferRays for an array the kernel may also write (out.reflected == rays): plain pointers throughout
+    const float4* rays;
+    __device__ __forceinline__ Ray operator()(uint64_t i) const {
+        const float4 s = rays[2 * i];
+        const float4 d = rays[2 * i + 1];
+        Ray ray;
+        ray.sx = s.x; ray.sy = s.y; ray.sz = s.z; ray.sw = s.w;
+        ray.dx = d.x; ray.dy = d.y; ray.dz = d.z; ray.dw = d.w;
+        return ray;
+    }
+};
+
+template <int AM, class RAYS>
+__device__ __forceinline__ void query_hits_body(const Scene& S, const GridDesc& g, const QueryBox& box, const RAYS& rays, uint64_t n,
+                                                const int32_t* mask, const QueryHits& out, QueryCounters* __restrict__ counters) {
+    WaveCount wc;
+    const uint64_t stride = (uint64_t)gridDim.x * kQueryBlock;
+    for (uint64_t base = (uint64_t)blockIdx.x * kQueryBlock; base < n; base += stride) {
+        const uint64_t i = base + threadIdx.x;
+        bool active = false, on_grid = false;
+        if (i < n) {
+            const Ray ray = rays(i);
+            active = mask ? (mask[i] >= 0) : true;
+            float T = kMaxFloat;
+            int idx = -1;
+            if (active) {
+                on_grid = query_on_grid(box, ray);
+                query_closest_one<AM>(S, g, on_grid, ray, T, idx, wc);
+            }
+            float4 P = make_float4(0.f, 0.f, 0.f, 0.f), N = P, RS = P, RD = P;
+            if (T < kMaxFloat) {
+                HitRec h;
+                // the frames' call; the affine shortcut (w taken from the ray) is the reference's 0*x + 0*y + 0*z + 1*w only for
+                // finite x, y, z, and a query's brute-force rays may hold an inf or a NaN: those fetch the bottom rows
+                materialise<AM>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u && finite3(ray));
+                Ray r;
+                reflection_ray<AM>(h, r);
+                P = make_float4(h.px, h.py, h.pz, h.pw);
+                N = make_float4(h.nx, h.ny, h.nz, 0.f);
+                RS = make_float4(r.sx, r.sy, r.sz, r.sw);
+                RD = make_float4(r.dx, r.dy, r.dz, r.dw);
+            }
+            if (out.t) out.t[i] = T;
+            if (out.index) out.index[i] = (T < kMaxFloat) ? idx : -1;  // (store_closest's rule, through pointers that may alias)
+            if (out.point) out.point[i] = P;
+            if (out.normal) out.normal[i] = N;
+            if (out.reflected) {
+                out.reflected[2 * i] = RS;
+                out.reflected[2 * i + 1] = RD;
+            }
+        }
+        wc.route(active, on_grid);
+    }
+    wc.flush(counters);
+}
+
+template <int AM>
+__global__ __launch_bounds__(kQueryBlock) void query_hits(const Scene S, const GridDesc g, const QueryBox box, const float4* rays, uint64_t n,
+                                                          const int32_t* mask, const QueryHits out, QueryCounters* __restrict__ counters) {
+    query_hits_body<AM>(S, g, box, AliasedRays{rays}, n, mask, out, counters);
+}
+
+template <int AM>
+__global__ __launch_bounds__(kQueryBlock) void query_primary_hits(const Scene S, const GridDesc g, const QueryBox box, const QueryCamera cam,
+                                                                  const uint64_t* __restrict__ items, uint64_t n, const QueryHits out,
+                                                                  QueryCounters* __restrict__ counters) {
+    query_hits_body<AM>(S, g, box, PrimaryRays{cam, items}, n, nullptr, out, counters);
+}
+
 dim3 query_blocks(uint64_t n) {
     const uint64_t blocks = (n + kQueryBlock - 1) / kQueryBlock;
     return dim3((uint32_t)(blocks < kQueryMaxBlocks ? blocks : kQueryMaxBlocks));
@@ -213,6 +294,43 @@ hipError_t launch_query_primary(const Scene& scene, const GridDesc& grid, const 
         case kUnfused: hipLaunchKernelGGL((query_primary<kUnfused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
         case kFused: hipLaunchKernelGGL((query_primary<kFused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
         case kDeviceCL: hipLaunchKernelGGL((query_primary<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+namespace {
+bool hits_refused(const QueryHits& o) {
+    return (!o.t && !o.index && !o.point && !o.normal && !o.reflected) || misaligned(o.t, 4) || misaligned(o.index, 4) ||
+           misaligned(o.point, 16) || misaligned(o.normal, 16) || misaligned(o.reflected, 16);
+}
+}  // namespace
+
+hipError_t launch_query_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays, uint64_t n,
+                             const int32_t* d_mask, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (!d_rays || misaligned(d_rays, 16) || misaligned(d_mask, 4) || hits_refused(out) || !d_counters) return hipErrorInvalidValue;
+    const dim3 blocks = query_blocks(n), block(kQueryBlock);
+    switch (arith) {
+        case kUnfused: hipLaunchKernelGGL((query_hits<kUnfused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
+        case kFused: hipLaunchKernelGGL((query_hits<kFused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
+        case kDeviceCL: hipLaunchKernelGGL((query_hits<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_query_primary_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
+                                     const uint64_t* d_items, uint64_t n, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (!d_items || misaligned(d_items, 8) || hits_refused(out) || !d_counters ||
+        (!camera.pinhole && (!camera.rays || misaligned(camera.rays, 16))) || (camera.pinhole && camera.width == 0))
+        return hipErrorInvalidValue;
+    const dim3 blocks = query_blocks(n), block(kQueryBlock);
+    switch (arith) {
+        case kUnfused: hipLaunchKernelGGL((query_primary_hits<kUnfused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
+        case kFused: hipLaunchKernelGGL((query_primary_hits<kFused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
+        case kDeviceCL: hipLaunchKernelGGL((query_primary_hits<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -1,5 +1,6 @@
 // rt_query_host.cpp - ray queries (hip_raytracer.h): rt_query_closest_device, rt_query_occluded_device, their host twins
-// rt_query_closest / rt_query_occluded, rt_query_primary and rt_get_query_info. A query reads the context's object records and grid as
+// rt_query_closest / rt_query_occluded, rt_query_primary, the hit-record queries rt_query_hits_device / rt_query_hits /
+// rt_query_primary_hits, and rt_get_query_info. A query reads the context's object records and grid as
 // the setters have left them and writes the caller's outputs and the context's counter block - nothing of the frame: not its rays,
 // camera, pose, shard, supersampling factor, aux buffers or state buffers. The device forms enqueue a memset, two event records and one
 // kernel (rt_query.hip) and return; after the first call, which makes the counter block and the events, nothing is allocated.
@@ -85,6 +86,19 @@ int ensure_query_support(rt_context* c) {
     return RT_OK;
 }
 
+// the context's own primary rays, for rt_query_primary / rt_query_primary_hits
+rt::QueryCamera query_camera(const rt_context* c) {
+    rt::QueryCamera cam = {};
+    cam.rays = c->pinhole ? nullptr : c->d_rays;
+    cam.pinhole = c->pinhole ? 1u : 0u;
+    cam.width = c->width ? c->width : 1;
+    cam.half_w = (float)c->width / 2.0f;
+    cam.half_h = (float)c->height / 2.0f;
+    cam.height_f = (float)c->height;
+    cam.z = c->z;
+    return cam;
+}
+
 enum class Kind { Closest, Occluded, Primary };
 
 // One query on `stream`: counters zeroed, event, kernel, event. All pointers are device memory; `d_in` the rays or, for Kind::Primary, the
@@ -103,15 +117,7 @@ int enqueue_query(rt_context* c, Kind kind, const void* d_in, uint64_t n, float*
     } else if (kind == Kind::Occluded) {
         e = rt::launch_query_occluded(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_occluded, c->d_query_counters, stream);
     } else {
-        rt::QueryCamera cam = {};
-        cam.rays = c->pinhole ? nullptr : c->d_rays;
-        cam.pinhole = c->pinhole ? 1u : 0u;
-        cam.width = c->width ? c->width : 1;
-        cam.half_w = (float)c->width / 2.0f;
-        cam.half_h = (float)c->height / 2.0f;
-        cam.height_f = (float)c->height;
-        cam.z = c->z;
-        e = rt::launch_query_primary(scene, grid, box, arith, cam, static_cast<const uint64_t*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
+        e = rt::launch_query_primary(scene, grid, box, arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
     }
     if (e != hipSuccess) return fail_hip(c, e, "query launch");
     RT_HIP(c, hipEventRecord(c->ev_query[1], stream));
@@ -139,6 +145,84 @@ int query_from_host(rt_context* c, Kind kind, const void* in, size_t in_bytes, u
     if (t) RT_HIP(c, hipMemcpyAsync(t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, stream));
     if (index) RT_HIP(c, hipMemcpyAsync(index, d_index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
     if (occluded) RT_HIP(c, hipMemcpyAsync(occluded, d_occ, (size_t)n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+// ---- hit records ---------------------------------------------------------------------------------------------------------------------
+// One hit-record query on `stream`, as enqueue_query: `d_in` the rays or, with `primary`, the work-items; `hits` device pointers.
+int enqueue_hits(rt_context* c, bool primary, const void* d_in, uint64_t n, const int32_t* d_mask, const rt::QueryHits& hits, hipStream_t stream) {
+    if (const int rc = ensure_query_support(c)) return rc;
+    const rt::Scene scene = query_scene(c);
+    const rt::QueryBox box = query_box(c);
+    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
+    const int arith = query_arith(c);
+    RT_HIP(c, hipMemsetAsync(c->d_query_counters, 0, sizeof(rt::QueryCounters), stream));
+    RT_HIP(c, hipEventRecord(c->ev_query[0], stream));
+    const hipError_t e = primary ? rt::launch_query_primary_hits(scene, grid, box, arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, hits,
+                                                                 c->d_query_counters, stream)
+                                 : rt::launch_query_hits(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_mask, hits,
+                                                         c->d_query_counters, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "hit-record query launch");
+    RT_HIP(c, hipEventRecord(c->ev_query[1], stream));
+    c->query_made = true;
+    return RT_OK;
+}
+
+rt::QueryHits device_hits(const rt_hits_t& o) {
+    return rt::QueryHits{o.t, o.index, reinterpret_cast<float4*>(o.point), reinterpret_cast<float4*>(o.normal), static_cast<float4*>(o.reflected)};
+}
+
+// what every form refuses of the output struct; `device`: its members are device pointers, whose alignment the kernel's stores need
+int check_hits(rt_context* c, const rt_hits_t* o, bool device) {
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    if (!o->t && !o->index && !o->point && !o->normal && !o->reflected) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
+    if (!device) return RT_OK;
+    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(o->point) | reinterpret_cast<uintptr_t>(o->normal) | reinterpret_cast<uintptr_t>(o->reflected)) & 15u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "point, normal and reflected must be 16-byte aligned");
+    return RT_OK;
+}
+
+// What hits_from_host stages per element, at most: the input (a 32-byte ray or an 8-byte work-item), the mask, t, index, point, normal
+// and the reflected ray; each of the first four arrays is padded to 16 bytes once.
+constexpr size_t kHitsStageBytesPerElement = sizeof(rt_ray) + 3 * 4 + 16 + 16 + sizeof(rt_ray);
+constexpr size_t kHitsStagePadding = 4 * 16;
+int check_hits_count(rt_context* c, uint64_t n) {
+    if (n > ((std::numeric_limits<size_t>::max)() - kHitsStagePadding) / kHitsStageBytesPerElement)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "too many elements: the staged records would not fit an address");
+    return RT_OK;
+}
+
+// The host forms: input, mask and the requested records staged in the context's patch buffer on the context's stream; synchronous.
+int hits_from_host(rt_context* c, bool primary, const void* in, size_t in_bytes, uint64_t n, const int32_t* mask, const rt_hits_t& out) {
+    RT_DEVICE(c);
+    const size_t count = (size_t)n;
+    const size_t off_mask = align16(in_bytes * count);
+    const size_t off_t = off_mask + align16(sizeof(int32_t) * count);
+    const size_t off_index = off_t + align16(sizeof(float) * count);
+    const size_t off_point = off_index + align16(sizeof(int32_t) * count);
+    const size_t off_normal = off_point + 16 * count;
+    const size_t off_refl = off_normal + 16 * count;
+    if (const int rc = ensure_patch_stage(c, off_refl + sizeof(rt_ray) * count)) return rc;
+    char* const stage = static_cast<char*>(c->d_patch_stage.p);
+    rt::QueryHits d = {};
+    d.t = out.t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
+    d.index = out.index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
+    d.point = out.point ? reinterpret_cast<float4*>(stage + off_point) : nullptr;
+    d.normal = out.normal ? reinterpret_cast<float4*>(stage + off_normal) : nullptr;
+    d.reflected = out.reflected ? reinterpret_cast<float4*>(stage + off_refl) : nullptr;
+    int32_t* const d_mask = mask ? reinterpret_cast<int32_t*>(stage + off_mask) : nullptr;
+    hipStream_t stream = c->stream;
+    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * count, hipMemcpyHostToDevice, stream));
+    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_hits(c, primary, stage, n, d_mask, d, stream)) return rc;
+    if (out.t) RT_HIP(c, hipMemcpyAsync(out.t, d.t, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
+    if (out.index) RT_HIP(c, hipMemcpyAsync(out.index, d.index, sizeof(int32_t) * count, hipMemcpyDeviceToHost, stream));
+    if (out.point) RT_HIP(c, hipMemcpyAsync(out.point, d.point, 16 * count, hipMemcpyDeviceToHost, stream));
+    if (out.normal) RT_HIP(c, hipMemcpyAsync(out.normal, d.normal, 16 * count, hipMemcpyDeviceToHost, stream));
+    if (out.reflected) RT_HIP(c, hipMemcpyAsync(out.reflected, d.reflected, sizeof(rt_ray) * count, hipMemcpyDeviceToHost, stream));
     RT_HIP(c, hipStreamSynchronize(stream));
     return RT_OK;
 }
@@ -202,6 +286,41 @@ int rt_query_primary(rt_context* c, const uint64_t* work_items, uint64_t n, floa
         return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
     if (n == 0) return RT_OK;
     return query_from_host(c, Kind::Primary, work_items, sizeof(uint64_t), n, t, index, nullptr);
+}
+
+int rt_query_hits_device(rt_context* c, const void* d_rays, uint64_t n, const int32_t* d_mask, const rt_hits_t* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, d_rays, n, true)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_mask) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the mask must be 4-byte aligned");
+    if (const int rc = check_hits(c, d_out, true)) return rc;
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_hits(c, false, d_rays, n, d_mask, device_hits(*d_out), static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_hits(rt_context* c, const void* rays, uint64_t n, const int32_t* mask, const rt_hits_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, rays, n, false)) return rc;
+    if (const int rc = check_hits_count(c, n)) return rc;
+    if (const int rc = check_hits(c, out, false)) return rc;
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (n == 0) return RT_OK;
+    return hits_from_host(c, false, rays, sizeof(rt_ray), n, mask, *out);
+}
+
+int rt_query_primary_hits(rt_context* c, const uint64_t* work_items, uint64_t n, const rt_hits_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
+    if (const int rc = check_hits_count(c, n)) return rc;
+    if (const int rc = check_hits(c, out, false)) return rc;
+    for (uint64_t k = 0; k < n; ++k)
+        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
+    if (const int rc = refuse_triangles(c)) return rc;
+    if (!c->pinhole && !c->have_rays)
+        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    if (n == 0) return RT_OK;
+    return hits_from_host(c, true, work_items, sizeof(uint64_t), n, nullptr, *out);
 }
 
 int rt_get_query_info(rt_context* c, rt_query_info_t* info) {

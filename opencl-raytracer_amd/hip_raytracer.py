@@ -48,6 +48,7 @@ EXPORTS = [
     "rt_set_visibility", "rt_set_visibility_device", "rt_set_visibility_multi", "rt_read_visibility",
     "rt_query_closest_device", "rt_query_occluded_device", "rt_query_closest", "rt_query_occluded", "rt_query_primary",
     "rt_get_query_info",
+    "rt_query_hits_device", "rt_query_hits", "rt_query_primary_hits",
 ]
 
 
@@ -152,6 +153,14 @@ class RTQueryInfo(ctypes.Structure):
     def as_dict(self):
         return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
 
+
+class RTHits(ctypes.Structure):
+    """rt_hits_t: five pointers, each may be NULL (not all)."""
+    _fields_ = [("t", ctypes.c_void_p), ("index", ctypes.c_void_p), ("point", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("reflected", ctypes.c_void_p)]
+
+
+HIT_FIELDS = ("t", "index", "point", "normal", "reflected")
 
 _lib = None
 
@@ -324,6 +333,13 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_query_primary.argtypes = [vp, vp, u64, vp, vp]
         lib.rt_get_query_info.restype = i32
         lib.rt_get_query_info.argtypes = [vp, ctypes.POINTER(RTQueryInfo)]
+    if hasattr(lib, "rt_query_hits_device"):  # (the same: a build from before hit-record queries)
+        lib.rt_query_hits_device.restype = i32
+        lib.rt_query_hits_device.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTHits), vp]
+        lib.rt_query_hits.restype = i32
+        lib.rt_query_hits.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTHits)]
+        lib.rt_query_primary_hits.restype = i32
+        lib.rt_query_primary_hits.argtypes = [vp, vp, u64, ctypes.POINTER(RTHits)]
     if path is None:
         _lib = lib
     return lib
@@ -433,6 +449,71 @@ def _pick(lib, ctx, work_items):
     t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
     _check_rc(lib, ctx, lib.rt_query_primary(ctx, _ptr(items), n, _ptr(t), _ptr(index)))
     return t, index
+
+
+def _wanted(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in HIT_FIELDS for w in want):
+        raise ValueError(f"want: a non-empty selection of {HIT_FIELDS}")
+    return want
+
+
+def _host_hits(n: int, want):
+    """numpy arrays for the wanted records and the rt_hits_t that points at them."""
+    shapes = {"t": ((n,), np.float32), "index": ((n,), np.int32), "point": ((n, 4), np.float32), "normal": ((n, 4), np.float32),
+              "reflected": ((n,), RAY_DTYPE)}
+    out = {w: np.zeros(*shapes[w]) for w in want}
+    return out, RTHits(**{w: (a.ctypes.data if a.size else None) for w, a in out.items()})
+
+
+def _query_hits(lib, ctx, rays, mask, want, out, device: int):
+    """What HIPRaytracer.query_hits and MultiHIPRaytracer.query_hits (through its shard 0) share."""
+    want = _wanted(want)
+    if _is_tensor(rays):
+        import torch
+        ptr, n, stream = _device_rays(rays, device)
+        shapes = {"t": ((n,), torch.float32), "index": ((n,), torch.int32), "point": ((n, 4), torch.float32),
+                  "normal": ((n, 4), torch.float32), "reflected": ((n, 8), torch.float32)}
+        res = {}
+        for w in want:
+            shape, dtype = shapes[w]
+            given = None if out is None else out.get(w)
+            if given is None:
+                res[w] = torch.empty(shape, dtype=dtype, device=rays.device)
+            else:
+                if not _is_tensor(given) or given.device != rays.device or given.dtype != dtype or not given.is_contiguous() or \
+                        given.numel() != int(np.prod(shape)):
+                    raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the rays' device")
+                res[w] = given
+        m_ptr = None
+        if mask is not None:
+            if not _is_tensor(mask) or mask.device != rays.device or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != n:
+                raise ValueError("mask: a contiguous int32 tensor on the rays' device, one entry per ray")
+            m_ptr = ctypes.c_void_p(mask.data_ptr()) if n else None
+        if n:
+            hits = RTHits(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_query_hits_device(ctx, ptr, n, m_ptr, ctypes.byref(hits), stream))
+        return res
+    if out is not None:
+        raise ValueError("out= takes device tensors: numpy rays return fresh arrays")
+    rays = rays_of(rays)
+    n = int(rays.shape[0])
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
+        if mask.shape[0] != n:
+            raise ValueError("mask: one int32 entry per ray")
+    res, hits = _host_hits(n, want)
+    if n:
+        _check_rc(lib, ctx, lib.rt_query_hits(ctx, _ptr(rays), n, _ptr(mask), ctypes.byref(hits)))
+    return res
+
+
+def _pick_hit(lib, ctx, work_items, want):
+    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
+    n = int(items.shape[0])
+    res, hits = _host_hits(n, _wanted(want))
+    _check_rc(lib, ctx, lib.rt_query_primary_hits(ctx, _ptr(items), n, ctypes.byref(hits)))
+    return res
 
 
 def _query_info(lib, ctx) -> dict:
@@ -880,6 +961,33 @@ class HIPRaytracer:
             return float(t[0]), int(index[0])
         return _pick(self._lib, self._ctx, i)
 
+    def query_hits(self, rays, mask=None, want=HIT_FIELDS, out=None):
+        """query_closest with the hit RECORD (rt_query_hits / rt_query_hits_device): a dict of the records named in `want` -
+        "t" float32[n] and "index" int32[n] exactly as query_closest's; "point" float32[n, 4], the view-space intersection;
+        "normal" float32[n, 4], the unit normal in xyz, w = 0; "reflected", the next ray of the reflection chain (RAY_DTYPE[n], or
+        float32[n, 8] for tensors) - in the context's arithmetic mode, as the frames compute them. Where index is -1 (a miss, a NaN
+        time, a masked ray) every record is zero. `mask`: int32 per ray, a negative entry is not traced and reads as a miss - pass
+        the previous bounce's index when following a chain (hits.chain). Arrays and tensors as query_closest; with tensors, `out`
+        may name existing tensors to write into: out["reflected"] may be `rays` itself and out["index"] may be `mask`."""
+        return _query_hits(self._lib, self._ctx, rays, mask, want, out, self._device)
+
+    def pick_hit(self, i, j=None, want=HIT_FIELDS):
+        """pick with the hit record (rt_query_primary_hits): pick_hit(i, j) -> a dict of the records of that one primary ray
+        (t a float, index an int, point / normal float32[4], reflected one RAY_DTYPE record); pick_hit(work_items) -> a dict of
+        arrays, as query_hits returns."""
+        if j is not None:
+            width = self._grid_width()
+            if not width:
+                raise ValueError("pick_hit(i, j) needs a camera or a pose; with a plain ray buffer use pick_hit(work_items)")
+            res = _pick_hit(self._lib, self._ctx, [int(j) * width + int(i)], want)
+            one = {w: a[0] for w, a in res.items()}
+            if "t" in one:
+                one["t"] = float(one["t"])
+            if "index" in one:
+                one["index"] = int(one["index"])
+            return one
+        return _pick_hit(self._lib, self._ctx, i, want)
+
     def _grid_width(self) -> int:
         """The width of the grid the rays in use were generated for: the camera's, or the last set_pose's (0: a plain ray buffer)."""
         st = self.stats()
@@ -1054,6 +1162,14 @@ class MultiHIPRaytracer:
     def pick(self, work_items):
         """HIPRaytracer.pick(work_items) through shard 0: frame work-items, regardless of the shards' tiles."""
         return _pick(self._lib, self._shard0(), work_items)
+
+    def query_hits(self, rays, mask=None, want=HIT_FIELDS, out=None):
+        """HIPRaytracer.query_hits through shard 0."""
+        return _query_hits(self._lib, self._shard0(), rays, mask, want, out, self._device0)
+
+    def pick_hit(self, work_items, want=HIT_FIELDS):
+        """HIPRaytracer.pick_hit(work_items) through shard 0."""
+        return _pick_hit(self._lib, self._shard0(), work_items, want)
 
     def query_info(self) -> dict:
         return _query_info(self._lib, self._shard0())

@@ -308,6 +308,32 @@ void query_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, f
     }
 }
 
+// the record stage for a tile of the caller's rays (CPURaytracer::HitRecords): finish_hit + reflection_ray for the winner index[i]
+// at time t[i]; zero records where there is no winner. The clones as render_tile's.
+__attribute__((target_clones("fma", "default")))
+void record_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, const float* t, const int32_t* index, rtm::vec4* point,
+                 rtm::vec4* normal, Ray3D* reflected) {
+    for (size_t i = first; i < last; ++i) {
+        point[i] = rtm::vec4();
+        normal[i] = rtm::vec4();
+        reflected[i].start = rtm::vec4();
+        reflected[i].direction = rtm::vec4();
+        if (index[i] < 0 || (size_t)index[i] >= sc.n_objs) continue;
+        Ray ray;
+        ray.start = F4{rays[i].start.x, rays[i].start.y, rays[i].start.z, rays[i].start.w};
+        ray.direction = F4{rays[i].direction.x, rays[i].direction.y, rays[i].direction.z, rays[i].direction.w};
+        Hit h;
+        h.time = t[i];
+        h.index = index[i];
+        finish_hit(sc, ray, h);
+        const Ray r = reflection_ray(h);
+        point[i] = rtm::vec4(h.intersection.x, h.intersection.y, h.intersection.z, h.intersection.w);
+        normal[i] = rtm::vec4(h.normal.x, h.normal.y, h.normal.z, 0.f);
+        reflected[i].start = rtm::vec4(r.start.x, r.start.y, r.start.z, r.start.w);
+        reflected[i].direction = rtm::vec4(r.direction.x, r.direction.y, r.direction.z, r.direction.w);
+    }
+}
+
 // what the kernels read of an object's two matrices: the surface's copies, and rows x, y, z of mvInverse for the object loop
 void set_transform(CPURaytracer::Surface& d, CPURaytracer::Instance& h, const rtm::mat4& mv, const rtm::mat4& inv) {
     std::memcpy(d.inv, inv.data(), sizeof(d.inv));
@@ -437,6 +463,25 @@ void CPURaytracer::QueryOccluded(const std::vector<Ray3D>& q, std::vector<uint8_
     QueryClosest(q, t, index);
     occluded.resize(q.size());
     for (size_t i = 0; i < q.size(); ++i) occluded[i] = (t[i] >= 1.f || t[i] < 0) ? 0 : 1;  // (.cl:229; a NaN reads occluded)
+}
+
+void CPURaytracer::HitRecords(const std::vector<Ray3D>& q, Hits& hits) const {
+    const size_t n = q.size();
+    if (hits.t.size() != n || hits.index.size() != n) throw std::invalid_argument("HitRecords: t and index must have one entry per ray");
+    hits.point.assign(n, rtm::vec4());
+    hits.normal.assign(n, rtm::vec4());
+    hits.reflected.assign(n, Ray3D(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f)));
+    const Scene sc{instances.data(), surfaces.data(), instances.size(), nullptr, 0};
+    record_tile(sc, q.data(), 0, n, hits.t.data(), hits.index.data(), hits.point.data(), hits.normal.data(), hits.reflected.data());
+}
+
+void CPURaytracer::QueryHits(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask, Hits& hits) const {
+    const size_t n = q.size();
+    if (!mask.empty() && mask.size() != n) throw std::invalid_argument("QueryHits: the mask must be empty or have one entry per ray");
+    QueryClosest(q, hits.t, hits.index);
+    for (size_t i = 0; i < mask.size(); ++i)
+        if (mask[i] < 0) { hits.t[i] = MAX_FLOAT; hits.index[i] = -1; }  // (not traced on the GPU; here the answer is dropped)
+    HitRecords(q, hits);
 }
 
 cl_float4* CPURaytracer::Render() {

@@ -72,6 +72,23 @@ public:
     void QueryClosest(const std::vector<Ray3D>& rays, std::vector<float>& t, std::vector<int32_t>& index) const;
     void QueryOccluded(const std::vector<Ray3D>& rays, std::vector<uint8_t>& occluded) const;
 
+    // Hit-record queries, the same option as HIPRaytracer's (hip_raytracer.h, "hit-record queries"), and its executable definition
+    // in the default arithmetic: QueryClosest's (t, index) and, where index >= 0, what raycast() leaves in the HitRecord of that
+    // winner at that time - finish_hit() and reflection_ray(), the functions Render() uses - one entry per ray. point:
+    // HitRecord.intersection; normal: HitRecord.normal in xyz, w = 0; reflected: the next ray of the reflection chain. Where
+    // index == -1 (a miss, a NaN time, a ray whose `mask` entry is negative: not traced, t = MAX_FLOAT) the records are zero.
+    // `mask` is empty or one entry per ray (std::invalid_argument otherwise).
+    struct Hits {
+        std::vector<float> t;
+        std::vector<int32_t> index;
+        std::vector<rtm::vec4> point, normal;
+        std::vector<Ray3D> reflected;
+    };
+    void QueryHits(const std::vector<Ray3D>& rays, const std::vector<int32_t>& mask, Hits& hits) const;
+    // The record stage alone, for a winner and a time of the caller's: point / normal / reflected of `hits` from its t and index
+    // (sized as `rays`; an index that is negative or beyond the objects gives zero records).
+    void HitRecords(const std::vector<Ray3D>& rays, Hits& hits) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

@@ -107,10 +107,12 @@ void HIPRaytracer::SetSupersampling(unsigned int s) {
 void HIPRaytracer::SetRays(const std::vector<Ray3D>& rays_) {
     if (multi) throw std::runtime_error("HIPRaytracer::SetRays: not available on the several-GPU object");
     if (rt_set_rays(ctx, rays_.data(), rays_.size()) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRays: ") + rt_last_error(ctx));
+    pose_width = 0;
 }
 
 void HIPRaytracer::SetPose(unsigned int width, unsigned int height, float z, const float m[9], const float origin[3], void* stream) {
     Check(multi ? rt_set_pose_multi(multi, width, height, z, m, origin) : rt_set_pose(ctx, width, height, z, m, origin, stream), "SetPose");
+    pose_width = width;
 }
 
 void HIPRaytracer::SetLights(const std::vector<Light>& lights_) {
@@ -180,6 +182,53 @@ rt_query_info_t HIPRaytracer::QueryInfo() {
     return info;
 }
 
+namespace {
+// n zero records and the rt_hits_t that points at them (Ray3D and rtm::vec4 are the ABI's 32- and 16-byte records)
+rt_hits_t sized(HIPRaytracer::Hits& h, size_t n) {
+    h.t.assign(n, 0.f);
+    h.index.assign(n, -1);
+    h.point.assign(n, rtm::vec4());
+    h.normal.assign(n, rtm::vec4());
+    Ray3D zero(rtm::vec3(0.f, 0.f, 0.f), rtm::vec3(0.f, 0.f, 0.f));
+    zero.start = rtm::vec4();
+    h.reflected.assign(n, zero);
+    rt_hits_t out;
+    out.t = h.t.data();
+    out.index = h.index.data();
+    out.point = reinterpret_cast<float*>(h.point.data());
+    out.normal = reinterpret_cast<float*>(h.normal.data());
+    out.reflected = h.reflected.data();
+    return out;
+}
+}  // namespace
+
+HIPRaytracer::Hits HIPRaytracer::QueryHits(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask) {
+    static_assert(sizeof(Ray3D) == 32 && sizeof(rtm::vec4) == 16, "the ABI's records");
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!mask.empty() && mask.size() != q.size()) throw std::runtime_error("HIPRaytracer::QueryHits: the mask must be empty or have one entry per ray");
+    Hits h;
+    const rt_hits_t out = sized(h, q.size());
+    if (!c || rt_query_hits(c, q.data(), q.size(), mask.empty() ? nullptr : mask.data(), &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::QueryHits: ") + (c ? rt_last_error(c) : "no context"));
+    return h;
+}
+
+HIPRaytracer::Hits HIPRaytracer::PickHits(const std::vector<uint64_t>& work_items) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    Hits h;
+    const rt_hits_t out = sized(h, work_items.size());
+    if (!c || rt_query_primary_hits(c, work_items.data(), work_items.size(), &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::PickHits: ") + (c ? rt_last_error(c) : "no context"));
+    return h;
+}
+
+HIPRaytracer::Hits HIPRaytracer::PickHit(unsigned int i, unsigned int j) {
+    const rt_stats_t st = Stats();
+    const unsigned int width = st.pinhole ? st.width : pose_width;
+    if (!width) throw std::runtime_error("HIPRaytracer::PickHit: needs a camera or a pose; with a plain ray buffer use PickHits");
+    return PickHits(std::vector<uint64_t>(1, (uint64_t)j * width + i));
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
@@ -197,6 +246,7 @@ rt_light_tiles_info_t HIPRaytracer::LightTilesInfo() {
 void HIPRaytracer::SetRaysDevice(const void* d_rays, size_t n, void* stream) {
     if (multi) throw std::runtime_error("HIPRaytracer::SetRaysDevice: not available on the several-GPU object");
     if (rt_set_rays_device(ctx, d_rays, n, stream) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::SetRaysDevice: ") + rt_last_error(ctx));
+    pose_width = 0;
 }
 
 size_t HIPRaytracer::Pixels() const {

@@ -103,6 +103,23 @@ public:
     void Pick(const std::vector<uint64_t>& work_items, std::vector<float>& t, std::vector<int32_t>& index);
     rt_query_info_t QueryInfo();
 
+    // Hit-record queries (hip_raytracer.h, "hit-record queries"): QueryClosest's (t, index) with WHERE the ray meets the winner and how
+    // the surface faces there - point: the view-space intersection; normal: the unit normal in xyz, w = 0; reflected: the next ray of
+    // the reflection chain - in the context's arithmetic mode, one entry per ray; zero records where index is -1. `mask`: empty, or
+    // one entry per ray - a negative entry is not traced and reads as a miss (pass the previous bounce's index along a chain).
+    // PickHit(i, j): the record under column i, row j of the camera's or the last SetPose's grid (std::runtime_error with a plain
+    // ray buffer: use PickHits); PickHits: of the frame's own primary rays of the work-items. Synchronous (rt_query_hits,
+    // rt_query_primary_hits); the several-GPU object asks its first shard.
+    struct Hits {
+        std::vector<float> t;
+        std::vector<int32_t> index;
+        std::vector<rtm::vec4> point, normal;
+        std::vector<Ray3D> reflected;
+    };
+    Hits QueryHits(const std::vector<Ray3D>& rays, const std::vector<int32_t>& mask = std::vector<int32_t>());
+    Hits PickHits(const std::vector<uint64_t>& work_items);
+    Hits PickHit(unsigned int i, unsigned int j);
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.
@@ -117,4 +134,5 @@ private:
     void Check(int rc, const char* method) const;  // throws "HIPRaytracer::<method>: " + the last error of ctx or of multi
     rt_context* ctx = nullptr;
     rt_multi* multi = nullptr;   // set instead of ctx by the several-GPU constructor
+    unsigned int pose_width = 0; // the last SetPose's grid width (0: the rays in use are the camera's or a plain buffer)
 };

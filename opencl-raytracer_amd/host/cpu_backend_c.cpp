@@ -37,6 +37,56 @@ Ray3D host_ray(const rt_ray& r) {
     h.direction = rtm::vec4(r.direction[0], r.direction[1], r.direction[2], r.direction[3]);
     return h;
 }
+
+std::vector<Ray3D> host_rays(const rt_ray* rays, uint64_t n) {
+    std::vector<Ray3D> q;
+    q.reserve(n);
+    for (uint64_t i = 0; i < n; ++i) q.push_back(host_ray(rays[i]));
+    return q;
+}
+
+// The backend of the query entries: constructed with `objs_` (no lights, no frame rays), then SetTransforms(t_first,
+// transforms_[0 .. t_count)) and SetVisibility(v_first, visible_[0 .. v_count)) (NULL with a count of 0: none). The vectors the
+// backend refers to live here. make() is false for arguments it cannot serve (triangle records, a range beyond the objects, a NULL
+// array with a count).
+struct QueryBackend {
+    std::vector<ObjectData> objects;
+    const std::vector<Light> no_lights;
+    const std::vector<Ray3D> no_rays;
+    std::unique_ptr<CPURaytracer> backend;
+    bool make(const void* objs_, uint32_t n_objs, unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count,
+              const void* transforms_, uint32_t t_first, uint32_t t_count) {
+        if ((!objs_ && n_objs) || (!visible_ && v_count) || (!transforms_ && t_count)) return false;
+        const rt_object_data* objs = static_cast<const rt_object_data*>(objs_);
+        objects.reserve(n_objs);
+        for (uint32_t i = 0; i < n_objs; ++i) {
+            const rt_object_data& d = objs[i];
+            if (d.type == 2u) return false;
+            ObjectData o(static_cast<ObjectData::PrimativeType>(d.type > 255u ? 255u : d.type), host_material(d.mat), rtm::mat4(1.f));
+            std::memcpy(o.mv.data(), d.mv, sizeof(d.mv));
+            std::memcpy(o.mvInverse.data(), d.mvInverse, sizeof(d.mvInverse));
+            std::memcpy(o.mvInverseTranspose.data(), d.mvInverseTranspose, sizeof(d.mvInverseTranspose));
+            objects.push_back(o);
+        }
+        backend.reset(new CPURaytracer(objects, no_lights, no_rays, 0, CPURaytracer::kHittest, threads));
+        try {
+            if (t_count) {
+                const rt_transform* src = static_cast<const rt_transform*>(transforms_);
+                std::vector<Transform> ts(t_count);
+                for (uint32_t i = 0; i < t_count; ++i) {
+                    std::memcpy(ts[i].mv.data(), src[i].mv, sizeof(src[i].mv));
+                    std::memcpy(ts[i].mvInverse.data(), src[i].mvInverse, sizeof(src[i].mvInverse));
+                }
+                backend->SetTransforms(t_first, ts);
+            }
+            if (v_count) {
+                const uint8_t* v = static_cast<const uint8_t*>(visible_);
+                backend->SetVisibility(v_first, std::vector<uint8_t>(v, v + v_count));
+            }
+        } catch (const std::exception&) { return false; }
+        return true;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -228,59 +278,61 @@ int cpu_rt_render_set_visibility(int kernel, uint32_t max_bounces, const void* o
     return rc;
 }
 
-// CPURaytracer::QueryClosest / QueryOccluded through the C entry: the backend is constructed with `objs_` (no lights, no frame rays),
-// SetTransforms(t_first, transforms_[0 .. t_count)) and SetVisibility(v_first, visible_[0 .. v_count)) are applied (NULL with a count
-// of 0: none), then the `n_rays` rt_ray records of `rays_` are queried. t, index (n_rays each) and occluded (n_rays bytes) may each be
+// CPURaytracer::QueryClosest / QueryOccluded through the C entry: on a QueryBackend of these objects, transforms and visibility the
+// `n_rays` rt_ray records of `rays_` are queried. t, index (n_rays each) and occluded (n_rays bytes) may each be
 // NULL. Returns 0, or -1 for arguments it cannot serve (triangle records, a range beyond the objects, a NULL array with a count).
 int cpu_rt_query(const void* objs_, uint32_t n_objs, const void* rays_, uint64_t n_rays, float* t, int32_t* index, uint8_t* occluded,
                  unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count, const void* transforms_, uint32_t t_first,
                  uint32_t t_count) {
-    if ((!rays_ && n_rays) || (!objs_ && n_objs) || (!visible_ && v_count) || (!transforms_ && t_count)) return -1;
-    const rt_object_data* objs = static_cast<const rt_object_data*>(objs_);
-    const rt_ray* rays = static_cast<const rt_ray*>(rays_);
-    std::vector<ObjectData> objects;
-    objects.reserve(n_objs);
-    for (uint32_t i = 0; i < n_objs; ++i) {
-        const rt_object_data& d = objs[i];
-        if (d.type == 2u) return -1;
-        ObjectData o(static_cast<ObjectData::PrimativeType>(d.type > 255u ? 255u : d.type), host_material(d.mat), rtm::mat4(1.f));
-        std::memcpy(o.mv.data(), d.mv, sizeof(d.mv));
-        std::memcpy(o.mvInverse.data(), d.mvInverse, sizeof(d.mvInverse));
-        std::memcpy(o.mvInverseTranspose.data(), d.mvInverseTranspose, sizeof(d.mvInverseTranspose));
-        objects.push_back(o);
-    }
-    const std::vector<Light> no_lights;
-    const std::vector<Ray3D> no_rays;
-    CPURaytracer backend(objects, no_lights, no_rays, 0, CPURaytracer::kHittest, threads);
-    try {
-        if (t_count) {
-            const rt_transform* src = static_cast<const rt_transform*>(transforms_);
-            std::vector<Transform> ts(t_count);
-            for (uint32_t i = 0; i < t_count; ++i) {
-                std::memcpy(ts[i].mv.data(), src[i].mv, sizeof(src[i].mv));
-                std::memcpy(ts[i].mvInverse.data(), src[i].mvInverse, sizeof(src[i].mvInverse));
-            }
-            backend.SetTransforms(t_first, ts);
-        }
-        if (v_count) {
-            const uint8_t* v = static_cast<const uint8_t*>(visible_);
-            backend.SetVisibility(v_first, std::vector<uint8_t>(v, v + v_count));
-        }
-    } catch (const std::exception&) { return -1; }
-    std::vector<Ray3D> q;
-    q.reserve(n_rays);
-    for (uint64_t i = 0; i < n_rays; ++i) q.push_back(host_ray(rays[i]));
+    if (!rays_ && n_rays) return -1;
+    QueryBackend q;
+    if (!q.make(objs_, n_objs, threads, visible_, v_first, v_count, transforms_, t_first, t_count)) return -1;
+    const std::vector<Ray3D> rays = host_rays(static_cast<const rt_ray*>(rays_), n_rays);
     if (t || index) {
         std::vector<float> qt;
         std::vector<int32_t> qi;
-        backend.QueryClosest(q, qt, qi);
+        q.backend->QueryClosest(rays, qt, qi);
         if (t && n_rays) std::memcpy(t, qt.data(), sizeof(float) * n_rays);
         if (index && n_rays) std::memcpy(index, qi.data(), sizeof(int32_t) * n_rays);
     }
     if (occluded) {
         std::vector<uint8_t> occ;
-        backend.QueryOccluded(q, occ);
+        q.backend->QueryOccluded(rays, occ);
         if (n_rays) std::memcpy(occluded, occ.data(), n_rays);
+    }
+    return 0;
+}
+
+// CPURaytracer::QueryHits / HitRecords through the C entry, on a backend made as cpu_rt_query's. records_only == 0: QueryHits with
+// `mask` (NULL or n_rays int32); t and index are OUTPUTS. records_only != 0: HitRecords; t and index are INPUTS. point, normal
+// (n_rays x 4 floats) and reflected (n_rays rt_ray records) may each be NULL; t and index may be NULL only as outputs. Returns 0 or -1.
+int cpu_rt_query_hits(const void* objs_, uint32_t n_objs, const void* rays_, uint64_t n_rays, const int32_t* mask, float* t, int32_t* index,
+                      float* point, float* normal, void* reflected, int records_only, unsigned int threads, const void* visible_,
+                      uint32_t v_first, uint32_t v_count, const void* transforms_, uint32_t t_first, uint32_t t_count) {
+    if ((!rays_ && n_rays) || (records_only && n_rays && (!t || !index))) return -1;
+    QueryBackend q;
+    if (!q.make(objs_, n_objs, threads, visible_, v_first, v_count, transforms_, t_first, t_count)) return -1;
+    const std::vector<Ray3D> rays = host_rays(static_cast<const rt_ray*>(rays_), n_rays);
+    CPURaytracer::Hits hits;
+    try {
+        if (records_only) {
+            hits.t.assign(t, t + n_rays);
+            hits.index.assign(index, index + n_rays);
+            q.backend->HitRecords(rays, hits);
+        } else {
+            q.backend->QueryHits(rays, mask ? std::vector<int32_t>(mask, mask + n_rays) : std::vector<int32_t>(), hits);
+        }
+    } catch (const std::exception&) { return -1; }
+    rt_ray* refl = static_cast<rt_ray*>(reflected);
+    for (uint64_t i = 0; i < n_rays; ++i) {
+        if (!records_only && t) t[i] = hits.t[i];
+        if (!records_only && index) index[i] = hits.index[i];
+        if (point) std::memcpy(point + 4 * i, &hits.point[i], 16);
+        if (normal) std::memcpy(normal + 4 * i, &hits.normal[i], 16);
+        if (refl) {
+            std::memcpy(refl[i].start, &hits.reflected[i].start, 16);
+            std::memcpy(refl[i].direction, &hits.reflected[i].direction, 16);
+        }
     }
     return 0;
 }

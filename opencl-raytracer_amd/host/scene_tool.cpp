@@ -12,8 +12,10 @@
 //                       matrix (row-major) from the origin (ox, oy, oz) - the backend's SetPose on the (sample) grid; also with --ss.
 //   scene_tool pick    <scene.txt> <W> <H> <i> <j> [hip|cpu] [z-bits|-]
 //                       the object under pixel (column i, row j) of the W x H picture: prints "pick <object index or -1> <t>
-//                       <backend>". HIPRaytracer::Pick on the GPU; with `cpu`, or where no GPU backend can be made,
-//                       CPURaytracer::QueryClosest of that pixel's ray - the same answer; z-bits as for render
+//                       <backend>" as its last line, behind "point <x> <y> <z> <w>" and "normal <x> <y> <z>" - where the ray
+//                       meets the object, in view space, and the unit normal there (zeros on a miss). HIPRaytracer::PickHits on
+//                       the GPU; with `cpu`, or where no GPU backend can be made, CPURaytracer::QueryHits of that pixel's ray -
+//                       the same answer; z-bits as for render
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -105,11 +107,13 @@ int main(int argc, char** argv) {
             const uint64_t item = (uint64_t)pj * (uint64_t)pw + (uint64_t)pi;
             std::vector<float> t;
             std::vector<int32_t> index;
+            rtm::vec4 point, normal;
             const char* backend_name = (argc > 7 && std::strcmp(argv[7], "cpu") == 0) ? "cpu" : "hip";
             if (std::strcmp(backend_name, "hip") == 0) {
                 try {
                     HIPRaytracer backend(objects, lights, grid, 0);
-                    backend.Pick(std::vector<uint64_t>(1, item), t, index);
+                    const HIPRaytracer::Hits hit = backend.PickHits(std::vector<uint64_t>(1, item));
+                    t = hit.t; index = hit.index; point = hit.point[0]; normal = hit.normal[0];
                 } catch (const std::exception& e) {  // (no GPU: the CPU backend's loop over the same ray - said on stderr and in the line)
                     std::fprintf(stderr, "pick: %s; using the CPU backend\n", e.what());
                     backend_name = "cpu";
@@ -117,8 +121,12 @@ int main(int argc, char** argv) {
             }
             if (std::strcmp(backend_name, "cpu") == 0) {
                 CPURaytracer backend(objects, lights, grid, 0);
-                backend.QueryClosest(std::vector<Ray3D>(1, grid[item]), t, index);
+                CPURaytracer::Hits hit;
+                backend.QueryHits(std::vector<Ray3D>(1, grid[item]), std::vector<int32_t>(), hit);
+                t = hit.t; index = hit.index; point = hit.point[0]; normal = hit.normal[0];
             }
+            std::printf("point %.9g %.9g %.9g %.9g\n", (double)point.x, (double)point.y, (double)point.z, (double)point.w);
+            std::printf("normal %.9g %.9g %.9g\n", (double)normal.x, (double)normal.y, (double)normal.z);
             std::printf("pick %d %.9g %s\n", (int)index[0], (double)t[0], backend_name);
             return 0;
         }
