@@ -934,16 +934,33 @@ __device__ __forceinline__ void shade_assign(const Scene& S, const HitRec& h, fl
 
 // next ray of the reflection chain: start = intersection + 0.001 * normalize(reflection), direction = reflection
 // (shade_and_reflect_kernel.cl:260-263, 275-277)
+// The start alone, from the hit point and the ray's direction (= the reflection vector): what reflection_ray() computes
+// and what every reader of a 16-byte reflection record (rt_wavefront.hip: reflection_rays_rebuilt) computes again from
+// the pixel's stored hit - one function, so that both are the same three fma of the same normalisation.
+template <int AM>
+__device__ __forceinline__ void reflection_origin(float px, float py, float pz, float dx, float dy, float dz,
+                                                  float& sx, float& sy, float& sz) {
+    float nx = dx, ny = dy, nz = dz;
+    normalize3_<AM>(nx, ny, nz);
+    sx = fma_<AM>(nx, 0.001f, px);
+    sy = fma_<AM>(ny, 0.001f, py);
+    sz = fma_<AM>(nz, 0.001f, pz);
+}
 template <int AM>
 __device__ __forceinline__ void reflection_ray(const HitRec& h, Ray& r) {
-    float nx = h.rx, ny = h.ry, nz = h.rz;
-    normalize3_<AM>(nx, ny, nz);
-    r.sx = fma_<AM>(nx, 0.001f, h.px);
-    r.sy = fma_<AM>(ny, 0.001f, h.py);
-    r.sz = fma_<AM>(nz, 0.001f, h.pz);
+    reflection_origin<AM>(h.px, h.py, h.pz, h.rx, h.ry, h.rz, r.sx, r.sy, r.sz);
     r.sw = fma_<AM>(0.0f, 0.001f, h.pw);
     r.dx = h.rx; r.dy = h.ry; r.dz = h.rz; r.dw = 0.0f;
 }
+
+// Fourth word of a 16-byte reflection record: bit 31 = the exact test against the object the ray leaves reported a hit
+// (begin_shade_lit: the walk must test that object like any other), bits 0-30 = the loop's `bounces` after the hit.
+constexpr uint32_t kReflectSelfHit = 0x80000000u;
+__host__ __device__ constexpr uint32_t reflection_word(bool self_hit, uint32_t bounces) {
+    return (self_hit ? kReflectSelfHit : 0u) | (bounces & ~kReflectSelfHit);
+}
+__host__ __device__ constexpr bool reflection_word_self_hit(uint32_t word) { return (word & kReflectSelfHit) != 0u; }
+__host__ __device__ constexpr uint32_t reflection_word_bounces(uint32_t word) { return word & ~kReflectSelfHit; }
 
 // __kernel shade_and_reflect for one work-item whose primary ray hit (shade_and_reflect_kernel.cl:253-284)
 template <int AM, bool COUNT>

@@ -110,7 +110,10 @@ struct BlockGrid {
     uint32_t enabled;
     uint32_t take_skips;       // the walk takes the empty-space steps of the headers (always set; RT_BLOCK_SKIPS=0 is the measurement knob:
                                // cfg4 12.2 -> 12.4 ms, cfg5 40 -> 48 ms without them)
+    uint32_t serves_closest;   // this frame's closest-hit rays go through the block walk (set per frame by run_wavefront, 0 in the stored
+                               // descriptor; it takes the struct's tail padding: no other offset moves)
 };
+static_assert(sizeof(BlockGrid) == 96, "serves_closest sits in what was padding: the kernel arguments keep their offsets");
 constexpr uint32_t kBlockBorder = 2;
 #ifndef RT_BLOCK_ENTRIES
 #define RT_BLOCK_ENTRIES 7   // candidates a block holds (<= 7); 4 / 5 / 6 with their best cell edge: 13.11 / 12.86 / 12.74 vs 12.67 ms per cfg4 frame

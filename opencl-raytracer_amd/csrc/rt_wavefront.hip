@@ -34,8 +34,11 @@ namespace rt {
 // four 256-byte requests to four arrays (the kernel is bound by the memory system, not by its arithmetic). The default
 // shade_and_reflect flow touches the first four blocks only; the rest belongs to literal mode, the `shade` kernel and
 // stale-specular light scans.
+// Where the block walk serves a frame that has lights and no triangles, the first record is half used: a reflection ray is
+// the 16 bytes {direction, word} at float4 index i of the same array, and its start is rebuilt from the F_PX block
+// (reflection_rays_rebuilt). The allocation is the same either way.
 enum : uint32_t {
-    F_SX, F_SY, F_SZ, F_SW, F_DX, F_DY, F_DZ, F_DW,          // closest-hit ray in flight (primary / reflection): ONE 32-byte record per pixel
+    F_SX, F_SY, F_SZ, F_SW, F_DX, F_DY, F_DZ, F_DW,          // closest-hit ray in flight (primary / reflection): ONE 32-byte record per pixel - or a 16-byte one (above)
     F_A0, F_A1, F_A2, F_A3, F_A4, F_A5, F_A6, F_A7,          // shadow ray in flight: a second 32-byte record (store_ray, slot 1)
     F_PX, F_PY, F_PZ, F_HIDX,                                  // hit being shaded: view-space point, object
     F_NX, F_NY, F_NZ, F_PHASE,                                 // ... its normal; phase word (phase | flags | light index << 10)
@@ -185,6 +188,41 @@ __device__ __forceinline__ Ray shadow_of_pixel(const WfParams& w, uint64_t i, bo
     Ray ray;
     float nlx, nly, nlz;
     shadow_ray_to<AM>(w.rp.scene.lights[li], hp.x, hp.y, hp.z, ray, nlx, nly, nlz);
+    return ray;
+}
+
+// The reflection ray a pixel has in flight where the block walk serves the frame (per frame, never per pixel: run_wavefront
+// sets BlockGrid::serves_closest): a 16-byte record {direction, word} at index i of the slot-0 array - half of the array is
+// simply unused - instead of the 32-byte ray. The start is reflection_origin() of the direction and the hit the ray left, and
+// that hit is the pixel's F_PX block for as long as the record is read: emit_shadow(new_hit) writes it in the step that emits
+// the ray, and the next such store comes after the materialise that consumes the ray (a stale-specular scan keeps the
+// block; wf_finish traces and resumes in one thread, in that order). F_PX.w, the hit's object, is the walk's note unless
+// the word says that the self-test hit (reflection_word, rt_device.h). 16 bytes per ray that wf_resume neither writes nor
+// reads; the walk reads the same 32 bytes, from two arrays. Same function, same inputs: bit for bit the ray that left.
+__device__ __forceinline__ bool reflection_rays_rebuilt(const WfParams& w) {
+    return shadow_rays_rebuilt(w) && w.bgrid.serves_closest != 0u && w.rp.scene.n_lights != 0u;
+}
+__device__ __forceinline__ void store_reflection(const WfParams& w, uint64_t i, const Ray& r, uint32_t word) {
+    reinterpret_cast<float4*>(w.st)[i] = make_float4(r.dx, r.dy, r.dz, __uint_as_float(word));
+}
+__device__ __forceinline__ float4 load_reflection(const WfParams& w, uint64_t i) { return reinterpret_cast<const float4*>(w.st)[i]; }
+// the ray of record `rec`, which left hit block `hp`; `note`: the object the walk need not test again (0xffffffff: none)
+template <int AM>
+__device__ __forceinline__ Ray reflection_of_record(const float4 rec, const float4 hp, uint32_t& note) {
+    Ray ray;
+    reflection_origin<AM>(hp.x, hp.y, hp.z, rec.x, rec.y, rec.z, ray.sx, ray.sy, ray.sz);
+    ray.sw = 1.0f;  // (what every ray of a grid-able frame carries: rt_create checks the preconditions)
+    ray.dx = rec.x; ray.dy = rec.y; ray.dz = rec.z; ray.dw = 0.0f;
+    note = reflection_word_self_hit(__float_as_uint(rec.w)) ? 0xffffffffu : __float_as_uint(hp.w);
+    return ray;
+}
+// The stored closest-hit ray of pixel i in whichever form the frame keeps it (one block load more for the 16-byte form; a
+// caller that holds the F_PX block - loop_step - rebuilds from that). The 32-byte form comes back as stored: direction.w is the note.
+template <int AM>
+__device__ __forceinline__ Ray stored_closest_ray(const WfParams& w, uint64_t i, uint32_t& note) {
+    if (reflection_rays_rebuilt(w)) return reflection_of_record<AM>(load_reflection(w, i), load_block(w, F_PX, i), note);
+    const Ray ray = load_ray(w, i, kSlotClosest);
+    note = __float_as_uint(ray.dw);
     return ray;
 }
 
@@ -1330,16 +1368,21 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                 const uint32_t entry = w.identity_queue ? mine : queue[mine];
                 const uint32_t p_pix = w.identity_queue ? mine : (entry & kQueuePixel);
                 Ray ray;
+                uint32_t ray_note = 0xffffffffu;
                 if (w.first_round != 0u) {
                     // (closest_ray's primary branch, with its divisors through an empty asm: their reciprocals, computed once per
                     // wave, would otherwise sit in vector registers across the whole loop - see the grid box below)
                     RenderParams rp = w.rp;
                     asm volatile("" : "+s"(rp.width), "+s"(rp.bundles_x), "+s"(rp.run_rays));
                     ray = primary_ray(rp, global_ray_of(rp, p_pix));
+                } else if (reflection_rays_rebuilt(w)) {
+                    // (the 16-byte record and the hit it left: the same 32 bytes, and a normalisation per ray of the batch)
+                    ray = reflection_of_record<AM>(load_reflection(w, p_pix), load_block(w, F_PX, p_pix), ray_note);
                 } else {
                     ray = load_ray(w, p_pix, kSlotClosest);
+                    ray_note = __float_as_uint(ray.dw);
                 }
-                const uint32_t note = __float_as_uint(ray.dw);  // begin_shade_lit's note: the object a reflection ray leaves
+                const uint32_t note = ray_note;  // begin_shade_lit's note: the object a reflection ray leaves
                 ray.sw = 1.0f; ray.dw = 0.0f;  // what every ray of a grid-able frame carries (rt_create checks the preconditions)
                 const float p_dd = ray.dx * ray.dx + ray.dy * ray.dy + ray.dz * ray.dz;
                 bool start = false, brute = false;
@@ -1758,10 +1801,12 @@ __device__ __forceinline__ void patch_nan_result(const WfParams& w, const Ray& r
         }
     }
 }
+template <int AM>
 __device__ __forceinline__ void closest_result(const WfParams& w, uint64_t i, bool primary, float& T, int& idx) {
     load_closest_result(w, i, T, idx);
     if (T == kMaxFloat && w.grid.enabled && !w.rp.scene.literal && w.rp.scene.nan_winner >= 0) {
-        const Ray ray = closest_ray(w, i, primary);
+        uint32_t note;
+        const Ray ray = primary ? closest_ray(w, i, true) : stored_closest_ray<AM>(w, i, note);
         if (nan_ray_outcome(ray, w.rp.scene.nan_winner, w.rp.scene.nan_winner_sphere) == kNanRayTimeNaN) {
             T = __builtin_nanf("");
             idx = w.rp.scene.nan_winner;
@@ -1968,6 +2013,7 @@ __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool pr
     if (sends) {
         Ray ray;
         reflection_ray<AM>(h, ray);
+        bool self_hit = false;
         if (c.w.grid.enabled) {
             // The ray starts a skin's width off the object it leaves, i.e. inside that object's registration sphere: the
             // grid walk would park it as its first candidate and spend a (sparsely filled) exact-test round on it. Its
@@ -1976,10 +2022,12 @@ __device__ __forceinline__ void begin_shade_lit(Ctx& c, const HitRec& h, bool pr
             // slot) that this object is done. If the test ever reports a hit, nothing is said and the walk tests it as usual.
             float t_self;
             bool sphere_self;
-            const bool self_hit = rows_candidate<AM, true>(rows, ray, t_self, sphere_self);  // (the record materialise() just read)
+            self_hit = rows_candidate<AM, true>(rows, ray, t_self, sphere_self);  // (the record materialise() just read)
             ray.dw = __uint_as_float(self_hit ? 0xffffffffu : (uint32_t)h.index);
         }
-        store_ray(c.w, c.i, ray, kSlotClosest);
+        // (the 16-byte form: the start is rebuilt from the F_PX block that emit_shadow writes below - reflection_rays_rebuilt)
+        if (reflection_rays_rebuilt(c.w)) store_reflection(c.w, c.i, ray, reflection_word(self_hit, spec_bounces));
+        else store_ray(c.w, c.i, ray, kSlotClosest);
         c.want_closest = true;
         c.traced += 1;
         flag = PH_FLAG_REFLECTION_SENT | PH_FLAG_REFLECTION_PENDING;
@@ -2131,12 +2179,15 @@ __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr,
             T = c.pre_res.x;
             idx = (int)__float_as_uint(c.pre_res.y);
             ray = c.pre_ray0;
+            // (the 16-byte form: resume_pixel put the record into the direction half; the start from the hit it preloaded)
+            if (reflection_rays_rebuilt(c.w)) reflection_origin<AM>(c.pre_hit.x, c.pre_hit.y, c.pre_hit.z, ray.dx, ray.dy, ray.dz, ray.sx, ray.sy, ray.sz);
             patch_nan_result(c.w, ray, T, idx);
         } else {
-            closest_result(c.w, i, false, T, idx);
+            closest_result<AM>(c.w, i, false, T, idx);
         }
         if (T == kMaxFloat) { finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces); return; }
-        if (!c.pre) ray = load_ray(c.w, i, kSlotClosest);
+        uint32_t note;
+        if (!c.pre) ray = stored_closest_ray<AM>(c.w, i, note);
         ray.dw = 0.0f;  // (a reflection ray's direction.w; the slot may carry begin_shade_lit's note to the walk)
         HitRec rh;
         ObjRows rows;
@@ -2154,7 +2205,14 @@ __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr,
     Ray ray;
     reflection_ray<AM>(from, ray);
     ray.dw = __uint_as_float(0xffffffffu);  // (no note for the walk - see begin_shade_lit; no traversal reads direction.w of a reflection ray)
-    store_ray(c.w, c.i, ray, kSlotClosest);
+    if (reflection_rays_rebuilt(c.w)) {
+        // a record is read together with the F_PX block of the hit it left, on every path: this one writes both. (With lights the
+        // ray leaves with its hit in begin_shade_lit and this is not reached; "no note" is the word's self-test bit.)
+        store_reflection(c.w, c.i, ray, reflection_word(true, bounces));
+        store_block(c.w, F_PX, c.i, make_float4(from.px, from.py, from.pz, __uint_as_float((uint32_t)from.index)));
+    } else {
+        store_ray(c.w, c.i, ray, kSlotClosest);
+    }
     store_loop_state(c, abr, abg, abb, rr, rg, rb, ap, bounces, true);
     U(c.w, F_PHASE, c.i) = PH_REFLECT;
     c.want_closest = true;
@@ -2196,7 +2254,7 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
     if (phase == PH_PRIMARY) {
         float T;
         int idx;
-        closest_result(w, i, true, T, idx);
+        closest_result<AM>(w, i, true, T, idx);
         const bool hit = (KERNEL == 2) ? !(T == kMaxFloat) : (T < kMaxFloat);
         c.traced += 1; c.reference += 1; c.hits += hit ? 1 : 0;
         if (w.rp.aux_t) w.rp.aux_t[pixel_of(w.rp, i)] = T;
@@ -2219,12 +2277,17 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
         c.pre_hit = load_block(w, F_PX, i);
         c.pre_res = load_block(w, F_RES_T, i);
         c.pre_acc = load_block(w, F_ABR, i);       // (not yet written in the primary phase: not read there either)
-        c.pre_ray0 = load_ray(w, i, kSlotClosest);  // (only meaningful when a reflection ray left with the hit)
+        if (reflection_rays_rebuilt(w)) {  // the 16-byte record, as the direction half; loop_step makes the start from pre_hit if it wants the ray
+            const float4 rec = load_reflection(w, i);
+            c.pre_ray0 = Ray{0.f, 0.f, 0.f, 1.0f, rec.x, rec.y, rec.z, rec.w};
+        } else {
+            c.pre_ray0 = load_ray(w, i, kSlotClosest);  // (only meaningful when a reflection ray left with the hit)
+        }
         resume_shadow<KERNEL, AM>(c, phase == PH_SHADOW_PRIMARY);
     } else if (phase == PH_REFLECT) {
         float T;
         int idx;
-        closest_result(w, i, false, T, idx);
+        closest_result<AM>(w, i, false, T, idx);
         const float4 acc = load_block(w, F_ABR, i), rc = load_block(w, F_RR, i);
         const float ap = acc.w;
         const uint32_t bounces = U(w, F_BOUNCES, i);
@@ -2233,7 +2296,8 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
         if (T == kMaxFloat || !(ap <= 0.999f)) {  // raycast() false, or the absorption test of the loop condition
             finish_reflect(c, AM, abr, abg, abb, rr, rg, rb, ap, bounces);
         } else {
-            Ray ray = load_ray(w, i, kSlotClosest);
+            uint32_t note;
+            Ray ray = stored_closest_ray<AM>(w, i, note);
             ray.dw = 0.0f;  // (a reflection ray's direction.w; the slot may carry begin_shade_lit's note to the walk)
             HitRec rh;
             ObjRows rows;
@@ -2330,12 +2394,12 @@ __global__ __launch_bounds__(256) void wf_finish(const WfParams wk) {
                     U(w, F_RES_ANY, c.i) = blocked ? 0u : 1u;
                 }
                 if (do_closest) {
-                    Ray ray = load_ray(w, c.i, kSlotClosest);
+                    uint32_t note;  // (16-byte records: from the word and the F_PX block, as the walk's prepare takes it)
+                    Ray ray = stored_closest_ray<AM>(w, c.i, note);
                     float T = kMaxFloat;
                     int idx = -1;
                     bool walked = false;
                     if (w.bgrid.enabled && w.grid.n_always == 0u) {  // the block grid (the ray's note names the object it leaves)
-                        const uint32_t note = __float_as_uint(ray.dw);
                         ray.sw = 1.0f; ray.dw = 0.0f;
                         walked = closest_hit_blocks<AM>(w.bgrid, w.grid, w.rp.scene.hot, ray, note, T, idx, tested);
                     }
@@ -2441,8 +2505,7 @@ static void launch_persistent(const WfParams& w, uint64_t n_max, uint32_t* ticke
     // scenes without triangles: the unified walk (walk_segment), where its record table was built; RT_WALK2=closest / any /
     // none picks which of the two walks use it (measurement knob)
     const char* walk2_env = std::getenv("RT_WALK2");  // (read per launch: tests switch walks inside one process)
-    const char* walk3_env = std::getenv("RT_WALK3");  // "0": closest-hit rays through walk_segment / trace_segment instead
-    if (!ANY && w.bgrid.enabled && !(walk3_env && walk3_env[0] == '0')) {
+    if (!ANY && w.bgrid.serves_closest) {  // (run_wavefront: the block grid is there, and RT_WALK3 is not "0" - closest-hit rays through walk_segment / trace_segment instead)
         if (tri) {  // (meshes: the same walk with the triangle branch in its exact tests)
             if (w.count_rays) hipLaunchKernelGGL((wf_walk_blocks<AM, true, true>), grid, block, 0, s, w, ticket);
             else hipLaunchKernelGGL((wf_walk_blocks<AM, false, true>), grid, block, 0, s, w, ticket);
@@ -2482,6 +2545,10 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
     w.tiles = buf.tiles;
     w.ltiles = buf.light_tiles;
     w.bgrid = buf.blocks;
+    {   // launch_persistent's choice of the closest-hit walk, made once for the frame: the form of the reflection records hangs on it
+        const char* walk3_env = std::getenv("RT_WALK3");
+        w.bgrid.serves_closest = (w.bgrid.enabled && !(walk3_env && walk3_env[0] == '0')) ? 1u : 0u;
+    }
     for (int a = 0; a < 2; ++a) { w.qs[a][0] = buf.q_closest[a]; w.qs[a][1] = buf.q_any[a]; }
     uint32_t* rs = buf.counts;
     if ((e = hipMemsetAsync(rs, 0, wavefront_counter_bytes(), stream)) != hipSuccess) return e;
