@@ -76,7 +76,9 @@ extern "C" {
  *      Later addition, same version: ray queries - rt_query_closest_device, rt_query_occluded_device, rt_query_closest,
  *      rt_query_occluded, rt_query_primary, rt_get_query_info. Additions only; detect by dlsym of rt_query_closest_device.
  *      Later addition, same version: hit-record queries - rt_hits_t, rt_query_hits_device, rt_query_hits, rt_query_primary_hits.
- *      Additions only; detect by dlsym of rt_query_hits_device. */
+ *      Additions only; detect by dlsym of rt_query_hits_device.
+ *      Later addition, same version: compact records - rt_compact_info_t, rt_get_compact_info. Additions only; detect by dlsym of
+ *      rt_get_compact_info. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -673,6 +675,24 @@ typedef struct rt_geometry_info_t {
 int rt_set_transforms(rt_context* ctx, const void* transforms, uint32_t first, uint32_t count);
 int rt_read_transforms(rt_context* ctx, void* transforms, uint32_t first, uint32_t count);
 int rt_get_geometry_info(const rt_context* ctx, rt_geometry_info_t* info);
+
+/* ---- compact records ---------------------------------------------------------------------------------------------------------------
+ * A scene whose spheres and boxes are all scale-and-translate instances - the upper 3x3 of mv and of mvInverse hold +0.0f, the bit
+ * pattern, in every off-diagonal place; bottom rows (0,0,0,1); no triangles - is `diagonal`. A context without triangles keeps a
+ * 64-byte record per object with the diagonals, the translations, the type and the absorption, and the round machine's shading
+ * kernels (wf_resume, wf_finish) read it instead of the full records while the scene is diagonal: the same arithmetic on rows rebuilt
+ * with literal zeros, so the same frame, bit for bit, from fewer scattered loads. rt_set_transforms may switch the predicate either
+ * way; rt_set_materials and rt_set_visibility keep the record's copies true. The walks, literal frames, the small-scene kernel, brute
+ * force and the queries read the full records. The environment variable RT_COMPACT_RECORDS=0, read by rt_create: no frame of the
+ * context reads the compact records (tests, A/B runs). */
+typedef struct rt_compact_info_t {
+    uint32_t table_built;      /* the context keeps compact records (it has no triangles)                                        */
+    uint32_t n_not_diagonal;   /* spheres / boxes whose matrices are not diagonal (rt_create, then every rt_set_transforms)       */
+    uint32_t allowed;          /* RT_COMPACT_RECORDS was not "0" at rt_create                                                     */
+    uint32_t in_use;           /* the NEXT frame through the round machine reads them: the scene is diagonal and affine, the      */
+                               /* frame is not a literal one                                                                      */
+} rt_compact_info_t;
+int rt_get_compact_info(const rt_context* ctx, rt_compact_info_t* info);
 
 /* ---- replaceable visibility ----------------------------------------------------------------------------------------------------
  * Which of a live context's objects are in the picture: a viewer that deletes the object under the mouse, switches a layer off or

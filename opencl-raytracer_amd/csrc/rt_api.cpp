@@ -266,8 +266,12 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             RT_TRY(hipMemcpy(c->d_shadow_pairs, spairs.data(), sizeof(rt::HotPair) * spairs.size(), hipMemcpyHostToDevice));
         }
         lap("pair streams (sort, upload)");
-        // one spare record keeps the arrays non-null for n_objs == 0
-        RT_TRY(hipMalloc((void**)&c->d_hot, sizeof(rt::HotObject) * (size_t)(n_objs + 1)));
+        // one spare record keeps the arrays non-null for n_objs == 0; without triangles the compact records follow the HotObjects
+        // (rt_device.h: compact_table), n_objs + 1 of them as well
+        bool any_triangle = false;
+        for (uint32_t i = 0; i < n_objs && !any_triangle; ++i) any_triangle = static_cast<const rt_object_data*>(objs)[i].type == 2u;
+        static_assert(sizeof(rt::CompactObject) == sizeof(rt::HotObject), "one allocation, two tables of n_objs + 1 records");
+        RT_TRY(hipMalloc((void**)&c->d_hot, sizeof(rt::HotObject) * (size_t)(n_objs + 1) * (any_triangle ? 1u : 2u)));
         RT_TRY(hipMalloc((void**)&c->d_cold, sizeof(rt::ColdObject) * (size_t)(n_objs + 1)));
         if (n_objs <= 64) {  // per-bundle culling is only used for scenes this small
             c->h_spheres.resize(4 * (size_t)n_objs);
@@ -301,6 +305,28 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             RT_TRY(hipMalloc((void**)&c->d_objrec, sizeof(rt::ObjectRecord) * rec.size()));
             RT_TRY(hipMemcpy(c->d_objrec, rec.data(), sizeof(rt::ObjectRecord) * rec.size(), hipMemcpyHostToDevice));
         }
+        if (!any_triangle) {   // the compact records, and which objects keep the scene from reading them (rt_compact.h)
+            const rt_object_data* od = static_cast<const rt_object_data*>(objs);
+            std::vector<rt::CompactObject> compact((size_t)n_objs + 1);
+            c->h_not_diagonal.assign(n_objs, 0);
+            std::atomic<uint32_t> not_diagonal{0};
+            parallel_for(n_objs, 16384, [&](size_t i0, size_t i1) {
+                uint32_t mine = 0;
+                for (size_t i = i0; i < i1; ++i) {
+                    compact[i] = pack_compact(od[i].mv, od[i].mvInverse, hot[i].type, cold[i].amb_absorb.w);
+                    c->h_not_diagonal[i] = object_not_diagonal(od[i].type, od[i].mv, od[i].mvInverse) ? 1 : 0;
+                    mine += c->h_not_diagonal[i];
+                }
+                not_diagonal.fetch_add(mine, std::memory_order_relaxed);
+            });
+            c->n_not_diagonal = not_diagonal.load();
+            std::memset(&compact[n_objs], 0, sizeof(rt::CompactObject));
+            compact[n_objs].type = 0xffffffffu;   // (as the spare HotObject: never hit)
+            c->d_compact = reinterpret_cast<rt::CompactObject*>(c->d_hot + n_objs + 1);
+            RT_TRY(hipMemcpy(c->d_compact, compact.data(), sizeof(rt::CompactObject) * compact.size(), hipMemcpyHostToDevice));
+            const char* env = std::getenv("RT_COMPACT_RECORDS");   // "0": no frame reads them (tests, A/B runs)
+            c->compact_allowed = !(env && env[0] == '0');
+        }
     }
     lap("hot / cold / object records");
     RT_TRY(hipMalloc((void**)&c->d_lights, sizeof(rt::LightRec) * (size_t)(n_lights + 1)));
@@ -317,8 +343,7 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
     for (uint32_t i = 0; i < n_objs && c->affine_w; ++i) {
         const rt_object_data& o = static_cast<const rt_object_data*>(objs)[i];
         if (o.type >= 2u) continue;  // vertices, not matrices - or a type that is never hit (RT_TYPE_HIDDEN among them): no kernel reads its rows
-        c->affine_w = o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
-                      o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f;
+        c->affine_w = bottom_rows_affine(o.mv, o.mvInverse);
     }
     {   // per object, for rt_set_transforms: the type and whether both bottom rows are (0,0,0,1) - affine_w is "none is not"
         c->h_kind.resize(n_objs);
@@ -327,8 +352,7 @@ int rt_create(rt_context** out_ctx, const void* objs, uint32_t n_objs, const voi
             uint32_t mine = 0;
             for (size_t i = i0; i < i1; ++i) {
                 const rt_object_data& o = static_cast<const rt_object_data*>(objs)[i];
-                const bool affine = o.type >= 2u || (o.mv[3] == 0.f && o.mv[7] == 0.f && o.mv[11] == 0.f && o.mv[15] == 1.f && o.mvInverse[3] == 0.f &&
-                                                     o.mvInverse[7] == 0.f && o.mvInverse[11] == 0.f && o.mvInverse[15] == 1.f);
+                const bool affine = o.type >= 2u || bottom_rows_affine(o.mv, o.mvInverse);
                 c->h_kind[i] = (uint8_t)(std::min(o.type, 3u) | (affine ? 0u : 0x80u));
                 mine += affine ? 0u : 1u;
             }

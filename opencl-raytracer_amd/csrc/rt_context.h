@@ -19,6 +19,7 @@
 #include "rt_transforms.h"
 #include "rt_visibility.h"
 #include "rt_query.h"
+#include "rt_compact.h"
 
 #include <hip/hip_runtime.h>
 
@@ -248,6 +249,15 @@ struct rt_context {
     // entries). A call stages its records in d_patch_stage and, behind them (at sizeof(rt_transform) * count of that call), their shadow slots.
     std::vector<uint8_t> h_kind;
     uint32_t n_not_affine = 0;
+    // Compact records (rt_device.h: CompactObject; rt_compact.h). A context without triangles keeps one per object BEHIND its HotObjects,
+    // in d_hot's allocation (d_compact = d_hot + n_objs + 1; null with triangles), and every patch pass keeps them true whatever
+    // the predicate says, so that a scene may become diagonal by rt_set_transforms without a rebuild. Per object whether it is a sphere /
+    // box that is not diagonal, how many are (maintained like n_not_affine), and whether RT_COMPACT_RECORDS allowed them at rt_create
+    // ("0": no). compact_in_use() is the frame's switch, Scene::diagonal.
+    rt::CompactObject* d_compact = nullptr;
+    std::vector<uint8_t> h_not_diagonal;
+    uint32_t n_not_diagonal = 0;
+    bool compact_allowed = false;
     std::vector<uint32_t> h_shadow_slot;
     std::vector<rt_light> h_lights;
     double grid_cell = 0.0, grid_diag = 0.0, grid_s_max = 0.0, grid_k2 = 1.0;
@@ -353,6 +363,12 @@ inline bool direction_in_domain(float dx, float dy, float dz) {
 // the grid (fine grid, block grid, light tiles) serves the rays in use: always a camera's, a ray buffer's unless a scan said no
 // - or the rays are a pose's from outside the box whose screen tiles were accepted (primary_outside: tiles for them, the grid for the rest)
 inline bool grid_in_use(const rt_context* c) { return c->grid.enabled && (c->pinhole || !c->rays_off_grid || c->primary_outside); }
+// Scene::diagonal of the next wavefront frame (0: the full records). Every sphere / box is an affine scale-and-translate instance,
+// there is no triangle, and the frame is not a literal one (those keep the full records).
+inline uint32_t compact_in_use(const rt_context* c) {
+    const bool diagonal = c->d_compact && scene_diagonal(c->has_triangles, c->affine_w, c->n_not_diagonal);
+    return (diagonal && c->compact_allowed && !(c->flags & RT_FLAG_LITERAL)) ? 1u : 0u;
+}
 
 // View-space bounding sphere of what the traversal tests for object o: { x : |A x + b| <= r0 } with A, b the
 // rows x,y,z of mvInverse (the kernels never consult mv for intersection) -> centre -A^-1 b, radius

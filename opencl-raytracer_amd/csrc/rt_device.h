@@ -62,10 +62,27 @@ struct ObjectRecord {
     float4 mv_row[3];    // as ColdObject::mv_row[0..2]
     float4 spare1;
 };
+// Scenes of scale-and-translate instances (Scene::diagonal: every sphere / box has an upper 3x3 of mv and of mvInverse whose
+// off-diagonal words are +0.0f, bit for bit; affine; no triangles): the 24 matrix words the frame's hot kernels gather hold 18 known
+// zeros. This is the other 6 with the type and the absorption in HALF a line, the exact tests' half first: an exact test reads 32 bytes
+// where the HotObject costs it 64, materialise() reads 64 where the ObjectRecord costs it 112. The readers put the rows back
+// together in registers, literal 0.0f in the empty places, and compute with them as with loaded rows (compact_inv_rows below).
+// Read by wf_resume and wf_finish; the walks keep the HotObject (docs/LOG.md: their use was built, measured and taken out).
+struct alignas(16) CompactObject {
+    float a0, a1, a2;    // mvInverse: m[0], m[5], m[10]
+    uint32_t type;       // as HotObject::type
+    float b0, b1, b2;    // mvInverse: m[12], m[13], m[14]
+    float absorption;    // as ObjectRecord::absorption
+    float s0, s1, s2;    // mv: m[0], m[5], m[10]
+    uint32_t pad0;
+    float x, y, z;       // mv: m[12], m[13], m[14]
+    uint32_t spare;
+};
 struct LightRec {    // the reference's 64-byte Light, unchanged
     float4 ambient, diffuse, specular, position;
 };
-static_assert(sizeof(HotObject) == 64 && sizeof(ColdObject) == 128 && sizeof(LightRec) == 64 && sizeof(ObjectRecord) == 128, "layout");
+static_assert(sizeof(HotObject) == 64 && sizeof(ColdObject) == 128 && sizeof(LightRec) == 64 && sizeof(ObjectRecord) == 128 &&
+              sizeof(CompactObject) == 64, "layout");
 
 // Read-only scene data is addressed through the constant address space: that tells the compiler the bytes
 // cannot change during the kernel, so a wave-uniform address becomes a scalar load (s_load_dwordx4/8/16) even
@@ -631,34 +648,32 @@ struct ObjRows {
     uint32_t type, pad0;
 };
 
+// Rows x, y, z of mvInverse from a CompactObject's first 32 bytes (two 16-byte loads), as HotObject::row0..2 hold them: the zeros
+// are literals, and they are multiplied with like any loaded word (0 * x is not 0 for a NaN, an infinity or the sign of a zero).
+__device__ __forceinline__ void compact_inv_rows(const CompactObject* __restrict__ o, float4& r0, float4& r1, float4& r2, uint32_t& type,
+                                                 float* absorption = nullptr) {
+    const float4* q = reinterpret_cast<const float4*>(o);
+    const float4 a = q[0], b = q[1];
+    r0 = make_float4(a.x, 0.0f, 0.0f, b.x);
+    r1 = make_float4(0.0f, a.y, 0.0f, b.y);
+    r2 = make_float4(0.0f, 0.0f, a.z, b.z);
+    type = __builtin_bit_cast(uint32_t, a.w);
+    if (absorption) *absorption = b.w;
+}
+// ... and rows x, y, z of mv from its second 32 bytes, as ColdObject::mv_row[0..2]
+__device__ __forceinline__ void compact_mv_rows(const CompactObject* __restrict__ o, float4& m0, float4& m1, float4& m2) {
+    const float4* q = reinterpret_cast<const float4*>(o);
+    const float4 s = q[2], x = q[3];
+    m0 = make_float4(s.x, 0.0f, 0.0f, x.x);
+    m1 = make_float4(0.0f, s.y, 0.0f, x.y);
+    m2 = make_float4(0.0f, 0.0f, s.z, x.z);
+}
+
+// the hit of a sphere / box from its rows, however they arrived (`c`: only touched for the bottom rows of a non-affine instance)
 template <int AM>
-__device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ objrec, const ColdObject* __restrict__ cold,
-                                            int index, float t, const Ray& ray, HitRec& h, bool affine = false, ObjRows* rows = nullptr,
-                                            float* absorption = nullptr) {
-    const ObjectRecord* o = objrec + index;
-    const ColdObject* c = cold + index;   // (only touched for the bottom rows of a non-affine instance)
-    const uint32_t type = o->type;
-    if (rows) { rows->r0 = o->inv_row[0]; rows->r1 = o->inv_row[1]; rows->r2 = o->inv_row[2]; rows->type = type; rows->pad0 = o->pad0; }
-    if (absorption) *absorption = o->absorption;
-    if (type == 2u) {  // triangle (extension): view-space point on the ray, normal = normalize(e1 x e2)
-        const float4 e1 = o->inv_row[1], e2 = o->inv_row[2];
-        h.px = fma_<AM>(t, ray.dx, ray.sx);
-        h.py = fma_<AM>(t, ray.dy, ray.sy);
-        h.pz = fma_<AM>(t, ray.dz, ray.sz);
-        h.pw = fma_<AM>(t, ray.dw, ray.sw);
-        float nx = e1.y * e2.z - e1.z * e2.y;
-        float ny = e1.z * e2.x - e1.x * e2.z;
-        float nz = e1.x * e2.y - e1.y * e2.x;
-        normalize3(nx, ny, nz);
-        h.nx = nx; h.ny = ny; h.nz = nz;
-        const float k2 = dot3(ray.dx, ray.dy, ray.dz, nx, ny, nz) * -2.0f;
-        h.rx = fma_<AM>(k2, nx, ray.dx);
-        h.ry = fma_<AM>(k2, ny, ray.dy);
-        h.rz = fma_<AM>(k2, nz, ray.dz);
-        h.index = index;
-        return;
-    }
-    const float4 r0 = o->inv_row[0], r1 = o->inv_row[1], r2 = o->inv_row[2];
+__device__ __forceinline__ void hit_from_rows(uint32_t type, const float4& r0, const float4& r1, const float4& r2, const float4& m0,
+                                              const float4& m1, const float4& m2, const ColdObject* __restrict__ c, bool affine, int index,
+                                              float t, const Ray& ray, HitRec& h) {
     const float sx = row4<AM>(r0.x, r0.y, r0.z, r0.w, ray.sx, ray.sy, ray.sz, ray.sw);
     const float sy = row4<AM>(r1.x, r1.y, r1.z, r1.w, ray.sx, ray.sy, ray.sz, ray.sw);
     const float sz = row4<AM>(r2.x, r2.y, r2.z, r2.w, ray.sx, ray.sy, ray.sz, ray.sw);
@@ -690,7 +705,6 @@ __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ obj
         if (py > 0.4998f) oy += 1.f; else if (py < -0.4998f) oy -= 1.f;
         if (pz > 0.4998f) oz += 1.f; else if (pz < -0.4998f) oz -= 1.f;
     }
-    const float4 m0 = o->mv_row[0], m1 = o->mv_row[1], m2 = o->mv_row[2];
     h.px = row4<AM>(m0.x, m0.y, m0.z, m0.w, px, py, pz, pw);
     h.py = row4<AM>(m1.x, m1.y, m1.z, m1.w, px, py, pz, pw);
     h.pz = row4<AM>(m2.x, m2.y, m2.z, m2.w, px, py, pz, pw);
@@ -710,6 +724,36 @@ __device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ obj
     h.ry = fma_<AM>(k2, ny, ray.dy);
     h.rz = fma_<AM>(k2, nz, ray.dz);
     h.index = index;
+}
+
+template <int AM>
+__device__ __forceinline__ void materialise(const ObjectRecord* __restrict__ objrec, const ColdObject* __restrict__ cold,
+                                            int index, float t, const Ray& ray, HitRec& h, bool affine = false, ObjRows* rows = nullptr,
+                                            float* absorption = nullptr) {
+    const ObjectRecord* o = objrec + index;
+    const ColdObject* c = cold + index;   // (only touched for the bottom rows of a non-affine instance)
+    const uint32_t type = o->type;
+    if (rows) { rows->r0 = o->inv_row[0]; rows->r1 = o->inv_row[1]; rows->r2 = o->inv_row[2]; rows->type = type; rows->pad0 = o->pad0; }
+    if (absorption) *absorption = o->absorption;
+    if (type == 2u) {  // triangle (extension): view-space point on the ray, normal = normalize(e1 x e2)
+        const float4 e1 = o->inv_row[1], e2 = o->inv_row[2];
+        h.px = fma_<AM>(t, ray.dx, ray.sx);
+        h.py = fma_<AM>(t, ray.dy, ray.sy);
+        h.pz = fma_<AM>(t, ray.dz, ray.sz);
+        h.pw = fma_<AM>(t, ray.dw, ray.sw);
+        float nx = e1.y * e2.z - e1.z * e2.y;
+        float ny = e1.z * e2.x - e1.x * e2.z;
+        float nz = e1.x * e2.y - e1.y * e2.x;
+        normalize3(nx, ny, nz);
+        h.nx = nx; h.ny = ny; h.nz = nz;
+        const float k2 = dot3(ray.dx, ray.dy, ray.dz, nx, ny, nz) * -2.0f;
+        h.rx = fma_<AM>(k2, nx, ray.dx);
+        h.ry = fma_<AM>(k2, ny, ray.dy);
+        h.rz = fma_<AM>(k2, nz, ray.dz);
+        h.index = index;
+        return;
+    }
+    hit_from_rows<AM>(type, o->inv_row[0], o->inv_row[1], o->inv_row[2], o->mv_row[0], o->mv_row[1], o->mv_row[2], c, affine, index, t, ray, h);
 }
 
 // ---- rays with a NaN in them ---------------------------------------------------------------------------------------
@@ -756,7 +800,30 @@ struct Scene {
     uint32_t fast_phong;  // RT_FLAG_FAST_PHONG: colour-only normalisations and the specular power on the fast hardware paths
     int nan_winner;            // index of the LAST sphere / box of the scene (-1: none) and whether it is a sphere:
     uint32_t nan_winner_sphere;  // what the reference's loop ends with for a ray with a NaN in it (nan_ray_outcome)
+    uint32_t diagonal;  // every sphere / box is a scale-and-translate instance and wf_resume / wf_finish read the compact records
+                        // (materialise_frame, last_light_blocked). In what was the struct's tail padding: the other members keep their offsets.
 };
+static_assert(sizeof(Scene) == 88, "Scene::diagonal takes the tail padding");
+// The compact table of a frame that reads it, or null for the full records (wave-uniform). It lives BEHIND the HotObjects, in their
+// allocation (n_objs + 1 records each, the spare one included): a frame needs no further pointer, and the kernels' arguments stay
+// what they were.
+__device__ __forceinline__ const CompactObject* compact_table(const Scene& S) {
+    return S.diagonal ? reinterpret_cast<const CompactObject*>(S.hot + S.n_objs + 1u) : nullptr;
+}
+
+// materialise() as the round machine calls it (wf_resume, wf_finish). `compact`: the scene's CompactObject table where the frame reads it
+// (Scene::diagonal, which implies `affine` and no triangles; wave-uniform), null for the full records. Only the loads differ: the rows
+// meet in registers and one copy of the arithmetic serves both record forms.
+template <int AM>
+__device__ __forceinline__ void materialise_frame(const Scene& S, const CompactObject* __restrict__ compact, int index, float t, const Ray& ray,
+                                                  HitRec& h, ObjRows& rows, float& absorption) {
+    if (!compact) { materialise<AM>(S.objrec, S.cold, index, t, ray, h, S.affine != 0u, &rows, &absorption); return; }
+    float4 m0, m1, m2;
+    compact_inv_rows(compact + index, rows.r0, rows.r1, rows.r2, rows.type, &absorption);
+    compact_mv_rows(compact + index, m0, m1, m2);
+    rows.pad0 = 0u;
+    hit_from_rows<AM>(rows.type, rows.r0, rows.r1, rows.r2, m0, m1, m2, S.cold + index, true, index, t, ray, h);
+}
 
 // secondary rays (shadow / reflection; direction.w == 0): pair stream in the wavefront kernels, one object at a
 // time in the monolithic kernel (SMALL)

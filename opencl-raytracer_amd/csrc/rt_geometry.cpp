@@ -17,10 +17,7 @@ rt_transform record_at(const void* transforms, size_t m) {  // (any alignment)
     return t;
 }
 
-bool bottom_rows_affine(const rt_transform& t) {  // rt_create's affine_w, per object
-    return t.mv[3] == 0.f && t.mv[7] == 0.f && t.mv[11] == 0.f && t.mv[15] == 1.f && t.mvInverse[3] == 0.f && t.mvInverse[7] == 0.f &&
-           t.mvInverse[11] == 0.f && t.mvInverse[15] == 1.f;
-}
+bool bottom_rows_affine(const rt_transform& t) { return rt::host::bottom_rows_affine(t.mv, t.mvInverse); }
 
 // what object_bound and bounding_sphere read of an object
 rt_object_data as_object(const rt_transform& t, uint32_t type) {
@@ -116,7 +113,7 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
     // (the copies take the bytes as they are: `transforms` may have any alignment)
     RT_HIP(c, hipMemcpyAsync(stage, transforms, slots_at, hipMemcpyHostToDevice, c->stream));
     RT_HIP(c, hipMemcpyAsync(stage + slots_at, slots.data(), sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    const rt::TransformTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->n_objs};
+    const rt::TransformTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->d_compact, c->n_objs};
     const hipError_t e = rt::launch_patch_transforms(reinterpret_cast<const float*>(stage), reinterpret_cast<const uint32_t*>(stage + slots_at), first,
                                                      count, to, c->stream);
     if (e != hipSuccess) return fail_hip(c, e, "transform patch launch");
@@ -135,6 +132,12 @@ int rt_set_transforms(rt_context* c, const void* transforms, uint32_t first, uin
         if (was != is) {
             c->n_not_affine = is ? c->n_not_affine - 1u : c->n_not_affine + 1u;
             kind = (uint8_t)((kind & 0x7fu) | (is ? 0u : 0x80u));
+        }
+        if (c->d_compact) {  // the scene's `diagonal` may flip either way (compact_in_use): the compact records follow every call
+            uint8_t& off = c->h_not_diagonal[first + m];
+            const uint8_t now = object_not_diagonal(kind & 0x7fu, t.mv, t.mvInverse) ? 1 : 0;
+            c->n_not_diagonal = c->n_not_diagonal - off + now;
+            off = now;
         }
         if (c->h_spheres.size() == 4 * (size_t)c->n_objs) {  // the small-scene kernel's culling rectangles follow (do_launch)
             const Sphere sp = bounding_sphere(as_object(t, kind & 0x7fu));
@@ -205,6 +208,8 @@ int rt_read_transforms(rt_context* c, void* transforms, uint32_t first, uint32_t
     RT_HIP(c, hipMemcpy(hot.data(), c->d_hot + first, sizeof(rt::HotObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(cold.data(), c->d_cold + first, sizeof(rt::ColdObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(rec.data(), c->d_objrec + first, sizeof(rt::ObjectRecord) * (size_t)count, hipMemcpyDeviceToHost));
+    std::vector<rt::CompactObject> compact(c->d_compact ? count : 0u);
+    if (c->d_compact) RT_HIP(c, hipMemcpy(compact.data(), c->d_compact + first, sizeof(rt::CompactObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(pairs.data(), c->d_pairs + p0, sizeof(rt::HotPair) * pairs.size(), hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(spairs.data(), c->d_shadow_pairs, sizeof(rt::HotPair) * spairs.size(), hipMemcpyDeviceToHost));
     uint8_t* out = static_cast<uint8_t*>(transforms);  // (any alignment: the records are assembled here and copied out)
@@ -232,8 +237,24 @@ int rt_read_transforms(rt_context* c, void* transforms, uint32_t first, uint32_t
             t.mvInverse[4 * k + 3] = word(cold[m].inv_row3, k);
             for (int r = 0; r < 4; ++r) t.mv[4 * k + r] = word(cold[m].mv_row[r], k);
         }
+        if (c->d_compact) {  // the twelve matrix words of the compact record: what pack_compact takes of the two matrices
+            const rt::CompactObject want = pack_compact(t.mv, t.mvInverse, compact[m].type, compact[m].absorption);
+            if (std::memcmp(&want, &compact[m], 12) != 0 || std::memcmp(&want.b0, &compact[m].b0, 12) != 0 || std::memcmp(&want.s0, &compact[m].s0, 12) != 0 ||
+                std::memcmp(&want.x, &compact[m].x, 12) != 0)
+                return disagree("the CompactObject does not hold the diagonal and the translation of the two matrices");
+        }
         std::memcpy(out + sizeof(rt_transform) * (size_t)m, &t, sizeof(t));
     }
+    return RT_OK;
+}
+
+int rt_get_compact_info(const rt_context* c, rt_compact_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    *info = rt_compact_info_t{};
+    info->table_built = c->d_compact ? 1u : 0u;
+    info->n_not_diagonal = c->n_not_diagonal;
+    info->allowed = c->compact_allowed ? 1u : 0u;
+    info->in_use = compact_in_use(c);
     return RT_OK;
 }
 

@@ -384,6 +384,24 @@ __device__ __forceinline__ bool rows_candidate(const ObjRows& o, const Ray& ray,
     return false;
 }
 
+// ... from whichever record form the frame reads (`compact`: wave-uniform, null for the full records): only the loads differ, the
+// rows meet in registers and one copy of the test serves both
+template <int AM, bool DW0>
+__device__ __forceinline__ bool exact_candidate(const HotObject* __restrict__ hot, const CompactObject* __restrict__ compact, uint32_t k,
+                                                const Ray& ray, float& t, bool& sphere) {
+    ObjRows rows;
+    if (compact) {
+        compact_inv_rows(compact + k, rows.r0, rows.r1, rows.r2, rows.type);
+        rows.pad0 = 0u;
+    } else {
+        const HotObject* o = hot + k;
+        rows.r0 = o->row0; rows.r1 = o->row1; rows.r2 = o->row2;
+        rows.type = o->type;
+        rows.pad0 = o->pad[0];
+    }
+    return rows_candidate<AM, DW0>(rows, ray, t, sphere);
+}
+
 // A ray with a NaN in it walks no cells; what the reference's loop ends with for it is nan_ray_outcome() (rt_device.h),
 // patched in where the walk's result is produced (shadow rays) or consumed (closest_result, rt_wavefront.hip).
 __device__ __forceinline__ bool nan_shadow_blocked(const Scene& S, const Ray& ray) {

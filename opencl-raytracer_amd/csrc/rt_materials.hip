@@ -10,7 +10,7 @@
 // (16 records) in one instruction; the fourth float4 holds the two scalars that belong into the w lanes of the first two, and
 // reaches lanes 0 and 1 by a shuffle within the group. Lane 0 stores amb_absorb and lane 1 dif_shine (16 bytes each), lane 2
 // the three specular floats - 12 bytes: the type bits behind them are never read, never written - and lane 3 the ObjectRecord's
-// absorption. The alternative, one lane per material, would issue four 16-byte loads per lane that lie 64 bytes apart across the
+// absorption and, where the context keeps compact records, the CompactObject's. The alternative, one lane per material, would issue four 16-byte loads per lane that lie 64 bytes apart across the
 // wave - each instruction touches 64 lines for 1 KiB of use. It was not built: the four-lane form patches cfg4's 100 000
 // materials in 8 microseconds, which is a launch, and leaves nothing to compare on.
 // A group is active or idle as a whole (the bound is a material count), so the shuffle's source lane is active whenever its
@@ -24,10 +24,11 @@ namespace {
 constexpr uint32_t kPatchBlock = 256;                 // 64 materials per workgroup, 16 per wave
 constexpr uint32_t kPatchLanes = 4;                   // lanes per material: one per float4 of the record
 static_assert(offsetof(ColdObject, amb_absorb) == 80 && offsetof(ColdObject, dif_shine) == 96 && offsetof(ColdObject, spec_type) == 112 &&
-              offsetof(ObjectRecord, absorption) == 56, "the patch addresses the records by member");
+              offsetof(ObjectRecord, absorption) == 56 && offsetof(CompactObject, absorption) == 28, "the patch addresses the records by member");
 
 __global__ __launch_bounds__(kPatchBlock) void patch_materials(const float4* __restrict__ materials, uint32_t first, uint32_t count,
-                                                               ColdObject* __restrict__ cold, ObjectRecord* __restrict__ objrec) {
+                                                               ColdObject* __restrict__ cold, ObjectRecord* __restrict__ objrec,
+                                                               CompactObject* __restrict__ compact) {
     const uint64_t t = (uint64_t)blockIdx.x * kPatchBlock + threadIdx.x;   // = 4 m + k: the index of this lane's float4
     const uint64_t m = t / kPatchLanes;
     const uint32_t k = (uint32_t)(t % kPatchLanes);
@@ -49,20 +50,21 @@ __global__ __launch_bounds__(kPatchBlock) void patch_materials(const float4* __r
         spec[0] = v.x;
         spec[1] = v.y;
         spec[2] = v.z;
-    } else if (objrec) {
-        objrec[o].absorption = v.x;
+    } else {
+        if (objrec) objrec[o].absorption = v.x;
+        if (compact) compact[o].absorption = v.x;
     }
 }
 
 }  // namespace
 
 hipError_t launch_patch_materials(const float4* d_materials, uint32_t first, uint32_t count, ColdObject* d_cold, ObjectRecord* d_objrec,
-                                  uint32_t n_objs, hipStream_t stream) {
+                                  CompactObject* d_compact, uint32_t n_objs, hipStream_t stream) {
     if ((uint64_t)first + (uint64_t)count > (uint64_t)n_objs) return hipErrorInvalidValue;
     if (count == 0) return hipSuccess;
     if (!d_materials || (reinterpret_cast<uintptr_t>(d_materials) & 15u) || !d_cold) return hipErrorInvalidValue;
     const uint64_t blocks = ((uint64_t)count * kPatchLanes + kPatchBlock - 1) / kPatchBlock;   // <= 2^26
-    hipLaunchKernelGGL(patch_materials, dim3((uint32_t)blocks), dim3(kPatchBlock), 0, stream, d_materials, first, count, d_cold, d_objrec);
+    hipLaunchKernelGGL(patch_materials, dim3((uint32_t)blocks), dim3(kPatchBlock), 0, stream, d_materials, first, count, d_cold, d_objrec, d_compact);
     return hipGetLastError();
 }
 

@@ -83,7 +83,7 @@ namespace {
 // trace: begun by the caller before its upload, if any (RT_MATERIALS_TRACE=1, tools/ab/set_materials_timing.py).
 int patch_materials_on(rt_context* c, const void* d_src, uint32_t first, uint32_t count, hipStream_t stream, PatchTrace& trace) {
     if (const int rc = trace.uploaded(stream)) return rc;
-    const hipError_t e = rt::launch_patch_materials(static_cast<const float4*>(d_src), first, count, c->d_cold, c->d_objrec, c->n_objs, stream);
+    const hipError_t e = rt::launch_patch_materials(static_cast<const float4*>(d_src), first, count, c->d_cold, c->d_objrec, c->d_compact, c->n_objs, stream);
     if (e != hipSuccess) return fail_hip(c, e, "material patch launch");
     if (const int rc = trace.patched(stream)) return rc;
     RT_HIP(c, hipStreamSynchronize(stream));  // synchronous like rt_set_lights: the array is the caller's again, any stream's next frame sees it
@@ -135,12 +135,17 @@ int rt_read_materials(rt_context* c, void* materials, uint32_t first, uint32_t c
     std::vector<rt::ObjectRecord> rec(count);
     RT_HIP(c, hipMemcpy(cold.data(), c->d_cold + first, sizeof(rt::ColdObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(rec.data(), c->d_objrec + first, sizeof(rt::ObjectRecord) * (size_t)count, hipMemcpyDeviceToHost));
+    std::vector<rt::CompactObject> compact(c->d_compact ? count : 0u);
+    if (c->d_compact) RT_HIP(c, hipMemcpy(compact.data(), c->d_compact + first, sizeof(rt::CompactObject) * (size_t)count, hipMemcpyDeviceToHost));
     uint8_t* out = static_cast<uint8_t*>(materials);  // (any alignment: the records are assembled here and copied out)
     for (uint32_t i = 0; i < count; ++i) {
         const rt::ColdObject& k = cold[i];
         if (std::memcmp(&k.amb_absorb.w, &rec[i].absorption, 4) != 0)
             return fail(c, RT_ERR_STATE, "rt_read_materials: object " + std::to_string((uint64_t)first + i) +
                                              ": ObjectRecord::absorption does not hold the bits of ColdObject::amb_absorb.w");
+        if (c->d_compact && std::memcmp(&k.amb_absorb.w, &compact[i].absorption, 4) != 0)
+            return fail(c, RT_ERR_STATE, "rt_read_materials: object " + std::to_string((uint64_t)first + i) +
+                                             ": CompactObject::absorption does not hold the bits of ColdObject::amb_absorb.w");
         rt_material m;
         std::memset(&m, 0, sizeof(m));  // the five words no kernel reads: 0
         std::memcpy(m.ambient, &k.amb_absorb, 12);

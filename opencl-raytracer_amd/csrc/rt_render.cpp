@@ -141,6 +141,7 @@ static int do_launch(rt_context* c, const Shard& sh, void* d_out, hipStream_t st
     }
     c->last_wavefront = use_wavefront(c);
     c->last_rounds = 0;
+    p.scene.diagonal = c->last_wavefront ? compact_in_use(c) : 0u;  // (the round machine's kernels alone read the compact records)
     if (c->last_wavefront) {  // one-time host-side set-up (buffers, per-camera screen tiles) stays outside the timed region
         StopWatch sw;
         const bool had_buffers = c->wf.capacity >= sh.n_local && c->wf.state;

@@ -10,6 +10,7 @@ struct HotPair;       // rt_device.h
 struct HotObject;
 struct ColdObject;
 struct ObjectRecord;
+struct CompactObject;
 
 // the record arrays of a context (rt_context.h); `n_objs` records each, (n_objs + 1) / 2 pairs in either stream
 struct TransformTargets {
@@ -18,13 +19,15 @@ struct TransformTargets {
     HotObject* hot;
     ColdObject* cold;
     ObjectRecord* objrec;
+    CompactObject* compact;   // null: the context keeps no compact records (triangles)
     uint32_t n_objs;
 };
 
 // Patches objects first .. first + count - 1 from `count` rt_transform records at d_transforms (128 bytes each, 16-byte aligned)
 // on `stream`. d_shadow_slots holds `count` positions: object first + m sits at position d_shadow_slots[m] of the shadow stream
 // (pair slot / 2, half slot & 1); in the traversal stream an object's position is its index. Written per object: HotObject::row0..2,
-// ColdObject::mv_row[0..3] and inv_row3, ObjectRecord::inv_row[0..2] and mv_row[0..2], and the object's half of its HotPair in both
+// ColdObject::mv_row[0..3] and inv_row3, ObjectRecord::inv_row[0..2] and mv_row[0..2], the twelve matrix words of its CompactObject
+// (whatever the matrices are: whether a frame reads them is the host's predicate), and the object's half of its HotPair in both
 // streams - the words repack_objects, pack_pairs and rt_create's ObjectRecord fill derive from the two matrices, the same bits.
 // Type words, pads, materials and the neighbour's half of a pair are never touched. The slots are NOT checked against n_objs here
 // (they are device memory): the caller passes a permutation's. hipErrorInvalidValue for a null or misaligned array, a null target or

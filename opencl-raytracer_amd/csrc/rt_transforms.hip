@@ -4,7 +4,8 @@
 // HotObject (rows x, y, z of mvInverse), the shading record ColdObject (mv by rows, row w of mvInverse), the round machine's
 // ObjectRecord (rows x, y, z of both), and the two pair streams, where the twelve words of mvInverse's rows x, y, z are interleaved
 // with those of a neighbour - the traversal stream pairs objects 2p and 2p + 1, the shadow stream pairs them in rt_create's size order.
-// Per object 128 bytes are read and 48 + 80 + 96 + 48 + 48 written. The values are moved, never computed with: NaNs keep their bits.
+// A context without triangles keeps a sixth copy, the CompactObject: the diagonal and the translation column of both (rt_device.h).
+// Per object 128 bytes are read and 48 + 80 + 96 + 48 + 48 (+ 48) written. The values are moved, never computed with: NaNs keep their bits.
 // What depends on the matrices beyond these words - bounds, registration spheres, tables - is the host's business (rt_geometry.cpp).
 //
 // Form kept: EIGHT LANES PER OBJECT, ONE PER MATRIX ROW. The upload is column-major and every record wants rows, so somebody has to
@@ -29,7 +30,8 @@ constexpr uint32_t kPatchLanes = 8;     // lanes per object: one per row of mv, 
 static_assert(offsetof(HotObject, row0) == 0 && offsetof(HotObject, row1) == 16 && offsetof(HotObject, row2) == 32 && offsetof(HotObject, type) == 48 &&
               offsetof(ColdObject, mv_row) == 0 && offsetof(ColdObject, inv_row3) == 64 && offsetof(ColdObject, amb_absorb) == 80 &&
               offsetof(ObjectRecord, inv_row) == 0 && offsetof(ObjectRecord, type) == 48 && offsetof(ObjectRecord, mv_row) == 64 &&
-              offsetof(ObjectRecord, spare1) == 112 && offsetof(HotPair, m) == 0 && offsetof(HotPair, type_a) == 96 && sizeof(f2) == 8,
+              offsetof(ObjectRecord, spare1) == 112 && offsetof(CompactObject, a0) == 0 && offsetof(CompactObject, b0) == 16 &&
+              offsetof(CompactObject, s0) == 32 && offsetof(CompactObject, x) == 48 && offsetof(HotPair, m) == 0 && offsetof(HotPair, type_a) == 96 && sizeof(f2) == 8,
               "the patch addresses the records by member");
 
 // the half `slot & 1` of pair `slot / 2`: words m[4 r + c][half], c = 0..3
@@ -53,7 +55,10 @@ __global__ __launch_bounds__(kPatchBlock) void patch_transforms(const float* __r
     const uint32_t o = first + (uint32_t)m;   // < n_objs (the launcher checked the range)
     if (k < 4u) {   // a row of mv
         to.cold[o].mv_row[r] = v;
-        if (r < 3u) to.objrec[o].mv_row[r] = v;
+        if (r < 3u) {
+            to.objrec[o].mv_row[r] = v;
+            if (to.compact) { (&to.compact[o].s0)[r] = (&v.x)[r]; (&to.compact[o].x)[r] = v.w; }   // the diagonal word and the translation's
+        }
         return;
     }
     if (r == 3u) {   // row w of mvInverse
@@ -62,6 +67,7 @@ __global__ __launch_bounds__(kPatchBlock) void patch_transforms(const float* __r
     }
     (&to.hot[o].row0)[r] = v;
     to.objrec[o].inv_row[r] = v;
+    if (to.compact) { (&to.compact[o].a0)[r] = (&v.x)[r]; (&to.compact[o].b0)[r] = v.w; }
     store_pair_row(to.pairs, o, r, v);
     const uint32_t slot = shadow_slots[m];
     if (slot < to.n_objs) store_pair_row(to.shadow_pairs, slot, r, v);   // (a permutation's slots always are)

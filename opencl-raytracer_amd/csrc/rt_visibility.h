@@ -11,6 +11,7 @@ struct HotPair;       // rt_device.h
 struct HotObject;
 struct ColdObject;
 struct ObjectRecord;
+struct CompactObject;
 
 constexpr uint32_t kTypeKeep = 0xffffffffu;   // in `create_types`: an object created with a type other than 0, 1, 2 - never written
 
@@ -21,6 +22,7 @@ struct VisibilityTargets {
     HotObject* hot;
     ColdObject* cold;
     ObjectRecord* objrec;
+    CompactObject* compact;   // null: the context keeps no compact records (triangles)
     const uint32_t* create_types;   // per object: the type word rt_create was given (0, 1, 2), or kTypeKeep
     const uint32_t* shadow_slots;   // per object: its position in the shadow stream (pair slot / 2, half slot & 1)
     uint32_t n_objs;

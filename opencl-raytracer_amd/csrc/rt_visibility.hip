@@ -4,7 +4,8 @@
 // force), ObjectRecord::type (the round machine's materialise), the fourth word of ColdObject::spec_type (type bits beside the specular
 // colour), and type_a / type_b of the object's half of its HotPair in the traversal stream (pair o / 2, half o & 1) and in the shadow
 // stream (where rt_create's size order put it). A type that is none of 0, 1, 2 is never hit - the reference's switch has no default -
-// so hiding an object is writing RT_TYPE_HIDDEN into all five, and showing it is writing the create-time word back. Per object one
+// so hiding an object is writing RT_TYPE_HIDDEN into all five, and showing it is writing the create-time word back. A context without
+// triangles keeps a sixth copy, CompactObject::type (the frames of scale-and-translate scenes), written with the others. Per object one
 // mask byte and two support words (create-time type, shadow slot) are read and five words written. The values are moved, never
 // computed with. What follows the types on the host - the NaN-ray winner, RT_FLAG_DEVICE_OPENCL's predicate - is rt_visibility_host.cpp's.
 //
@@ -27,7 +28,7 @@ namespace rt {
 namespace {
 
 constexpr uint32_t kPatchBlock = 128;   // 128 objects per workgroup, 64 per wave (nothing is shared: a small group only spreads the scattered stores over more CUs)
-static_assert(offsetof(HotObject, type) == 48 && offsetof(ObjectRecord, type) == 48 && offsetof(ColdObject, spec_type) == 112 &&
+static_assert(offsetof(HotObject, type) == 48 && offsetof(ObjectRecord, type) == 48 && offsetof(CompactObject, type) == 12 && offsetof(ColdObject, spec_type) == 112 &&
               offsetof(HotPair, type_a) == 96 && offsetof(HotPair, type_b) == 100, "the patch addresses the records by member");
 
 __global__ __launch_bounds__(kPatchBlock) void patch_visibility(const uint8_t* __restrict__ visible, uint32_t first, uint32_t count, VisibilityTargets to) {
@@ -39,6 +40,7 @@ __global__ __launch_bounds__(kPatchBlock) void patch_visibility(const uint8_t* _
     const uint32_t word = visible[m] ? created : RT_TYPE_HIDDEN;
     to.hot[o].type = word;
     to.objrec[o].type = word;
+    if (to.compact) to.compact[o].type = word;
     reinterpret_cast<uint32_t*>(&to.cold[o].spec_type)[3] = word;   // the type bits; the three specular floats stay
     (&to.pairs[o >> 1].type_a)[o & 1u] = word;
     const uint32_t slot = to.shadow_slots[o];

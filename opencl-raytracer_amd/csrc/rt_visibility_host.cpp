@@ -71,7 +71,7 @@ int set_visibility_from(rt_context* c, const uint8_t* d_src, hipStream_t stream,
     if (const int rc = trace.begin(stream)) return rc;
     if (h_mask) RT_HIP(c, hipMemcpyAsync(c->d_patch_stage.p, h_mask, (size_t)count, hipMemcpyHostToDevice, stream));
     if (const int rc = trace.uploaded(stream)) return rc;
-    const rt::VisibilityTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->d_vis_types, c->d_vis_slots, c->n_objs};
+    const rt::VisibilityTargets to{c->d_pairs, c->d_shadow_pairs, c->d_hot, c->d_cold, c->d_objrec, c->d_compact, c->d_vis_types, c->d_vis_slots, c->n_objs};
     const hipError_t e = rt::launch_patch_visibility(d_src, first, count, to, stream);
     if (e != hipSuccess) return fail_hip(c, e, "visibility patch launch");
     if (const int rc = trace.patched(stream)) return rc;
@@ -118,6 +118,8 @@ int rt_read_visibility(rt_context* c, uint8_t* visible, uint32_t first, uint32_t
     RT_HIP(c, hipMemcpy(hot.data(), c->d_hot + first, sizeof(rt::HotObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(cold.data(), c->d_cold + first, sizeof(rt::ColdObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(rec.data(), c->d_objrec + first, sizeof(rt::ObjectRecord) * (size_t)count, hipMemcpyDeviceToHost));
+    std::vector<rt::CompactObject> compact(c->d_compact ? count : 0u);
+    if (c->d_compact) RT_HIP(c, hipMemcpy(compact.data(), c->d_compact + first, sizeof(rt::CompactObject) * (size_t)count, hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(pairs.data(), c->d_pairs + p0, sizeof(rt::HotPair) * pairs.size(), hipMemcpyDeviceToHost));
     RT_HIP(c, hipMemcpy(spairs.data(), c->d_shadow_pairs, sizeof(rt::HotPair) * spairs.size(), hipMemcpyDeviceToHost));
     for (uint32_t m = 0; m < count; ++m) {
@@ -129,6 +131,7 @@ int rt_read_visibility(rt_context* c, uint8_t* visible, uint32_t first, uint32_t
         uint32_t bits = 0;
         std::memcpy(&bits, &cold[m].spec_type.w, 4);
         if (rec[m].type != word) return disagree("ObjectRecord::type does not hold HotObject::type");
+        if (c->d_compact && compact[m].type != word) return disagree("CompactObject::type does not hold HotObject::type");
         if (bits != word) return disagree("the type bits of ColdObject::spec_type do not hold HotObject::type");
         if ((&pairs[o / 2u - p0].type_a)[o & 1u] != word) return disagree("the traversal pair stream does not hold HotObject::type");
         if ((&spairs[slot / 2u].type_a)[slot & 1u] != word) return disagree("the shadow pair stream does not hold HotObject::type");

@@ -114,6 +114,9 @@ __device__ __forceinline__ bool resolve_round(WfParams& w) {
     return rs[RS_FINISH] == 0u;
 }
 
+// the compact records as wf_resume and wf_finish read them (materialise, last_light_blocked): wave-uniform, null for the full records
+__device__ __forceinline__ const CompactObject* resume_compact(const WfParams& w) { return compact_table(w.rp.scene); }
+
 // Work-item -> pixel of this rank's frame part. Pinhole frames are walked in 8x8-pixel tiles (work-items 64k ..
 // 64k+63 = one tile), so that the 64 rays a wave traces together, and the rays in flight on the chip, are
 // neighbours in the image in both directions; pixel state and queues are indexed by work-item, only the primary
@@ -1878,6 +1881,7 @@ template <int AM>
 __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, uint32_t& tests) {
     ray.sw = 1.0f; ray.dw = 0.0f;  // as the walk's hand-out (rt_create checks the preconditions of a grid-able frame)
     const HotObject* __restrict__ hot = w.rp.scene.hot;
+    const CompactObject* __restrict__ compact = resume_compact(w);
     const float chk = ((ray.sx + ray.sy) + ray.sz) + ((ray.dx + ray.dy) + ray.dz);
     uint32_t tile;
     float cut;
@@ -1899,7 +1903,7 @@ __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, u
                 float t;
                 bool sphere_type;
                 ++tests;
-                if (lane_candidate<AM, true, true>(hot + ids[e], ray, t, sphere_type) && !(t >= 1.f)) return true;
+                if (exact_candidate<AM, true>(hot, compact, ids[e], ray, t, sphere_type) && !(t >= 1.f)) return true;
             }
             if (q0.x == 0u) return false;
             b = q0.x;
@@ -1915,7 +1919,7 @@ __device__ __forceinline__ bool last_light_blocked(const WfParams& w, Ray ray, u
             float t;
             bool sphere;
             ++tests;
-            if (lane_candidate<AM, true, true>(hot + __float_as_uint(aux.y), ray, t, sphere) && !(t >= 1.f)) return true;
+            if (exact_candidate<AM, true>(hot, compact, __float_as_uint(aux.y), ray, t, sphere) && !(t >= 1.f)) return true;
         }
         return false;
     }
@@ -2192,7 +2196,7 @@ __device__ __forceinline__ void loop_step(Ctx& c, const HitRec& from, float abr,
         HitRec rh;
         ObjRows rows;
         float absorb_rh;
-        materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
+        materialise_frame<AM>(S, resume_compact(c.w), idx, T, ray, rh, rows, absorb_rh);
         store_loop_state(c, abr, abg, abb, rr, rg, rb, ap, bounces, false);
         if (c.pre) {  // the step may go on to shade rh on the spot (shade_last_light_inline): what it preloaded is now this
             c.pre_acc = make_float4(abr, abg, abb, ap);
@@ -2269,7 +2273,7 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
             HitRec h;
             ObjRows rows;
             float absorb_h;
-            materialise<AM>(S.objrec, S.cold, idx, T, ray, h, S.affine != 0u, &rows, &absorb_h);
+            materialise_frame<AM>(S, resume_compact(w), idx, T, ray, h, rows, absorb_h);
             begin_shade<KERNEL, AM>(c, h, true, w.rp.max_bounces, absorb_h, rows);
         }
     } else if (phase == PH_SHADOW_PRIMARY || phase == PH_SHADOW_REFLECT) {
@@ -2302,7 +2306,7 @@ __device__ __forceinline__ void resume_pixel(Ctx& c) {
             HitRec rh;
             ObjRows rows;
             float absorb_rh;
-            materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u, &rows, &absorb_rh);
+            materialise_frame<AM>(S, resume_compact(w), idx, T, ray, rh, rows, absorb_rh);
             begin_shade<KERNEL, AM>(c, rh, false, bounces, ap + (1.f - ap) * absorb_rh, rows);
         }
     }
@@ -2326,9 +2330,12 @@ __device__ __forceinline__ void add_ray_counters(const WfParams& w, const Ctx& c
 #ifndef RT_RESUME_WAVES_PER_EU
 #define RT_RESUME_WAVES_PER_EU 4
 #endif
-template <int KERNEL, int AM>
-__global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(RT_RESUME_WAVES_PER_EU))) void wf_resume(const WfParams wk) {
+// (COMPACT: whether the pixels' state machines read the compact records is a wave-uniform word of `w`, and everything below is
+// inlined - set here to what the launch already knows, the word folds and each of the two kernels holds one record form's loads)
+template <int KERNEL, int AM, bool COMPACT>
+__device__ __forceinline__ void resume_kernel(const WfParams& wk) {
     WfParams w = wk;
+    w.rp.scene.diagonal = COMPACT ? 1u : 0u;
     if (!resolve_round(w)) return;
     if (blockIdx.x * kResumeThreads >= w.n_prev_closest + w.n_prev_any) return;  // the grid is sized for the most the queues can hold
     // In the default flow the reflection ray leaves with its hit's first shadow ray: every closest-queue entry of a big round is a
@@ -2345,6 +2352,15 @@ __global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(
     }
     block_push(c.want_closest, c.want_any, (uint32_t)c.i, w.q_closest, w.q_any, w.counts, c.any_flag);
     if (w.count_rays) add_ray_counters(w, c);
+}
+template <int KERNEL, int AM>
+__global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(RT_RESUME_WAVES_PER_EU))) void wf_resume(const WfParams wk) {
+    resume_kernel<KERNEL, AM, false>(wk);
+}
+// ... of a scale-and-translate scene (Scene::diagonal)
+template <int KERNEL, int AM>
+__global__ __launch_bounds__(kResumeThreads) __attribute__((amdgpu_waves_per_eu(RT_RESUME_WAVES_PER_EU))) void wf_resume_compact(const WfParams wk) {
+    resume_kernel<KERNEL, AM, true>(wk);
 }
 
 // The tail of a frame: once only a sliver of the pixels is still alive (stale-specular light scans, the odd long
@@ -2637,8 +2653,12 @@ static hipError_t run_wavefront(WfParams w, WavefrontBuffers& buf, hipStream_t s
             }
         }
         const uint64_t total_max = nc_max + na_max;
-        hipLaunchKernelGGL((wf_resume<KERNEL, AM>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
-                           dim3(kResumeThreads), 0, stream, w);
+        if (KERNEL != 0 && w.rp.scene.diagonal)  // (the hit test materialises nothing)
+            hipLaunchKernelGGL((wf_resume_compact<(KERNEL != 0 ? KERNEL : 1), AM>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
+                               dim3(kResumeThreads), 0, stream, w);
+        else
+            hipLaunchKernelGGL((wf_resume<KERNEL, AM>), dim3((uint32_t)((total_max + kResumeThreads - 1) / kResumeThreads)),
+                               dim3(kResumeThreads), 0, stream, w);
         if ((e2 = hipGetLastError()) != hipSuccess) return e2;
         hipLaunchKernelGGL(wf_advance, dim3(1), dim3(256), 0, stream, rs, (uint32_t)finish_threshold, use_grid ? 1u : 0u);
         return hipGetLastError();

@@ -49,6 +49,7 @@ EXPORTS = [
     "rt_query_closest_device", "rt_query_occluded_device", "rt_query_closest", "rt_query_occluded", "rt_query_primary",
     "rt_get_query_info",
     "rt_query_hits_device", "rt_query_hits", "rt_query_primary_hits",
+    "rt_get_compact_info",
 ]
 
 
@@ -142,6 +143,14 @@ class RTGeometryInfo(ctypes.Structure):
         out["dynamic_ids"] = [int(v) for v in self.dynamic_ids[:out["n_dynamic"]]]
         out["patch_device_ms"] = float(self.patch_device_ms)
         return out
+
+
+class RTCompactInfo(ctypes.Structure):
+    _fields_ = [("table_built", ctypes.c_uint32), ("n_not_diagonal", ctypes.c_uint32), ("allowed", ctypes.c_uint32),
+                ("in_use", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class RTQueryInfo(ctypes.Structure):
@@ -340,6 +349,9 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_query_hits.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTHits)]
         lib.rt_query_primary_hits.restype = i32
         lib.rt_query_primary_hits.argtypes = [vp, vp, u64, ctypes.POINTER(RTHits)]
+    if hasattr(lib, "rt_get_compact_info"):  # (the same: a build from before compact records)
+        lib.rt_get_compact_info.restype = i32
+        lib.rt_get_compact_info.argtypes = [vp, ctypes.POINTER(RTCompactInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -899,6 +911,13 @@ class HIPRaytracer:
         """rt_read_transforms: the TRANSFORM_DTYPE records of objects first .. first + count - 1 (count None: up to the last
         object), reassembled from the device records; RTError if two copies of a word disagree."""
         return self._read_range(self._lib.rt_read_transforms, TRANSFORM_DTYPE, first, count)
+
+    def compact_info(self) -> dict:
+        """rt_get_compact_info: table_built, n_not_diagonal, allowed (RT_COMPACT_RECORDS was not "0") and in_use (the next frame
+        through the round machine reads the compact records; 0: the full records)."""
+        info = RTCompactInfo()
+        self._check(self._lib.rt_get_compact_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
 
     def geometry_info(self) -> dict:
         """rt_get_geometry_info: grid_built, n_unbounded, n_dynamic, dynamic_capacity, dynamic_ids (a list of n_dynamic object
