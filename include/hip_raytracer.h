@@ -875,6 +875,73 @@ int rt_query_hits_device(rt_context* ctx, const void* d_rays, uint64_t n, const 
 int rt_query_hits(rt_context* ctx, const void* rays, uint64_t n, const int32_t* mask, const rt_hits_t* out);
 int rt_query_primary_hits(rt_context* ctx, const uint64_t* work_items, uint64_t n, const rt_hits_t* out);
 
+/* ---- shaded queries ----------------------------------------------------------------------------------------------------------------
+ * WHAT COLOUR comes back along a ray of the caller's own: the whole shading path - primary hit, light loop with its shadow rays,
+ * reflection chain - for any number of rays, on a live context, without a frame. Light and reflection probes for a rasteriser, a mirror
+ * or portal texture of a few thousand rays, extra sub-pixel rays at the edge pixels rt_render_aux's index shows, foveated or progressive
+ * refinement, the colour under the mouse - without replacing the frame's rays (rt_set_rays_device wants exactly the context's ray
+ * count, is synchronous, drops the camera or pose and lets one bad ray switch the frame to the literal loops) and without a second
+ * context (its creation time, a second grid, and none of this context's setters). Additions only: the ABI version stays 3, and a caller
+ * detects support by dlsym of rt_query_shade_device.
+ *
+ * Contract. Element i of rgba, t and index is, bit for bit, what a FRESH context delivers for work-item i - rt_render for rgba,
+ * rt_render_aux for t and index - when it is created with the context's current objects (the create-time array through
+ * records.with_transforms / with_materials / with_visibility as set so far), its current lights, the same kernel (RT_KERNEL_SHADE or
+ * RT_KERNEL_SHADE_AND_REFLECT), the same max_bounces, the same arithmetic flags (RT_FLAG_UNFUSED, RT_FLAG_FAST_PHONG,
+ * RT_FLAG_DEVICE_OPENCL), RT_FLAG_NO_RAYGEN and these n rays. That includes the background (0,0,0,1) of a miss and the per-kernel rule
+ * of rt_set_aux_device for a NaN primary time. n is ANY count, independent of the context's ray count. A query reads the records, the
+ * lights and the grid as rt_set_transforms, rt_set_visibility, rt_set_materials and rt_set_lights have left them and writes only the
+ * caller's outputs and a context-owned counter block. The frame's rays, camera, pose, shard, supersampling factor, aux buffers, state
+ * buffers and packed buffers are untouched: a render before and after a query is the same frame.
+ *
+ * Route, decided by each lane for EVERY ray of its own path (csrc/rt_query_shade.hip; rays.query_shade_route is the executable
+ * definition). A ray - primary, shadow or reflection - is served by the grid walks exactly when the predicate of "ray queries" above
+ * admits it (one function, shared with those kernels); shadow and reflection rays start on surfaces inside the box, as the frames' do.
+ * Every other ray runs the ordered loop over all objects. A PATH is literal - the forward light loop, closest-hit shadow tests, no
+ * dead-ray elimination: RT_FLAG_LITERAL - when the context is literal (by flag, for a degenerate instance, or by RT_FLAG_DEVICE_OPENCL's
+ * predicate on its lights), or when its primary ray fails the DOMAIN part of the predicate: a non-finite component, start.w != 1,
+ * direction.w != 0, dd outside (1e-30, 1e30). That is what a fresh context does for the whole frame when one such ray is in its buffer.
+ * A primary ray that fails only the box test takes the brute-force loop for that one ray and the default path behind it. On the
+ * default path a shadow ray with a NaN in it gets the closed form of the frames (the last sphere / box of the scene decides).
+ * Invariant this rests on: a literal frame and a default frame agree bit for bit on every ray inside the domain (RT_FLAG_LITERAL:
+ * "Results are identical"). So a batch that mixes rays of every class can be compared with ONE fresh context, which renders all of
+ * it literally (tests/test_query_shade_gpu.py does).
+ *
+ * Mask. d_mask is NULL or n int32, as for rt_query_hits_device: a ray with a negative entry is not traced, reads as a miss - the
+ * background colour, t = MAX_FLOAT, index = -1 - and enters no counter.
+ *
+ * rt_query_shade_device: `d_out` points to a HOST struct, read during the call, whose members are device pointers on the context's
+ * device (each may be NULL, not all). d_rays and rgba 16-BYTE ALIGNED; t, index and d_mask 4-byte aligned. ASYNCHRONOUS on hip_stream
+ * (NULL: the legacy default stream): no host synchronisation, no allocation after the first call. Rays and outputs must not overlap.
+ * rt_query_shade: the host twin, synchronous, staged through the context's grow-only patch buffer; members of `out` are host arrays.
+ * rt_query_primary_shade: the pick with its colour - rt_query_primary's work-items and rules (RT_ERR_STATE without rays), host results.
+ * rt_get_query_shade_info: the LAST shaded query's counters, from a block of its own (rt_get_query_info keeps reporting the last plain
+ * or hit-record query); waits for that query. RT_ERR_STATE before the first shaded query.
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: what rt_query_hits_device refuses for its arguments, a NULL struct, all members
+ * NULL. RT_ERR_STATE: an RT_KERNEL_HITTEST context (a time is not a colour); a context with triangles. n == 0 returns RT_OK with
+ * nothing launched.
+ *
+ * NOT part of this call: _multi forms (rt_multi_context(m, 0) answers); bytes out (rt_pack_device takes the float4 result); refilling
+ * a wave's idle lanes (one lane keeps its ray until the path ends, so a wave lasts as long as its longest path); contexts with
+ * triangles. */
+typedef struct rt_shade_t {    /* every member may be NULL, not all of them */
+    float*   rgba;    /* n x float4 - the pixel a frame would hold for this ray */
+    float*   t;       /* n floats   - primary hit time, as rt_set_aux_device defines it for the context's kernel */
+    int32_t* index;   /* n int32    - primary winner, same rule */
+} rt_shade_t;
+typedef struct rt_query_shade_info_t {
+    uint64_t n_rays, n_grid, n_brute;   /* traced primary rays and their route (n_grid + n_brute == n_rays; masked rays not counted) */
+    uint64_t n_literal;                 /* primary rays whose whole path ran the literal loops */
+    uint64_t hit_rays;                  /* as rt_stats_t::hit_pixels of the fresh context */
+    uint64_t rays_traced, rays_reference; /* as rt_stats_t's, summed over the batch */
+    uint64_t object_tests;              /* exact ray-object tests of every ray of the paths (a brute-force ray: 2 per pair record visited) */
+    double   device_ms;
+} rt_query_shade_info_t;
+int rt_query_shade_device(rt_context* ctx, const void* d_rays, uint64_t n, const int32_t* d_mask, const rt_shade_t* d_out, void* hip_stream);
+int rt_query_shade(rt_context* ctx, const void* rays, uint64_t n, const int32_t* mask, const rt_shade_t* out);
+int rt_query_primary_shade(rt_context* ctx, const uint64_t* work_items, uint64_t n, const rt_shade_t* out);
+int rt_get_query_shade_info(rt_context* ctx, rt_query_shade_info_t* info);
+
 void rt_destroy(rt_context* ctx);
 
 /* ---- several GPUs from one process ------------------------------------------------------------------------------------

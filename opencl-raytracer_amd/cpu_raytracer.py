@@ -57,6 +57,10 @@ def load_library():
         if hasattr(lib, "cpu_rt_query_hits"):
             lib.cpu_rt_query_hits.restype = ctypes.c_int
             lib.cpu_rt_query_hits.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_uint, vp, u32, u32, vp, u32, u32]
+        if hasattr(lib, "cpu_rt_query_shade"):
+            lib.cpu_rt_query_shade.restype = ctypes.c_int
+            lib.cpu_rt_query_shade.argtypes = [ctypes.c_int, u32, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_uint,
+                                               vp, u32, u32, vp, u32, u32, vp, u32, u32]
         _lib = lib
     return _lib
 
@@ -218,6 +222,39 @@ class CPURaytracer:
     def hit_records(self, rays, t, index):
         """The record stage alone: point / normal / reflected for the given winner and time per ray (index < 0: zero records)."""
         return self._hits(rays, None, t, index)
+
+    # -- shaded queries: CPURaytracer::QueryShade, the option HIPRaytracer.query_shade is on the GPU ---------------------------------
+    def query_shade(self, rays, mask=None):
+        """The colour along `rays` - any number of rays of the caller's own, a RAY_DTYPE array or an (n, 8) float32 array - over the
+        CURRENT objects, materials and lights (set_transforms / set_visibility / set_materials / set_lights as set so far), with
+        this object's kernel and MAX_BOUNCES: a dict of "rgba" float32[n, 4], the pixel a fresh CPURaytracer's Render() holds for
+        that ray ((0, 0, 0, 1) on a miss), and "t" float32[n], "index" int32[n], the primary hit as the kernel takes it (a NaN time is
+        a hit for shade_and_reflect, a miss for shade). A ray whose `mask` entry is negative reads as a miss (t = MAX_FLOAT) and is not
+        counted. The definition of HIPRaytracer.query_shade that runs without a GPU; the frame's rays do not enter.
+        self.shade_info: n_rays (traced), rays_reference, hit_rays of the call."""
+        if self.kernel not in (1, 2):
+            raise ValueError("query_shade: a time is not a colour (query_closest answers a hittest object)")
+        rays = rays_of(rays)
+        n = len(rays)
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
+            if len(mask) != n:
+                raise ValueError("query_shade: the mask has one int32 entry per ray")
+        rgba = np.zeros((n, 4), dtype=np.float32)
+        t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+        counts = np.zeros(3, dtype=np.uint64)
+
+        def ptr(a):
+            return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+        vis, xf, mats = self.visible, self.transforms, self.materials
+        rc = self._lib.cpu_rt_query_shade(self.kernel, self.max_bounces, ptr(self.objects), len(self.objects), ptr(self.lights),
+                                          len(self.lights), ptr(rays), n, ptr(mask), ptr(rgba), ptr(t), ptr(index), ptr(counts),
+                                          self.threads, ptr(vis), 0, len(vis) if vis is not None else 0,
+                                          ptr(xf), 0, len(xf) if xf is not None else 0, ptr(mats), 0, len(mats) if mats is not None else 0)
+        if rc != 0:
+            raise ValueError("cpu_rt_query_shade: unsupported arguments (triangle records are a HIP-backend extension)")
+        self.shade_info = {"n_rays": int(counts[0]), "rays_reference": int(counts[1]), "hit_rays": int(counts[2])}
+        return {"rgba": rgba, "t": t, "index": index}
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)

@@ -277,6 +277,11 @@ struct rt_context {
     rt::QueryCounters* d_query_counters = nullptr;
     hipEvent_t ev_query[2] = {};
     bool query_made = false;
+    // Shaded queries (rt_query_shade*): their own counter block and event pair, so that rt_get_query_info keeps reporting the last plain
+    // or hit-record query.
+    rt::QueryShadeCounters* d_query_shade_counters = nullptr;
+    hipEvent_t ev_query_shade[2] = {};
+    bool query_shade_made = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;

@@ -838,6 +838,15 @@ __device__ __forceinline__ bool any_secondary(const Scene& S, const Ray& ray) {
     else return any_hit_before_one<AM>(S.pairs, S.n_pairs, ray);
 }
 
+// Who traces the secondary rays of the shading functions below. The default is the small-scene traversal of the monolithic kernel
+// (closest_secondary / any_secondary with SMALL = true): today's calls. rt_query_shade.hip passes one that routes every ray by itself.
+struct SmallSceneTracer {
+    template <int AM>
+    __device__ __forceinline__ void closest(const Scene& S, const Ray& ray, float& T, int& idx) const { closest_secondary<AM, true>(S, ray, T, idx); }
+    template <int AM>
+    __device__ __forceinline__ bool any(const Scene& S, const Ray& ray) const { return any_secondary<AM, true>(S, ray); }
+};
+
 struct LightGeom {
     float nlx, nly, nlz;  // normalised light vector
     float nDotL, rDotV;
@@ -892,8 +901,8 @@ __device__ __forceinline__ void light_geometry(const LightRec& L, const HitRec& 
 }
 
 // lit iff the reference's `shadowcastHit.time >= 1.f || shadowcastHit.time < 0` (:229)
-template <int AM, bool COUNT>
-__device__ __forceinline__ bool light_visible(const Scene& S, const Ray& shadow, Counters& ctr) {
+template <int AM, bool COUNT, class TRACER = SmallSceneTracer>
+__device__ __forceinline__ bool light_visible(const Scene& S, const Ray& shadow, Counters& ctr, TRACER tracer = TRACER()) {
     if constexpr (COUNT) ctr.traced += 1;
     if (!S.literal) {  // the any-hit test is order-free: a NaN shadow ray's outcome is not (`time >= 1 || time < 0`, :229)
         const int k = nan_ray_outcome(shadow, S.nan_winner, S.nan_winner_sphere);
@@ -902,18 +911,18 @@ __device__ __forceinline__ bool light_visible(const Scene& S, const Ray& shadow,
     if (S.literal) {
         float T = kMaxFloat;
         int idx = -1;
-        closest_secondary<AM, true>(S, shadow, T, idx);
+        tracer.template closest<AM>(S, shadow, T, idx);
         return (T >= 1.f || T < 0);
     }
-    return !any_secondary<AM, true>(S, shadow);
+    return !tracer.template any<AM>(S, shadow);
 }
 
 // The light loop in the reference's order. ACCUMULATE: shade_kernel.cl:252 (sum over lights);
 // otherwise shade_and_reflect_kernel.cl:238 (assignment - the last light's terms survive). Both carry the
 // stale specular: it is re-assigned only when lit with nDotL > 0 and zeroed when shadowed (:229-237).
-template <int AM, bool ACCUMULATE, bool COUNT>
+template <int AM, bool ACCUMULATE, bool COUNT, class TRACER = SmallSceneTracer>
 __device__ __forceinline__ void shade_forward(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
-                                              Counters& ctr) {
+                                              Counters& ctr, TRACER tracer = TRACER()) {
     const ColdObject* c = S.cold + h.index;
     const float4 amb = c->amb_absorb, dif = c->dif_shine, spec = c->spec_type;
     float nvx = h.nx, nvy = h.ny, nvz = h.nz;
@@ -927,7 +936,7 @@ __device__ __forceinline__ void shade_forward(const Scene& S, const HitRec& h, f
         const LightRec L = S.lights[li];
         LightGeom g;
         light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
-        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr);
+        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr, tracer);
         const float ar = amb.x * L.ambient.x, ag = amb.y * L.ambient.y, ab = amb.z * L.ambient.z;
         float dr, dg, db;
         if (lit) {
@@ -952,9 +961,9 @@ __device__ __forceinline__ void shade_forward(const Scene& S, const HitRec& h, f
 // shade_and_reflect's colour without tracing the shadow rays whose result cannot reach it: ambient and
 // diffuse come from the last light only; the specular from the last light j that was either shadowed
 // (-> 0) or lit with nDotL > 0. Scan backwards from the last light and stop at j.
-template <int AM, bool COUNT>
+template <int AM, bool COUNT, class TRACER = SmallSceneTracer>
 __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
-                                                      Counters& ctr) {
+                                                      Counters& ctr, TRACER tracer = TRACER()) {
     cr = 0.f; cg = 0.f; cb = 0.f;
     if constexpr (COUNT) ctr.reference += S.n_lights;
     if (S.n_lights == 0) return;
@@ -972,7 +981,7 @@ __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitR
         const LightRec L = S.lights[li];
         LightGeom g;
         light_geometry<AM>(L, h, nvx, nvy, nvz, vvx, vvy, vvz, g, S.fast_phong != 0u);
-        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr);
+        const bool lit = light_visible<AM, COUNT>(S, g.shadow, ctr, tracer);
         if (li == S.n_lights - 1) {
             ar = amb.x * L.ambient.x; ag = amb.y * L.ambient.y; ab = amb.z * L.ambient.z;
             if (lit) {
@@ -992,11 +1001,11 @@ __device__ __forceinline__ void shade_last_light_wins(const Scene& S, const HitR
     cr = (ar + dr) + sr; cg = (ag + dg) + sg; cb = (ab + db) + sb;
 }
 
-template <int AM, bool COUNT>
+template <int AM, bool COUNT, class TRACER = SmallSceneTracer>
 __device__ __forceinline__ void shade_assign(const Scene& S, const HitRec& h, float& cr, float& cg, float& cb,
-                                             Counters& ctr) {
-    if (S.literal) shade_forward<AM, false, COUNT>(S, h, cr, cg, cb, ctr);
-    else shade_last_light_wins<AM, COUNT>(S, h, cr, cg, cb, ctr);
+                                             Counters& ctr, TRACER tracer = TRACER()) {
+    if (S.literal) shade_forward<AM, false, COUNT>(S, h, cr, cg, cb, ctr, tracer);
+    else shade_last_light_wins<AM, COUNT>(S, h, cr, cg, cb, ctr, tracer);
 }
 
 // next ray of the reflection chain: start = intersection + 0.001 * normalize(reflection), direction = reflection
@@ -1030,11 +1039,11 @@ __host__ __device__ constexpr bool reflection_word_self_hit(uint32_t word) { ret
 __host__ __device__ constexpr uint32_t reflection_word_bounces(uint32_t word) { return word & ~kReflectSelfHit; }
 
 // __kernel shade_and_reflect for one work-item whose primary ray hit (shade_and_reflect_kernel.cl:253-284)
-template <int AM, bool COUNT>
+template <int AM, bool COUNT, class TRACER = SmallSceneTracer>
 __device__ __forceinline__ void shade_and_reflect_pixel(const Scene& S, uint32_t max_bounces, const HitRec& hit,
-                                                        float& outr, float& outg, float& outb, Counters& ctr) {
+                                                        float& outr, float& outg, float& outb, Counters& ctr, TRACER tracer = TRACER()) {
     float cr, cg, cb;
-    shade_assign<AM, COUNT>(S, hit, cr, cg, cb, ctr);
+    shade_assign<AM, COUNT>(S, hit, cr, cg, cb, ctr, tracer);
     float ap = S.cold[hit.index].amb_absorb.w;
     float abr = cr * ap, abg = cg * ap, abb = cb * ap;
     float rr = 0.f, rg = 0.f, rb = 0.f;  // reflectColor
@@ -1053,12 +1062,12 @@ __device__ __forceinline__ void shade_and_reflect_pixel(const Scene& S, uint32_t
         reflection_ray<AM>(from, ray);
         float T = kMaxFloat;
         int idx = -1;
-        closest_secondary<AM, true>(S, ray, T, idx);
+        tracer.template closest<AM>(S, ray, T, idx);
         if (T == kMaxFloat) break;  // raycast() returned false (:173)
         if (!absorbing) break;
         HitRec rh;
         materialise<AM>(S.objrec, S.cold, idx, T, ray, rh, S.affine != 0u);
-        shade_assign<AM, COUNT>(S, rh, rr, rg, rb, ctr);
+        shade_assign<AM, COUNT>(S, rh, rr, rg, rb, ctr, tracer);
         const float ra = (1.f - ap) * S.cold[rh.index].amb_absorb.w;
         abr = fma_<AM>(ra, rr, abr); abg = fma_<AM>(ra, rg, abg); abb = fma_<AM>(ra, rb, abb);
         ap = ap + ra;

@@ -60,4 +60,26 @@ hipError_t launch_query_hits(const Scene& scene, const GridDesc& grid, const Que
 hipError_t launch_query_primary_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
                                      const uint64_t* d_items, uint64_t n, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream);
 
+// Shaded queries (hip_raytracer.h: rt_shade_t with device pointers; rt_query_shade.hip). Every member may be null, not all of them;
+// rgba 16-byte aligned, t / index 4-byte aligned.
+struct QueryShade {
+    float4* rgba;
+    float* t;
+    int32_t* index;
+};
+// What a shaded query adds up, once per wave: QueryCounters for the PRIMARY rays (their route; `tests` counts every ray of the paths),
+// the primary rays whose path ran the literal loops, and what Counters holds for a counted frame - primary hits as the context's
+// kernel takes them, rays issued, rays the reference semantics trace.
+struct QueryShadeCounters {
+    QueryCounters q;
+    unsigned long long n_literal, hits, traced, reference;
+};
+// One thread per ray runs the reference's per-pixel program (kernel 1: shade, 2: shade_and_reflect with scene-independent
+// `max_bounces`) with a tracer that routes every ray of the path by itself. scene.literal: the context is literal (every path is);
+// scene.fast_phong as the frames fill it. Rays: d_rays, or - d_items non-null - the camera's primary rays of those work-items.
+// d_mask: null, or n int32 - a negative entry is not traced, not counted and reads as a miss (background, MAX_FLOAT, -1).
+hipError_t launch_query_shade(const Scene& scene, const GridDesc& grid, const QueryBox& box, int kernel, int arith, uint32_t max_bounces,
+                              const float4* d_rays, const QueryCamera& camera, const uint64_t* d_items, uint64_t n, const int32_t* d_mask,
+                              const QueryShade& out, QueryShadeCounters* d_counters, hipStream_t stream);
+
 }  // namespace rt

@@ -1,6 +1,7 @@
 // rt_query_host.cpp - ray queries (hip_raytracer.h): rt_query_closest_device, rt_query_occluded_device, their host twins
 // rt_query_closest / rt_query_occluded, rt_query_primary, the hit-record queries rt_query_hits_device / rt_query_hits /
-// rt_query_primary_hits, and rt_get_query_info. A query reads the context's object records and grid as
+// rt_query_primary_hits, the shaded queries rt_query_shade_device / rt_query_shade / rt_query_primary_shade with their own
+// rt_get_query_shade_info, and rt_get_query_info. A query reads the context's object records and grid as
 // the setters have left them and writes the caller's outputs and the context's counter block - nothing of the frame: not its rays,
 // camera, pose, shard, supersampling factor, aux buffers or state buffers. The device forms enqueue a memset, two event records and one
 // kernel (rt_query.hip) and return; after the first call, which makes the counter block and the events, nothing is allocated.
@@ -227,6 +228,92 @@ int hits_from_host(rt_context* c, bool primary, const void* in, size_t in_bytes,
     return RT_OK;
 }
 
+// ---- shaded queries ------------------------------------------------------------------------------------------------------------------
+// Every path of a shaded query is literal on a context that is literal by its OBJECTS, by the caller's wish or by its LIGHTS
+// (RT_FLAG_DEVICE_OPENCL's predicate, rt_light_setup.cpp: a zero-direction shadow ray has no order-free answer) - the reasons that do
+// not depend on the frame's rays. The first two also keep the grid from answering (grid_serves_queries); the third does not.
+bool shade_context_literal(const rt_context* c) {
+    return (c->user_flags & RT_FLAG_LITERAL) || c->degenerate_literal || c->lights_literal;
+}
+
+int refuse_shade_context(rt_context* c) {
+    if (c->kernel == RT_KERNEL_HITTEST)
+        return fail(c, RT_ERR_STATE, "shaded queries on an RT_KERNEL_HITTEST context: a time is not a colour (rt_query_closest answers there)");
+    return refuse_triangles(c);
+}
+
+int check_shade(rt_context* c, const rt_shade_t* o, bool device) {
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    if (!o->rgba && !o->t && !o->index) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
+    if (!device) return RT_OK;
+    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(o->rgba) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba must be 16-byte aligned");
+    return RT_OK;
+}
+
+int ensure_shade_support(rt_context* c) {
+    if (!c->d_query_shade_counters) RT_HIP(c, hipMalloc((void**)&c->d_query_shade_counters, sizeof(rt::QueryShadeCounters)));
+    for (hipEvent_t& e : c->ev_query_shade)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    return RT_OK;
+}
+
+// One shaded query on `stream`, as enqueue_hits: `d_in` the rays or, with `primary`, the work-items; `out` device pointers.
+int enqueue_shade(rt_context* c, bool primary, const void* d_in, uint64_t n, const int32_t* d_mask, const rt::QueryShade& out, hipStream_t stream) {
+    if (const int rc = ensure_shade_support(c)) return rc;
+    rt::Scene scene = query_scene(c);
+    scene.literal = shade_context_literal(c) ? 1u : 0u;
+    scene.fast_phong = (c->flags & RT_FLAG_FAST_PHONG) ? 1u : 0u;
+    const rt::QueryBox box = query_box(c);
+    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
+    RT_HIP(c, hipMemsetAsync(c->d_query_shade_counters, 0, sizeof(rt::QueryShadeCounters), stream));
+    RT_HIP(c, hipEventRecord(c->ev_query_shade[0], stream));
+    const hipError_t e = rt::launch_query_shade(scene, grid, box, c->kernel, query_arith(c), c->max_bounces,
+                                                primary ? nullptr : static_cast<const float4*>(d_in), primary ? query_camera(c) : rt::QueryCamera{},
+                                                primary ? static_cast<const uint64_t*>(d_in) : nullptr, n, d_mask, out, c->d_query_shade_counters, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "shaded query launch");
+    RT_HIP(c, hipEventRecord(c->ev_query_shade[1], stream));
+    c->query_shade_made = true;
+    return RT_OK;
+}
+
+// What shade_from_host stages per element, at most: the input (a 32-byte ray or an 8-byte work-item), the mask, rgba, t, index; each
+// array but the last is padded to 16 bytes once.
+constexpr size_t kShadeStageBytesPerElement = sizeof(rt_ray) + 4 + 16 + 4 + 4;
+constexpr size_t kShadeStagePadding = 4 * 16;
+int check_shade_count(rt_context* c, uint64_t n) {
+    if (n > ((std::numeric_limits<size_t>::max)() - kShadeStagePadding) / kShadeStageBytesPerElement)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "too many elements: the staged records would not fit an address");
+    return RT_OK;
+}
+
+// The host forms: input, mask and the requested outputs staged in the context's patch buffer on the context's stream; synchronous.
+int shade_from_host(rt_context* c, bool primary, const void* in, size_t in_bytes, uint64_t n, const int32_t* mask, const rt_shade_t& out) {
+    RT_DEVICE(c);
+    const size_t count = (size_t)n;
+    const size_t off_mask = align16(in_bytes * count);
+    const size_t off_rgba = off_mask + align16(sizeof(int32_t) * count);
+    const size_t off_t = off_rgba + 16 * count;
+    const size_t off_index = off_t + align16(sizeof(float) * count);
+    if (const int rc = ensure_patch_stage(c, off_index + align16(sizeof(int32_t) * count))) return rc;
+    char* const stage = static_cast<char*>(c->d_patch_stage.p);
+    rt::QueryShade d = {};
+    d.rgba = out.rgba ? reinterpret_cast<float4*>(stage + off_rgba) : nullptr;
+    d.t = out.t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
+    d.index = out.index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
+    int32_t* const d_mask = mask ? reinterpret_cast<int32_t*>(stage + off_mask) : nullptr;
+    hipStream_t stream = c->stream;
+    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * count, hipMemcpyHostToDevice, stream));
+    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_shade(c, primary, stage, n, d_mask, d, stream)) return rc;
+    if (out.rgba) RT_HIP(c, hipMemcpyAsync(out.rgba, d.rgba, 16 * count, hipMemcpyDeviceToHost, stream));
+    if (out.t) RT_HIP(c, hipMemcpyAsync(out.t, d.t, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
+    if (out.index) RT_HIP(c, hipMemcpyAsync(out.index, d.index, sizeof(int32_t) * count, hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
 }  // namespace
 }  // namespace rt::host
 
@@ -321,6 +408,63 @@ int rt_query_primary_hits(rt_context* c, const uint64_t* work_items, uint64_t n,
         return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
     if (n == 0) return RT_OK;
     return hits_from_host(c, true, work_items, sizeof(uint64_t), n, nullptr, *out);
+}
+
+int rt_query_shade_device(rt_context* c, const void* d_rays, uint64_t n, const int32_t* d_mask, const rt_shade_t* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, d_rays, n, true)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_mask) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the mask must be 4-byte aligned");
+    if (const int rc = check_shade(c, d_out, true)) return rc;
+    if (const int rc = refuse_shade_context(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_shade(c, false, d_rays, n, d_mask, rt::QueryShade{reinterpret_cast<float4*>(d_out->rgba), d_out->t, d_out->index},
+                         static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_query_shade(rt_context* c, const void* rays, uint64_t n, const int32_t* mask, const rt_shade_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_query_rays(c, rays, n, false)) return rc;
+    if (const int rc = check_shade_count(c, n)) return rc;
+    if (const int rc = check_shade(c, out, false)) return rc;
+    if (const int rc = refuse_shade_context(c)) return rc;
+    if (n == 0) return RT_OK;
+    return shade_from_host(c, false, rays, sizeof(rt_ray), n, mask, *out);
+}
+
+int rt_query_primary_shade(rt_context* c, const uint64_t* work_items, uint64_t n, const rt_shade_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
+    if (const int rc = check_shade_count(c, n)) return rc;
+    if (const int rc = check_shade(c, out, false)) return rc;
+    for (uint64_t k = 0; k < n; ++k)
+        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
+    if (const int rc = refuse_shade_context(c)) return rc;
+    if (!c->pinhole && !c->have_rays)
+        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    if (n == 0) return RT_OK;
+    return shade_from_host(c, true, work_items, sizeof(uint64_t), n, nullptr, *out);
+}
+
+int rt_get_query_shade_info(rt_context* c, rt_query_shade_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->query_shade_made) return fail(c, RT_ERR_STATE, "rt_get_query_shade_info: no shaded query has been made on this context");
+    RT_DEVICE(c);
+    RT_HIP(c, hipEventSynchronize(c->ev_query_shade[1]));  // the last shaded query's stream, up to the query
+    rt::QueryShadeCounters ctr = {};
+    RT_HIP(c, hipMemcpy(&ctr, c->d_query_shade_counters, sizeof(ctr), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_query_shade[0], c->ev_query_shade[1]));
+    info->n_rays = ctr.q.n_rays;
+    info->n_grid = ctr.q.n_grid;
+    info->n_brute = ctr.q.n_brute;
+    info->n_literal = ctr.n_literal;
+    info->hit_rays = ctr.hits;
+    info->rays_traced = ctr.traced;
+    info->rays_reference = ctr.reference;
+    info->object_tests = ctr.q.tests;
+    info->device_ms = (double)ms;
+    return RT_OK;
 }
 
 int rt_get_query_info(rt_context* c, rt_query_info_t* info) {

@@ -49,6 +49,7 @@ EXPORTS = [
     "rt_query_closest_device", "rt_query_occluded_device", "rt_query_closest", "rt_query_occluded", "rt_query_primary",
     "rt_get_query_info",
     "rt_query_hits_device", "rt_query_hits", "rt_query_primary_hits",
+    "rt_query_shade_device", "rt_query_shade", "rt_query_primary_shade", "rt_get_query_shade_info",
     "rt_get_compact_info",
 ]
 
@@ -170,6 +171,25 @@ class RTHits(ctypes.Structure):
 
 
 HIT_FIELDS = ("t", "index", "point", "normal", "reflected")
+
+
+class RTShade(ctypes.Structure):
+    """rt_shade_t: three pointers, each may be NULL (not all)."""
+    _fields_ = [("rgba", ctypes.c_void_p), ("t", ctypes.c_void_p), ("index", ctypes.c_void_p)]
+
+
+class RTQueryShadeInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_rays", ctypes.c_uint64), ("n_grid", ctypes.c_uint64), ("n_brute", ctypes.c_uint64), ("n_literal", ctypes.c_uint64),
+        ("hit_rays", ctypes.c_uint64), ("rays_traced", ctypes.c_uint64), ("rays_reference", ctypes.c_uint64),
+        ("object_tests", ctypes.c_uint64), ("device_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
+
+
+SHADE_FIELDS = ("rgba", "t", "index")
 
 _lib = None
 
@@ -349,6 +369,15 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_query_hits.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTHits)]
         lib.rt_query_primary_hits.restype = i32
         lib.rt_query_primary_hits.argtypes = [vp, vp, u64, ctypes.POINTER(RTHits)]
+    if hasattr(lib, "rt_query_shade_device"):
+        lib.rt_query_shade_device.restype = i32
+        lib.rt_query_shade_device.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTShade), vp]
+        lib.rt_query_shade.restype = i32
+        lib.rt_query_shade.argtypes = [vp, vp, u64, vp, ctypes.POINTER(RTShade)]
+        lib.rt_query_primary_shade.restype = i32
+        lib.rt_query_primary_shade.argtypes = [vp, vp, u64, ctypes.POINTER(RTShade)]
+        lib.rt_get_query_shade_info.restype = i32
+        lib.rt_get_query_shade_info.argtypes = [vp, ctypes.POINTER(RTQueryShadeInfo)]
     if hasattr(lib, "rt_get_compact_info"):  # (the same: a build from before compact records)
         lib.rt_get_compact_info.restype = i32
         lib.rt_get_compact_info.argtypes = [vp, ctypes.POINTER(RTCompactInfo)]
@@ -525,6 +554,69 @@ def _pick_hit(lib, ctx, work_items, want):
     n = int(items.shape[0])
     res, hits = _host_hits(n, _wanted(want))
     _check_rc(lib, ctx, lib.rt_query_primary_hits(ctx, _ptr(items), n, ctypes.byref(hits)))
+    return res
+
+
+def _shade_wanted(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in SHADE_FIELDS for w in want):
+        raise ValueError(f"want: a non-empty selection of {SHADE_FIELDS}")
+    return want
+
+
+def _host_shade(n: int, want):
+    """numpy arrays for the wanted outputs and the rt_shade_t that points at them."""
+    shapes = {"rgba": ((n, 4), np.float32), "t": ((n,), np.float32), "index": ((n,), np.int32)}
+    out = {w: np.zeros(*shapes[w]) for w in want}
+    return out, RTShade(**{w: (a.ctypes.data if a.size else None) for w, a in out.items()})
+
+
+def _query_shade(lib, ctx, rays, mask, want, out, device: int):
+    """HIPRaytracer.query_shade: rt_query_shade for numpy rays, rt_query_shade_device on torch's current stream for a device tensor."""
+    want = _shade_wanted(want)
+    if _is_tensor(rays):
+        import torch
+        ptr, n, stream = _device_rays(rays, device)
+        shapes = {"rgba": ((n, 4), torch.float32), "t": ((n,), torch.float32), "index": ((n,), torch.int32)}
+        res = {}
+        for w in want:
+            shape, dtype = shapes[w]
+            given = None if out is None else out.get(w)
+            if given is None:
+                res[w] = torch.empty(shape, dtype=dtype, device=rays.device)
+            else:
+                if not _is_tensor(given) or given.device != rays.device or given.dtype != dtype or not given.is_contiguous() or \
+                        given.numel() != int(np.prod(shape)):
+                    raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the rays' device")
+                res[w] = given
+        m_ptr = None
+        if mask is not None:
+            if not _is_tensor(mask) or mask.device != rays.device or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != n:
+                raise ValueError("mask: a contiguous int32 tensor on the rays' device, one entry per ray")
+            m_ptr = ctypes.c_void_p(mask.data_ptr()) if n else None
+        if n:
+            shade = RTShade(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_query_shade_device(ctx, ptr, n, m_ptr, ctypes.byref(shade), stream))
+        return res
+    if out is not None:
+        raise ValueError("out= takes device tensors: numpy rays return fresh arrays")
+    rays = rays_of(rays)
+    n = int(rays.shape[0])
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
+        if mask.shape[0] != n:
+            raise ValueError("mask: one int32 entry per ray")
+    res, shade = _host_shade(n, want)
+    if n:
+        _check_rc(lib, ctx, lib.rt_query_shade(ctx, _ptr(rays), n, _ptr(mask), ctypes.byref(shade)))
+    return res
+
+
+def _pick_shade(lib, ctx, work_items, want):
+    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
+    n = int(items.shape[0])
+    res, shade = _host_shade(n, _shade_wanted(want))
+    _check_rc(lib, ctx, lib.rt_query_primary_shade(ctx, _ptr(items), n, ctypes.byref(shade)))
     return res
 
 
@@ -1006,6 +1098,42 @@ class HIPRaytracer:
                 one["index"] = int(one["index"])
             return one
         return _pick_hit(self._lib, self._ctx, i, want)
+
+    # -- shaded queries (hip_raytracer.h: the colour along rays that are not the frame's; the frame is untouched) ------------------
+    def query_shade(self, rays, mask=None, want=("rgba",), out=None):
+        """The COLOUR along `rays` - any number of rays of the caller's own - on the context's current objects, materials and lights,
+        with its kernel, MAX_BOUNCES and arithmetic: a dict of the outputs named in `want` - "rgba" float32[n, 4], the pixel a fresh
+        context created with these rays renders, bit for bit ((0, 0, 0, 1) on a miss); "t" float32[n] and "index" int32[n], its
+        render_aux(). `mask`: int32 per ray, a negative entry is not traced and reads as a miss. Arrays and tensors as query_hits: a
+        numpy ray array (RAY_DTYPE records or float32 (n, 8)) goes through rt_query_shade (synchronous, numpy results); a torch
+        tensor on the context's device goes through rt_query_shade_device on torch's current stream, with no host synchronisation,
+        and `out` may name existing tensors to write into. CPURaytracer.query_shade is the definition that runs without a GPU;
+        rays.query_shade_route says which route each ray takes. Refused on a hittest context and on one with triangles."""
+        return _query_shade(self._lib, self._ctx, rays, mask, want, out, self._device)
+
+    def pick_colour(self, i, j=None, want=("rgba",)):
+        """The colour under the mouse (rt_query_primary_shade): pick_colour(i, j) -> float32[4], the pixel of column i, row j of the
+        pinhole / posed grid as an unsharded, unfiltered frame holds it (with `want` of more than "rgba": a dict, t a float and index
+        an int). pick_colour(work_items) -> a dict of arrays, as query_shade returns."""
+        if j is not None:
+            width = self._grid_width()
+            if not width:
+                raise ValueError("pick_colour(i, j) needs a camera or a pose; with a plain ray buffer use pick_colour(work_items)")
+            res = _pick_shade(self._lib, self._ctx, [int(j) * width + int(i)], want)
+            one = {w: a[0] for w, a in res.items()}
+            if "t" in one:
+                one["t"] = float(one["t"])
+            if "index" in one:
+                one["index"] = int(one["index"])
+            return one["rgba"] if tuple(one) == ("rgba",) else one
+        return _pick_shade(self._lib, self._ctx, i, want)
+
+    def query_shade_info(self) -> dict:
+        """rt_get_query_shade_info: n_rays, n_grid, n_brute (primary rays per route), n_literal (paths on the literal loops), hit_rays,
+        rays_traced, rays_reference, object_tests and device_ms of the last query_shade / pick_colour; waits for it."""
+        info = RTQueryShadeInfo()
+        self._check(self._lib.rt_get_query_shade_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
 
     def _grid_width(self) -> int:
         """The width of the grid the rays in use were generated for: the camera's, or the last set_pose's (0: a plain ray buffer)."""

@@ -334,6 +334,35 @@ void record_tile(const Scene& sc, const Ray3D* rays, size_t first, size_t last, 
     }
 }
 
+// one work-item per ray of the caller's (CPURaytracer::QueryShade): the pixel Render() would hold, and the primary (t, index) as the
+// kernel takes them (a NaN time is a hit of shade_and_reflect only). A ray whose mask entry is negative reads as a miss. The clones
+// as render_tile's.
+template <int KERNEL>
+__attribute__((target_clones("fma", "default")))
+void shade_tile(const Scene& sc, const Ray3D* rays, const int32_t* mask, size_t first, size_t last, unsigned int max_bounces, rtm::vec4* rgba,
+                float* t, int32_t* index, uint64_t& traced, uint64_t& hits, uint64_t& primaries) {
+    for (size_t i = first; i < last; ++i) {
+        rgba[i] = rtm::vec4(0.f, 0.f, 0.f, 1.f);
+        t[i] = MAX_FLOAT;
+        index[i] = -1;
+        if (mask && mask[i] < 0) continue;
+        primaries += 1;
+        Ray ray;
+        ray.start = F4{rays[i].start.x, rays[i].start.y, rays[i].start.z, rays[i].start.w};
+        ray.direction = F4{rays[i].direction.x, rays[i].direction.y, rays[i].direction.z, rays[i].direction.w};
+        float time = MAX_FLOAT;
+        int k = -1;
+        closest(sc, ray, time, k);
+        t[i] = time;
+        float out[3] = {0.f, 0.f, 0.f};
+        if (work_item<KERNEL>(sc, rays[i], max_bounces, out, traced)) {
+            hits += 1;
+            index[i] = k;
+            rgba[i] = rtm::vec4(out[0], out[1], out[2], 1.0f);
+        }
+    }
+}
+
 // what the kernels read of an object's two matrices: the surface's copies, and rows x, y, z of mvInverse for the object loop
 void set_transform(CPURaytracer::Surface& d, CPURaytracer::Instance& h, const rtm::mat4& mv, const rtm::mat4& inv) {
     std::memcpy(d.inv, inv.data(), sizeof(d.inv));
@@ -482,6 +511,41 @@ void CPURaytracer::QueryHits(const std::vector<Ray3D>& q, const std::vector<int3
     for (size_t i = 0; i < mask.size(); ++i)
         if (mask[i] < 0) { hits.t[i] = MAX_FLOAT; hits.index[i] = -1; }  // (not traced on the GPU; here the answer is dropped)
     HitRecords(q, hits);
+}
+
+void CPURaytracer::QueryShade(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask, Shade& out) const {
+    const size_t n = q.size();
+    if (!mask.empty() && mask.size() != n) throw std::invalid_argument("QueryShade: the mask must be empty or have one entry per ray");
+    if (kernel == kHittest) throw std::invalid_argument("QueryShade: a time is not a colour (QueryClosest answers a hittest object)");
+    out.rgba.assign(n, rtm::vec4(0.f, 0.f, 0.f, 1.f));
+    out.t.assign(n, MAX_FLOAT);
+    out.index.assign(n, -1);
+    const Scene sc{instances.data(), surfaces.data(), instances.size(), Lights().data(), Lights().size()};
+    const int32_t* m = mask.empty() ? nullptr : mask.data();
+    const size_t tile = 64;
+    std::atomic<size_t> next{0};
+    std::atomic<uint64_t> total_rays{0}, total_hits{0}, total_primaries{0};
+    auto worker = [&]() {
+        uint64_t traced = 0, hits = 0, primaries = 0;
+        for (;;) {
+            const size_t first = next.fetch_add(tile);
+            if (first >= n) break;
+            const size_t last = std::min(n, first + tile);
+            if (kernel == kShade) shade_tile<1>(sc, q.data(), m, first, last, max_bounces, out.rgba.data(), out.t.data(), out.index.data(), traced, hits, primaries);
+            else shade_tile<2>(sc, q.data(), m, first, last, max_bounces, out.rgba.data(), out.t.data(), out.index.data(), traced, hits, primaries);
+        }
+        total_rays += traced;
+        total_hits += hits;
+        total_primaries += primaries;
+    };
+    const unsigned int nt = (unsigned int)std::min<size_t>(n_threads, std::max<size_t>(1, (n + tile - 1) / tile));
+    std::vector<std::thread> pool;
+    for (unsigned int k = 1; k < nt; ++k) pool.emplace_back(worker);
+    worker();
+    for (std::thread& th : pool) th.join();
+    out.n_rays = total_primaries.load();
+    out.rays_reference = total_rays.load();
+    out.hit_rays = total_hits.load();
 }
 
 cl_float4* CPURaytracer::Render() {

@@ -89,6 +89,21 @@ public:
     // (sized as `rays`; an index that is negative or beyond the objects gives zero records).
     void HitRecords(const std::vector<Ray3D>& rays, Hits& hits) const;
 
+    // Shaded queries, the same option as HIPRaytracer's (hip_raytracer.h, "shaded queries"), and the definition that runs without a
+    // GPU: per ray of the caller's own - any number - the pixel Render() would hold for it (rgba; a miss is {0,0,0,1}) and the
+    // primary (t, index) as this object's kernel takes them (a NaN time is a hit for shade_and_reflect, a miss for shade), over the
+    // CURRENT objects, materials and lights (the setters as called so far). A ray whose `mask` entry is negative reads as a miss
+    // (t = MAX_FLOAT, index -1) and is not counted. `mask` is empty or one entry per ray; std::invalid_argument otherwise and for a
+    // hittest object. Render() is not disturbed. n_rays: traced primary rays; rays_reference: every ray of their paths, as
+    // RaysTraced() counts a frame; hit_rays as HitPixels().
+    struct Shade {
+        std::vector<rtm::vec4> rgba;
+        std::vector<float> t;
+        std::vector<int32_t> index;
+        uint64_t n_rays = 0, rays_reference = 0, hit_rays = 0;
+    };
+    void QueryShade(const std::vector<Ray3D>& rays, const std::vector<int32_t>& mask, Shade& out) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

@@ -229,6 +229,53 @@ HIPRaytracer::Hits HIPRaytracer::PickHit(unsigned int i, unsigned int j) {
     return PickHits(std::vector<uint64_t>(1, (uint64_t)j * width + i));
 }
 
+namespace {
+rt_shade_t sized(HIPRaytracer::Shade& s, size_t n) {
+    s.rgba.assign(n, rtm::vec4());
+    s.t.assign(n, 0.f);
+    s.index.assign(n, -1);
+    rt_shade_t out;
+    out.rgba = reinterpret_cast<float*>(s.rgba.data());
+    out.t = s.t.data();
+    out.index = s.index.data();
+    return out;
+}
+}  // namespace
+
+HIPRaytracer::Shade HIPRaytracer::QueryShade(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask) {
+    static_assert(sizeof(Ray3D) == 32 && sizeof(rtm::vec4) == 16, "the ABI's records");
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!mask.empty() && mask.size() != q.size()) throw std::runtime_error("HIPRaytracer::QueryShade: the mask must be empty or have one entry per ray");
+    Shade s;
+    const rt_shade_t out = sized(s, q.size());
+    if (!c || rt_query_shade(c, q.data(), q.size(), mask.empty() ? nullptr : mask.data(), &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::QueryShade: ") + (c ? rt_last_error(c) : "no context"));
+    return s;
+}
+
+HIPRaytracer::Shade HIPRaytracer::PickColours(const std::vector<uint64_t>& work_items) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    Shade s;
+    const rt_shade_t out = sized(s, work_items.size());
+    if (!c || rt_query_primary_shade(c, work_items.data(), work_items.size(), &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::PickColours: ") + (c ? rt_last_error(c) : "no context"));
+    return s;
+}
+
+rtm::vec4 HIPRaytracer::PickColour(unsigned int i, unsigned int j) {
+    const rt_stats_t st = Stats();
+    const unsigned int width = st.pinhole ? st.width : pose_width;
+    if (!width) throw std::runtime_error("HIPRaytracer::PickColour: needs a camera or a pose; with a plain ray buffer use PickColours");
+    return PickColours(std::vector<uint64_t>(1, (uint64_t)j * width + i)).rgba[0];
+}
+
+rt_query_shade_info_t HIPRaytracer::QueryShadeInfo() {
+    rt_query_shade_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_query_shade_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::QueryShadeInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

@@ -120,6 +120,24 @@ public:
     Hits PickHits(const std::vector<uint64_t>& work_items);
     Hits PickHit(unsigned int i, unsigned int j);
 
+    // Shaded queries (hip_raytracer.h, "shaded queries"): the COLOUR along rays of the caller's own - any number - on the objects,
+    // materials and lights as the setters have left them, with this object's kernel, MAX_BOUNCES and arithmetic; the frame is
+    // untouched. rgba[i]: the pixel a fresh object constructed with these rays renders, bit for bit ((0,0,0,1) on a miss); t[i],
+    // index[i]: its primary hit as the kernel takes it. `mask`: empty, or one entry per ray - a negative entry is not traced and reads
+    // as a miss. PickColour(i, j): the pixel under column i, row j of the camera's or the last SetPose's grid as an unsharded,
+    // unfiltered frame holds it (std::runtime_error with a plain ray buffer: use PickColours); PickColours: of the frame's own primary
+    // rays of the work-items. Synchronous (rt_query_shade, rt_query_primary_shade); the several-GPU object asks its first shard.
+    // Throws std::runtime_error with the library's message for what it refuses (a hittest object, a scene with triangles).
+    struct Shade {
+        std::vector<rtm::vec4> rgba;
+        std::vector<float> t;
+        std::vector<int32_t> index;
+    };
+    Shade QueryShade(const std::vector<Ray3D>& rays, const std::vector<int32_t>& mask = std::vector<int32_t>());
+    Shade PickColours(const std::vector<uint64_t>& work_items);
+    rtm::vec4 PickColour(unsigned int i, unsigned int j);
+    rt_query_shade_info_t QueryShadeInfo();
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

@@ -38,6 +38,16 @@ Ray3D host_ray(const rt_ray& r) {
     return h;
 }
 
+Light host_light(const rt_light& d) {
+    LightProperties p;
+    p.ambient = rtm::vec3(d.ambient[0], d.ambient[1], d.ambient[2]);
+    p.diffuse = rtm::vec3(d.diffuse[0], d.diffuse[1], d.diffuse[2]);
+    p.specular = rtm::vec3(d.specular[0], d.specular[1], d.specular[2]);
+    Light l(p, rtm::mat4(1.f));
+    l.lightPosition = rtm::vec4(d.position[0], d.position[1], d.position[2], d.position[3]);
+    return l;
+}
+
 std::vector<Ray3D> host_rays(const rt_ray* rays, uint64_t n) {
     std::vector<Ray3D> q;
     q.reserve(n);
@@ -48,15 +58,20 @@ std::vector<Ray3D> host_rays(const rt_ray* rays, uint64_t n) {
 // The backend of the query entries: constructed with `objs_` (no lights, no frame rays), then SetTransforms(t_first,
 // transforms_[0 .. t_count)) and SetVisibility(v_first, visible_[0 .. v_count)) (NULL with a count of 0: none). The vectors the
 // backend refers to live here. make() is false for arguments it cannot serve (triangle records, a range beyond the objects, a NULL
-// array with a count).
+// array with a count). The shaded query adds what a colour needs: lights, the kernel with its MAX_BOUNCES, and SetMaterials(m_first,
+// materials_[0 .. m_count)).
 struct QueryBackend {
     std::vector<ObjectData> objects;
-    const std::vector<Light> no_lights;
+    std::vector<Light> lights;
     const std::vector<Ray3D> no_rays;
     std::unique_ptr<CPURaytracer> backend;
     bool make(const void* objs_, uint32_t n_objs, unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count,
-              const void* transforms_, uint32_t t_first, uint32_t t_count) {
-        if ((!objs_ && n_objs) || (!visible_ && v_count) || (!transforms_ && t_count)) return false;
+              const void* transforms_, uint32_t t_first, uint32_t t_count, const void* lights_ = nullptr, uint32_t n_lights = 0,
+              int kernel = 0, uint32_t max_bounces = 0, const void* materials_ = nullptr, uint32_t m_first = 0, uint32_t m_count = 0) {
+        if ((!objs_ && n_objs) || (!visible_ && v_count) || (!transforms_ && t_count) || (!lights_ && n_lights) || (!materials_ && m_count) ||
+            kernel < 0 || kernel > 2)
+            return false;
+        for (uint32_t i = 0; i < n_lights; ++i) lights.push_back(host_light(static_cast<const rt_light*>(lights_)[i]));
         const rt_object_data* objs = static_cast<const rt_object_data*>(objs_);
         objects.reserve(n_objs);
         for (uint32_t i = 0; i < n_objs; ++i) {
@@ -68,8 +83,13 @@ struct QueryBackend {
             std::memcpy(o.mvInverseTranspose.data(), d.mvInverseTranspose, sizeof(d.mvInverseTranspose));
             objects.push_back(o);
         }
-        backend.reset(new CPURaytracer(objects, no_lights, no_rays, 0, CPURaytracer::kHittest, threads));
+        backend.reset(new CPURaytracer(objects, lights, no_rays, max_bounces, static_cast<CPURaytracer::Kernel>(kernel), threads));
         try {
+            if (m_count) {
+                std::vector<Material> ms;
+                for (uint32_t i = 0; i < m_count; ++i) ms.push_back(host_material(static_cast<const rt_material*>(materials_)[i]));
+                backend->SetMaterials(m_first, ms);
+            }
             if (t_count) {
                 const rt_transform* src = static_cast<const rt_transform*>(transforms_);
                 std::vector<Transform> ts(t_count);
@@ -129,16 +149,7 @@ int cpu_rt_render_supersampled(int kernel, uint32_t max_bounces, const void* obj
     }
     std::vector<Light> ls;
     ls.reserve(n_lights);
-    for (uint32_t i = 0; i < n_lights; ++i) {
-        const rt_light& d = lights[i];
-        LightProperties p;
-        p.ambient = rtm::vec3(d.ambient[0], d.ambient[1], d.ambient[2]);
-        p.diffuse = rtm::vec3(d.diffuse[0], d.diffuse[1], d.diffuse[2]);
-        p.specular = rtm::vec3(d.specular[0], d.specular[1], d.specular[2]);
-        Light l(p, rtm::mat4(1.f));
-        l.lightPosition = rtm::vec4(d.position[0], d.position[1], d.position[2], d.position[3]);
-        ls.push_back(l);
-    }
+    for (uint32_t i = 0; i < n_lights; ++i) ls.push_back(host_light(lights[i]));
     std::vector<Ray3D> rs;
     rs.reserve(n_rays);
     for (uint64_t i = 0; i < n_rays; ++i) rs.push_back(host_ray(rays[i]));
@@ -334,6 +345,32 @@ int cpu_rt_query_hits(const void* objs_, uint32_t n_objs, const void* rays_, uin
             std::memcpy(refl[i].direction, &hits.reflected[i].direction, 16);
         }
     }
+    return 0;
+}
+
+// CPURaytracer::QueryShade through the C entry, on a backend made as cpu_rt_query's plus `lights_`, the colour `kernel` (1, 2) with
+// `max_bounces`, and SetMaterials(m_first, materials_[0 .. m_count)). `mask`: NULL or n_rays int32. rgba (n_rays x 4 floats), t and
+// index (n_rays each) may each be NULL; counts (or NULL) receives n_rays traced, rays_reference, hit_rays. Returns 0 or -1.
+int cpu_rt_query_shade(int kernel, uint32_t max_bounces, const void* objs_, uint32_t n_objs, const void* lights_, uint32_t n_lights,
+                       const void* rays_, uint64_t n_rays, const int32_t* mask, float* rgba, float* t, int32_t* index, uint64_t* counts,
+                       unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count, const void* transforms_, uint32_t t_first,
+                       uint32_t t_count, const void* materials_, uint32_t m_first, uint32_t m_count) {
+    if ((!rays_ && n_rays) || kernel < 1 || kernel > 2) return -1;
+    QueryBackend q;
+    if (!q.make(objs_, n_objs, threads, visible_, v_first, v_count, transforms_, t_first, t_count, lights_, n_lights, kernel, max_bounces,
+                materials_, m_first, m_count))
+        return -1;
+    const std::vector<Ray3D> rays = host_rays(static_cast<const rt_ray*>(rays_), n_rays);
+    CPURaytracer::Shade out;
+    try {
+        q.backend->QueryShade(rays, mask ? std::vector<int32_t>(mask, mask + n_rays) : std::vector<int32_t>(), out);
+    } catch (const std::exception&) { return -1; }
+    for (uint64_t i = 0; i < n_rays; ++i) {
+        if (rgba) std::memcpy(rgba + 4 * i, &out.rgba[i], 16);
+        if (t) t[i] = out.t[i];
+        if (index) index[i] = out.index[i];
+    }
+    if (counts) { counts[0] = out.n_rays; counts[1] = out.rays_reference; counts[2] = out.hit_rays; }
     return 0;
 }
 

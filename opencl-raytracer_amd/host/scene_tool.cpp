@@ -107,13 +107,14 @@ int main(int argc, char** argv) {
             const uint64_t item = (uint64_t)pj * (uint64_t)pw + (uint64_t)pi;
             std::vector<float> t;
             std::vector<int32_t> index;
-            rtm::vec4 point, normal;
+            rtm::vec4 point, normal, colour;
             const char* backend_name = (argc > 7 && std::strcmp(argv[7], "cpu") == 0) ? "cpu" : "hip";
             if (std::strcmp(backend_name, "hip") == 0) {
                 try {
                     HIPRaytracer backend(objects, lights, grid, 0);
                     const HIPRaytracer::Hits hit = backend.PickHits(std::vector<uint64_t>(1, item));
                     t = hit.t; index = hit.index; point = hit.point[0]; normal = hit.normal[0];
+                    colour = backend.PickColours(std::vector<uint64_t>(1, item)).rgba[0];
                 } catch (const std::exception& e) {  // (no GPU: the CPU backend's loop over the same ray - said on stderr and in the line)
                     std::fprintf(stderr, "pick: %s; using the CPU backend\n", e.what());
                     backend_name = "cpu";
@@ -124,7 +125,11 @@ int main(int argc, char** argv) {
                 CPURaytracer::Hits hit;
                 backend.QueryHits(std::vector<Ray3D>(1, grid[item]), std::vector<int32_t>(), hit);
                 t = hit.t; index = hit.index; point = hit.point[0]; normal = hit.normal[0];
+                CPURaytracer::Shade shade;
+                backend.QueryShade(std::vector<Ray3D>(1, grid[item]), std::vector<int32_t>(), shade);
+                colour = shade.rgba[0];
             }
+            std::printf("colour %.9g %.9g %.9g %.9g\n", (double)colour.x, (double)colour.y, (double)colour.z, (double)colour.w);
             std::printf("point %.9g %.9g %.9g %.9g\n", (double)point.x, (double)point.y, (double)point.z, (double)point.w);
             std::printf("normal %.9g %.9g %.9g\n", (double)normal.x, (double)normal.y, (double)normal.z);
             std::printf("pick %d %.9g %s\n", (int)index[0], (double)t[0], backend_name);

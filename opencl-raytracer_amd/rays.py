@@ -4,6 +4,8 @@ ray_verdict(rays)  what the ray scan (csrc/rt_rays.hip) reports about a ray arra
                    in float32 with the same order of operations, and the box of the origins.
 query_route(...)   which of a ray query's rays (hip_raytracer.h, "ray queries"; csrc/rt_query.hip) the grid serves and which run the
                    ordered loop over all objects: the kernel's per-ray predicate, in float32 with the same order of operations.
+query_shade_route(...)  the same for a shaded query (hip_raytracer.h, "shaded queries"; csrc/rt_query_shade.hip): the route of each
+                   primary ray, and which paths run the literal loops.
 posed_rays(...)    a pinhole grid seen through a rotation, from a common origin: the rays of a panned, tilted, rolled or
                    moved camera, in a stated float32 order, so that a caller who computes them elsewhere (on the GPU) can
                    reproduce them bit for bit. rt_set_pose / rt_generate_rays_device (hip_raytracer.h, "posed cameras";
@@ -80,6 +82,44 @@ def query_route(rays: np.ndarray, box_lo, box_hi) -> np.ndarray:
         in_domain = (dd > F(1.0e-30)) & (dd < F(1.0e30))
         inside = ((s[:, :3] >= lo) & (s[:, :3] <= hi)).all(axis=1)
     return finite & (s[:, 3] == F(1.0)) & (d[:, 3] == F(0.0)) & in_domain & inside
+
+
+def query_in_domain(rays: np.ndarray) -> np.ndarray:
+    """bool per ray: the DOMAIN part of query_route - every component finite, start.w == 1, direction.w == 0, dd in (1e-30, 1e30) -
+    without the box. float32, every operation rounded, left to right."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    d = rays["direction"].astype(F, copy=False)
+    s = rays["start"].astype(F, copy=False)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(s).all(axis=1) & np.isfinite(d).all(axis=1)
+        dd = ((d[:, 0] * d[:, 0]).astype(F) + (d[:, 1] * d[:, 1]).astype(F)).astype(F)
+        dd = (dd + (d[:, 2] * d[:, 2]).astype(F)).astype(F)
+        in_domain = (dd > F(1.0e-30)) & (dd < F(1.0e30))
+    return finite & (s[:, 3] == F(1.0)) & (d[:, 3] == F(0.0)) & in_domain
+
+
+def query_shade_route(rays: np.ndarray, box_lo, box_hi, literal: bool = False, mask=None) -> dict:
+    """The route of a shaded query's PRIMARY rays and the kind of their paths: a dict of bool arrays, one entry per ray -
+
+        "traced"   the ray is traced at all (its `mask` entry is not negative; no mask: every ray)
+        "grid"     traced, and query_route(rays, box_lo, box_hi) admits it: the grid walk finds its primary hit
+        "brute"    traced, and not: the ordered loop over all objects does
+        "literal"  traced, and its whole path runs the literal loops (the forward light loop, closest-hit shadow tests, no dead-ray
+                   elimination): the context is literal (`literal`: created with literal=True, a degenerate instance, or
+                   device_opencl's predicate on the lights) or the ray fails query_in_domain
+
+    so that n_grid, n_brute and n_literal of query_shade_info() are their sums. box_lo / box_hi as for query_route (None: the grid
+    serves no query). A primary ray that fails only the box test is "brute" and not "literal": the brute-force loop for that one ray,
+    the default path behind it. Every LATER ray of a path - shadow, reflection - is routed by query_route's predicate again, by the
+    lane that traces it; those rays start on surfaces, which lie inside the box."""
+    rays = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+    n = len(rays)
+    traced = np.ones(n, dtype=bool) if mask is None else (np.asarray(mask).reshape(-1) >= 0)
+    if len(traced) != n:
+        raise ValueError("mask: one entry per ray")
+    grid = query_route(rays, box_lo, box_hi) & traced
+    lit = (np.ones(n, dtype=bool) if literal else ~query_in_domain(rays)) & traced
+    return {"traced": traced, "grid": grid, "brute": traced & ~grid, "literal": lit}
 
 
 def posed_rays(width: int, height: int, z: float, rotation3x3, origin=(0.0, 0.0, 0.0)) -> np.ndarray:
