@@ -78,7 +78,9 @@ extern "C" {
  *      Later addition, same version: hit-record queries - rt_hits_t, rt_query_hits_device, rt_query_hits, rt_query_primary_hits.
  *      Additions only; detect by dlsym of rt_query_hits_device.
  *      Later addition, same version: compact records - rt_compact_info_t, rt_get_compact_info. Additions only; detect by dlsym of
- *      rt_get_compact_info. */
+ *      rt_get_compact_info.
+ *      Later addition, same version: G-buffer frames - rt_gbuffer_t, rt_gbuffer_info_t, rt_render_gbuffer_device, rt_render_gbuffer,
+ *      rt_get_gbuffer_info. Additions only; detect by dlsym of rt_render_gbuffer_device. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -863,7 +865,7 @@ int rt_get_query_info(rt_context* ctx, rt_query_info_t* info);
  *
  * NOT part of this call: contexts with triangles; a multi-GPU split of one query; refilling idle lanes; a whole-frame G-buffer entry
  * point (rt_generate_rays_device + rt_query_hits_device give one; a pose outside the box would send every primary ray down the
- * brute-force route); materials in the record (rt_read_materials by index has them). */
+ * brute-force route - "G-buffer frames" below is that addition); materials in the record (rt_read_materials by index has them). */
 typedef struct rt_hits_t {      /* every member may be NULL, not all of them */
     float*   t;          /* n floats      - as rt_query_closest                                   */
     int32_t* index;      /* n int32       - as rt_query_closest (the hittest rule)                */
@@ -941,6 +943,65 @@ int rt_query_shade_device(rt_context* ctx, const void* d_rays, uint64_t n, const
 int rt_query_shade(rt_context* ctx, const void* rays, uint64_t n, const int32_t* mask, const rt_shade_t* out);
 int rt_query_primary_shade(rt_context* ctx, const uint64_t* work_items, uint64_t n, const rt_shade_t* out);
 int rt_get_query_shade_info(rt_context* ctx, rt_query_shade_info_t* info);
+
+/* ---- G-buffer frames ---------------------------------------------------------------------------------------------------------------
+ * MORE THAN A COLOUR per work-item of the frame: depth, object id, hit point, surface normal and albedo of the primary hit - what a
+ * denoiser, edge-directed anti-aliasing, outlines, depth compositing with a rasteriser and deferred relighting start from. The pass is
+ * the frame pipeline's own primary round, run as a hittest frame (screen tiles, the grid, the literal, brute-force and no-grid routes,
+ * a pose outside the grid's box served from its tiles - whatever rt_render_device takes for these rays), and one streaming kernel
+ * behind it that turns (t, index) into records (csrc/rt_gbuffer.hip). It works on a context of any rt_kernel - on an RT_KERNEL_HITTEST
+ * context it is rt_render_aux plus records - and on contexts WITH triangles, which the queries refuse.
+ *
+ * Element i of every member belongs to local work-item i of the context's current shard, in the order rt_render_device writes pixels:
+ * rt_local_rays() elements, the padding of a ragged last tile included (it reads as a miss).
+ *   t, index   what rt_render_aux delivers on a fresh RT_KERNEL_HITTEST context with the current objects, flags and primary rays: the
+ *              loop's time (MAX_FLOAT on a miss, its NaN where it ends with NaN) and the winner where t < MAX_FLOAT, else -1. A hidden
+ *              object is never named.
+ *   point, normal  on a context without triangles, bit for bit what rt_query_primary_hits returns for the work-item's global index
+ *              ("hit-record queries": the arithmetic flags, the affine shortcut only for a ray of finite x, y, z, the zero box normal
+ *              per mode, RT_FLAG_FAST_PHONG playing no part). For a triangle winner: point = t * d + s per component (one fma in the
+ *              fused modes, product then sum under RT_FLAG_UNFUSED), normal = normalize(e1 x e2), never contracted
+ *              (hits.hit_records is the executable definition). All-zero bytes where index == -1.
+ *   albedo     where index >= 0: (diffuse.r, diffuse.g, diffuse.b, 1) of rt_read_materials(ctx, .., index, 1), moved, not computed
+ *              with (a NaN or an inf passes through); zero bytes where index == -1.
+ * The pass sees the context as the setters left it - camera, pose, ray buffer, shard, materials, transforms, visibility (lights play
+ * no part) - and leaves the FRAME alone: a render before and after it is the same frame, aux buffers set for the next render stay set
+ * for the next render, and rt_get_stats, rt_timing_* and last_kernel_ms keep describing renders (the pass has event pairs of its own:
+ * rt_get_gbuffer_info).
+ * Supersampling. Records are per SAMPLE, as rt_local_rays() counts them; nothing is filtered (a mean of ids or normals means nothing).
+ * Unlike aux buffers, the pass is accepted with any factor.
+ *
+ * rt_render_gbuffer_device: `d_out` points to a HOST struct, read during the call, whose members are device pointers on the context's
+ * device (each may be NULL, not all). point, normal and albedo 16-BYTE ALIGNED; t and index 4-byte aligned. Stream semantics are
+ * rt_render_device's: NULL is the legacy default stream, the large-scene path may synchronise once per batch of rounds, and the record
+ * kernel is enqueued behind the trace on the same stream with no further host synchronisation. (t, index) the caller did not ask for
+ * are staged in context-owned, grow-only buffers that rt_destroy frees: nothing is allocated after the first pass of a given size.
+ * That staging, the pass's discard buffer for the hittest frame's own float and the frame's state buffers are the CONTEXT's: two passes,
+ * or a pass and a render, of one context on different streams must be ordered by the caller, as two renders must.
+ * rt_render_gbuffer: the host twin, synchronous, on the context's stream; members of `out` are host arrays, staged through
+ * context-owned buffers; only the requested members are copied out.
+ * rt_get_gbuffer_info: the LAST pass; waits for it. RT_ERR_STATE before the first pass.
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: a NULL struct, all members NULL, a misaligned device member. RT_ERR_STATE: no
+ * primary rays yet. rt_local_rays() == 0 returns RT_OK with nothing launched.
+ *
+ * NOT part of this call (each would be its own addition): _multi forms (rt_multi_context(m, r) gives each shard's); byte outputs; a
+ * reflected ray (rt_query_hits_device has it); the passes of rt_render's large frames (the pass is one launch over the shard); lifting
+ * the queries' refusal of contexts with triangles. */
+typedef struct rt_gbuffer_t {   /* every member may be NULL, not all of them; rt_local_rays() elements each */
+    float*   t;        /* float   - primary hit time, the hittest rule (MAX_FLOAT on a miss, the loop's NaN where it ends with NaN) */
+    int32_t* index;    /* int32   - winner where t < MAX_FLOAT, else -1 */
+    float*   point;    /* float4  - HitRecord.intersection, as rt_hits_t::point */
+    float*   normal;   /* float4  - HitRecord.normal in xyz, w = 0, as rt_hits_t::normal */
+    float*   albedo;   /* float4  - the winner's diffuse rgb as rt_read_materials returns it, w = 1 */
+} rt_gbuffer_t;
+typedef struct rt_gbuffer_info_t {
+    uint64_t n_items, hits;                 /* work-items of the pass (padding included), those with index >= 0 */
+    double   trace_ms, records_ms;          /* event pairs around the primary round and around the record kernel */
+    uint32_t wavefront, reserved;
+} rt_gbuffer_info_t;
+int rt_render_gbuffer_device(rt_context* ctx, const rt_gbuffer_t* d_out, void* hip_stream);
+int rt_render_gbuffer(rt_context* ctx, const rt_gbuffer_t* out);          /* host arrays, synchronous */
+int rt_get_gbuffer_info(rt_context* ctx, rt_gbuffer_info_t* info);        /* RT_ERR_STATE before the first pass */
 
 void rt_destroy(rt_context* ctx);
 

@@ -61,6 +61,9 @@ def load_library():
             lib.cpu_rt_query_shade.restype = ctypes.c_int
             lib.cpu_rt_query_shade.argtypes = [ctypes.c_int, u32, vp, u32, vp, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_uint,
                                                vp, u32, u32, vp, u32, u32, vp, u32, u32]
+        if hasattr(lib, "cpu_rt_render_gbuffer"):
+            lib.cpu_rt_render_gbuffer.restype = ctypes.c_int
+            lib.cpu_rt_render_gbuffer.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_uint, vp, u32, u32, vp, u32, u32, vp, u32, u32]
         _lib = lib
     return _lib
 
@@ -255,6 +258,38 @@ class CPURaytracer:
             raise ValueError("cpu_rt_query_shade: unsupported arguments (triangle records are a HIP-backend extension)")
         self.shade_info = {"n_rays": int(counts[0]), "rays_reference": int(counts[1]), "hit_rays": int(counts[2])}
         return {"rgba": rgba, "t": t, "index": index}
+
+    # -- G-buffer frames: CPURaytracer::RenderGBuffer, the option HIPRaytracer.render_gbuffer is on the GPU ----------------------------
+    def current_rays(self) -> np.ndarray:
+        """The primary rays the next Render() traces: set_rays' / set_pose's (rays.posed_rays), else the constructor's."""
+        if self.new_rays is not None:
+            return self.new_rays
+        if self.pose is not None:
+            from . import rays as RY
+            w, h, z, m, o = self.pose
+            return RY.posed_rays(w, h, z, m.reshape(3, 3), o)
+        return self.rays
+
+    def render_gbuffer(self):
+        """The primary hit of every ray of this object (set_rays / set_pose as set so far), in ray order: a dict of "t" float32[n] and
+        "index" int32[n] (query_closest's), "point" and "normal" float32[n, 4] (query_hits'), and "albedo" float32[n, 4] - the
+        winner's diffuse rgb (set_materials as set so far) with w = 1; zero records where index is -1. QueryHits over the primary
+        rays plus the material lookup: the definition of HIPRaytracer.render_gbuffer (unsharded, in the default arithmetic) that runs
+        without a GPU. No triangles, as everywhere in this backend."""
+        rays = np.ascontiguousarray(self.current_rays(), dtype=RAY_DTYPE)
+        n = len(rays)
+        t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+        point, normal, albedo = (np.zeros((n, 4), dtype=np.float32) for _ in range(3))
+
+        def ptr(a):
+            return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+        vis, xf, mats = self.visible, self.transforms, self.materials
+        rc = self._lib.cpu_rt_render_gbuffer(ptr(self.objects), len(self.objects), ptr(rays), n, ptr(t), ptr(index), ptr(point), ptr(normal),
+                                             ptr(albedo), self.threads, ptr(vis), 0, len(vis) if vis is not None else 0,
+                                             ptr(xf), 0, len(xf) if xf is not None else 0, ptr(mats), 0, len(mats) if mats is not None else 0)
+        if rc != 0:
+            raise ValueError("cpu_rt_render_gbuffer: unsupported arguments (triangle records are a HIP-backend extension)")
+        return {"t": t, "index": index, "point": point, "normal": normal, "albedo": albedo}
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)

@@ -946,6 +946,9 @@ void rt_destroy(rt_context* c) {
     if (c->query_shade_made) (void)hipEventSynchronize(c->ev_query_shade[1]);
     if (c->d_query_shade_counters) (void)hipFree(c->d_query_shade_counters);
     for (hipEvent_t ev : c->ev_query_shade) if (ev) (void)hipEventDestroy(ev);
+    if (c->gbuffer_made) (void)hipEventSynchronize(c->ev_gb[3]);  // (a device-form pass may still run on the caller's stream)
+    if (c->d_gb_hits) (void)hipFree(c->d_gb_hits);
+    for (hipEvent_t ev : c->ev_gb) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_xf) if (ev) (void)hipEventDestroy(ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);

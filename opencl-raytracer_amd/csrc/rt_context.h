@@ -19,6 +19,7 @@
 #include "rt_transforms.h"
 #include "rt_visibility.h"
 #include "rt_query.h"
+#include "rt_gbuffer.h"
 #include "rt_compact.h"
 
 #include <hip/hip_runtime.h>
@@ -282,6 +283,16 @@ struct rt_context {
     rt::QueryShadeCounters* d_query_shade_counters = nullptr;
     hipEvent_t ev_query_shade[2] = {};
     bool query_shade_made = false;
+    // G-buffer frames (rt_render_gbuffer*, rt_render.cpp): the staging of (t, index) where the caller did not ask for them and of the
+    // host twin's records (grow-only), the hit count the record kernel adds to, two event pairs of its own - [0], [1] around the
+    // primary round, [2], [3] around the record kernel - and what rt_get_gbuffer_info reports of the last pass. The hittest frame's
+    // `out` (MAX_FLOAT for a NaN time, where t keeps the NaN) goes to d_gb_out, which nothing reads.
+    rt::host::Buffer d_gb_t, d_gb_index, d_gb_out, d_gb_point, d_gb_normal, d_gb_albedo;
+    unsigned long long* d_gb_hits = nullptr;
+    hipEvent_t ev_gb[4] = {};
+    bool gbuffer_made = false;
+    uint64_t gb_items = 0;
+    bool gb_wavefront = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -483,6 +494,10 @@ struct PatchTrace {
 private:
     int mark(int k, hipStream_t stream);
 };
+// rt_query_host.cpp: the records, the arithmetic mode and the primary rays as a query reads them; the G-buffer pass reads the same
+rt::Scene query_scene(const rt_context* c);
+int query_arith(const rt_context* c);
+rt::QueryCamera query_camera(const rt_context* c);
 // rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched

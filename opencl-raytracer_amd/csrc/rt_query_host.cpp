@@ -8,6 +8,44 @@
 #include "rt_context.h"
 
 namespace rt::host {
+
+// shared with the G-buffer pass (rt_render.cpp), declared in rt_context.h
+// the records as do_launch hands them to a frame (rt_api.cpp); a query reads the traversal's part of them
+rt::Scene query_scene(const rt_context* c) {
+    rt::Scene s = {};
+    s.pairs = c->d_pairs;
+    s.n_pairs = c->n_pairs;
+    s.hot = c->d_hot;
+    s.bounds = c->d_bounds;
+    s.cold = c->d_cold;
+    s.objrec = c->d_objrec;
+    s.lights = c->d_lights;
+    s.n_objs = c->n_objs;
+    s.n_lights = c->n_lights;
+    s.affine = (c->affine_w && !c->has_triangles) ? 1u : 0u;
+    s.nan_winner = c->nan_winner;
+    s.nan_winner_sphere = c->nan_winner_sphere ? 1u : 0u;
+    return s;
+}
+
+// RT_FLAG_FAST_PHONG does not touch t: the mode is the two arithmetic flags'
+int query_arith(const rt_context* c) {
+    return (c->flags & RT_FLAG_DEVICE_OPENCL) ? rt::kDeviceCL : ((c->flags & RT_FLAG_UNFUSED) ? rt::kUnfused : rt::kFused);
+}
+
+// the context's own primary rays, for rt_query_primary / rt_query_primary_hits
+rt::QueryCamera query_camera(const rt_context* c) {
+    rt::QueryCamera cam = {};
+    cam.rays = c->pinhole ? nullptr : c->d_rays;
+    cam.pinhole = c->pinhole ? 1u : 0u;
+    cam.width = c->width ? c->width : 1;
+    cam.half_w = (float)c->width / 2.0f;
+    cam.half_h = (float)c->height / 2.0f;
+    cam.height_f = (float)c->height;
+    cam.z = c->z;
+    return cam;
+}
+
 namespace {
 
 // rt_context::grid_box_lo / hi as floats that lie INSIDE the double box: lo rounded up, hi rounded down
@@ -41,29 +79,6 @@ rt::QueryBox query_box(const rt_context* c) {
     return b;
 }
 
-// the records as do_launch hands them to a frame (rt_api.cpp); a query reads the traversal's part of them
-rt::Scene query_scene(const rt_context* c) {
-    rt::Scene s = {};
-    s.pairs = c->d_pairs;
-    s.n_pairs = c->n_pairs;
-    s.hot = c->d_hot;
-    s.bounds = c->d_bounds;
-    s.cold = c->d_cold;
-    s.objrec = c->d_objrec;
-    s.lights = c->d_lights;
-    s.n_objs = c->n_objs;
-    s.n_lights = c->n_lights;
-    s.affine = (c->affine_w && !c->has_triangles) ? 1u : 0u;
-    s.nan_winner = c->nan_winner;
-    s.nan_winner_sphere = c->nan_winner_sphere ? 1u : 0u;
-    return s;
-}
-
-// RT_FLAG_FAST_PHONG does not touch t: the mode is the two arithmetic flags'
-int query_arith(const rt_context* c) {
-    return (c->flags & RT_FLAG_DEVICE_OPENCL) ? rt::kDeviceCL : ((c->flags & RT_FLAG_UNFUSED) ? rt::kUnfused : rt::kFused);
-}
-
 int refuse_triangles(rt_context* c) {
     if (c->has_triangles)
         return fail(c, RT_ERR_STATE, "ray queries on a context with triangle records: the ordered loop over the pair stream does not know type 2, "
@@ -85,19 +100,6 @@ int ensure_query_support(rt_context* c) {
     for (hipEvent_t& e : c->ev_query)
         if (!e) RT_HIP(c, hipEventCreate(&e));
     return RT_OK;
-}
-
-// the context's own primary rays, for rt_query_primary / rt_query_primary_hits
-rt::QueryCamera query_camera(const rt_context* c) {
-    rt::QueryCamera cam = {};
-    cam.rays = c->pinhole ? nullptr : c->d_rays;
-    cam.pinhole = c->pinhole ? 1u : 0u;
-    cam.width = c->width ? c->width : 1;
-    cam.half_w = (float)c->width / 2.0f;
-    cam.half_h = (float)c->height / 2.0f;
-    cam.height_f = (float)c->height;
-    cam.z = c->z;
-    return cam;
 }
 
 enum class Kind { Closest, Occluded, Primary };

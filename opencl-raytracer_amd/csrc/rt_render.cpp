@@ -64,14 +64,10 @@ static int ensure_wavefront(rt_context* c, const Shard& sh) {
 
 // One launch: the work-items of shard `sh` of the context's rays into d_out. The shard is an argument - the context's own
 // (rt_set_shard) or one pass of render_in_passes - and nothing here, nor settle_outside_pose and refresh_screen_tiles below it,
-// reads the context's.
-static int do_launch(rt_context* c, const Shard& sh, void* d_out, hipStream_t stream, bool count) {
-    if (sh.n_local == 0) {  // empty launch: nothing to render, nothing to time
-        if (count) c->counters = rt::Counters{};
-        c->aux_t = nullptr;
-        c->aux_index = nullptr;
-        return RT_OK;
-    }
+// reads the context's. So are the kernel number, the aux pair and the event pair around the kernels: a frame passes the context's
+// (launch_frame), the G-buffer pass RT_KERNEL_HITTEST with arrays and events of its own. sh.n_local > 0.
+static int do_launch(rt_context* c, const Shard& sh, int kernel, void* d_out, float* aux_t, int32_t* aux_index, hipEvent_t ev_begin,
+                     hipEvent_t ev_end, hipStream_t stream, bool count) {
     if (!c->pinhole && !c->have_rays)
         return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
     rt::RenderParams p;
@@ -121,8 +117,8 @@ static int do_launch(rt_context* c, const Shard& sh, void* d_out, hipStream_t st
     }
     p.max_bounces = c->max_bounces;
     p.out = d_out;
-    p.aux_t = c->aux_t;
-    p.aux_index = c->aux_index;
+    p.aux_t = aux_t;
+    p.aux_index = aux_index;
     p.counters = c->d_counters;
 
     RT_DEVICE(c);
@@ -168,14 +164,27 @@ static int do_launch(rt_context* c, const Shard& sh, void* d_out, hipStream_t st
         }
     }
     if (count) RT_HIP(c, hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters), stream));
-    const uint32_t slot = c->ev_count % kTimingSlots;
-    RT_HIP(c, hipEventRecord(c->ev_begin[slot], stream));
+    RT_HIP(c, hipEventRecord(ev_begin, stream));
     hipError_t e;
     const int arith = (c->flags & RT_FLAG_DEVICE_OPENCL) ? rt::kDeviceCL : ((c->flags & RT_FLAG_UNFUSED) ? rt::kUnfused : rt::kFused);
-    if (c->last_wavefront) e = rt::launch_wavefront(p, c->kernel, arith, count, c->wf, stream, &c->last_rounds);
-    else e = rt::launch_render(p, c->kernel, arith, count, stream);
+    if (c->last_wavefront) e = rt::launch_wavefront(p, kernel, arith, count, c->wf, stream, &c->last_rounds);
+    else e = rt::launch_render(p, kernel, arith, count, stream);
     if (e != hipSuccess) return fail_hip(c, e, "kernel launch");
-    RT_HIP(c, hipEventRecord(c->ev_end[slot], stream));
+    RT_HIP(c, hipEventRecord(ev_end, stream));
+    return RT_OK;
+}
+
+// A frame's launch: the context's kernel, its pending aux pair and the next timing slot.
+static int launch_frame(rt_context* c, const Shard& sh, void* d_out, hipStream_t stream, bool count) {
+    if (sh.n_local == 0) {  // empty launch: nothing to render, nothing to time
+        if (count) c->counters = rt::Counters{};
+        c->aux_t = nullptr;
+        c->aux_index = nullptr;
+        return RT_OK;
+    }
+    const uint32_t slot = c->ev_count % kTimingSlots;
+    const int rc = do_launch(c, sh, c->kernel, d_out, c->aux_t, c->aux_index, c->ev_begin[slot], c->ev_end[slot], stream, count);
+    if (rc) return rc;
     c->ev_count += 1;
     // aux buffers apply to one render only
     c->aux_t = nullptr;
@@ -208,7 +217,7 @@ static int resolve_on(rt_context* c, const void* d_src, uint64_t n_samples, int 
 // d_dst, and floats are traced straight into d_dst (d_stage is not looked at).
 static int render_pixels(rt_context* c, const Shard& sh, void* d_stage, int format, void* d_dst, hipStream_t stream) {
     const bool staged = c->ss > 1 || format;
-    const int rc = do_launch(c, sh, staged ? d_stage : d_dst, stream, false);
+    const int rc = launch_frame(c, sh, staged ? d_stage : d_dst, stream, false);
     if (rc || !staged || sh.n_local == 0) return rc;
     return c->ss > 1 ? resolve_on(c, d_stage, sh.n_local, format, d_dst, stream) : pack_on(c, d_stage, sh.n_local, format, d_dst, stream);
 }
@@ -330,6 +339,64 @@ static int render_to_host(rt_context* c, int format, const void** out) {
     if (bytes) RT_HIP(c, hipMemcpyAsync(h_pixels.p, d_pixels.p, bytes, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(c, hipStreamSynchronize(c->stream));  // Render() is synchronous (OpenCLRaytracer.cpp:94)
     *out = h_pixels.p;
+    return RT_OK;
+}
+
+// ---- G-buffer frames (hip_raytracer.h) -----------------------------------------------------------------------------------------------
+// what both forms refuse of the output struct; `device`: its members are device pointers, whose alignment the kernels' stores need
+static int check_gbuffer(rt_context* c, const rt_gbuffer_t* o, bool device) {
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    if (!o->t && !o->index && !o->point && !o->normal && !o->albedo) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
+    if (!device) return RT_OK;
+    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(o->point) | reinterpret_cast<uintptr_t>(o->normal) | reinterpret_cast<uintptr_t>(o->albedo)) & 15u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "point, normal and albedo must be 16-byte aligned");
+    return RT_OK;
+}
+
+static int check_gbuffer_rays(rt_context* c) {
+    if (!c->pinhole && !c->have_rays)
+        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    return RT_OK;
+}
+
+// One pass over the context's shard on `stream`; the members of `o` are device pointers (each may be null). The primary round of the
+// frame pipeline as a hittest frame - t is its aux_t (the loop's value, a NaN included), index its aux_index; the frame's own float
+// goes to a buffer of the pass's own that nobody reads - then the record kernel behind it on the same stream. Nothing of the frame's state is left changed: the pending
+// aux pair, the timing slots and the route rt_get_stats reports stay the renders'. c->shard.n_local > 0.
+static int enqueue_gbuffer(rt_context* c, const rt_gbuffer_t& o, hipStream_t stream) {
+    const Shard& sh = c->shard;
+    const size_t n = (size_t)sh.n_local;
+    if (!c->d_gb_hits) RT_HIP(c, hipMalloc((void**)&c->d_gb_hits, sizeof(unsigned long long)));
+    for (hipEvent_t& e : c->ev_gb)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    float* d_t = o.t;
+    int32_t* d_index = o.index;
+    c->gbuffer_made = false;  // until this pass is enqueued whole: rt_get_gbuffer_info never pairs events of two passes
+    int rc = c->d_gb_out.grow(c, n * sizeof(float));
+    if (rc == RT_OK && !d_t) rc = c->d_gb_t.grow(c, n * sizeof(float));
+    if (rc == RT_OK && !d_index) rc = c->d_gb_index.grow(c, n * sizeof(int32_t));
+    if (rc) return rc;
+    if (!d_t) d_t = static_cast<float*>(c->d_gb_t.p);
+    if (!d_index) d_index = static_cast<int32_t*>(c->d_gb_index.p);
+    const bool frame_wavefront = c->last_wavefront;
+    const uint32_t frame_rounds = c->last_rounds;
+    rc = do_launch(c, sh, RT_KERNEL_HITTEST, c->d_gb_out.p, d_t, d_index, c->ev_gb[0], c->ev_gb[1], stream, false);
+    c->gb_wavefront = c->last_wavefront;
+    c->last_wavefront = frame_wavefront;
+    c->last_rounds = frame_rounds;
+    if (rc) return rc;
+    RT_HIP(c, hipMemsetAsync(c->d_gb_hits, 0, sizeof(unsigned long long), stream));
+    RT_HIP(c, hipEventRecord(c->ev_gb[2], stream));
+    const rt::GBufferShard shard{c->n_rays, sh.n_local, sh.tile_rays ? sh.tile_rays : 1, sh.rank, sh.world};
+    const rt::GBufferRecords rec{d_t, d_index, reinterpret_cast<float4*>(o.point), reinterpret_cast<float4*>(o.normal),
+                                 reinterpret_cast<float4*>(o.albedo)};
+    const hipError_t e = rt::launch_gbuffer_records(query_scene(c), query_camera(c), shard, query_arith(c), rec, c->d_gb_hits, stream);
+    if (e != hipSuccess) return fail_hip(c, e, "G-buffer record launch");
+    RT_HIP(c, hipEventRecord(c->ev_gb[3], stream));
+    c->gbuffer_made = true;
+    c->gb_items = sh.n_local;
     return RT_OK;
 }
 
@@ -455,7 +522,7 @@ int rt_render_aux(rt_context* c, float* hit_t, int32_t* hit_index) {
     }
     c->aux_t = d_t;
     c->aux_index = d_i;
-    rc = do_launch(c, c->shard, c->d_out.p, c->stream, false);
+    rc = launch_frame(c, c->shard, c->d_out.p, c->stream, false);
     hipError_t e = hipSuccess;
     if (rc == RT_OK) e = hipStreamSynchronize(c->stream);
     if (rc == RT_OK && e == hipSuccess && hit_t && n) e = hipMemcpy(hit_t, d_t, n * 4, hipMemcpyDeviceToHost);
@@ -472,7 +539,7 @@ int rt_count_rays(rt_context* c) {
     RT_DEVICE(c);
     int rc = c->d_out.grow(c, (size_t)c->shard.n_local * elem_bytes(c));
     if (rc) return rc;
-    rc = do_launch(c, c->shard, c->d_out.p, c->stream, true);
+    rc = launch_frame(c, c->shard, c->d_out.p, c->stream, true);
     if (rc) return rc;
     if (c->shard.n_local == 0) return RT_OK;
     RT_HIP(c, hipStreamSynchronize(c->stream));
@@ -489,6 +556,68 @@ int rt_count_rays(rt_context* c) {
                          (double)v[3] / v[0], (double)v[4] / v[0], (double)v[5] / v[0], (double)v[2] / v[0], (double)v[2] / (v[1] ? v[1] : 1));
         }
     }
+    return RT_OK;
+}
+
+// NULL is the legacy default stream, as for rt_render_device
+int rt_render_gbuffer_device(rt_context* c, const rt_gbuffer_t* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_gbuffer(c, d_out, true)) return rc;
+    if (c->shard.n_local == 0) return RT_OK;
+    if (const int rc = check_gbuffer_rays(c)) return rc;
+    RT_DEVICE(c);
+    return enqueue_gbuffer(c, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host twin: every requested member staged in a context-owned buffer, on the context's stream; synchronous
+int rt_render_gbuffer(rt_context* c, const rt_gbuffer_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_gbuffer(c, out, false)) return rc;
+    if (c->shard.n_local == 0) return RT_OK;
+    if (const int rc = check_gbuffer_rays(c)) return rc;
+    RT_DEVICE(c);
+    const size_t n = (size_t)c->shard.n_local;
+    int rc = RT_OK;
+    if (out->t) rc = c->d_gb_t.grow(c, n * sizeof(float));
+    if (rc == RT_OK && out->index) rc = c->d_gb_index.grow(c, n * sizeof(int32_t));
+    if (rc == RT_OK && out->point) rc = c->d_gb_point.grow(c, n * 16);
+    if (rc == RT_OK && out->normal) rc = c->d_gb_normal.grow(c, n * 16);
+    if (rc == RT_OK && out->albedo) rc = c->d_gb_albedo.grow(c, n * 16);
+    if (rc) return rc;
+    rt_gbuffer_t d = {};
+    d.t = out->t ? static_cast<float*>(c->d_gb_t.p) : nullptr;
+    d.index = out->index ? static_cast<int32_t*>(c->d_gb_index.p) : nullptr;
+    d.point = out->point ? static_cast<float*>(c->d_gb_point.p) : nullptr;
+    d.normal = out->normal ? static_cast<float*>(c->d_gb_normal.p) : nullptr;
+    d.albedo = out->albedo ? static_cast<float*>(c->d_gb_albedo.p) : nullptr;
+    hipStream_t stream = c->stream;
+    rc = enqueue_gbuffer(c, d, stream);
+    if (rc) return rc;
+    if (out->t) RT_HIP(c, hipMemcpyAsync(out->t, d.t, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out->index) RT_HIP(c, hipMemcpyAsync(out->index, d.index, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (out->point) RT_HIP(c, hipMemcpyAsync(out->point, d.point, n * 16, hipMemcpyDeviceToHost, stream));
+    if (out->normal) RT_HIP(c, hipMemcpyAsync(out->normal, d.normal, n * 16, hipMemcpyDeviceToHost, stream));
+    if (out->albedo) RT_HIP(c, hipMemcpyAsync(out->albedo, d.albedo, n * 16, hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+int rt_get_gbuffer_info(rt_context* c, rt_gbuffer_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->gbuffer_made) return fail(c, RT_ERR_STATE, "rt_get_gbuffer_info: no G-buffer pass has been made on this context");
+    RT_DEVICE(c);
+    RT_HIP(c, hipEventSynchronize(c->ev_gb[3]));  // the last pass's stream, up to the record kernel
+    unsigned long long hits = 0;
+    RT_HIP(c, hipMemcpy(&hits, c->d_gb_hits, sizeof(hits), hipMemcpyDeviceToHost));
+    float trace = 0.f, records = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&trace, c->ev_gb[0], c->ev_gb[1]));
+    RT_HIP(c, hipEventElapsedTime(&records, c->ev_gb[2], c->ev_gb[3]));
+    info->n_items = c->gb_items;
+    info->hits = hits;
+    info->trace_ms = (double)trace;
+    info->records_ms = (double)records;
+    info->wavefront = c->gb_wavefront ? 1u : 0u;
+    info->reserved = 0;
     return RT_OK;
 }
 

@@ -255,6 +255,11 @@ class ShardedHIPRaytracer:
         torch.cuda.synchronize(self.device)
         self.rt.set_transforms(transforms, first)
 
+    def render_gbuffer(self, want=("t", "index", "point", "normal", "albedo"), out=None):
+        """The G-buffer of THIS rank's tiles (HIPRaytracer.render_gbuffer): rt.local_rays elements per member, in the order of the
+        rank's pixels (samples, with supersample=s). The per-rank form: nothing is exchanged."""
+        return self.rt.render_gbuffer(want, out)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

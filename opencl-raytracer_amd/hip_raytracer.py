@@ -51,6 +51,7 @@ EXPORTS = [
     "rt_query_hits_device", "rt_query_hits", "rt_query_primary_hits",
     "rt_query_shade_device", "rt_query_shade", "rt_query_primary_shade", "rt_get_query_shade_info",
     "rt_get_compact_info",
+    "rt_render_gbuffer_device", "rt_render_gbuffer", "rt_get_gbuffer_info",
 ]
 
 
@@ -190,6 +191,25 @@ class RTQueryShadeInfo(ctypes.Structure):
 
 
 SHADE_FIELDS = ("rgba", "t", "index")
+
+
+class RTGBuffer(ctypes.Structure):
+    """rt_gbuffer_t: five pointers, each may be NULL (not all)."""
+    _fields_ = [("t", ctypes.c_void_p), ("index", ctypes.c_void_p), ("point", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("albedo", ctypes.c_void_p)]
+
+
+class RTGBufferInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_items", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("trace_ms", ctypes.c_double), ("records_ms", ctypes.c_double),
+        ("wavefront", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_ if n != "reserved"}
+
+
+GBUFFER_FIELDS = ("t", "index", "point", "normal", "albedo")
 
 _lib = None
 
@@ -381,6 +401,13 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
     if hasattr(lib, "rt_get_compact_info"):  # (the same: a build from before compact records)
         lib.rt_get_compact_info.restype = i32
         lib.rt_get_compact_info.argtypes = [vp, ctypes.POINTER(RTCompactInfo)]
+    if hasattr(lib, "rt_render_gbuffer_device"):  # (the same: a build from before G-buffer frames)
+        lib.rt_render_gbuffer_device.restype = i32
+        lib.rt_render_gbuffer_device.argtypes = [vp, ctypes.POINTER(RTGBuffer), vp]
+        lib.rt_render_gbuffer.restype = i32
+        lib.rt_render_gbuffer.argtypes = [vp, ctypes.POINTER(RTGBuffer)]
+        lib.rt_get_gbuffer_info.restype = i32
+        lib.rt_get_gbuffer_info.argtypes = [vp, ctypes.POINTER(RTGBufferInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -617,6 +644,43 @@ def _pick_shade(lib, ctx, work_items, want):
     n = int(items.shape[0])
     res, shade = _host_shade(n, _shade_wanted(want))
     _check_rc(lib, ctx, lib.rt_query_primary_shade(ctx, _ptr(items), n, ctypes.byref(shade)))
+    return res
+
+
+def _gbuffer_wanted(want):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in GBUFFER_FIELDS for w in want):
+        raise ValueError(f"want: a non-empty selection of {GBUFFER_FIELDS}")
+    return want
+
+
+def _render_gbuffer(lib, ctx, n: int, want, out, device: int):
+    """HIPRaytracer.render_gbuffer: numpy arrays through rt_render_gbuffer, or - with `out` - torch tensors through
+    rt_render_gbuffer_device on torch's current stream. n: the context's local work-items."""
+    want = _gbuffer_wanted(want)
+    if out is not None:
+        import torch
+        shapes = {"t": ((n,), torch.float32), "index": ((n,), torch.int32), "point": ((n, 4), torch.float32),
+                  "normal": ((n, 4), torch.float32), "albedo": ((n, 4), torch.float32)}
+        res, stream = {}, 0
+        for w in want:
+            shape, dtype = shapes[w]
+            given = out.get(w)
+            if not _is_tensor(given) or not given.is_cuda or given.dtype != dtype or not given.is_contiguous() or \
+                    given.numel() != int(np.prod(shape)) or (given.device.index is not None and given.device.index != device):
+                raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the context's device")
+            res[w] = given
+            stream = _current_stream_of(given)
+        if n:
+            gb = RTGBuffer(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_render_gbuffer_device(ctx, ctypes.byref(gb), ctypes.c_void_p(stream) if stream else None))
+        return res
+    shapes = {"t": ((n,), np.float32), "index": ((n,), np.int32), "point": ((n, 4), np.float32), "normal": ((n, 4), np.float32),
+              "albedo": ((n, 4), np.float32)}
+    res = {w: np.zeros(*shapes[w]) for w in want}
+    if n:
+        gb = RTGBuffer(**{w: a.ctypes.data for w, a in res.items()})
+        _check_rc(lib, ctx, lib.rt_render_gbuffer(ctx, ctypes.byref(gb)))
     return res
 
 
@@ -1133,6 +1197,24 @@ class HIPRaytracer:
         rays_traced, rays_reference, object_tests and device_ms of the last query_shade / pick_colour; waits for it."""
         info = RTQueryShadeInfo()
         self._check(self._lib.rt_get_query_shade_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
+
+    # -- G-buffer frames (hip_raytracer.h: depth, id, point, normal and albedo per work-item; the frame is untouched) ------------------
+    def render_gbuffer(self, want=GBUFFER_FIELDS, out=None):
+        """The primary hit of every local work-item (rt_render_gbuffer / rt_render_gbuffer_device): a dict of the members named in
+        `want`, local_rays elements each, in the order render_device writes pixels - "t" float32[n] and "index" int32[n] as a fresh
+        hittest context's render_aux(); "point" and "normal" float32[n, 4] as query_hits / pick_hit give them for the work-item (on a
+        triangle winner: hits.hit_records' type-2 branch); "albedo" float32[n, 4], the winner's diffuse rgb with w = 1. Zero records
+        where index is -1. Returns numpy arrays; with `out` - a dict of contiguous torch tensors on the context's device, one per
+        wanted member - the pass is enqueued on torch's current stream with no host synchronisation and `out`'s tensors are
+        returned. Per SAMPLE under supersampling; works on any kernel and on contexts with triangles.
+        CPURaytracer.render_gbuffer is the definition that runs without a GPU."""
+        return _render_gbuffer(self._lib, self._ctx, self.local_rays, want, out, self._device)
+
+    def gbuffer_info(self) -> dict:
+        """rt_get_gbuffer_info: n_items, hits, trace_ms, records_ms and wavefront of the last render_gbuffer; waits for it."""
+        info = RTGBufferInfo()
+        self._check(self._lib.rt_get_gbuffer_info(self._ctx, ctypes.byref(info)))
         return info.as_dict()
 
     def _grid_width(self) -> int:

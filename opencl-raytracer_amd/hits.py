@@ -3,7 +3,9 @@
 hit_records(objects, rays, t, index): what raycast() leaves in the HitRecord of winner index[i] at time t[i], and the next ray of the
 reflection chain, in float32 with ONE IEEE operation per step: the association is that of row4, materialise, normalize3 and
 reflection_ray in csrc/rt_device.h, and nothing is fused - so this is the executable definition of the record stage under
-RT_FLAG_UNFUSED, bit for bit (HIPRaytracer(..., fused=False).query_hits). The default mode contracts the multiply-adds the OpenCL
+RT_FLAG_UNFUSED, bit for bit (HIPRaytracer(..., fused=False).query_hits). A triangle winner (type 2, the extension of DESIGN.md
+section 11; only a G-buffer frame delivers one, the queries refuse such contexts) takes materialise()'s type-2 branch: the point on
+the ray itself and normalize(e1 x e2) of the record's edges, `fused=True` giving the point's single rounding. The default mode contracts the multiply-adds the OpenCL
 front-end contracts (CPURaytracer.query_hits is its definition), RT_FLAG_DEVICE_OPENCL additionally uses the device's normalize().
 
 chain(query, rays, bounces): follow a reflection chain with the mask, so that a miss is never traced again.
@@ -42,9 +44,39 @@ def _normalize3(x, y, z):
     return x / length, y / length, z / length
 
 
-def hit_records(objects, rays, t, index, affine=None):
+def _fma(a, b, c):
+    """fl(a * b + c) with ONE rounding, for float32 arrays: the product of two float32 is exact in float64, and the float64 sum
+    is rounded to float32 by way of round-to-odd (the sum's error term decides the sticky bit), so no double rounding."""
+    a, b, c = (np.asarray(v, dtype=F).astype(np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)                      # two_sum: p + c == s + err exactly
+    u = s.view(np.uint64) if s.ndim else np.array([s]).view(np.uint64)
+    u = u.copy()
+    finite = np.isfinite(s) & (err != 0) & ((u & np.uint64(1)) == 0)
+    # round to odd: an inexact sum whose last bit is even moves one ulp towards the error
+    up = finite & ((err > 0) == (s > 0))
+    down = finite & ~up
+    u[up] += np.uint64(1)
+    u[down] -= np.uint64(1)
+    fix = np.where(finite & (s == 0), s, u.view(np.float64).reshape(s.shape))
+    return fix.astype(F)
+
+
+def triangle_edges(objects):
+    """(v0, e1, e2) float32[n, 3] of type-2 records as the kernels hold them (rt_device.h: HotObject of a triangle): the vertices are
+    columns 0, 1, 2 of mv (x, y, z in elements 4 k .. 4 k + 2), e1 = v1 - v0 and e2 = v2 - v0 in float32."""
+    mv = objects["mv"].reshape(-1, 16).astype(F)
+    v0, v1, v2 = mv[:, 0:3], mv[:, 4:7], mv[:, 8:11]
+    return v0, (v1 - v0).astype(F), (v2 - v0).astype(F)
+
+
+def hit_records(objects, rays, t, index, affine=None, fused=False):
     """point float32[n, 4], normal float32[n, 4] (w = 0) and reflected RAY_DTYPE[n] as a dict, for winner index[i] at time t[i];
-    zero records where index[i] < 0. `affine`: the scene's flag (None: scene_is_affine(objects))."""
+    zero records where index[i] < 0. `affine`: the scene's flag (None: scene_is_affine(objects)). A triangle winner: point =
+    t * d + s per component (w included) - product then sum, or with `fused` one single-rounded fma, the fused modes' - and normal =
+    normalize(e1 x e2), never contracted; `fused` touches nothing else."""
     objects = np.ascontiguousarray(objects, dtype=OBJECT_DTYPE)
     rays = rays_of(rays)
     t = np.asarray(t, dtype=F).reshape(-1)
@@ -86,6 +118,25 @@ def hit_records(objects, rays, t, index, affine=None):
         direction = np.stack([rx, ry, rz, np.zeros_like(rx)], axis=1)
     reflected["start"][sel] = start
     reflected["direction"][sel] = direction
+    tri = kind == 2
+    if tri.any():   # materialise()'s type-2 branch (rt_device.h)
+        k = sel[tri]
+        _, e1, e2 = triangle_edges(o[tri])
+        s3, d3, T3 = s[tri], d[tri], T[tri]
+        with np.errstate(all="ignore"):
+            if fused:
+                P = np.stack([_fma(T3, d3[:, c], s3[:, c]) for c in range(4)], axis=1)
+            else:
+                P = np.stack([T3 * d3[:, c] + s3[:, c] for c in range(4)], axis=1)
+            nx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+            ny = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+            nz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+            nx, ny, nz = _normalize3(nx, ny, nz)
+        point[k] = P.astype(F)
+        normal[k] = np.stack([nx, ny, nz, np.zeros_like(nx)], axis=1)
+        # (the reflected ray of a triangle winner is not part of any call: the record stays zero)
+        reflected["start"][k] = 0
+        reflected["direction"][k] = 0
     return {"point": point, "normal": normal, "reflected": reflected}
 
 

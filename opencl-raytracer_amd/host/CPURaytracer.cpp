@@ -513,6 +513,23 @@ void CPURaytracer::QueryHits(const std::vector<Ray3D>& q, const std::vector<int3
     HitRecords(q, hits);
 }
 
+void CPURaytracer::RenderGBuffer(GBuffer& out) const {
+    Hits hits;
+    QueryHits(Rays(), std::vector<int32_t>(), hits);
+    const size_t n = hits.t.size();
+    out.albedo.assign(n, rtm::vec4(0.f, 0.f, 0.f, 0.f));
+    for (size_t i = 0; i < n; ++i) {
+        const int32_t k = hits.index[i];
+        if (k < 0 || (size_t)k >= surfaces.size()) continue;
+        const Surface& s = surfaces[(size_t)k];
+        out.albedo[i] = rtm::vec4(s.diffuse[0], s.diffuse[1], s.diffuse[2], 1.f);
+    }
+    out.t.swap(hits.t);
+    out.index.swap(hits.index);
+    out.point.swap(hits.point);
+    out.normal.swap(hits.normal);
+}
+
 void CPURaytracer::QueryShade(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask, Shade& out) const {
     const size_t n = q.size();
     if (!mask.empty() && mask.size() != n) throw std::invalid_argument("QueryShade: the mask must be empty or have one entry per ray");

@@ -104,6 +104,17 @@ public:
     };
     void QueryShade(const std::vector<Ray3D>& rays, const std::vector<int32_t>& mask, Shade& out) const;
 
+    // G-buffer frames, the same option as HIPRaytracer's (hip_raytracer.h, "G-buffer frames"), and the definition that runs without a
+    // GPU: QueryHits over this object's own primary rays (SetRays / SetPose as set so far), one entry per ray in ray order, and the
+    // winner's diffuse colour with w = 1 as `albedo` (SetMaterials as set so far); zero records where index == -1. No triangles
+    // here, as everywhere in this backend. Render() is not disturbed.
+    struct GBuffer {
+        std::vector<float> t;
+        std::vector<int32_t> index;
+        std::vector<rtm::vec4> point, normal, albedo;
+    };
+    void RenderGBuffer(GBuffer& out) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

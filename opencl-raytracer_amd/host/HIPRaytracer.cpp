@@ -276,6 +276,34 @@ rt_query_shade_info_t HIPRaytracer::QueryShadeInfo() {
     return info;
 }
 
+HIPRaytracer::GBuffer HIPRaytracer::RenderGBuffer(unsigned int shard) {
+    static_assert(sizeof(rtm::vec4) == 16, "the ABI's records");
+    rt_context* c = multi ? rt_multi_context(multi, shard) : ctx;
+    if (!c) throw std::runtime_error("HIPRaytracer::RenderGBuffer: no context");
+    const size_t n = (size_t)rt_local_rays(c);
+    GBuffer g;
+    g.t.assign(n, 0.f);
+    g.index.assign(n, -1);
+    g.point.assign(n, rtm::vec4());
+    g.normal.assign(n, rtm::vec4());
+    g.albedo.assign(n, rtm::vec4());
+    rt_gbuffer_t out;
+    out.t = g.t.data();
+    out.index = g.index.data();
+    out.point = reinterpret_cast<float*>(g.point.data());
+    out.normal = reinterpret_cast<float*>(g.normal.data());
+    out.albedo = reinterpret_cast<float*>(g.albedo.data());
+    if (n && rt_render_gbuffer(c, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::RenderGBuffer: ") + rt_last_error(c));
+    return g;
+}
+
+rt_gbuffer_info_t HIPRaytracer::GBufferInfo(unsigned int shard) {
+    rt_gbuffer_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, shard) : ctx;
+    if (!c || rt_get_gbuffer_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::GBufferInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

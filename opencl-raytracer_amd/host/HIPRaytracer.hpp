@@ -138,6 +138,20 @@ public:
     rtm::vec4 PickColour(unsigned int i, unsigned int j);
     rt_query_shade_info_t QueryShadeInfo();
 
+    // G-buffer frames (hip_raytracer.h, "G-buffer frames"): the primary hit of every local work-item of the frame - t, index, the
+    // view-space point, the unit normal (w = 0) and the winner's diffuse colour (w = 1) - one entry per work-item (per sample under
+    // supersampling) in the order Render() writes pixels; zero records where index is -1. The pass is the frame's own primary round
+    // plus one streaming kernel, follows every setter and leaves the frame alone; it works with every kernel and on scenes with
+    // triangles. Synchronous (rt_render_gbuffer). The several-GPU object has no gathered form: `shard` names the device whose own
+    // tiles are delivered. GBufferInfo(): rt_get_gbuffer_info of that shard's last pass.
+    struct GBuffer {
+        std::vector<float> t;
+        std::vector<int32_t> index;
+        std::vector<rtm::vec4> point, normal, albedo;
+    };
+    GBuffer RenderGBuffer(unsigned int shard = 0);
+    rt_gbuffer_info_t GBufferInfo(unsigned int shard = 0);
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

@@ -63,7 +63,7 @@ std::vector<Ray3D> host_rays(const rt_ray* rays, uint64_t n) {
 struct QueryBackend {
     std::vector<ObjectData> objects;
     std::vector<Light> lights;
-    const std::vector<Ray3D> no_rays;
+    std::vector<Ray3D> primary_rays;   // the backend's own rays: none for the queries, the frame's for cpu_rt_render_gbuffer (set before make())
     std::unique_ptr<CPURaytracer> backend;
     bool make(const void* objs_, uint32_t n_objs, unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count,
               const void* transforms_, uint32_t t_first, uint32_t t_count, const void* lights_ = nullptr, uint32_t n_lights = 0,
@@ -83,7 +83,7 @@ struct QueryBackend {
             std::memcpy(o.mvInverseTranspose.data(), d.mvInverseTranspose, sizeof(d.mvInverseTranspose));
             objects.push_back(o);
         }
-        backend.reset(new CPURaytracer(objects, lights, no_rays, max_bounces, static_cast<CPURaytracer::Kernel>(kernel), threads));
+        backend.reset(new CPURaytracer(objects, lights, primary_rays, max_bounces, static_cast<CPURaytracer::Kernel>(kernel), threads));
         try {
             if (m_count) {
                 std::vector<Material> ms;
@@ -344,6 +344,32 @@ int cpu_rt_query_hits(const void* objs_, uint32_t n_objs, const void* rays_, uin
             std::memcpy(refl[i].start, &hits.reflected[i].start, 16);
             std::memcpy(refl[i].direction, &hits.reflected[i].direction, 16);
         }
+    }
+    return 0;
+}
+
+// CPURaytracer::RenderGBuffer through the C entry, on a backend made as cpu_rt_query's with `rays_` as its primary rays and
+// SetMaterials(m_first, materials_[0 .. m_count)). t, index (n_rays each), point, normal and albedo (n_rays x 4 floats) may each be
+// NULL. Returns 0 or -1.
+int cpu_rt_render_gbuffer(const void* objs_, uint32_t n_objs, const void* rays_, uint64_t n_rays, float* t, int32_t* index, float* point,
+                          float* normal, float* albedo, unsigned int threads, const void* visible_, uint32_t v_first, uint32_t v_count,
+                          const void* transforms_, uint32_t t_first, uint32_t t_count, const void* materials_, uint32_t m_first,
+                          uint32_t m_count) {
+    if (!rays_ && n_rays) return -1;
+    QueryBackend q;
+    q.primary_rays = host_rays(static_cast<const rt_ray*>(rays_), n_rays);
+    if (!q.make(objs_, n_objs, threads, visible_, v_first, v_count, transforms_, t_first, t_count, nullptr, 0, 0, 0, materials_, m_first, m_count))
+        return -1;
+    CPURaytracer::GBuffer g;
+    try {
+        q.backend->RenderGBuffer(g);
+    } catch (const std::exception&) { return -1; }
+    for (uint64_t i = 0; i < n_rays; ++i) {
+        if (t) t[i] = g.t[i];
+        if (index) index[i] = g.index[i];
+        if (point) std::memcpy(point + 4 * i, &g.point[i], 16);
+        if (normal) std::memcpy(normal + 4 * i, &g.normal[i], 16);
+        if (albedo) std::memcpy(albedo + 4 * i, &g.albedo[i], 16);
     }
     return 0;
 }

@@ -16,6 +16,11 @@
 //                       meets the object, in view space, and the unit normal there (zeros on a miss). HIPRaytracer::PickHits on
 //                       the GPU; with `cpu`, or where no GPU backend can be made, CPURaytracer::QueryHits of that pixel's ray -
 //                       the same answer; z-bits as for render
+//   scene_tool gbuffer <scene.txt> <W> <H> <out-prefix> [hip|cpu] [z-bits|-]
+//                       the primary hits of the W x H picture as two binary PPMs (HIPRaytracer::RenderGBuffer; with `cpu`, or where
+//                       no GPU backend can be made, CPURaytracer::RenderGBuffer - the same records): <out-prefix>_normal.ppm, the
+//                       unit normal mapped as 0.5 n + 0.5, and <out-prefix>_depth.ppm, t divided by the largest finite t of the
+//                       frame; a miss is black in both. Bytes by the rule of ppm.format_p6 (floor(255 v), clamped)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -133,6 +138,60 @@ int main(int argc, char** argv) {
             std::printf("point %.9g %.9g %.9g %.9g\n", (double)point.x, (double)point.y, (double)point.z, (double)point.w);
             std::printf("normal %.9g %.9g %.9g\n", (double)normal.x, (double)normal.y, (double)normal.z);
             std::printf("pick %d %.9g %s\n", (int)index[0], (double)t[0], backend_name);
+            return 0;
+        }
+        if (std::strcmp(argv[1], "gbuffer") == 0) {
+            if (argc < 6) { std::fprintf(stderr, "usage: scene_tool gbuffer <scene.txt> <W> <H> <out-prefix> [hip|cpu] [z-bits|-]\n"); return 1; }
+            const int gw = std::atoi(argv[3]), gh = std::atoi(argv[4]);
+            if (gw <= 0 || gh <= 0) { std::fprintf(stderr, "gbuffer: W > 0, H > 0\n"); return 1; }
+            float gfov = rtm::radians(60.f);
+            gfov *= 0.5f;
+            float gz = -((gh / 2.0f) / tanf(gfov));
+            if (argc > 7 && std::strcmp(argv[7], "-") != 0) { const uint32_t bits = (uint32_t)std::strtoul(argv[7], nullptr, 16); std::memcpy(&gz, &bits, 4); }
+            std::vector<Ray3D> grid;
+            grid.reserve((size_t)gw * gh);
+            for (int jj = 0; jj < gh; ++jj)
+                for (int ii = 0; ii < gw; ++ii)
+                    grid.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - gw / 2.0f, (float)(gh - jj) - gh / 2.0f, gz));
+            const size_t n = grid.size();
+            std::vector<float> t;
+            std::vector<int32_t> index;
+            std::vector<rtm::vec4> normal;
+            const char* backend_name = (argc > 6 && std::strcmp(argv[6], "cpu") == 0) ? "cpu" : "hip";
+            if (std::strcmp(backend_name, "hip") == 0) {
+                try {
+                    HIPRaytracer backend(objects, lights, grid, 0);
+                    HIPRaytracer::GBuffer g = backend.RenderGBuffer();
+                    t.swap(g.t); index.swap(g.index); normal.swap(g.normal);
+                } catch (const std::exception& e) {  // (no GPU: the CPU backend's records - said on stderr and in the last line)
+                    std::fprintf(stderr, "gbuffer: %s; using the CPU backend\n", e.what());
+                    backend_name = "cpu";
+                }
+            }
+            if (std::strcmp(backend_name, "cpu") == 0) {
+                CPURaytracer backend(objects, lights, grid, 0);
+                CPURaytracer::GBuffer g;
+                backend.RenderGBuffer(g);
+                t.swap(g.t); index.swap(g.index); normal.swap(g.normal);
+            }
+            float t_max = 0.f;
+            size_t hits = 0;
+            for (size_t i = 0; i < n; ++i)
+                if (index[i] >= 0) { ++hits; if (std::isfinite(t[i]) && t[i] > t_max) t_max = t[i]; }
+            // floor(255 v) clamped to 0 .. 255, NaN -> 0: ppm.quantise_bytes
+            auto level = [](float v) { const float f = std::floor(v * 255.0f); return (uint8_t)(f >= 0.0f ? (f >= 255.0f ? 255.0f : f) : 0.0f); };
+            std::vector<uint8_t> nb(3 * n, 0), db(3 * n, 0);
+            for (size_t i = 0; i < n; ++i) {
+                if (index[i] < 0) continue;
+                nb[3 * i] = level(0.5f * normal[i].x + 0.5f);
+                nb[3 * i + 1] = level(0.5f * normal[i].y + 0.5f);
+                nb[3 * i + 2] = level(0.5f * normal[i].z + 0.5f);
+                db[3 * i] = db[3 * i + 1] = db[3 * i + 2] = t_max > 0.f ? level(t[i] / t_max) : (uint8_t)0;
+            }
+            const std::string prefix(argv[5]);
+            PPMExporter::ExportP6(prefix + "_normal.ppm", (size_t)gw, (size_t)gh, nb.data(), 3);
+            PPMExporter::ExportP6(prefix + "_depth.ppm", (size_t)gw, (size_t)gh, db.data(), 3);
+            std::printf("gbuffer %zu hits of %zu, largest t %.9g, %s\n", hits, n, (double)t_max, backend_name);
             return 0;
         }
         if (argc < 7) return 1;
