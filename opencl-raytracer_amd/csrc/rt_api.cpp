@@ -940,15 +940,12 @@ void rt_destroy(rt_context* c) {
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->h_scan) (void)hipHostFree(c->h_scan);
-    if (c->query_made) (void)hipEventSynchronize(c->ev_query[1]);  // (a device-form query may still run on the caller's stream)
-    if (c->d_query_counters) (void)hipFree(c->d_query_counters);
-    for (hipEvent_t ev : c->ev_query) if (ev) (void)hipEventDestroy(ev);
-    if (c->query_shade_made) (void)hipEventSynchronize(c->ev_query_shade[1]);
-    if (c->d_query_shade_counters) (void)hipFree(c->d_query_shade_counters);
-    for (hipEvent_t ev : c->ev_query_shade) if (ev) (void)hipEventDestroy(ev);
-    if (c->gbuffer_made) (void)hipEventSynchronize(c->ev_gb[3]);  // (a device-form pass may still run on the caller's stream)
-    if (c->d_gb_hits) (void)hipFree(c->d_gb_hits);
-    for (hipEvent_t ev : c->ev_gb) if (ev) (void)hipEventDestroy(ev);
+    for (CountedSlot* s : {&c->query, &c->query_shade, &c->gb_records}) {
+        if (s->made) (void)hipEventSynchronize(s->ev[1]);  // (a device-form query or pass may still run on the caller's stream)
+        if (s->d_counters) (void)hipFree(s->d_counters);
+        for (hipEvent_t ev : s->ev) if (ev) (void)hipEventDestroy(ev);
+    }
+    for (hipEvent_t ev : c->ev_gb_trace) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_xf) if (ev) (void)hipEventDestroy(ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);

@@ -30,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <new>
 #include <string>
@@ -114,6 +115,16 @@ struct Buffer {
     Buffer(const Buffer&) = delete;
     Buffer& operator=(const Buffer&) = delete;
     int grow(rt_context* c, size_t need) { return grow_buffer(c, p, bytes, need, pinned_host); }
+};
+
+// What a query family keeps on its context (enqueue_counted and read_counted, below): the counter block its kernels add to,
+// the event pair around the last kernel - both made by the family's first call - and whether there has been one.
+struct CountedSlot {
+    const size_t counter_bytes;
+    void* d_counters = nullptr;
+    hipEvent_t ev[2] = {};
+    bool made = false;
+    explicit CountedSlot(size_t bytes) : counter_bytes(bytes) {}
 };
 
 }  // namespace rt::host
@@ -273,24 +284,19 @@ struct rt_context {
     std::vector<uint8_t> h_hidden;
     uint32_t* d_vis_types = nullptr;
     uint32_t* d_vis_slots = nullptr;
-    // Ray queries (rt_query_*, rt_query_host.cpp): the counter block the query kernels add to, the event pair around the last query
-    // (both made by the first query), and whether there has been one. The host twins stage rays and results in d_patch_stage.
-    rt::QueryCounters* d_query_counters = nullptr;
-    hipEvent_t ev_query[2] = {};
-    bool query_made = false;
-    // Shaded queries (rt_query_shade*): their own counter block and event pair, so that rt_get_query_info keeps reporting the last plain
-    // or hit-record query.
-    rt::QueryShadeCounters* d_query_shade_counters = nullptr;
-    hipEvent_t ev_query_shade[2] = {};
-    bool query_shade_made = false;
+    // Ray queries (rt_query_*, rt_query_host.cpp): the slot of the plain and hit-record queries (rt::QueryCounters). The host twins stage
+    // rays and results in d_patch_stage.
+    rt::host::CountedSlot query{sizeof(rt::QueryCounters)};
+    // Shaded queries (rt_query_shade*): a slot of their own (rt::QueryShadeCounters), so that rt_get_query_info keeps reporting the last
+    // plain or hit-record query.
+    rt::host::CountedSlot query_shade{sizeof(rt::QueryShadeCounters)};
     // G-buffer frames (rt_render_gbuffer*, rt_render.cpp): the staging of (t, index) where the caller did not ask for them and of the
-    // host twin's records (grow-only), the hit count the record kernel adds to, two event pairs of its own - [0], [1] around the
-    // primary round, [2], [3] around the record kernel - and what rt_get_gbuffer_info reports of the last pass. The hittest frame's
-    // `out` (MAX_FLOAT for a NaN time, where t keeps the NaN) goes to d_gb_out, which nothing reads.
+    // host twin's records (grow-only), the slot of the record kernel (its counter block is the hit count; `made` says a whole pass
+    // has been enqueued), an event pair of its own around the primary round, and what rt_get_gbuffer_info reports of the last pass.
+    // The hittest frame's `out` (MAX_FLOAT for a NaN time, where t keeps the NaN) goes to d_gb_out, which nothing reads.
     rt::host::Buffer d_gb_t, d_gb_index, d_gb_out, d_gb_point, d_gb_normal, d_gb_albedo;
-    unsigned long long* d_gb_hits = nullptr;
-    hipEvent_t ev_gb[4] = {};
-    bool gbuffer_made = false;
+    rt::host::CountedSlot gb_records{sizeof(unsigned long long)};
+    hipEvent_t ev_gb_trace[2] = {};
     uint64_t gb_items = 0;
     bool gb_wavefront = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
@@ -498,6 +504,43 @@ private:
 rt::Scene query_scene(const rt_context* c);
 int query_arith(const rt_context* c);
 rt::QueryCamera query_camera(const rt_context* c);
+// ... and the one path of the query families, the G-buffer pass among them:
+// the slot's counter block and event pair exist (made by the first call)
+int ensure_counted(rt_context* c, CountedSlot& s);
+// One counted kernel on `stream`: the counters zeroed, event, launch() - a hipError_t; `what` names it in a failure -, event; then the
+// slot is `made`. Asynchronous.
+template <class Launch>
+int enqueue_counted(rt_context* c, CountedSlot& s, hipStream_t stream, const char* what, Launch&& launch) {
+    if (const int rc = ensure_counted(c, s)) return rc;
+    RT_HIP(c, hipMemsetAsync(s.d_counters, 0, s.counter_bytes, stream));
+    RT_HIP(c, hipEventRecord(s.ev[0], stream));
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail_hip(c, e, what);
+    RT_HIP(c, hipEventRecord(s.ev[1], stream));
+    s.made = true;
+    return RT_OK;
+}
+// what the info readers share: waits for the slot's last kernel, reads its counter block into `counters` and takes the time between its events
+int read_counted(rt_context* c, const CountedSlot& s, void* counters, double* ms);
+// What every form refuses of an output struct `o` with the `members` (pointer, alignment: 4 the scalar arrays, 16 the vector arrays);
+// `device`: they are device pointers, whose alignment the kernels' stores need. The two texts name the family's members.
+struct OutputMember { const void* p; uintptr_t align; };
+int check_outputs(rt_context* c, const void* o, std::initializer_list<OutputMember> members, bool device, const char* scalars_misaligned,
+                  const char* vectors_misaligned);
+int refuse_no_primary_rays(rt_context* c);
+// The device copies of a host form's wanted outputs and their way back: select() hands out the device array of a wanted member (a
+// null host pointer: not wanted, null), finish() copies every selected array to its host array on `stream` and waits for the stream.
+struct CopyBack {
+    struct Item { void* host; const void* dev; size_t bytes; } items[5];
+    int count = 0;
+    template <class T>
+    T* select(void* host, void* dev, size_t bytes) {
+        if (!host) return nullptr;
+        items[count++] = Item{host, dev, bytes};
+        return static_cast<T*>(dev);
+    }
+    int finish(rt_context* c, hipStream_t stream) const;
+};
 // rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched

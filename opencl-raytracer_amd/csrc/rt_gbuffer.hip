@@ -69,18 +69,13 @@ hipError_t launch_gbuffer_records(const Scene& scene, const QueryCamera& camera,
                                   const GBufferRecords& rec, unsigned long long* d_hits, hipStream_t stream) {
     if (shard.n_local == 0) return hipSuccess;
     if (!rec.t || !rec.index || misaligned(rec.t, 4) || misaligned(rec.index, 4) || misaligned(rec.point, 16) ||
-        misaligned(rec.normal, 16) || misaligned(rec.albedo, 16) || !d_hits || shard.tile_rays == 0 ||
-        (!camera.pinhole && (!camera.rays || misaligned(camera.rays, 16))) || (camera.pinhole && camera.width == 0))
+        misaligned(rec.normal, 16) || misaligned(rec.albedo, 16) || !d_hits || shard.tile_rays == 0 || camera_refused(camera))
         return hipErrorInvalidValue;
     const uint64_t want = (shard.n_local + kQueryBlock - 1) / kQueryBlock;
-    const dim3 blocks((uint32_t)(want < kGBufferMaxBlocks ? want : kGBufferMaxBlocks)), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((gbuffer_records<kUnfused>), blocks, block, 0, stream, scene, camera, shard, rec, d_hits); break;
-        case kFused: hipLaunchKernelGGL((gbuffer_records<kFused>), blocks, block, 0, stream, scene, camera, shard, rec, d_hits); break;
-        case kDeviceCL: hipLaunchKernelGGL((gbuffer_records<kDeviceCL>), blocks, block, 0, stream, scene, camera, shard, rec, d_hits); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    const dim3 blocks((uint32_t)(want < kGBufferMaxBlocks ? want : kGBufferMaxBlocks));
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((gbuffer_records<am()>), blocks, dim3(kQueryBlock), 0, stream, scene, camera, shard, rec, d_hits);
+    });
 }
 
 }  // namespace rt

@@ -87,14 +87,7 @@ __global__ __launch_bounds__(kQueryBlock) void query_occluded(const Scene S, con
 // AliasedRays, and no pointer on the way from the kernel's parameters to a load or store of rays, mask or outputs is __restrict__.
 struct AliasedRays {  // BufferRays for an array the kernel may also write (out.reflected == rays): plain pointers throughout
     const float4* rays;
-    __device__ __forceinline__ Ray operator()(uint64_t i) const {
-        const float4 s = rays[2 * i];
-        const float4 d = rays[2 * i + 1];
-        Ray ray;
-        ray.sx = s.x; ray.sy = s.y; ray.sz = s.z; ray.sw = s.w;
-        ray.dx = d.x; ray.dy = d.y; ray.dz = d.z; ray.dw = d.w;
-        return ray;
-    }
+    __device__ __forceinline__ Ray operator()(uint64_t i) const { return load_ray_aliased(rays, i); }
 };
 
 template <int AM, class RAYS>
@@ -159,53 +152,35 @@ __global__ __launch_bounds__(kQueryBlock) void query_primary_hits(const Scene S,
 hipError_t launch_query_closest(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays,
                                 uint64_t n, float* d_t, int32_t* d_index, QueryCounters* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if (!d_rays || misaligned(d_rays, 16) || (!d_t && !d_index) || misaligned(d_t, 4) || misaligned(d_index, 4) || !d_counters)
-        return hipErrorInvalidValue;
-    const dim3 blocks = query_blocks(n), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_closest<kUnfused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_t, d_index, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_closest<kFused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_t, d_index, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_closest<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_t, d_index, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (!d_rays || misaligned(d_rays, 16) || outputs_refused({{d_t, 4}, {d_index, 4}}) || !d_counters) return hipErrorInvalidValue;
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((query_closest<am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, d_rays, n, d_t, d_index, d_counters);
+    });
 }
 
 hipError_t launch_query_occluded(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const float4* d_rays,
                                  uint64_t n, uint8_t* d_occluded, QueryCounters* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (!d_rays || misaligned(d_rays, 16) || !d_occluded || !d_counters) return hipErrorInvalidValue;
-    const dim3 blocks = query_blocks(n), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_occluded<kUnfused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_occluded, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_occluded<kFused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_occluded, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_occluded<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_occluded, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((query_occluded<am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, d_rays, n, d_occluded, d_counters);
+    });
 }
 
 hipError_t launch_query_primary(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
                                 const uint64_t* d_items, uint64_t n, float* d_t, int32_t* d_index, QueryCounters* d_counters,
                                 hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if (!d_items || misaligned(d_items, 8) || (!d_t && !d_index) || misaligned(d_t, 4) || misaligned(d_index, 4) || !d_counters ||
-        (!camera.pinhole && (!camera.rays || misaligned(camera.rays, 16))) || (camera.pinhole && camera.width == 0))
+    if (!d_items || misaligned(d_items, 8) || outputs_refused({{d_t, 4}, {d_index, 4}}) || !d_counters || camera_refused(camera))
         return hipErrorInvalidValue;
-    const dim3 blocks = query_blocks(n), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_primary<kUnfused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_primary<kFused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_primary<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((query_primary<am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, camera, d_items, n, d_t, d_index, d_counters);
+    });
 }
 
 namespace {
 bool hits_refused(const QueryHits& o) {
-    return (!o.t && !o.index && !o.point && !o.normal && !o.reflected) || misaligned(o.t, 4) || misaligned(o.index, 4) ||
-           misaligned(o.point, 16) || misaligned(o.normal, 16) || misaligned(o.reflected, 16);
+    return outputs_refused({{o.t, 4}, {o.index, 4}, {o.point, 16}, {o.normal, 16}, {o.reflected, 16}});
 }
 }  // namespace
 
@@ -213,30 +188,18 @@ hipError_t launch_query_hits(const Scene& scene, const GridDesc& grid, const Que
                              const int32_t* d_mask, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (!d_rays || misaligned(d_rays, 16) || misaligned(d_mask, 4) || hits_refused(out) || !d_counters) return hipErrorInvalidValue;
-    const dim3 blocks = query_blocks(n), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_hits<kUnfused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_hits<kFused>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_hits<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((query_hits<am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, d_rays, n, d_mask, out, d_counters);
+    });
 }
 
 hipError_t launch_query_primary_hits(const Scene& scene, const GridDesc& grid, const QueryBox& box, int arith, const QueryCamera& camera,
                                      const uint64_t* d_items, uint64_t n, const QueryHits& out, QueryCounters* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if (!d_items || misaligned(d_items, 8) || hits_refused(out) || !d_counters ||
-        (!camera.pinhole && (!camera.rays || misaligned(camera.rays, 16))) || (camera.pinhole && camera.width == 0))
-        return hipErrorInvalidValue;
-    const dim3 blocks = query_blocks(n), block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_primary_hits<kUnfused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_primary_hits<kFused>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_primary_hits<kDeviceCL>), blocks, block, 0, stream, scene, grid, box, camera, d_items, n, out, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (!d_items || misaligned(d_items, 8) || hits_refused(out) || !d_counters || camera_refused(camera)) return hipErrorInvalidValue;
+    return launch_for_arith(arith, [&](auto am) {
+        hipLaunchKernelGGL((query_primary_hits<am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, camera, d_items, n, out, d_counters);
+    });
 }
 
 }  // namespace rt

@@ -1,6 +1,10 @@
 // rt_query_device.h - what the query kernels share (rt_query.hip, rt_query_shade.hip): the per-ray route predicate, the ray sources,
-// the workgroup shape and the once-per-wave counter flush. Device code; included by the two kernel units only.
+// the workgroup shape and the once-per-wave counter flush - and, host side, what their launchers share: the arithmetic dispatch and the
+// argument predicates. Included by the kernel units only (rt_gbuffer.hip with them).
 #pragma once
+
+#include <initializer_list>
+#include <type_traits>
 
 #include "rt_query.h"
 
@@ -31,7 +35,8 @@ __device__ __forceinline__ bool query_predicate(const QueryBox& b, const Ray& r)
 __device__ __forceinline__ bool query_on_grid(const QueryBox& b, const Ray& r) { return query_predicate<true>(b, r); }
 __device__ __forceinline__ bool query_in_domain(const Ray& r) { return query_predicate<false>(QueryBox{}, r); }
 
-__device__ __forceinline__ Ray load_ray(const float4* __restrict__ rays, uint64_t i) {
+// ray i of an array the kernel may also write (rt_query.hip: AliasedRays): a plain pointer
+__device__ __forceinline__ Ray load_ray_aliased(const float4* rays, uint64_t i) {
     const float4 s = rays[2 * i];
     const float4 d = rays[2 * i + 1];
     Ray ray;
@@ -39,6 +44,7 @@ __device__ __forceinline__ Ray load_ray(const float4* __restrict__ rays, uint64_
     ray.dx = d.x; ray.dy = d.y; ray.dz = d.z; ray.dw = d.w;
     return ray;
 }
+__device__ __forceinline__ Ray load_ray(const float4* __restrict__ rays, uint64_t i) { return load_ray_aliased(rays, i); }
 
 // work-item g's primary ray: the pinhole grid of rt_set_camera (rt_wavefront.hip: primary_ray) or the context's buffer
 __device__ __forceinline__ Ray camera_ray(const QueryCamera& c, uint64_t g) {
@@ -108,5 +114,33 @@ inline dim3 query_blocks(uint64_t n) {
 }
 
 inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; }
+
+// what every launcher that reads primary rays refuses of the camera
+inline bool camera_refused(const QueryCamera& c) {
+    return (!c.pinhole && (!c.rays || misaligned(c.rays, 16))) || (c.pinhole && c.width == 0);
+}
+
+// ... and of a set of outputs of which each may be null, not all: none given, or one misaligned
+struct OutputPointer { const void* p; uintptr_t align; };
+inline bool outputs_refused(std::initializer_list<OutputPointer> outputs) {
+    bool any = false;
+    for (const OutputPointer& o : outputs) {
+        if (misaligned(o.p, o.align)) return true;
+        any = any || o.p;
+    }
+    return !any;
+}
+
+// The run-time arithmetic mode as a compile-time constant: launch(std::integral_constant<int, kUnfused | kFused | kDeviceCL>) once.
+template <class Launch>
+hipError_t launch_for_arith(int arith, Launch&& launch) {
+    switch (arith) {
+        case kUnfused: launch(std::integral_constant<int, kUnfused>{}); break;
+        case kFused: launch(std::integral_constant<int, kFused>{}); break;
+        case kDeviceCL: launch(std::integral_constant<int, kDeviceCL>{}); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 }  // namespace rt

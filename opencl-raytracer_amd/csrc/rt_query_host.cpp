@@ -94,140 +94,155 @@ int check_query_rays(rt_context* c, const void* rays, uint64_t n, bool device) {
     return RT_OK;
 }
 
-// the counter block and the event pair: made by the first query
-int ensure_query_support(rt_context* c) {
-    if (!c->d_query_counters) RT_HIP(c, hipMalloc((void**)&c->d_query_counters, sizeof(rt::QueryCounters)));
-    for (hipEvent_t& e : c->ev_query)
-        if (!e) RT_HIP(c, hipEventCreate(&e));
-    return RT_OK;
+// What the three primary forms refuse of (work_items, n) and of the context, in their order: the array, then `arguments()` - the
+// form's own count bound and outputs -, the range of every work-item, `refuse_context`, and a context without primary rays (which
+// comes before the n == 0 return). Nothing is touched.
+template <class Arguments>
+int check_primary(rt_context* c, const uint64_t* work_items, uint64_t n, Arguments arguments, int (*refuse_context)(rt_context*)) {
+    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
+    if (const int rc = arguments()) return rc;
+    for (uint64_t k = 0; k < n; ++k)
+        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
+    if (const int rc = refuse_context(c)) return rc;
+    return refuse_no_primary_rays(c);
 }
 
-enum class Kind { Closest, Occluded, Primary };
+// what every query launch reads of the context
+struct QueryInputs {
+    rt::Scene scene;
+    rt::QueryBox box;
+    rt::GridDesc grid;
+    int arith;
+    explicit QueryInputs(const rt_context* c)
+        : scene(query_scene(c)), box(query_box(c)), grid(box.grid ? c->grid : rt::GridDesc{}), arith(query_arith(c)) {}
+};
 
-// One query on `stream`: counters zeroed, event, kernel, event. All pointers are device memory; `d_in` the rays or, for Kind::Primary, the
-// work-items. Asynchronous.
-int enqueue_query(rt_context* c, Kind kind, const void* d_in, uint64_t n, float* d_t, int32_t* d_index, uint8_t* d_occluded, hipStream_t stream) {
-    if (const int rc = ensure_query_support(c)) return rc;
-    const rt::Scene scene = query_scene(c);
-    const rt::QueryBox box = query_box(c);
-    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
-    const int arith = query_arith(c);
-    RT_HIP(c, hipMemsetAsync(c->d_query_counters, 0, sizeof(rt::QueryCounters), stream));
-    RT_HIP(c, hipEventRecord(c->ev_query[0], stream));
-    hipError_t e = hipSuccess;
-    if (kind == Kind::Closest) {
-        e = rt::launch_query_closest(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
-    } else if (kind == Kind::Occluded) {
-        e = rt::launch_query_occluded(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_occluded, c->d_query_counters, stream);
-    } else {
-        e = rt::launch_query_primary(scene, grid, box, arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, d_t, d_index, c->d_query_counters, stream);
-    }
-    if (e != hipSuccess) return fail_hip(c, e, "query launch");
-    RT_HIP(c, hipEventRecord(c->ev_query[1], stream));
-    c->query_made = true;
-    return RT_OK;
-}
+// ---- staging in the patch buffer -----------------------------------------------------------------------------------------------------
+// A host form stages its arrays behind one another in the context's patch buffer (rt_object_patch.cpp). One row per array, in that
+// order: its bytes per element and whether the array is padded to 16 bytes. Row 0 is the input at its largest, a 32-byte ray (an
+// 8-byte work-item for the primary forms); then, where the family has one, the mask; then the outputs in the order they are copied back.
+struct StageField { size_t elem; bool padded; };
+enum { qIn, qT, qIndex, qOccluded };
+constexpr StageField kQueryStage[] = {{sizeof(rt_ray), true}, {sizeof(float), true}, {sizeof(int32_t), true}, {1, true}};
+enum { hIn, hMask, hT, hIndex, hPoint, hNormal, hReflected };
+constexpr StageField kHitsStage[] = {{sizeof(rt_ray), true}, {sizeof(int32_t), true}, {sizeof(float), true}, {sizeof(int32_t), true},
+                                     {16, false},            {16, false},             {sizeof(rt_ray), false}};
+enum { sIn, sMask, sRgba, sT, sIndex };
+constexpr StageField kShadeStage[] = {{sizeof(rt_ray), true}, {sizeof(int32_t), true}, {16, false}, {sizeof(float), true}, {sizeof(int32_t), true}};
 
 size_t align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 
-// The host twins and rt_query_primary: input and results staged in the context's patch buffer (rt_object_patch.cpp), on the context's
-// stream; synchronous. `in_bytes` bytes of input per element.
+// The count bound of a table: what it stages per element, at most, and what its padded arrays add, at most, must fit an address.
+template <size_t N>
+constexpr size_t stage_max_count(const StageField (&fields)[N]) {
+    size_t per_element = 0, padding = 0;
+    for (const StageField& f : fields) {
+        per_element += f.elem;
+        padding += f.padded ? 16 : 0;
+    }
+    return ((std::numeric_limits<size_t>::max)() - padding) / per_element;
+}
+static_assert(stage_max_count(kHitsStage) == ((std::numeric_limits<size_t>::max)() - 64) / 108, "rt_query_hits' bound: 108 bytes, four pads");
+static_assert(stage_max_count(kShadeStage) == ((std::numeric_limits<size_t>::max)() - 64) / 60, "rt_query_shade's bound: 60 bytes, four pads");
+
+template <size_t N>
+int check_stage_count(rt_context* c, const StageField (&fields)[N], uint64_t n) {
+    if (n > stage_max_count(fields)) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many elements: the staged records would not fit an address");
+    return RT_OK;
+}
+
+// The layout of one call: n elements per row, `in_bytes` per element of the input.
+template <size_t N>
+struct Stage {
+    const StageField (&fields)[N];
+    const size_t in_bytes, n;
+    size_t off[N];
+    size_t total = 0;
+    char* base = nullptr;
+    CopyBack back;
+    Stage(const StageField (&f)[N], size_t in_bytes_, uint64_t n_) : fields(f), in_bytes(in_bytes_), n((size_t)n_) {
+        for (size_t k = 0; k < N; ++k) {
+            off[k] = total;
+            total += fields[k].padded ? align16(bytes(k)) : bytes(k);
+        }
+    }
+    size_t bytes(size_t k) const { return (k ? fields[k].elem : in_bytes) * n; }
+    int bind(rt_context* c) {  // the patch buffer holds the layout
+        if (const int rc = ensure_patch_stage(c, total)) return rc;
+        base = static_cast<char*>(c->d_patch_stage.p);
+        return RT_OK;
+    }
+    template <class T>
+    T* at(size_t k) const { return reinterpret_cast<T*>(base + off[k]); }
+    // row k as the device array of the output `host` (null: not wanted), to be copied back
+    template <class T>
+    T* out(size_t k, void* host) { return back.select<T>(host, base + off[k], bytes(k)); }
+};
+
+enum class Kind { Closest, Occluded, Primary };
+
+// One query on `stream` (enqueue_counted). All pointers are device memory; `d_in` the rays or, for Kind::Primary, the work-items.
+int enqueue_query(rt_context* c, Kind kind, const void* d_in, uint64_t n, float* d_t, int32_t* d_index, uint8_t* d_occluded, hipStream_t stream) {
+    return enqueue_counted(c, c->query, stream, "query launch", [&] {
+        const QueryInputs q(c);
+        rt::QueryCounters* const counters = static_cast<rt::QueryCounters*>(c->query.d_counters);
+        if (kind == Kind::Closest)
+            return rt::launch_query_closest(q.scene, q.grid, q.box, q.arith, static_cast<const float4*>(d_in), n, d_t, d_index, counters, stream);
+        if (kind == Kind::Occluded)
+            return rt::launch_query_occluded(q.scene, q.grid, q.box, q.arith, static_cast<const float4*>(d_in), n, d_occluded, counters, stream);
+        return rt::launch_query_primary(q.scene, q.grid, q.box, q.arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, d_t, d_index, counters, stream);
+    });
+}
+
+// The host twins and rt_query_primary: input and results staged on the context's stream; synchronous. `in_bytes` bytes of input per element.
 int query_from_host(rt_context* c, Kind kind, const void* in, size_t in_bytes, uint64_t n, float* t, int32_t* index, uint8_t* occluded) {
     RT_DEVICE(c);
-    const size_t off_t = align16(in_bytes * (size_t)n);
-    const size_t off_index = off_t + align16(sizeof(float) * (size_t)n);
-    const size_t off_occ = off_index + align16(sizeof(int32_t) * (size_t)n);
-    if (const int rc = ensure_patch_stage(c, off_occ + align16((size_t)n))) return rc;
-    char* const stage = static_cast<char*>(c->d_patch_stage.p);
-    float* const d_t = t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
-    int32_t* const d_index = index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
-    uint8_t* const d_occ = occluded ? reinterpret_cast<uint8_t*>(stage + off_occ) : nullptr;
+    Stage st(kQueryStage, in_bytes, n);
+    if (const int rc = st.bind(c)) return rc;
+    float* const d_t = st.out<float>(qT, t);
+    int32_t* const d_index = st.out<int32_t>(qIndex, index);
+    uint8_t* const d_occ = st.out<uint8_t>(qOccluded, occluded);
     hipStream_t stream = c->stream;
-    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * (size_t)n, hipMemcpyHostToDevice, stream));
-    if (const int rc = enqueue_query(c, kind, stage, n, d_t, d_index, d_occ, stream)) return rc;
-    if (t) RT_HIP(c, hipMemcpyAsync(t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    if (index) RT_HIP(c, hipMemcpyAsync(index, d_index, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    if (occluded) RT_HIP(c, hipMemcpyAsync(occluded, d_occ, (size_t)n, hipMemcpyDeviceToHost, stream));
-    RT_HIP(c, hipStreamSynchronize(stream));
-    return RT_OK;
+    RT_HIP(c, hipMemcpyAsync(st.base, in, st.bytes(qIn), hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_query(c, kind, st.base, n, d_t, d_index, d_occ, stream)) return rc;
+    return st.back.finish(c, stream);
 }
 
 // ---- hit records ---------------------------------------------------------------------------------------------------------------------
 // One hit-record query on `stream`, as enqueue_query: `d_in` the rays or, with `primary`, the work-items; `hits` device pointers.
 int enqueue_hits(rt_context* c, bool primary, const void* d_in, uint64_t n, const int32_t* d_mask, const rt::QueryHits& hits, hipStream_t stream) {
-    if (const int rc = ensure_query_support(c)) return rc;
-    const rt::Scene scene = query_scene(c);
-    const rt::QueryBox box = query_box(c);
-    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
-    const int arith = query_arith(c);
-    RT_HIP(c, hipMemsetAsync(c->d_query_counters, 0, sizeof(rt::QueryCounters), stream));
-    RT_HIP(c, hipEventRecord(c->ev_query[0], stream));
-    const hipError_t e = primary ? rt::launch_query_primary_hits(scene, grid, box, arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, hits,
-                                                                 c->d_query_counters, stream)
-                                 : rt::launch_query_hits(scene, grid, box, arith, static_cast<const float4*>(d_in), n, d_mask, hits,
-                                                         c->d_query_counters, stream);
-    if (e != hipSuccess) return fail_hip(c, e, "hit-record query launch");
-    RT_HIP(c, hipEventRecord(c->ev_query[1], stream));
-    c->query_made = true;
-    return RT_OK;
+    return enqueue_counted(c, c->query, stream, "hit-record query launch", [&] {
+        const QueryInputs q(c);
+        rt::QueryCounters* const counters = static_cast<rt::QueryCounters*>(c->query.d_counters);
+        return primary ? rt::launch_query_primary_hits(q.scene, q.grid, q.box, q.arith, query_camera(c), static_cast<const uint64_t*>(d_in), n, hits,
+                                                       counters, stream)
+                       : rt::launch_query_hits(q.scene, q.grid, q.box, q.arith, static_cast<const float4*>(d_in), n, d_mask, hits, counters, stream);
+    });
 }
 
 rt::QueryHits device_hits(const rt_hits_t& o) {
     return rt::QueryHits{o.t, o.index, reinterpret_cast<float4*>(o.point), reinterpret_cast<float4*>(o.normal), static_cast<float4*>(o.reflected)};
 }
 
-// what every form refuses of the output struct; `device`: its members are device pointers, whose alignment the kernel's stores need
 int check_hits(rt_context* c, const rt_hits_t* o, bool device) {
-    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
-    if (!o->t && !o->index && !o->point && !o->normal && !o->reflected) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
-    if (!device) return RT_OK;
-    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(o->point) | reinterpret_cast<uintptr_t>(o->normal) | reinterpret_cast<uintptr_t>(o->reflected)) & 15u)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "point, normal and reflected must be 16-byte aligned");
-    return RT_OK;
+    const rt_hits_t m = o ? *o : rt_hits_t{};
+    return check_outputs(c, o, {{m.t, 4}, {m.index, 4}, {m.point, 16}, {m.normal, 16}, {m.reflected, 16}}, device,
+                         "t and index must be 4-byte aligned", "point, normal and reflected must be 16-byte aligned");
 }
 
-// What hits_from_host stages per element, at most: the input (a 32-byte ray or an 8-byte work-item), the mask, t, index, point, normal
-// and the reflected ray; each of the first four arrays is padded to 16 bytes once.
-constexpr size_t kHitsStageBytesPerElement = sizeof(rt_ray) + 3 * 4 + 16 + 16 + sizeof(rt_ray);
-constexpr size_t kHitsStagePadding = 4 * 16;
-int check_hits_count(rt_context* c, uint64_t n) {
-    if (n > ((std::numeric_limits<size_t>::max)() - kHitsStagePadding) / kHitsStageBytesPerElement)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "too many elements: the staged records would not fit an address");
-    return RT_OK;
-}
-
-// The host forms: input, mask and the requested records staged in the context's patch buffer on the context's stream; synchronous.
+// The host forms: input, mask and the wanted records staged on the context's stream; synchronous.
 int hits_from_host(rt_context* c, bool primary, const void* in, size_t in_bytes, uint64_t n, const int32_t* mask, const rt_hits_t& out) {
     RT_DEVICE(c);
-    const size_t count = (size_t)n;
-    const size_t off_mask = align16(in_bytes * count);
-    const size_t off_t = off_mask + align16(sizeof(int32_t) * count);
-    const size_t off_index = off_t + align16(sizeof(float) * count);
-    const size_t off_point = off_index + align16(sizeof(int32_t) * count);
-    const size_t off_normal = off_point + 16 * count;
-    const size_t off_refl = off_normal + 16 * count;
-    if (const int rc = ensure_patch_stage(c, off_refl + sizeof(rt_ray) * count)) return rc;
-    char* const stage = static_cast<char*>(c->d_patch_stage.p);
-    rt::QueryHits d = {};
-    d.t = out.t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
-    d.index = out.index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
-    d.point = out.point ? reinterpret_cast<float4*>(stage + off_point) : nullptr;
-    d.normal = out.normal ? reinterpret_cast<float4*>(stage + off_normal) : nullptr;
-    d.reflected = out.reflected ? reinterpret_cast<float4*>(stage + off_refl) : nullptr;
-    int32_t* const d_mask = mask ? reinterpret_cast<int32_t*>(stage + off_mask) : nullptr;
+    Stage st(kHitsStage, in_bytes, n);
+    if (const int rc = st.bind(c)) return rc;
+    const rt::QueryHits d{st.out<float>(hT, out.t), st.out<int32_t>(hIndex, out.index), st.out<float4>(hPoint, out.point),
+                          st.out<float4>(hNormal, out.normal), st.out<float4>(hReflected, out.reflected)};
+    int32_t* const d_mask = mask ? st.at<int32_t>(hMask) : nullptr;
     hipStream_t stream = c->stream;
-    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * count, hipMemcpyHostToDevice, stream));
-    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
-    if (const int rc = enqueue_hits(c, primary, stage, n, d_mask, d, stream)) return rc;
-    if (out.t) RT_HIP(c, hipMemcpyAsync(out.t, d.t, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
-    if (out.index) RT_HIP(c, hipMemcpyAsync(out.index, d.index, sizeof(int32_t) * count, hipMemcpyDeviceToHost, stream));
-    if (out.point) RT_HIP(c, hipMemcpyAsync(out.point, d.point, 16 * count, hipMemcpyDeviceToHost, stream));
-    if (out.normal) RT_HIP(c, hipMemcpyAsync(out.normal, d.normal, 16 * count, hipMemcpyDeviceToHost, stream));
-    if (out.reflected) RT_HIP(c, hipMemcpyAsync(out.reflected, d.reflected, sizeof(rt_ray) * count, hipMemcpyDeviceToHost, stream));
-    RT_HIP(c, hipStreamSynchronize(stream));
-    return RT_OK;
+    RT_HIP(c, hipMemcpyAsync(st.base, in, st.bytes(hIn), hipMemcpyHostToDevice, stream));
+    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, st.bytes(hMask), hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_hits(c, primary, st.base, n, d_mask, d, stream)) return rc;
+    return st.back.finish(c, stream);
 }
 
 // ---- shaded queries ------------------------------------------------------------------------------------------------------------------
@@ -245,78 +260,82 @@ int refuse_shade_context(rt_context* c) {
 }
 
 int check_shade(rt_context* c, const rt_shade_t* o, bool device) {
-    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
-    if (!o->rgba && !o->t && !o->index) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
-    if (!device) return RT_OK;
-    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(o->rgba) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "rgba must be 16-byte aligned");
-    return RT_OK;
-}
-
-int ensure_shade_support(rt_context* c) {
-    if (!c->d_query_shade_counters) RT_HIP(c, hipMalloc((void**)&c->d_query_shade_counters, sizeof(rt::QueryShadeCounters)));
-    for (hipEvent_t& e : c->ev_query_shade)
-        if (!e) RT_HIP(c, hipEventCreate(&e));
-    return RT_OK;
+    const rt_shade_t m = o ? *o : rt_shade_t{};
+    return check_outputs(c, o, {{m.rgba, 16}, {m.t, 4}, {m.index, 4}}, device, "t and index must be 4-byte aligned", "rgba must be 16-byte aligned");
 }
 
 // One shaded query on `stream`, as enqueue_hits: `d_in` the rays or, with `primary`, the work-items; `out` device pointers.
 int enqueue_shade(rt_context* c, bool primary, const void* d_in, uint64_t n, const int32_t* d_mask, const rt::QueryShade& out, hipStream_t stream) {
-    if (const int rc = ensure_shade_support(c)) return rc;
-    rt::Scene scene = query_scene(c);
-    scene.literal = shade_context_literal(c) ? 1u : 0u;
-    scene.fast_phong = (c->flags & RT_FLAG_FAST_PHONG) ? 1u : 0u;
-    const rt::QueryBox box = query_box(c);
-    const rt::GridDesc grid = box.grid ? c->grid : rt::GridDesc{};
-    RT_HIP(c, hipMemsetAsync(c->d_query_shade_counters, 0, sizeof(rt::QueryShadeCounters), stream));
-    RT_HIP(c, hipEventRecord(c->ev_query_shade[0], stream));
-    const hipError_t e = rt::launch_query_shade(scene, grid, box, c->kernel, query_arith(c), c->max_bounces,
-                                                primary ? nullptr : static_cast<const float4*>(d_in), primary ? query_camera(c) : rt::QueryCamera{},
-                                                primary ? static_cast<const uint64_t*>(d_in) : nullptr, n, d_mask, out, c->d_query_shade_counters, stream);
-    if (e != hipSuccess) return fail_hip(c, e, "shaded query launch");
-    RT_HIP(c, hipEventRecord(c->ev_query_shade[1], stream));
-    c->query_shade_made = true;
-    return RT_OK;
+    return enqueue_counted(c, c->query_shade, stream, "shaded query launch", [&] {
+        QueryInputs q(c);
+        q.scene.literal = shade_context_literal(c) ? 1u : 0u;
+        q.scene.fast_phong = (c->flags & RT_FLAG_FAST_PHONG) ? 1u : 0u;
+        return rt::launch_query_shade(q.scene, q.grid, q.box, c->kernel, q.arith, c->max_bounces, primary ? nullptr : static_cast<const float4*>(d_in),
+                                      primary ? query_camera(c) : rt::QueryCamera{}, primary ? static_cast<const uint64_t*>(d_in) : nullptr, n, d_mask,
+                                      out, static_cast<rt::QueryShadeCounters*>(c->query_shade.d_counters), stream);
+    });
 }
 
-// What shade_from_host stages per element, at most: the input (a 32-byte ray or an 8-byte work-item), the mask, rgba, t, index; each
-// array but the last is padded to 16 bytes once.
-constexpr size_t kShadeStageBytesPerElement = sizeof(rt_ray) + 4 + 16 + 4 + 4;
-constexpr size_t kShadeStagePadding = 4 * 16;
-int check_shade_count(rt_context* c, uint64_t n) {
-    if (n > ((std::numeric_limits<size_t>::max)() - kShadeStagePadding) / kShadeStageBytesPerElement)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "too many elements: the staged records would not fit an address");
-    return RT_OK;
-}
-
-// The host forms: input, mask and the requested outputs staged in the context's patch buffer on the context's stream; synchronous.
+// The host forms, as hits_from_host.
 int shade_from_host(rt_context* c, bool primary, const void* in, size_t in_bytes, uint64_t n, const int32_t* mask, const rt_shade_t& out) {
     RT_DEVICE(c);
-    const size_t count = (size_t)n;
-    const size_t off_mask = align16(in_bytes * count);
-    const size_t off_rgba = off_mask + align16(sizeof(int32_t) * count);
-    const size_t off_t = off_rgba + 16 * count;
-    const size_t off_index = off_t + align16(sizeof(float) * count);
-    if (const int rc = ensure_patch_stage(c, off_index + align16(sizeof(int32_t) * count))) return rc;
-    char* const stage = static_cast<char*>(c->d_patch_stage.p);
-    rt::QueryShade d = {};
-    d.rgba = out.rgba ? reinterpret_cast<float4*>(stage + off_rgba) : nullptr;
-    d.t = out.t ? reinterpret_cast<float*>(stage + off_t) : nullptr;
-    d.index = out.index ? reinterpret_cast<int32_t*>(stage + off_index) : nullptr;
-    int32_t* const d_mask = mask ? reinterpret_cast<int32_t*>(stage + off_mask) : nullptr;
+    Stage st(kShadeStage, in_bytes, n);
+    if (const int rc = st.bind(c)) return rc;
+    const rt::QueryShade d{st.out<float4>(sRgba, out.rgba), st.out<float>(sT, out.t), st.out<int32_t>(sIndex, out.index)};
+    int32_t* const d_mask = mask ? st.at<int32_t>(sMask) : nullptr;
     hipStream_t stream = c->stream;
-    RT_HIP(c, hipMemcpyAsync(stage, in, in_bytes * count, hipMemcpyHostToDevice, stream));
-    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, sizeof(int32_t) * count, hipMemcpyHostToDevice, stream));
-    if (const int rc = enqueue_shade(c, primary, stage, n, d_mask, d, stream)) return rc;
-    if (out.rgba) RT_HIP(c, hipMemcpyAsync(out.rgba, d.rgba, 16 * count, hipMemcpyDeviceToHost, stream));
-    if (out.t) RT_HIP(c, hipMemcpyAsync(out.t, d.t, sizeof(float) * count, hipMemcpyDeviceToHost, stream));
-    if (out.index) RT_HIP(c, hipMemcpyAsync(out.index, d.index, sizeof(int32_t) * count, hipMemcpyDeviceToHost, stream));
+    RT_HIP(c, hipMemcpyAsync(st.base, in, st.bytes(sIn), hipMemcpyHostToDevice, stream));
+    if (mask) RT_HIP(c, hipMemcpyAsync(d_mask, mask, st.bytes(sMask), hipMemcpyHostToDevice, stream));
+    if (const int rc = enqueue_shade(c, primary, st.base, n, d_mask, d, stream)) return rc;
+    return st.back.finish(c, stream);
+}
+
+}  // namespace
+
+// ---- what the families share, the G-buffer pass (rt_render.cpp) among them; declared in rt_context.h ----------------------------------
+int ensure_counted(rt_context* c, CountedSlot& s) {
+    if (!s.d_counters) RT_HIP(c, hipMalloc(&s.d_counters, s.counter_bytes));
+    for (hipEvent_t& e : s.ev)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    return RT_OK;
+}
+
+int read_counted(rt_context* c, const CountedSlot& s, void* counters, double* ms) {
+    RT_HIP(c, hipEventSynchronize(s.ev[1]));  // the last call's stream, up to its kernel
+    RT_HIP(c, hipMemcpy(counters, s.d_counters, s.counter_bytes, hipMemcpyDeviceToHost));
+    float elapsed = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&elapsed, s.ev[0], s.ev[1]));
+    *ms = (double)elapsed;
+    return RT_OK;
+}
+
+int check_outputs(rt_context* c, const void* o, std::initializer_list<OutputMember> members, bool device, const char* scalars_misaligned,
+                  const char* vectors_misaligned) {
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    uintptr_t any = 0, scalars = 0, vectors = 0;
+    for (const OutputMember& m : members) {
+        any |= reinterpret_cast<uintptr_t>(m.p);
+        (m.align == 4 ? scalars : vectors) |= reinterpret_cast<uintptr_t>(m.p);
+    }
+    if (!any) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
+    if (!device) return RT_OK;
+    if (scalars & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, scalars_misaligned);
+    if (vectors & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, vectors_misaligned);
+    return RT_OK;
+}
+
+int refuse_no_primary_rays(rt_context* c) {
+    if (!c->pinhole && !c->have_rays)
+        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    return RT_OK;
+}
+
+int CopyBack::finish(rt_context* c, hipStream_t stream) const {
+    for (int k = 0; k < count; ++k) RT_HIP(c, hipMemcpyAsync(items[k].host, items[k].dev, items[k].bytes, hipMemcpyDeviceToHost, stream));
     RT_HIP(c, hipStreamSynchronize(stream));
     return RT_OK;
 }
 
-}  // namespace
 }  // namespace rt::host
 
 using namespace rt::host;
@@ -365,14 +384,12 @@ int rt_query_occluded(rt_context* c, const void* rays, uint64_t n, uint8_t* occl
 
 int rt_query_primary(rt_context* c, const uint64_t* work_items, uint64_t n, float* t, int32_t* index) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
-    if (n > (std::numeric_limits<uint64_t>::max)() / sizeof(rt_ray)) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many work-items");
-    if (!t && !index) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
-    for (uint64_t k = 0; k < n; ++k)
-        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
-    if (const int rc = refuse_triangles(c)) return rc;
-    if (!c->pinhole && !c->have_rays)
-        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    const auto arguments = [&] {
+        if (n > (std::numeric_limits<uint64_t>::max)() / sizeof(rt_ray)) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many work-items");
+        if (!t && !index) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+        return (int)RT_OK;
+    };
+    if (const int rc = check_primary(c, work_items, n, arguments, refuse_triangles)) return rc;
     if (n == 0) return RT_OK;
     return query_from_host(c, Kind::Primary, work_items, sizeof(uint64_t), n, t, index, nullptr);
 }
@@ -391,7 +408,7 @@ int rt_query_hits_device(rt_context* c, const void* d_rays, uint64_t n, const in
 int rt_query_hits(rt_context* c, const void* rays, uint64_t n, const int32_t* mask, const rt_hits_t* out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (const int rc = check_query_rays(c, rays, n, false)) return rc;
-    if (const int rc = check_hits_count(c, n)) return rc;
+    if (const int rc = check_stage_count(c, kHitsStage, n)) return rc;
     if (const int rc = check_hits(c, out, false)) return rc;
     if (const int rc = refuse_triangles(c)) return rc;
     if (n == 0) return RT_OK;
@@ -400,14 +417,11 @@ int rt_query_hits(rt_context* c, const void* rays, uint64_t n, const int32_t* ma
 
 int rt_query_primary_hits(rt_context* c, const uint64_t* work_items, uint64_t n, const rt_hits_t* out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
-    if (const int rc = check_hits_count(c, n)) return rc;
-    if (const int rc = check_hits(c, out, false)) return rc;
-    for (uint64_t k = 0; k < n; ++k)
-        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
-    if (const int rc = refuse_triangles(c)) return rc;
-    if (!c->pinhole && !c->have_rays)
-        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    const auto arguments = [&] {
+        const int rc = check_stage_count(c, kHitsStage, n);
+        return rc ? rc : check_hits(c, out, false);
+    };
+    if (const int rc = check_primary(c, work_items, n, arguments, refuse_triangles)) return rc;
     if (n == 0) return RT_OK;
     return hits_from_host(c, true, work_items, sizeof(uint64_t), n, nullptr, *out);
 }
@@ -427,7 +441,7 @@ int rt_query_shade_device(rt_context* c, const void* d_rays, uint64_t n, const i
 int rt_query_shade(rt_context* c, const void* rays, uint64_t n, const int32_t* mask, const rt_shade_t* out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (const int rc = check_query_rays(c, rays, n, false)) return rc;
-    if (const int rc = check_shade_count(c, n)) return rc;
+    if (const int rc = check_stage_count(c, kShadeStage, n)) return rc;
     if (const int rc = check_shade(c, out, false)) return rc;
     if (const int rc = refuse_shade_context(c)) return rc;
     if (n == 0) return RT_OK;
@@ -436,27 +450,21 @@ int rt_query_shade(rt_context* c, const void* rays, uint64_t n, const int32_t* m
 
 int rt_query_primary_shade(rt_context* c, const uint64_t* work_items, uint64_t n, const rt_shade_t* out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
-    if (n != 0 && !work_items) return fail(c, RT_ERR_INVALID_ARGUMENT, "the work-item array is NULL with a non-zero count");
-    if (const int rc = check_shade_count(c, n)) return rc;
-    if (const int rc = check_shade(c, out, false)) return rc;
-    for (uint64_t k = 0; k < n; ++k)
-        if (work_items[k] >= c->n_rays) return fail(c, RT_ERR_INVALID_ARGUMENT, "a work-item is not below the context's ray count");
-    if (const int rc = refuse_shade_context(c)) return rc;
-    if (!c->pinhole && !c->have_rays)
-        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
+    const auto arguments = [&] {
+        const int rc = check_stage_count(c, kShadeStage, n);
+        return rc ? rc : check_shade(c, out, false);
+    };
+    if (const int rc = check_primary(c, work_items, n, arguments, refuse_shade_context)) return rc;
     if (n == 0) return RT_OK;
     return shade_from_host(c, true, work_items, sizeof(uint64_t), n, nullptr, *out);
 }
 
 int rt_get_query_shade_info(rt_context* c, rt_query_shade_info_t* info) {
     if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->query_shade_made) return fail(c, RT_ERR_STATE, "rt_get_query_shade_info: no shaded query has been made on this context");
+    if (!c->query_shade.made) return fail(c, RT_ERR_STATE, "rt_get_query_shade_info: no shaded query has been made on this context");
     RT_DEVICE(c);
-    RT_HIP(c, hipEventSynchronize(c->ev_query_shade[1]));  // the last shaded query's stream, up to the query
     rt::QueryShadeCounters ctr = {};
-    RT_HIP(c, hipMemcpy(&ctr, c->d_query_shade_counters, sizeof(ctr), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_query_shade[0], c->ev_query_shade[1]));
+    if (const int rc = read_counted(c, c->query_shade, &ctr, &info->device_ms)) return rc;
     info->n_rays = ctr.q.n_rays;
     info->n_grid = ctr.q.n_grid;
     info->n_brute = ctr.q.n_brute;
@@ -465,24 +473,19 @@ int rt_get_query_shade_info(rt_context* c, rt_query_shade_info_t* info) {
     info->rays_traced = ctr.traced;
     info->rays_reference = ctr.reference;
     info->object_tests = ctr.q.tests;
-    info->device_ms = (double)ms;
     return RT_OK;
 }
 
 int rt_get_query_info(rt_context* c, rt_query_info_t* info) {
     if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->query_made) return fail(c, RT_ERR_STATE, "rt_get_query_info: no query has been made on this context");
+    if (!c->query.made) return fail(c, RT_ERR_STATE, "rt_get_query_info: no query has been made on this context");
     RT_DEVICE(c);
-    RT_HIP(c, hipEventSynchronize(c->ev_query[1]));  // the last query's stream, up to the query
     rt::QueryCounters ctr = {};
-    RT_HIP(c, hipMemcpy(&ctr, c->d_query_counters, sizeof(ctr), hipMemcpyDeviceToHost));
-    float ms = 0.f;
-    RT_HIP(c, hipEventElapsedTime(&ms, c->ev_query[0], c->ev_query[1]));
+    if (const int rc = read_counted(c, c->query, &ctr, &info->device_ms)) return rc;
     info->n_rays = ctr.n_rays;
     info->n_grid = ctr.n_grid;
     info->n_brute = ctr.n_brute;
     info->object_tests = ctr.tests;
-    info->device_ms = (double)ms;
     return RT_OK;
 }
 

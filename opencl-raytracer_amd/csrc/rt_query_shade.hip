@@ -117,39 +117,26 @@ __global__ __launch_bounds__(kQueryBlock) void query_shade(const Scene S, const 
     }
 }
 
-template <int KERNEL>
-hipError_t launch_arith(int arith, dim3 blocks, hipStream_t stream, const Scene& scene, const GridDesc& grid, const QueryBox& box,
-                        uint32_t max_bounces, const float4* d_rays, const QueryCamera& camera, const uint64_t* d_items, uint64_t n,
-                        const int32_t* d_mask, const QueryShade& out, QueryShadeCounters* d_counters) {
-    const dim3 block(kQueryBlock);
-    switch (arith) {
-        case kUnfused: hipLaunchKernelGGL((query_shade<KERNEL, kUnfused>), blocks, block, 0, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters); break;
-        case kFused: hipLaunchKernelGGL((query_shade<KERNEL, kFused>), blocks, block, 0, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters); break;
-        case kDeviceCL: hipLaunchKernelGGL((query_shade<KERNEL, kDeviceCL>), blocks, block, 0, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_query_shade(const Scene& scene, const GridDesc& grid, const QueryBox& box, int kernel, int arith, uint32_t max_bounces,
                               const float4* d_rays, const QueryCamera& camera, const uint64_t* d_items, uint64_t n, const int32_t* d_mask,
                               const QueryShade& out, QueryShadeCounters* d_counters, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if ((!out.rgba && !out.t && !out.index) || misaligned(out.rgba, 16) || misaligned(out.t, 4) || misaligned(out.index, 4) ||
-        misaligned(d_mask, 4) || !d_counters)
-        return hipErrorInvalidValue;
+    if (outputs_refused({{out.rgba, 16}, {out.t, 4}, {out.index, 4}}) || misaligned(d_mask, 4) || !d_counters) return hipErrorInvalidValue;
     if (d_items) {
-        if (misaligned(d_items, 8) || (!camera.pinhole && (!camera.rays || misaligned(camera.rays, 16))) || (camera.pinhole && camera.width == 0))
-            return hipErrorInvalidValue;
+        if (misaligned(d_items, 8) || camera_refused(camera)) return hipErrorInvalidValue;
     } else if (!d_rays || misaligned(d_rays, 16)) {
         return hipErrorInvalidValue;
     }
-    const dim3 blocks = query_blocks(n);
+    const auto launch = [&](auto k) {
+        return launch_for_arith(arith, [&](auto am) {
+            hipLaunchKernelGGL((query_shade<decltype(k)::value, am()>), query_blocks(n), dim3(kQueryBlock), 0, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters);
+        });
+    };
     switch (kernel) {
-        case 1: return launch_arith<1>(arith, blocks, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters);
-        case 2: return launch_arith<2>(arith, blocks, stream, scene, grid, box, max_bounces, d_rays, camera, d_items, n, d_mask, out, d_counters);
+        case 1: return launch(std::integral_constant<int, 1>{});
+        case 2: return launch(std::integral_constant<int, 2>{});
         default: return hipErrorInvalidValue;
     }
 }

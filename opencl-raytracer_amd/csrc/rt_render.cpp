@@ -343,22 +343,10 @@ static int render_to_host(rt_context* c, int format, const void** out) {
 }
 
 // ---- G-buffer frames (hip_raytracer.h) -----------------------------------------------------------------------------------------------
-// what both forms refuse of the output struct; `device`: its members are device pointers, whose alignment the kernels' stores need
 static int check_gbuffer(rt_context* c, const rt_gbuffer_t* o, bool device) {
-    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
-    if (!o->t && !o->index && !o->point && !o->normal && !o->albedo) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
-    if (!device) return RT_OK;
-    if ((reinterpret_cast<uintptr_t>(o->t) | reinterpret_cast<uintptr_t>(o->index)) & 3u)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "t and index must be 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(o->point) | reinterpret_cast<uintptr_t>(o->normal) | reinterpret_cast<uintptr_t>(o->albedo)) & 15u)
-        return fail(c, RT_ERR_INVALID_ARGUMENT, "point, normal and albedo must be 16-byte aligned");
-    return RT_OK;
-}
-
-static int check_gbuffer_rays(rt_context* c) {
-    if (!c->pinhole && !c->have_rays)
-        return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
-    return RT_OK;
+    const rt_gbuffer_t m = o ? *o : rt_gbuffer_t{};
+    return check_outputs(c, o, {{m.t, 4}, {m.index, 4}, {m.point, 16}, {m.normal, 16}, {m.albedo, 16}}, device,
+                         "t and index must be 4-byte aligned", "point, normal and albedo must be 16-byte aligned");
 }
 
 // One pass over the context's shard on `stream`; the members of `o` are device pointers (each may be null). The primary round of the
@@ -368,12 +356,12 @@ static int check_gbuffer_rays(rt_context* c) {
 static int enqueue_gbuffer(rt_context* c, const rt_gbuffer_t& o, hipStream_t stream) {
     const Shard& sh = c->shard;
     const size_t n = (size_t)sh.n_local;
-    if (!c->d_gb_hits) RT_HIP(c, hipMalloc((void**)&c->d_gb_hits, sizeof(unsigned long long)));
-    for (hipEvent_t& e : c->ev_gb)
+    if (const int rc = ensure_counted(c, c->gb_records)) return rc;
+    for (hipEvent_t& e : c->ev_gb_trace)
         if (!e) RT_HIP(c, hipEventCreate(&e));
     float* d_t = o.t;
     int32_t* d_index = o.index;
-    c->gbuffer_made = false;  // until this pass is enqueued whole: rt_get_gbuffer_info never pairs events of two passes
+    c->gb_records.made = false;  // until this pass is enqueued whole: rt_get_gbuffer_info never pairs events of two passes
     int rc = c->d_gb_out.grow(c, n * sizeof(float));
     if (rc == RT_OK && !d_t) rc = c->d_gb_t.grow(c, n * sizeof(float));
     if (rc == RT_OK && !d_index) rc = c->d_gb_index.grow(c, n * sizeof(int32_t));
@@ -382,20 +370,19 @@ static int enqueue_gbuffer(rt_context* c, const rt_gbuffer_t& o, hipStream_t str
     if (!d_index) d_index = static_cast<int32_t*>(c->d_gb_index.p);
     const bool frame_wavefront = c->last_wavefront;
     const uint32_t frame_rounds = c->last_rounds;
-    rc = do_launch(c, sh, RT_KERNEL_HITTEST, c->d_gb_out.p, d_t, d_index, c->ev_gb[0], c->ev_gb[1], stream, false);
+    rc = do_launch(c, sh, RT_KERNEL_HITTEST, c->d_gb_out.p, d_t, d_index, c->ev_gb_trace[0], c->ev_gb_trace[1], stream, false);
     c->gb_wavefront = c->last_wavefront;
     c->last_wavefront = frame_wavefront;
     c->last_rounds = frame_rounds;
     if (rc) return rc;
-    RT_HIP(c, hipMemsetAsync(c->d_gb_hits, 0, sizeof(unsigned long long), stream));
-    RT_HIP(c, hipEventRecord(c->ev_gb[2], stream));
-    const rt::GBufferShard shard{c->n_rays, sh.n_local, sh.tile_rays ? sh.tile_rays : 1, sh.rank, sh.world};
-    const rt::GBufferRecords rec{d_t, d_index, reinterpret_cast<float4*>(o.point), reinterpret_cast<float4*>(o.normal),
-                                 reinterpret_cast<float4*>(o.albedo)};
-    const hipError_t e = rt::launch_gbuffer_records(query_scene(c), query_camera(c), shard, query_arith(c), rec, c->d_gb_hits, stream);
-    if (e != hipSuccess) return fail_hip(c, e, "G-buffer record launch");
-    RT_HIP(c, hipEventRecord(c->ev_gb[3], stream));
-    c->gbuffer_made = true;
+    rc = enqueue_counted(c, c->gb_records, stream, "G-buffer record launch", [&] {
+        const rt::GBufferShard shard{c->n_rays, sh.n_local, sh.tile_rays ? sh.tile_rays : 1, sh.rank, sh.world};
+        const rt::GBufferRecords rec{d_t, d_index, reinterpret_cast<float4*>(o.point), reinterpret_cast<float4*>(o.normal),
+                                     reinterpret_cast<float4*>(o.albedo)};
+        return rt::launch_gbuffer_records(query_scene(c), query_camera(c), shard, query_arith(c), rec,
+                                          static_cast<unsigned long long*>(c->gb_records.d_counters), stream);
+    });
+    if (rc) return rc;
     c->gb_items = sh.n_local;
     return RT_OK;
 }
@@ -564,7 +551,7 @@ int rt_render_gbuffer_device(rt_context* c, const rt_gbuffer_t* d_out, void* hip
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (const int rc = check_gbuffer(c, d_out, true)) return rc;
     if (c->shard.n_local == 0) return RT_OK;
-    if (const int rc = check_gbuffer_rays(c)) return rc;
+    if (const int rc = refuse_no_primary_rays(c)) return rc;
     RT_DEVICE(c);
     return enqueue_gbuffer(c, *d_out, static_cast<hipStream_t>(hip_stream));
 }
@@ -574,48 +561,39 @@ int rt_render_gbuffer(rt_context* c, const rt_gbuffer_t* out) {
     if (!c) return RT_ERR_INVALID_ARGUMENT;
     if (const int rc = check_gbuffer(c, out, false)) return rc;
     if (c->shard.n_local == 0) return RT_OK;
-    if (const int rc = check_gbuffer_rays(c)) return rc;
+    if (const int rc = refuse_no_primary_rays(c)) return rc;
     RT_DEVICE(c);
     const size_t n = (size_t)c->shard.n_local;
-    int rc = RT_OK;
-    if (out->t) rc = c->d_gb_t.grow(c, n * sizeof(float));
-    if (rc == RT_OK && out->index) rc = c->d_gb_index.grow(c, n * sizeof(int32_t));
-    if (rc == RT_OK && out->point) rc = c->d_gb_point.grow(c, n * 16);
-    if (rc == RT_OK && out->normal) rc = c->d_gb_normal.grow(c, n * 16);
-    if (rc == RT_OK && out->albedo) rc = c->d_gb_albedo.grow(c, n * 16);
-    if (rc) return rc;
-    rt_gbuffer_t d = {};
-    d.t = out->t ? static_cast<float*>(c->d_gb_t.p) : nullptr;
-    d.index = out->index ? static_cast<int32_t*>(c->d_gb_index.p) : nullptr;
-    d.point = out->point ? static_cast<float*>(c->d_gb_point.p) : nullptr;
-    d.normal = out->normal ? static_cast<float*>(c->d_gb_normal.p) : nullptr;
-    d.albedo = out->albedo ? static_cast<float*>(c->d_gb_albedo.p) : nullptr;
-    hipStream_t stream = c->stream;
-    rc = enqueue_gbuffer(c, d, stream);
-    if (rc) return rc;
-    if (out->t) RT_HIP(c, hipMemcpyAsync(out->t, d.t, n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out->index) RT_HIP(c, hipMemcpyAsync(out->index, d.index, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (out->point) RT_HIP(c, hipMemcpyAsync(out->point, d.point, n * 16, hipMemcpyDeviceToHost, stream));
-    if (out->normal) RT_HIP(c, hipMemcpyAsync(out->normal, d.normal, n * 16, hipMemcpyDeviceToHost, stream));
-    if (out->albedo) RT_HIP(c, hipMemcpyAsync(out->albedo, d.albedo, n * 16, hipMemcpyDeviceToHost, stream));
-    RT_HIP(c, hipStreamSynchronize(stream));
-    return RT_OK;
+    const struct {
+        void* host;
+        Buffer& buffer;
+        size_t bytes;
+    } members[] = {{out->t, c->d_gb_t, n * sizeof(float)}, {out->index, c->d_gb_index, n * sizeof(int32_t)}, {out->point, c->d_gb_point, n * 16},
+                   {out->normal, c->d_gb_normal, n * 16}, {out->albedo, c->d_gb_albedo, n * 16}};
+    void* d[5] = {};
+    CopyBack back;
+    for (int k = 0; k < 5; ++k) {
+        if (!members[k].host) continue;
+        if (const int rc = members[k].buffer.grow(c, members[k].bytes)) return rc;
+        d[k] = back.select<void>(members[k].host, members[k].buffer.p, members[k].bytes);
+    }
+    const rt_gbuffer_t device{static_cast<float*>(d[0]), static_cast<int32_t*>(d[1]), static_cast<float*>(d[2]), static_cast<float*>(d[3]),
+                              static_cast<float*>(d[4])};
+    if (const int rc = enqueue_gbuffer(c, device, c->stream)) return rc;
+    return back.finish(c, c->stream);
 }
 
 int rt_get_gbuffer_info(rt_context* c, rt_gbuffer_info_t* info) {
     if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
-    if (!c->gbuffer_made) return fail(c, RT_ERR_STATE, "rt_get_gbuffer_info: no G-buffer pass has been made on this context");
+    if (!c->gb_records.made) return fail(c, RT_ERR_STATE, "rt_get_gbuffer_info: no G-buffer pass has been made on this context");
     RT_DEVICE(c);
-    RT_HIP(c, hipEventSynchronize(c->ev_gb[3]));  // the last pass's stream, up to the record kernel
     unsigned long long hits = 0;
-    RT_HIP(c, hipMemcpy(&hits, c->d_gb_hits, sizeof(hits), hipMemcpyDeviceToHost));
-    float trace = 0.f, records = 0.f;
-    RT_HIP(c, hipEventElapsedTime(&trace, c->ev_gb[0], c->ev_gb[1]));
-    RT_HIP(c, hipEventElapsedTime(&records, c->ev_gb[2], c->ev_gb[3]));
+    if (const int rc = read_counted(c, c->gb_records, &hits, &info->records_ms)) return rc;  // (waits for the record kernel)
+    float trace = 0.f;
+    RT_HIP(c, hipEventElapsedTime(&trace, c->ev_gb_trace[0], c->ev_gb_trace[1]));
     info->n_items = c->gb_items;
     info->hits = hits;
     info->trace_ms = (double)trace;
-    info->records_ms = (double)records;
     info->wavefront = c->gb_wavefront ? 1u : 0u;
     info->reserved = 0;
     return RT_OK;

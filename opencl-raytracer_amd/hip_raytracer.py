@@ -171,7 +171,9 @@ class RTHits(ctypes.Structure):
                 ("reflected", ctypes.c_void_p)]
 
 
-HIT_FIELDS = ("t", "index", "point", "normal", "reflected")
+# One table per family of outputs: name -> (trailing shape, numpy dtype, torch dtype); in the order of the C struct's members.
+_T, _INDEX, _VEC4 = ((), np.float32, "float32"), ((), np.int32, "int32"), ((4,), np.float32, "float32")
+HIT_FIELDS = {"t": _T, "index": _INDEX, "point": _VEC4, "normal": _VEC4, "reflected": ((8,), RAY_DTYPE, "float32")}
 
 
 class RTShade(ctypes.Structure):
@@ -190,7 +192,7 @@ class RTQueryShadeInfo(ctypes.Structure):
         return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
 
 
-SHADE_FIELDS = ("rgba", "t", "index")
+SHADE_FIELDS = {"rgba": _VEC4, "t": _T, "index": _INDEX}
 
 
 class RTGBuffer(ctypes.Structure):
@@ -209,7 +211,7 @@ class RTGBufferInfo(ctypes.Structure):
         return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_ if n != "reserved"}
 
 
-GBUFFER_FIELDS = ("t", "index", "point", "normal", "albedo")
+GBUFFER_FIELDS = {"t": _T, "index": _INDEX, "point": _VEC4, "normal": _VEC4, "albedo": _VEC4}
 
 _lib = None
 
@@ -512,174 +514,132 @@ def _query_occluded(lib, ctx, rays, device: int):
 
 
 def _pick(lib, ctx, work_items):
-    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
-    n = int(items.shape[0])
+    items, n = _items(work_items)
     t, index = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
     _check_rc(lib, ctx, lib.rt_query_primary(ctx, _ptr(items), n, _ptr(t), _ptr(index)))
     return t, index
 
 
-def _wanted(want):
+def _items(work_items):
+    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
+    return items, int(items.shape[0])
+
+
+def _wanted(want, fields):
     want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in HIT_FIELDS for w in want):
-        raise ValueError(f"want: a non-empty selection of {HIT_FIELDS}")
+    if not want or any(w not in fields for w in want):
+        raise ValueError(f"want: a non-empty selection of {tuple(fields)}")
     return want
 
 
-def _host_hits(n: int, want):
-    """numpy arrays for the wanted records and the rt_hits_t that points at them."""
-    shapes = {"t": ((n,), np.float32), "index": ((n,), np.int32), "point": ((n, 4), np.float32), "normal": ((n, 4), np.float32),
-              "reflected": ((n,), RAY_DTYPE)}
-    out = {w: np.zeros(*shapes[w]) for w in want}
-    return out, RTHits(**{w: (a.ctypes.data if a.size else None) for w, a in out.items()})
+def _host_outputs(n: int, want, fields, struct):
+    """numpy arrays for the wanted members (a structured dtype holds its trailing shape itself) and the C struct that points at them."""
+    out = {}
+    for w in want:
+        trailing, dtype, _ = fields[w]
+        out[w] = np.zeros((n,) if np.dtype(dtype).names else (n, *trailing), dtype)
+    return out, struct(**{w: (a.ctypes.data if a.size else None) for w, a in out.items()})
+
+
+def _device_outputs(n: int, want, out, fields, fits, where: str, device=None):
+    """torch tensors for the wanted members: out[w] where `out` names one - it must pass fits(tensor), `where` says what that asks -
+    else a fresh one on `device`."""
+    import torch
+    res = {}
+    for w in want:
+        trailing, _, dtype = fields[w]
+        shape, dtype = (n, *trailing), getattr(torch, dtype)
+        given = None if out is None else out.get(w)
+        if given is None and device is not None:
+            res[w] = torch.empty(shape, dtype=dtype, device=device)
+            continue
+        if not _is_tensor(given) or not fits(given) or given.dtype != dtype or not given.is_contiguous() or given.numel() != int(np.prod(shape)):
+            raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on {where}")
+        res[w] = given
+    return res
+
+
+def _device_mask(mask, rays, n: int):
+    import torch
+    if mask is None:
+        return None
+    if not _is_tensor(mask) or mask.device != rays.device or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != n:
+        raise ValueError("mask: a contiguous int32 tensor on the rays' device, one entry per ray")
+    return ctypes.c_void_p(mask.data_ptr()) if n else None
+
+
+def _query_masked(lib, ctx, rays, mask, want, out, device: int, fields, struct, host_call, device_call):
+    """What query_hits and query_shade share: `host_call` for numpy rays, `device_call` on torch's current stream for a device tensor."""
+    want = _wanted(want, fields)
+    if _is_tensor(rays):
+        ptr, n, stream = _device_rays(rays, device)
+        res = _device_outputs(n, want, out, fields, lambda t: t.device == rays.device, "the rays' device", rays.device)
+        m_ptr = _device_mask(mask, rays, n)
+        if n:
+            _check_rc(lib, ctx, device_call(ctx, ptr, n, m_ptr, ctypes.byref(struct(**{w: a.data_ptr() for w, a in res.items()})), stream))
+        return res
+    if out is not None:
+        raise ValueError("out= takes device tensors: numpy rays return fresh arrays")
+    rays = rays_of(rays)
+    n = int(rays.shape[0])
+    if mask is not None:
+        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
+        if mask.shape[0] != n:
+            raise ValueError("mask: one int32 entry per ray")
+    res, outputs = _host_outputs(n, want, fields, struct)
+    if n:
+        _check_rc(lib, ctx, host_call(ctx, _ptr(rays), n, _ptr(mask), ctypes.byref(outputs)))
+    return res
 
 
 def _query_hits(lib, ctx, rays, mask, want, out, device: int):
     """What HIPRaytracer.query_hits and MultiHIPRaytracer.query_hits (through its shard 0) share."""
-    want = _wanted(want)
-    if _is_tensor(rays):
-        import torch
-        ptr, n, stream = _device_rays(rays, device)
-        shapes = {"t": ((n,), torch.float32), "index": ((n,), torch.int32), "point": ((n, 4), torch.float32),
-                  "normal": ((n, 4), torch.float32), "reflected": ((n, 8), torch.float32)}
-        res = {}
-        for w in want:
-            shape, dtype = shapes[w]
-            given = None if out is None else out.get(w)
-            if given is None:
-                res[w] = torch.empty(shape, dtype=dtype, device=rays.device)
-            else:
-                if not _is_tensor(given) or given.device != rays.device or given.dtype != dtype or not given.is_contiguous() or \
-                        given.numel() != int(np.prod(shape)):
-                    raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the rays' device")
-                res[w] = given
-        m_ptr = None
-        if mask is not None:
-            if not _is_tensor(mask) or mask.device != rays.device or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != n:
-                raise ValueError("mask: a contiguous int32 tensor on the rays' device, one entry per ray")
-            m_ptr = ctypes.c_void_p(mask.data_ptr()) if n else None
-        if n:
-            hits = RTHits(**{w: a.data_ptr() for w, a in res.items()})
-            _check_rc(lib, ctx, lib.rt_query_hits_device(ctx, ptr, n, m_ptr, ctypes.byref(hits), stream))
-        return res
-    if out is not None:
-        raise ValueError("out= takes device tensors: numpy rays return fresh arrays")
-    rays = rays_of(rays)
-    n = int(rays.shape[0])
-    if mask is not None:
-        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
-        if mask.shape[0] != n:
-            raise ValueError("mask: one int32 entry per ray")
-    res, hits = _host_hits(n, want)
-    if n:
-        _check_rc(lib, ctx, lib.rt_query_hits(ctx, _ptr(rays), n, _ptr(mask), ctypes.byref(hits)))
-    return res
-
-
-def _pick_hit(lib, ctx, work_items, want):
-    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
-    n = int(items.shape[0])
-    res, hits = _host_hits(n, _wanted(want))
-    _check_rc(lib, ctx, lib.rt_query_primary_hits(ctx, _ptr(items), n, ctypes.byref(hits)))
-    return res
-
-
-def _shade_wanted(want):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in SHADE_FIELDS for w in want):
-        raise ValueError(f"want: a non-empty selection of {SHADE_FIELDS}")
-    return want
-
-
-def _host_shade(n: int, want):
-    """numpy arrays for the wanted outputs and the rt_shade_t that points at them."""
-    shapes = {"rgba": ((n, 4), np.float32), "t": ((n,), np.float32), "index": ((n,), np.int32)}
-    out = {w: np.zeros(*shapes[w]) for w in want}
-    return out, RTShade(**{w: (a.ctypes.data if a.size else None) for w, a in out.items()})
+    return _query_masked(lib, ctx, rays, mask, want, out, device, HIT_FIELDS, RTHits, lib.rt_query_hits, lib.rt_query_hits_device)
 
 
 def _query_shade(lib, ctx, rays, mask, want, out, device: int):
     """HIPRaytracer.query_shade: rt_query_shade for numpy rays, rt_query_shade_device on torch's current stream for a device tensor."""
-    want = _shade_wanted(want)
-    if _is_tensor(rays):
-        import torch
-        ptr, n, stream = _device_rays(rays, device)
-        shapes = {"rgba": ((n, 4), torch.float32), "t": ((n,), torch.float32), "index": ((n,), torch.int32)}
-        res = {}
-        for w in want:
-            shape, dtype = shapes[w]
-            given = None if out is None else out.get(w)
-            if given is None:
-                res[w] = torch.empty(shape, dtype=dtype, device=rays.device)
-            else:
-                if not _is_tensor(given) or given.device != rays.device or given.dtype != dtype or not given.is_contiguous() or \
-                        given.numel() != int(np.prod(shape)):
-                    raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the rays' device")
-                res[w] = given
-        m_ptr = None
-        if mask is not None:
-            if not _is_tensor(mask) or mask.device != rays.device or mask.dtype != torch.int32 or not mask.is_contiguous() or mask.numel() != n:
-                raise ValueError("mask: a contiguous int32 tensor on the rays' device, one entry per ray")
-            m_ptr = ctypes.c_void_p(mask.data_ptr()) if n else None
-        if n:
-            shade = RTShade(**{w: a.data_ptr() for w, a in res.items()})
-            _check_rc(lib, ctx, lib.rt_query_shade_device(ctx, ptr, n, m_ptr, ctypes.byref(shade), stream))
-        return res
-    if out is not None:
-        raise ValueError("out= takes device tensors: numpy rays return fresh arrays")
-    rays = rays_of(rays)
-    n = int(rays.shape[0])
-    if mask is not None:
-        mask = np.ascontiguousarray(np.asarray(mask).reshape(-1), dtype=np.int32)
-        if mask.shape[0] != n:
-            raise ValueError("mask: one int32 entry per ray")
-    res, shade = _host_shade(n, want)
-    if n:
-        _check_rc(lib, ctx, lib.rt_query_shade(ctx, _ptr(rays), n, _ptr(mask), ctypes.byref(shade)))
+    return _query_masked(lib, ctx, rays, mask, want, out, device, SHADE_FIELDS, RTShade, lib.rt_query_shade, lib.rt_query_shade_device)
+
+
+def _pick_outputs(lib, ctx, work_items, want, fields, struct, call):
+    items, n = _items(work_items)
+    res, outputs = _host_outputs(n, _wanted(want, fields), fields, struct)
+    _check_rc(lib, ctx, call(ctx, _ptr(items), n, ctypes.byref(outputs)))
     return res
+
+
+def _pick_hit(lib, ctx, work_items, want):
+    return _pick_outputs(lib, ctx, work_items, want, HIT_FIELDS, RTHits, lib.rt_query_primary_hits)
 
 
 def _pick_shade(lib, ctx, work_items, want):
-    items = np.ascontiguousarray(np.asarray(work_items).reshape(-1), dtype=np.uint64)
-    n = int(items.shape[0])
-    res, shade = _host_shade(n, _shade_wanted(want))
-    _check_rc(lib, ctx, lib.rt_query_primary_shade(ctx, _ptr(items), n, ctypes.byref(shade)))
-    return res
+    return _pick_outputs(lib, ctx, work_items, want, SHADE_FIELDS, RTShade, lib.rt_query_primary_shade)
 
 
-def _gbuffer_wanted(want):
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in GBUFFER_FIELDS for w in want):
-        raise ValueError(f"want: a non-empty selection of {GBUFFER_FIELDS}")
-    return want
+def _one_element(res: dict) -> dict:
+    """pick_hit(i, j) / pick_colour(i, j): the single element of every array, t a float and index an int."""
+    one = {w: a[0] for w, a in res.items()}
+    if "t" in one:
+        one["t"] = float(one["t"])
+    if "index" in one:
+        one["index"] = int(one["index"])
+    return one
 
 
 def _render_gbuffer(lib, ctx, n: int, want, out, device: int):
     """HIPRaytracer.render_gbuffer: numpy arrays through rt_render_gbuffer, or - with `out` - torch tensors through
     rt_render_gbuffer_device on torch's current stream. n: the context's local work-items."""
-    want = _gbuffer_wanted(want)
+    want = _wanted(want, GBUFFER_FIELDS)
     if out is not None:
-        import torch
-        shapes = {"t": ((n,), torch.float32), "index": ((n,), torch.int32), "point": ((n, 4), torch.float32),
-                  "normal": ((n, 4), torch.float32), "albedo": ((n, 4), torch.float32)}
-        res, stream = {}, 0
-        for w in want:
-            shape, dtype = shapes[w]
-            given = out.get(w)
-            if not _is_tensor(given) or not given.is_cuda or given.dtype != dtype or not given.is_contiguous() or \
-                    given.numel() != int(np.prod(shape)) or (given.device.index is not None and given.device.index != device):
-                raise ValueError(f"out[{w!r}]: a contiguous {dtype} tensor of {int(np.prod(shape))} elements on the context's device")
-            res[w] = given
-            stream = _current_stream_of(given)
+        res = _device_outputs(n, want, out, GBUFFER_FIELDS, lambda t: t.is_cuda and t.device.index in (None, device), "the context's device")
         if n:
+            stream = _current_stream_of(res[want[-1]])
             gb = RTGBuffer(**{w: a.data_ptr() for w, a in res.items()})
             _check_rc(lib, ctx, lib.rt_render_gbuffer_device(ctx, ctypes.byref(gb), ctypes.c_void_p(stream) if stream else None))
         return res
-    shapes = {"t": ((n,), np.float32), "index": ((n,), np.int32), "point": ((n, 4), np.float32), "normal": ((n, 4), np.float32),
-              "albedo": ((n, 4), np.float32)}
-    res = {w: np.zeros(*shapes[w]) for w in want}
+    res, gb = _host_outputs(n, want, GBUFFER_FIELDS, RTGBuffer)
     if n:
-        gb = RTGBuffer(**{w: a.ctypes.data for w, a in res.items()})
         _check_rc(lib, ctx, lib.rt_render_gbuffer(ctx, ctypes.byref(gb)))
     return res
 
@@ -1154,13 +1114,7 @@ class HIPRaytracer:
             width = self._grid_width()
             if not width:
                 raise ValueError("pick_hit(i, j) needs a camera or a pose; with a plain ray buffer use pick_hit(work_items)")
-            res = _pick_hit(self._lib, self._ctx, [int(j) * width + int(i)], want)
-            one = {w: a[0] for w, a in res.items()}
-            if "t" in one:
-                one["t"] = float(one["t"])
-            if "index" in one:
-                one["index"] = int(one["index"])
-            return one
+            return _one_element(_pick_hit(self._lib, self._ctx, [int(j) * width + int(i)], want))
         return _pick_hit(self._lib, self._ctx, i, want)
 
     # -- shaded queries (hip_raytracer.h: the colour along rays that are not the frame's; the frame is untouched) ------------------
@@ -1183,12 +1137,7 @@ class HIPRaytracer:
             width = self._grid_width()
             if not width:
                 raise ValueError("pick_colour(i, j) needs a camera or a pose; with a plain ray buffer use pick_colour(work_items)")
-            res = _pick_shade(self._lib, self._ctx, [int(j) * width + int(i)], want)
-            one = {w: a[0] for w, a in res.items()}
-            if "t" in one:
-                one["t"] = float(one["t"])
-            if "index" in one:
-                one["index"] = int(one["index"])
+            one = _one_element(_pick_shade(self._lib, self._ctx, [int(j) * width + int(i)], want))
             return one["rgba"] if tuple(one) == ("rgba",) else one
         return _pick_shade(self._lib, self._ctx, i, want)
 
