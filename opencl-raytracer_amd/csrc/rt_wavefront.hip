@@ -1178,9 +1178,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WA
 #define RT_WALK3_REFILL_MIN RT_WALK2_REFILL_MIN
 #endif
 #ifndef RT_WALK3_TAKE_MIN
-#define RT_WALK3_TAKE_MIN RT_WALK3_REFILL_MIN  // idle lanes that make a prepare / take worth its round, where rays come from the stash. A take is
-#endif                             // a copy, and 4 / 8 / 12 are faster than 16 by ~0.15 ms per cfg4 frame - but 8 against 16 missed "every run faster
-                                   // than every run" in seven alternated runs by one pair (docs/LOG.md, first section): not kept
+#define RT_WALK3_TAKE_MIN 8        // idle lanes that make a prepare / take worth its round, where rays come from the stash (the mesh instances keep
+#endif                             // RT_WALK3_REFILL_MIN = 16). A take is a copy: 8 against 16, seven alternated runs, every run faster, medians
+                                   // -0.14 ms per cfg4 frame against a range of 0.06 (docs/LOG.md, first section; an earlier session's drift had hidden it)
 #ifndef RT_WALK3_DEFER_PENDING
 #define RT_WALK3_DEFER_PENDING 16  // exact tests of the block walk once this many lanes hold a candidate (a trip is ~300 instructions here, the
 #endif                             // test ~150): cfg4 frame with 8 / 12 / 16 / 24: 12.07 / 11.93 / 11.99 / 12.06 ms, 16 with half the lanes stuck: 11.92
@@ -1196,6 +1196,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WA
 #ifndef RT_STATS_TAIL
 #define RT_STATS_TAIL 0
 #endif
+#ifndef RT_STATS_STALLS
+#define RT_STATS_STALLS 0          // engineering build: the counted render's last column of [walk closest] (hand-out rounds) becomes the lane-trips
+#endif                             // that ended in a wait for the parking slot - each is followed by a second look at the same block
 #ifndef RT_BLOCK_SKIP_CAP
 #define RT_BLOCK_SKIP_CAP 8   // empty-space steps a lane takes per trip beyond the first (the other lanes of the wave wait for it)
 #endif
@@ -1263,6 +1266,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
 
     unsigned long long s_rays = 0, s_trips = 0, s_live = 0, s_fetch = 0, s_pre = 0, s_flush = 0, s_refill = 0;  // STATS only
     unsigned long long t_dry = 0; uint32_t my_trips = 0, max_trips = 0, trips_after = 0;  // STATS + RT_STATS_TAIL
+    unsigned long long s_stall = 0;  // STATS + RT_STATS_STALLS
     // The lane's state bits live in ONE vector register and are changed with vector and / or: as `bool`s carried round
     // the loop the compiler keeps them as 64-bit lane masks in scalar registers, and every merge of divergent paths costs
     // an andn2 / and / or triple per flag (round 2's walk: 0.75 scalar instructions per vector instruction).
@@ -1556,6 +1560,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
             }
             const uint32_t cell = (uint32_t)__builtin_fmaf(__builtin_fmaf(fz, wny_f, fy), wnx_f, fx);  // (whole numbers below 2^24: exact)
             cur = stalled != 0u ? (b | (back << 24)) : (adv ? cell : nxt);
+            if (STATS && RT_STATS_STALLS && stalled != 0u) ++s_stall;
         }
         // ---- the exact tests, when enough lanes wait for them ----
         const unsigned long long pending = __ballot((fl & kPend) != 0u);
@@ -1597,7 +1602,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
         if (lane == 0u) atomicMax(&acc[7], (unsigned long long)mt);
         const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), 0ull, 0ull};
 #else
-        const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), s_flush, s_refill};
+        const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), s_flush, RT_STATS_STALLS ? wave_sum64(s_stall) : s_refill};
 #endif
         if (lane == 0u)
             for (int j = 0; j < 8; ++j)
