@@ -80,7 +80,9 @@ extern "C" {
  *      Later addition, same version: compact records - rt_compact_info_t, rt_get_compact_info. Additions only; detect by dlsym of
  *      rt_get_compact_info.
  *      Later addition, same version: G-buffer frames - rt_gbuffer_t, rt_gbuffer_info_t, rt_render_gbuffer_device, rt_render_gbuffer,
- *      rt_get_gbuffer_info. Additions only; detect by dlsym of rt_render_gbuffer_device. */
+ *      rt_get_gbuffer_info. Additions only; detect by dlsym of rt_render_gbuffer_device.
+ *      Later addition, same version: the block walk's occupied range - rt_block_range_t, rt_get_block_range. Additions only; detect
+ *      by dlsym of rt_get_block_range. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -695,6 +697,22 @@ typedef struct rt_compact_info_t {
                                /* frame is not a literal one                                                                      */
 } rt_compact_info_t;
 int rt_get_compact_info(const rt_context* ctx, rt_compact_info_t* info);
+
+/* ---- the block walk's occupied range -------------------------------------------------------------------------------------------
+ * Closest-hit rays of a grid-able context walk a coarse grid of blocks over the grid's box - the objects' box united with the ray
+ * origins known to rt_create. A walk ends where its ray leaves the axis-aligned range of cells that hold an object, not where it
+ * leaves the box: no cell beyond that range can hold a hit. The range is taken at rt_create and holds for the context's life
+ * (moved objects are tested by every ray, hidden ones keep their cells). The environment variable RT_BLOCK_BOX_STOP=0, read by
+ * rt_create: the whole grid is the range - the same kernels, walks that end at the box (tests, A/B runs). */
+typedef struct rt_block_range_t {
+    uint32_t built;        /* the context has a block grid (else every other field is 0)                                          */
+    uint32_t whole_grid;   /* the range is the whole grid: RT_BLOCK_BOX_STOP=0, no occupied cell, or objects out to every face    */
+    int32_t cells[3];      /* cells of the grid proper along x, y, z                                                              */
+    int32_t lo[3], hi[3];  /* lowest and highest occupied cell along x, y, z (0 <= lo <= hi < cells)                              */
+    float cell;            /* cell edge                                                                                           */
+    float face_lo[3], face_hi[3];  /* the range's faces in view space, as the walks compute a cell wall: origin + cell * index    */
+} rt_block_range_t;
+int rt_get_block_range(const rt_context* ctx, rt_block_range_t* range);
 
 /* ---- replaceable visibility ----------------------------------------------------------------------------------------------------
  * Which of a live context's objects are in the picture: a viewer that deletes the object under the mouse, switches a layer off or

@@ -201,6 +201,7 @@ struct rt_context {
     bool degenerate_literal = false, lights_literal = false;
     std::vector<double> h_obj_bounds;
     rt::BlockGrid blocks = {};              // the closest-hit walk's coarse grid of 32-byte blocks (rt_grid.h: BlockGrid)
+    int32_t block_occ[6] = {0, 0, 0, -1, -1, -1};  // its occupied range in cells of the grid proper: lowest x, y, z, highest x, y, z (rt_get_block_range)
     uint4* d_walk_blocks = nullptr;
     uint32_t* d_walk_ids = nullptr;
     std::vector<float4> h_walk;             // the unified walk's records while they are being put together (rt_grid.h: GridDesc::walk_rec)

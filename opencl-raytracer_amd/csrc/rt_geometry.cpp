@@ -258,6 +258,27 @@ int rt_get_compact_info(const rt_context* c, rt_compact_info_t* info) {
     return RT_OK;
 }
 
+int rt_get_block_range(const rt_context* c, rt_block_range_t* range) {
+    if (!c || !range) return RT_ERR_INVALID_ARGUMENT;
+    *range = rt_block_range_t{};
+    const rt::BlockGrid& b = c->blocks;
+    if (!b.enabled) return RT_OK;
+    range->built = 1u;
+    const int32_t cells[3] = {b.nx, b.ny, b.nz};
+    bool whole = true;
+    for (int a = 0; a < 3; ++a) {
+        range->cells[a] = cells[a];
+        range->lo[a] = c->block_occ[a];
+        range->hi[a] = c->block_occ[3 + a];
+        whole = whole && range->lo[a] == 0 && range->hi[a] == cells[a] - 1;
+    }
+    range->whole_grid = whole ? 1u : 0u;
+    range->cell = b.cell;
+    range->face_lo[0] = b.occ.lox; range->face_lo[1] = b.occ.loy; range->face_lo[2] = b.occ.loz;
+    range->face_hi[0] = b.occ.hix; range->face_hi[1] = b.occ.hiy; range->face_hi[2] = b.occ.hiz;
+    return RT_OK;
+}
+
 int rt_get_geometry_info(const rt_context* c, rt_geometry_info_t* info) {
     if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
     *info = c->geo_info;

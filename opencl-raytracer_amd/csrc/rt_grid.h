@@ -30,6 +30,7 @@
 #pragma once
 
 #include "rt_device.h"
+#include "rt_walk_box.h"
 
 namespace rt {
 
@@ -112,8 +113,14 @@ struct BlockGrid {
                                // cfg4 12.2 -> 12.4 ms, cfg5 40 -> 48 ms without them)
     uint32_t serves_closest;   // this frame's closest-hit rays go through the block walk (set per frame by run_wavefront, 0 in the stored
                                // descriptor; it takes the struct's tail padding: no other offset moves)
+    WalkBox occ;               // faces of the axis-aligned range of OCCUPIED cells (rt_walk_box.h): a walk ends where its ray leaves it. Taken
+                               // when the table is built and valid for the context's life - nothing rebuilds the table: rt_set_transforms
+                               // puts a moved object on the always-list, which every ray tests, and rt_set_visibility only patches record
+                               // types. RT_BLOCK_BOX_STOP=0 (measurement knob), an empty table: the whole grid - the grid-box rule.
 };
-static_assert(sizeof(BlockGrid) == 96, "serves_closest sits in what was padding: the kernel arguments keep their offsets");
+// (24 bytes behind the earlier 96: the members of WfParams and WfBuffers that follow a BlockGrid move by 24; both are passed
+// by value and stay far below the 4 KiB of a kernel-argument block - rt_wavefront.hip asserts it)
+static_assert(sizeof(BlockGrid) == 120, "the occupied range sits behind serves_closest: nothing in front of it moves");
 constexpr uint32_t kBlockBorder = 2;
 #ifndef RT_BLOCK_ENTRIES
 #define RT_BLOCK_ENTRIES 7   // candidates a block holds (<= 7); 4 / 5 / 6 with their best cell edge: 13.11 / 12.86 / 12.74 vs 12.67 ms per cfg4 frame

@@ -230,6 +230,7 @@ int upload_walk_records(rt_context* c) {
 static int build_walk_blocks(rt_context* c, uint32_t n, const std::vector<Bound>& sph, const std::vector<double>& rg, double cell_fine,
                       const double glo[3], const double ghi[3], double K2) {
     c->blocks = rt::BlockGrid{};
+    for (int a = 0; a < 3; ++a) { c->block_occ[a] = 0; c->block_occ[3 + a] = -1; }
     SetupTrace lap("block grid");
     if (std::getenv("RT_NO_WALK3") || c->h_grid_pre.size() != n) return RT_OK;  // (measurement knob: the record walk)
     double factor = 1.67;
@@ -307,6 +308,26 @@ static int build_walk_blocks(rt_context* c, uint32_t n, const std::vector<Bound>
         }
     }
     lap("registration");
+    // The axis-aligned range of occupied cells, per axis of the grid proper (rt_walk_box.h: a walk ends where its ray leaves it).
+    // Nothing on a live context rebuilds these tables - rt_set_transforms puts a moved object on the always-list, rt_set_visibility
+    // only patches record types - so the range found here holds for the context's life. No occupied cell, or RT_BLOCK_BOX_STOP=0
+    // (measurement knob: the same kernels with the grid-box rule): the whole grid.
+    int occ_lo[3] = {dim[0], dim[1], dim[2]}, occ_hi[3] = {-1, -1, -1};
+    for (int z = 0; z < dim[2]; ++z)
+        for (int y = 0; y < dim[1]; ++y) {
+            const size_t row = cell_index(0, y, z);
+            int x0 = 0, x1 = dim[0] - 1;
+            while (x0 <= x1 && start[row + x0 + 1] == start[row + x0]) ++x0;
+            if (x0 > x1) continue;
+            while (start[row + x1 + 1] == start[row + x1]) --x1;
+            occ_lo[0] = std::min(occ_lo[0], x0); occ_hi[0] = std::max(occ_hi[0], x1);
+            occ_lo[1] = std::min(occ_lo[1], y); occ_hi[1] = std::max(occ_hi[1], y);
+            occ_lo[2] = std::min(occ_lo[2], z); occ_hi[2] = std::max(occ_hi[2], z);
+        }
+    bool box_stop = occ_hi[0] >= 0;
+    if (const char* env = std::getenv("RT_BLOCK_BOX_STOP")) box_stop = box_stop && env[0] != '0';
+    if (!box_stop)
+        for (int a = 0; a < 3; ++a) { occ_lo[a] = 0; occ_hi[a] = dim[a] - 1; }
     // blocks
     struct Enc { uint32_t word; uint32_t id; int s; };
     // Two sweeps over the cells, each on several threads: (1) every entry of a cell encoded on the finest of the four lattices that
@@ -448,10 +469,18 @@ static int build_walk_blocks(rt_context* c, uint32_t n, const std::vector<Bound>
     b.ids = c->d_walk_ids;
     b.none = c->n_objs;
     b.enabled = 1u;
+    // (the faces as the device computes a cell wall, lo + cell * i: the whole grid gives walk_begin's own box, bit for bit)
+    b.occ.lox = walk_box_face(lof[0], cellf, occ_lo[0]); b.occ.hix = walk_box_face(lof[0], cellf, occ_hi[0] + 1);
+    b.occ.loy = walk_box_face(lof[1], cellf, occ_lo[1]); b.occ.hiy = walk_box_face(lof[1], cellf, occ_hi[1] + 1);
+    b.occ.loz = walk_box_face(lof[2], cellf, occ_lo[2]); b.occ.hiz = walk_box_face(lof[2], cellf, occ_hi[2] + 1);
+    for (int a = 0; a < 3; ++a) { c->block_occ[a] = occ_lo[a]; c->block_occ[3 + a] = occ_hi[a]; }
     if (std::getenv("RT_WALK_STATS"))
         std::fprintf(stderr, "[blocks] %d x %d x %d cells, edge %g, %llu entries, %zu blocks (%llu chained), scale 0/1/2/3/whole-cell: %llu %llu %llu %llu %llu\n",
                      dim[0], dim[1], dim[2], (double)cellf, (unsigned long long)total, blocks.size() / 8, (unsigned long long)chain_blocks,
                      (unsigned long long)hist[0], (unsigned long long)hist[1], (unsigned long long)hist[2], (unsigned long long)hist[3], (unsigned long long)hist[4]);
+    if (std::getenv("RT_WALK_STATS"))
+        std::fprintf(stderr, "[blocks] occupied cells %d..%d x %d..%d x %d..%d%s\n", occ_lo[0], occ_hi[0], occ_lo[1], occ_hi[1], occ_lo[2], occ_hi[2],
+                     box_stop ? "" : " (the whole grid)");
     return RT_OK;
 }
 

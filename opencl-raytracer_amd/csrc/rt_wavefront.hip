@@ -99,6 +99,7 @@ struct WfParams {
                               // (no wf_begin, no queue to write and read back, no phase words - frames without padding work-items)
     uint32_t count_rays;  // instrumentation on
 };
+static_assert(sizeof(WfParams) + sizeof(void*) <= 4096, "passed by value, beside a pointer: a kernel-argument block holds 4 KiB");
 
 // Kernel prologue: the round's queues and their lengths, read from device memory (wave-uniform scalar loads; the
 // values were written by wf_advance, an earlier kernel of the same stream). False: the frame is past its rounds.
@@ -1199,6 +1200,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RT_WALK2_WA
 #ifndef RT_STATS_STALLS
 #define RT_STATS_STALLS 0          // engineering build: the counted render's last column of [walk closest] (hand-out rounds) becomes the lane-trips
 #endif                             // that ended in a wait for the parking slot - each is followed by a second look at the same block
+#ifndef RT_STATS_VOID
+#define RT_STATS_VOID 0            // engineering build: the last two columns of [walk closest] (exact rounds, hand-out rounds) become the wave-level
+#endif                             // passes of the empty-space loop and the walking lane-trips whose cell lies outside the occupied range;
+                                   // 2: the same counters while the prepared rays stop at the grid box - what the stop at the range removes
 #ifndef RT_BLOCK_SKIP_CAP
 #define RT_BLOCK_SKIP_CAP 8   // empty-space steps a lane takes per trip beyond the first (the other lanes of the wave wait for it)
 #endif
@@ -1267,6 +1272,7 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
     unsigned long long s_rays = 0, s_trips = 0, s_live = 0, s_fetch = 0, s_pre = 0, s_flush = 0, s_refill = 0;  // STATS only
     unsigned long long t_dry = 0; uint32_t my_trips = 0, max_trips = 0, trips_after = 0;  // STATS + RT_STATS_TAIL
     unsigned long long s_stall = 0;  // STATS + RT_STATS_STALLS
+    unsigned long long s_void_pass = 0, s_void_trips = 0;  // STATS + RT_STATS_VOID
     // The lane's state bits live in ONE vector register and are changed with vector and / or: as `bool`s carried round
     // the loop the compiler keeps them as 64-bit lane masks in scalar registers, and every merge of divergent paths costs
     // an andn2 / and / or triple per flag (round 2's walk: 0.75 scalar instructions per vector instruction).
@@ -1341,7 +1347,9 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                     fx = (float)(w0.ix + (int)kBlockBorder); fy = (float)(w0.iy + (int)kBlockBorder); fz = (float)(w0.iz + (int)kBlockBorder);
                     cur = ((uint32_t)(w0.iz + (int)kBlockBorder) * bg.wny + (uint32_t)(w0.iy + (int)kBlockBorder)) * bg.wnx + (uint32_t)(w0.ix + (int)kBlockBorder);
                     tx = w0.tx; ty = w0.ty; tz = w0.tz; dtx = w0.dtx; dty = w0.dty; dtz = w0.dtz;
-                    t_stop = __builtin_fminf(w0.t_exit + 0.25f * dmin, 3.0e38f);
+                    // (the walk ends where the ray leaves the occupied cells - rt_walk_box.h - with walk_begin's reciprocals made anew: this
+                    // runs once per ray, in lanes whose walk registers are free)
+                    t_stop = walk_box_stop(w0.t_exit, walk_box_exit(rsx, rsy, rsz, rdx, rdy, rdz, __builtin_amdgcn_rcpf(rdx), __builtin_amdgcn_rcpf(rdy), __builtin_amdgcn_rcpf(rdz), bg.occ), dmin);
                 }
                 {   // objects every ray must test (usually none); a ray the walk is not made for tests them all
                     const uint32_t n_loop = brute ? w.rp.scene.n_objs : g.n_always;
@@ -1430,7 +1438,14 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                     stash[SF_FZ][sl] = __float_as_uint((float)(w0.iz + (int)kBlockBorder));
                     stash[SF_TX][sl] = __float_as_uint(w0.tx); stash[SF_TY][sl] = __float_as_uint(w0.ty); stash[SF_TZ][sl] = __float_as_uint(w0.tz);
                     stash[SF_DTX][sl] = __float_as_uint(w0.dtx); stash[SF_DTY][sl] = __float_as_uint(w0.dty); stash[SF_DTZ][sl] = __float_as_uint(w0.dtz);
-                    stash[SF_TSTOP][sl] = __float_as_uint(__builtin_fminf(w0.t_exit + 0.25f * dmin, 3.0e38f));
+                    // The walk ends where the ray leaves the occupied cells (rt_walk_box.h), if that is before the grid box's far side. (The
+                    // six faces go through an empty asm, as the grid box above: made here, not kept in registers across the loop. The
+                    // reciprocals are walk_begin's - the same instruction on the same operands, which the compiler merges.)
+                    WalkBox ob = bg.occ;
+                    asm volatile("" : "+s"(ob.lox), "+s"(ob.loy), "+s"(ob.loz), "+s"(ob.hix), "+s"(ob.hiy), "+s"(ob.hiz));
+                    const float t_box = walk_box_exit(ray.sx, ray.sy, ray.sz, ray.dx, ray.dy, ray.dz, __builtin_amdgcn_rcpf(ray.dx), __builtin_amdgcn_rcpf(ray.dy),
+                                                      __builtin_amdgcn_rcpf(ray.dz), ob);
+                    stash[SF_TSTOP][sl] = __float_as_uint(walk_box_stop(w0.t_exit, RT_STATS_VOID == 2 ? 3.0e38f : t_box, dmin));
                     stash[SF_DONE][sl] = (w.first_round == 0u) ? note : 0xffffffffu;
                 }
             }
@@ -1495,6 +1510,11 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
         // ---- one trip: the block under the cursor ----
         const bool walking = (fl & (kAlive | kOver)) == kAlive;
         uint32_t stalled = 0u;
+        uint32_t skip_passes = 0u;  // STATS + RT_STATS_VOID: this lane's passes of the empty-space loop in this trip
+        if (STATS && RT_STATS_VOID && walking) {  // (a cell's centre is half a cell from every face of the range: no rounding can misplace it)
+            const float ccx = __builtin_fmaf(fx, bg.cell, bg.c0x), ccy = __builtin_fmaf(fy, bg.cell, bg.c0y), ccz = __builtin_fmaf(fz, bg.cell, bg.c0z);
+            if (ccx < bg.occ.lox || ccx > bg.occ.hix || ccy < bg.occ.loy || ccy > bg.occ.hiy || ccz < bg.occ.loz || ccz > bg.occ.hiz) ++s_void_trips;
+        }
         if (STATS) { if (lane == 0u) { ++s_trips; s_live += (unsigned long long)__popcll(live); } if (walking) { s_pre += kBlockEntries; ++my_trips; max_trips = my_trips > max_trips ? my_trips : max_trips; if ((cur & 0xffffffu) < bg.n_cells) ++s_fetch; } if (RT_STATS_TAIL && t_dry == 0 && next >= seg_end && !more) t_dry = wall_clock64(); if (t_dry != 0) ++trips_after; }
         if (walking) {
             const uint32_t b = cur & 0xffffffu, pos = cur >> 24;
@@ -1556,12 +1576,16 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
                     const bool out = tm > limit;
                     fl |= out ? kOver : 0u;
                     more = out ? 0u : more - 1u;
+                    if (STATS && RT_STATS_VOID) ++skip_passes;
                 }
             }
             const uint32_t cell = (uint32_t)__builtin_fmaf(__builtin_fmaf(fz, wny_f, fy), wnx_f, fx);  // (whole numbers below 2^24: exact)
             cur = stalled != 0u ? (b | (back << 24)) : (adv ? cell : nxt);
             if (STATS && RT_STATS_STALLS && stalled != 0u) ++s_stall;
         }
+        if (STATS && RT_STATS_VOID)  // the wave runs the loop as often as the lane that needs it most
+            for (uint32_t p = 1u; p <= (uint32_t)RT_BLOCK_SKIP_CAP; ++p)
+                if (__ballot(skip_passes >= p) != 0ull && lane == 0u) ++s_void_pass;
         // ---- the exact tests, when enough lanes wait for them ----
         const unsigned long long pending = __ballot((fl & kPend) != 0u);
         if (pending != 0ull) {
@@ -1602,7 +1626,8 @@ __device__ __forceinline__ void block_segment(const WfParams& w, const uint32_t*
         if (lane == 0u) atomicMax(&acc[7], (unsigned long long)mt);
         const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), 0ull, 0ull};
 #else
-        const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), s_flush, RT_STATS_STALLS ? wave_sum64(s_stall) : s_refill};
+        const unsigned long long v[8] = {wave_sum64(s_rays), s_trips, s_live, wave_sum64(s_fetch), wave_sum64(s_pre), wave_sum64(tested), RT_STATS_VOID ? s_void_pass : s_flush,
+                                         RT_STATS_VOID ? wave_sum64(s_void_trips) : (RT_STATS_STALLS ? wave_sum64(s_stall) : s_refill)};
 #endif
         if (lane == 0u)
             for (int j = 0; j < 8; ++j)
@@ -1623,7 +1648,9 @@ __device__ __forceinline__ bool closest_hit_blocks(const BlockGrid& bg, const Gr
     const float dmin = __builtin_fminf(__builtin_fminf(w0.dtx, w0.dty), w0.dtz);
     if (!(dd > 1.0e-30f && dd < 1.0e30f && w0.t_enter <= 4096.f * dmin)) return false;
     const float slack = kWalkSlackCells * bg.cell * __builtin_amdgcn_rsqf(dd) * 1.0001f;
-    const float t_stop = __builtin_fminf(w0.t_exit + 0.25f * dmin, 3.0e38f);
+    // (block_segment's stop, through the same helper: the two block walks visit the same cells)
+    const float t_stop = walk_box_stop(w0.t_exit, walk_box_exit(ray.sx, ray.sy, ray.sz, ray.dx, ray.dy, ray.dz, __builtin_amdgcn_rcpf(ray.dx),
+                                                               __builtin_amdgcn_rcpf(ray.dy), __builtin_amdgcn_rcpf(ray.dz), bg.occ), dmin);
     float fx = (float)(w0.ix + (int)kBlockBorder), fy = (float)(w0.iy + (int)kBlockBorder), fz = (float)(w0.iz + (int)kBlockBorder);
     float tx = w0.tx, ty = w0.ty, tz = w0.tz;
     const float wnx_f = (float)bg.wnx, wny_f = (float)bg.wny;

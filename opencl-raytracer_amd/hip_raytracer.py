@@ -51,6 +51,7 @@ EXPORTS = [
     "rt_query_hits_device", "rt_query_hits", "rt_query_primary_hits",
     "rt_query_shade_device", "rt_query_shade", "rt_query_primary_shade", "rt_get_query_shade_info",
     "rt_get_compact_info",
+    "rt_get_block_range",
     "rt_render_gbuffer_device", "rt_render_gbuffer", "rt_get_gbuffer_info",
 ]
 
@@ -153,6 +154,15 @@ class RTCompactInfo(ctypes.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RTBlockRange(ctypes.Structure):
+    _fields_ = [("built", ctypes.c_uint32), ("whole_grid", ctypes.c_uint32), ("cells", ctypes.c_int32 * 3), ("lo", ctypes.c_int32 * 3),
+                ("hi", ctypes.c_int32 * 3), ("cell", ctypes.c_float), ("face_lo", ctypes.c_float * 3), ("face_hi", ctypes.c_float * 3)]
+
+    def as_dict(self):
+        return dict(built=int(self.built), whole_grid=int(self.whole_grid), cells=list(self.cells), lo=list(self.lo), hi=list(self.hi),
+                    cell=float(self.cell), face_lo=list(self.face_lo), face_hi=list(self.face_hi))
 
 
 class RTQueryInfo(ctypes.Structure):
@@ -403,6 +413,9 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
     if hasattr(lib, "rt_get_compact_info"):  # (the same: a build from before compact records)
         lib.rt_get_compact_info.restype = i32
         lib.rt_get_compact_info.argtypes = [vp, ctypes.POINTER(RTCompactInfo)]
+    if hasattr(lib, "rt_get_block_range"):  # (the same: a build from before the occupied range)
+        lib.rt_get_block_range.restype = i32
+        lib.rt_get_block_range.argtypes = [vp, ctypes.POINTER(RTBlockRange)]
     if hasattr(lib, "rt_render_gbuffer_device"):  # (the same: a build from before G-buffer frames)
         lib.rt_render_gbuffer_device.restype = i32
         lib.rt_render_gbuffer_device.argtypes = [vp, ctypes.POINTER(RTGBuffer), vp]
@@ -1033,6 +1046,13 @@ class HIPRaytracer:
         through the round machine reads the compact records; 0: the full records)."""
         info = RTCompactInfo()
         self._check(self._lib.rt_get_compact_info(self._ctx, ctypes.byref(info)))
+        return info.as_dict()
+
+    def block_range(self) -> dict:
+        """rt_get_block_range: the block walk's grid (built, cells, cell) and the range of its occupied cells (lo, hi per axis,
+        face_lo, face_hi in view space; whole_grid: a walk ends at the grid box). Closest-hit walks end where a ray leaves it."""
+        info = RTBlockRange()
+        self._check(self._lib.rt_get_block_range(self._ctx, ctypes.byref(info)))
         return info.as_dict()
 
     def geometry_info(self) -> dict:
