@@ -82,7 +82,9 @@ extern "C" {
  *      Later addition, same version: G-buffer frames - rt_gbuffer_t, rt_gbuffer_info_t, rt_render_gbuffer_device, rt_render_gbuffer,
  *      rt_get_gbuffer_info. Additions only; detect by dlsym of rt_render_gbuffer_device.
  *      Later addition, same version: the block walk's occupied range - rt_block_range_t, rt_get_block_range. Additions only; detect
- *      by dlsym of rt_get_block_range. */
+ *      by dlsym of rt_get_block_range.
+ *      Later addition, same version: ambient-occlusion frames - rt_ao_params_t, rt_ao_t, rt_ao_info_t, rt_ao_device, rt_ao,
+ *      rt_render_ao_device, rt_render_ao, rt_get_ao_info. Additions only; detect by dlsym of rt_render_ao_device. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -1020,6 +1022,64 @@ typedef struct rt_gbuffer_info_t {
 int rt_render_gbuffer_device(rt_context* ctx, const rt_gbuffer_t* d_out, void* hip_stream);
 int rt_render_gbuffer(rt_context* ctx, const rt_gbuffer_t* out);          /* host arrays, synchronous */
 int rt_get_gbuffer_info(rt_context* ctx, rt_gbuffer_info_t* info);        /* RT_ERR_STATE before the first pass */
+
+/* ---- ambient-occlusion frames ------------------------------------------------------------------------------------------------------
+ * The first CONSUMER of a G-buffer: K occlusion rays per work-item, started at its hit point along directions of a caller's table on
+ * the normal's side, traced and counted in ONE kernel (csrc/rt_ao.hip) - instead of a G-buffer pass, n * K rays of 32 bytes built by
+ * the caller, rt_query_occluded_device and a reduction. ao.py (rays, reduce) is the executable definition.
+ *
+ * Per item i: point[i] and normal[i] (float4, as rt_gbuffer_t / rt_hits_t deliver them) and, optionally, index[i] (int32; NULL: every
+ * item may be live). The item's global work-item number g is i for rt_ao*; for rt_render_ao* it is the shard's global index (the
+ * mapping of rt_set_shard), so that a sharded frame equals the unsharded one item for item.
+ *   live       index[i] >= 0 (where index is given) and point.xyz, normal.xyz all finite. A dead item traces nothing, reads
+ *              unoccluded = K and ao = 1.0f, and enters no counter.
+ *   set        h = (uint32)g * 0x9E3779B1u (mod 2^32), set = (h >> 16) % n_sets.
+ *   sample k   d = dirs[set * K + k].xyz; s = (d.x * n.x + d.y * n.y) + d.z * n.z; if s < 0 then d = -d (a NaN or zero s keeps d);
+ *              start.c = p.c + (bias * n.c) for c = x, y, z; start.w = 1; direction = (d, 0). All fp32, every product and sum
+ *              rounded, nothing contracted, in every arithmetic mode. The library neither normalises nor scales a direction: its
+ *              LENGTH IS THE OCCLUSION RADIUS, as for every occlusion query (something on start .. start + direction).
+ *   result     unoccluded[i] = K - sum over k of occluded(ray(i, k)), a uint8; occluded is exactly rt_query_occluded's answer for that
+ *              ray on this context: the per-ray route ("ray queries"), the grid's any-hit walk on the grid, off it - literal
+ *              contexts, a start outside the box, contexts without a grid - the ordered loop with !(T >= 1 || T < 0).
+ *              ao[i] = (float)unoccluded[i] * (1.0f / K), exact for these K.
+ * The normal is the reference's (mv * (n, 0), not the inverse transpose) and is NOT turned towards the viewer: a non-uniformly scaled
+ * sphere can occlude some of its own samples. That is the reference's geometry.
+ *
+ * rt_ao_params_t: samples K is one of 1, 2, 4, 8, 16, 32, 64; n_sets 1 .. 4096; bias finite and >= 0; reserved 0; dirs n_sets * K
+ * float4 (w ignored), 16-byte aligned - device memory for the _device forms, host memory for the twins, which stage it through the
+ * context's grow-only patch buffer as the query twins stage their rays. rt_ao_t: each member may be NULL, not both; ao 4-byte
+ * aligned, unoccluded of any alignment. Outputs must not overlap inputs.
+ *
+ * rt_ao_device: the pass alone on n items of the caller's, any n; point and normal 16-byte aligned, index 4-byte aligned. It touches
+ * only the caller's outputs and a counter block of its own, is asynchronous (no host synchronisation; NULL is the legacy default
+ * stream) and works on a context of any rt_kernel, also one without primary rays. rt_ao: its host twin, synchronous.
+ * rt_render_ao_device: rt_local_rays() elements in rt_render_device's order - per SAMPLE under supersampling, per shard when sharded.
+ * It runs the G-buffer pass ("G-buffer frames") into context-owned, grow-only staging (index, point, normal), then the AO kernel on
+ * the same stream; stream semantics are rt_render_gbuffer_device's; nothing is allocated after the first call of a size. The frame
+ * is left alone exactly as the G-buffer pass leaves it, and rt_get_gbuffer_info afterwards describes the internal pass. The staging is
+ * the CONTEXT's: order two passes of one context on different streams, as two renders. rt_render_ao: the host twin, synchronous.
+ * rt_get_ao_info: the LAST pass of either kind; waits for it. n_grid + n_brute == n_rays == K * n_live; gbuffer_ms is 0 for rt_ao*.
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: a NULL params or out struct, both outputs NULL, another K, n_sets outside
+ * 1 .. 4096, a bias that is negative or not finite, reserved != 0, NULL dirs, NULL point or normal with n != 0, a misaligned device
+ * pointer. RT_ERR_STATE: a context with triangles (the queries' reason); rt_render_ao* without primary rays; rt_get_ao_info before the
+ * first pass. n == 0 or rt_local_rays() == 0 returns RT_OK with nothing launched.
+ *
+ * NOT part of this call: cosine weights or normalisation inside the library; turning the normal to the viewer; bent normals; a
+ * filtered result under supersampling; byte or _multi forms; fusing the G-buffer's record kernel into the AO kernel; refilling idle
+ * lanes; contexts with triangles. */
+typedef struct rt_ao_params_t { uint32_t samples, n_sets; float bias; uint32_t reserved; const void* dirs; } rt_ao_params_t;
+typedef struct rt_ao_t { uint8_t* unoccluded; float* ao; } rt_ao_t;                /* each may be NULL, not both */
+typedef struct rt_ao_info_t {
+    uint64_t n_items, n_live, n_rays, n_grid, n_brute, object_tests;  /* items of the pass, the live ones, rays, rays per route, exact tests */
+    double   gbuffer_ms, ao_ms;                                       /* event pairs around the internal G-buffer pass and the AO kernel */
+} rt_ao_info_t;
+int rt_ao_device(rt_context* ctx, const float* d_point, const float* d_normal, const int32_t* d_index, uint64_t n,
+                 const rt_ao_params_t* params, const rt_ao_t* d_out, void* hip_stream);   /* the pass alone, any n, asynchronous */
+int rt_ao(rt_context* ctx, const float* point, const float* normal, const int32_t* index, uint64_t n, const rt_ao_params_t* params,
+          const rt_ao_t* out);
+int rt_render_ao_device(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_t* d_out, void* hip_stream);  /* G-buffer pass + the pass */
+int rt_render_ao(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_t* out);
+int rt_get_ao_info(rt_context* ctx, rt_ao_info_t* info);                  /* RT_ERR_STATE before the first pass */
 
 void rt_destroy(rt_context* ctx);
 

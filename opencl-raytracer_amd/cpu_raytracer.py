@@ -291,6 +291,26 @@ class CPURaytracer:
             raise ValueError("cpu_rt_render_gbuffer: unsupported arguments (triangle records are a HIP-backend extension)")
         return {"t": t, "index": index, "point": point, "normal": normal, "albedo": albedo}
 
+    # -- ambient-occlusion frames: the composition HIPRaytracer.render_ao is defined as (ao.py) ----------------------------------------
+    def ao_pass(self, point, normal, index, dirs, samples: int, bias: float = 1e-3, items=None):
+        """{"unoccluded": uint8[n], "ao": float32[n]} for items of the caller's: ao.rays -> query_occluded over the rays of the live
+        items -> ao.reduce. The definition of HIPRaytracer.ao_pass in the default arithmetic; `items`: the global work-item
+        numbers that choose the sets (None: 0 .. n - 1)."""
+        from . import ao as AO
+        rays, live = AO.rays(point, normal, index, dirs, samples, bias, items)
+        occluded = np.zeros(len(rays), dtype=np.uint8)
+        traced = np.repeat(live, samples)
+        if traced.any():
+            occluded[traced] = self.query_occluded(np.ascontiguousarray(rays[traced]))
+        unoccluded, ao = AO.reduce(occluded, live, samples)
+        return {"unoccluded": unoccluded, "ao": ao}
+
+    def render_ao(self, dirs, samples: int, bias: float = 1e-3):
+        """Ambient occlusion of every ray of this object, in ray order: render_gbuffer -> ao_pass. The definition of
+        HIPRaytracer.render_ao (unsharded, in the default arithmetic) that runs without a GPU."""
+        g = self.render_gbuffer()
+        return self.ao_pass(g["point"], g["normal"], g["index"], dirs, samples, bias)
+
     def Render(self) -> np.ndarray:
         n = len(self.rays)
         n_out = n // (self.supersample * self.supersample) if self.supersample in (2, 3, 4) else n

@@ -20,6 +20,7 @@
 #include "rt_visibility.h"
 #include "rt_query.h"
 #include "rt_gbuffer.h"
+#include "rt_ao.h"
 #include "rt_compact.h"
 
 #include <hip/hip_runtime.h>
@@ -300,6 +301,14 @@ struct rt_context {
     hipEvent_t ev_gb_trace[2] = {};
     uint64_t gb_items = 0;
     bool gb_wavefront = false;
+    // Ambient-occlusion frames (rt_ao*, rt_render_ao*; rt_query_host.cpp, rt_render.cpp): the slot of the pass (rt::AoCounters), the items
+    // of the last one, whether it was a frame form and then the event pair around its internal G-buffer pass. The frame forms stage that
+    // pass's index, point and normal in d_gb_index / d_gb_point / d_gb_normal (the G-buffer host twin's, which is synchronous); the host
+    // twins stage the direction table and their results in d_patch_stage.
+    rt::host::CountedSlot ao{sizeof(rt::AoCounters)};
+    hipEvent_t ev_ao_gbuffer[2] = {};
+    uint64_t ao_items = 0;
+    bool ao_frame = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -529,6 +538,13 @@ struct OutputMember { const void* p; uintptr_t align; };
 int check_outputs(rt_context* c, const void* o, std::initializer_list<OutputMember> members, bool device, const char* scalars_misaligned,
                   const char* vectors_misaligned);
 int refuse_no_primary_rays(rt_context* c);
+// Ambient occlusion (rt_query_host.cpp; the frame forms are rt_render.cpp's). check_ao: what every form refuses of its parameter and
+// output structs (`device`: dirs and the outputs are device pointers, whose alignment the kernel needs); refuse_ao_context: a context with
+// triangles. enqueue_ao: one pass over `shard.n_local` items on `stream`, every pointer device memory; asynchronous.
+int check_ao(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* out, bool device);
+int refuse_ao_context(rt_context* c);
+int enqueue_ao(rt_context* c, const rt::GBufferShard& shard, const float* d_point, const float* d_normal, const int32_t* d_index,
+               const rt_ao_params_t& params, const rt_ao_t& d_out, hipStream_t stream);
 // The device copies of a host form's wanted outputs and their way back: select() hands out the device array of a wanted member (a
 // null host pointer: not wanted, null), finish() copies every selected array to its host array on `stream` and waits for the stream.
 struct CopyBack {
@@ -542,6 +558,10 @@ struct CopyBack {
     }
     int finish(rt_context* c, hipStream_t stream) const;
 };
+// A host form of the ambient-occlusion pass: its direction table (copied on `stream`), the wanted results (selected in `back`) and
+// `extra` bytes of the caller's own (16-byte aligned, at d_extra) behind one another in the patch buffer; d_params / d_out are the device forms' arguments.
+int stage_ao_host(rt_context* c, const rt_ao_params_t& params, const rt_ao_t& out, uint64_t n, size_t extra, hipStream_t stream,
+                  rt_ao_params_t& d_params, rt_ao_t& d_out, CopyBack& back, char*& d_extra);
 // rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched

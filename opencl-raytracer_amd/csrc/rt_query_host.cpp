@@ -1,7 +1,8 @@
 // rt_query_host.cpp - ray queries (hip_raytracer.h): rt_query_closest_device, rt_query_occluded_device, their host twins
 // rt_query_closest / rt_query_occluded, rt_query_primary, the hit-record queries rt_query_hits_device / rt_query_hits /
 // rt_query_primary_hits, the shaded queries rt_query_shade_device / rt_query_shade / rt_query_primary_shade with their own
-// rt_get_query_shade_info, and rt_get_query_info. A query reads the context's object records and grid as
+// rt_get_query_shade_info, and rt_get_query_info; and the ambient-occlusion pass on items of the caller's, rt_ao_device / rt_ao with
+// rt_get_ao_info (its frame forms are rt_render.cpp's). A query reads the context's object records and grid as
 // the setters have left them and writes the caller's outputs and the context's counter block - nothing of the frame: not its rays,
 // camera, pose, shard, supersampling factor, aux buffers or state buffers. The device forms enqueue a memset, two event records and one
 // kernel (rt_query.hip) and return; after the first call, which makes the counter block and the events, nothing is allocated.
@@ -324,6 +325,74 @@ int check_outputs(rt_context* c, const void* o, std::initializer_list<OutputMemb
     return RT_OK;
 }
 
+// ---- ambient occlusion (hip_raytracer.h, "ambient-occlusion frames"; the frame form is rt_render.cpp's) ---------------------------------
+int check_ao(rt_context* c, const rt_ao_params_t* p, const rt_ao_t* o, bool device) {
+    if (!p) return fail(c, RT_ERR_INVALID_ARGUMENT, "the parameter struct is NULL");
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    if (!o->unoccluded && !o->ao) return fail(c, RT_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    if (p->samples == 0 || p->samples > 64 || (p->samples & (p->samples - 1u)))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "samples is one of 1, 2, 4, 8, 16, 32, 64");
+    if (p->n_sets < 1 || p->n_sets > 4096) return fail(c, RT_ERR_INVALID_ARGUMENT, "n_sets is 1 .. 4096");
+    if (!(p->bias >= 0.f) || !std::isfinite(p->bias)) return fail(c, RT_ERR_INVALID_ARGUMENT, "bias must be finite and not negative");
+    if (p->reserved != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    if (!p->dirs) return fail(c, RT_ERR_INVALID_ARGUMENT, "the direction table is NULL");
+    if (!device) return RT_OK;
+    if (reinterpret_cast<uintptr_t>(p->dirs) & 15u) return fail(c, RT_ERR_INVALID_ARGUMENT, "the direction table must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(o->ao) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "ao must be 4-byte aligned");
+    return RT_OK;
+}
+
+int refuse_ao_context(rt_context* c) {
+    if (c->has_triangles)
+        return fail(c, RT_ERR_STATE, "ambient occlusion on a context with triangle records: its rays are occlusion queries, and the ordered "
+                                     "loop over the pair stream does not know type 2");
+    return RT_OK;
+}
+
+int enqueue_ao(rt_context* c, const rt::GBufferShard& shard, const float* d_point, const float* d_normal, const int32_t* d_index,
+               const rt_ao_params_t& p, const rt_ao_t& d_out, hipStream_t stream) {
+    const int rc = enqueue_counted(c, c->ao, stream, "ambient-occlusion launch", [&] {
+        const QueryInputs q(c);
+        const rt::AoInputs in{reinterpret_cast<const float4*>(d_point), reinterpret_cast<const float4*>(d_normal), d_index,
+                              static_cast<const float4*>(p.dirs),      p.samples, p.n_sets, p.bias, 1.0f / (float)p.samples};
+        return rt::launch_ao(q.scene, q.grid, q.box, q.arith, shard, in, rt::AoOutputs{d_out.unoccluded, d_out.ao},
+                             static_cast<rt::AoCounters*>(c->ao.d_counters), stream);
+    });
+    if (rc) return rc;
+    c->ao_items = shard.n_local;
+    return RT_OK;
+}
+
+int stage_ao_host(rt_context* c, const rt_ao_params_t& p, const rt_ao_t& out, uint64_t n, size_t extra, hipStream_t stream,
+                  rt_ao_params_t& d_p, rt_ao_t& d_out, CopyBack& back, char*& d_extra) {
+    const size_t dirs_bytes = (size_t)p.n_sets * p.samples * 16u;
+    const size_t off_unoccluded = dirs_bytes, off_ao = off_unoccluded + align16((size_t)n), off_extra = off_ao + align16((size_t)n * sizeof(float));
+    if (const int rc = ensure_patch_stage(c, off_extra + extra)) return rc;
+    char* const base = static_cast<char*>(c->d_patch_stage.p);
+    RT_HIP(c, hipMemcpyAsync(base, p.dirs, dirs_bytes, hipMemcpyHostToDevice, stream));
+    d_p = p;
+    d_p.dirs = base;
+    d_out.unoccluded = back.select<uint8_t>(out.unoccluded, base + off_unoccluded, (size_t)n);
+    d_out.ao = back.select<float>(out.ao, base + off_ao, (size_t)n * sizeof(float));
+    d_extra = base + off_extra;
+    return RT_OK;
+}
+
+namespace {
+
+// what rt_ao_device and rt_ao refuse of (point, normal, index, n); nothing is touched
+int check_ao_items(rt_context* c, const float* point, const float* normal, const int32_t* index, uint64_t n, bool device) {
+    if (n != 0 && (!point || !normal)) return fail(c, RT_ERR_INVALID_ARGUMENT, "point or normal is NULL with a non-zero count");
+    if (n > (std::numeric_limits<size_t>::max)() / 64u) return fail(c, RT_ERR_INVALID_ARGUMENT, "too many items");
+    if (!device) return RT_OK;
+    if ((reinterpret_cast<uintptr_t>(point) | reinterpret_cast<uintptr_t>(normal)) & 15u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "point and normal must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(index) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "index must be 4-byte aligned");
+    return RT_OK;
+}
+
+}  // namespace
+
 int refuse_no_primary_rays(rt_context* c) {
     if (!c->pinhole && !c->have_rays)
         return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
@@ -473,6 +542,62 @@ int rt_get_query_shade_info(rt_context* c, rt_query_shade_info_t* info) {
     info->rays_traced = ctr.traced;
     info->rays_reference = ctr.reference;
     info->object_tests = ctr.q.tests;
+    return RT_OK;
+}
+
+int rt_ao_device(rt_context* c, const float* d_point, const float* d_normal, const int32_t* d_index, uint64_t n, const rt_ao_params_t* params,
+                 const rt_ao_t* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_ao(c, params, d_out, true)) return rc;
+    if (const int rc = check_ao_items(c, d_point, d_normal, d_index, n, true)) return rc;
+    if (const int rc = refuse_ao_context(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    c->ao_frame = false;
+    return enqueue_ao(c, rt::GBufferShard{n, n, 1, 0, 1}, d_point, d_normal, d_index, *params, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host twin: items, table and results staged in the patch buffer on the context's stream; synchronous
+int rt_ao(rt_context* c, const float* point, const float* normal, const int32_t* index, uint64_t n, const rt_ao_params_t* params, const rt_ao_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_ao(c, params, out, false)) return rc;
+    if (const int rc = check_ao_items(c, point, normal, index, n, false)) return rc;
+    if (const int rc = refuse_ao_context(c)) return rc;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    hipStream_t stream = c->stream;
+    const size_t vec_bytes = (size_t)n * 16u, index_bytes = (size_t)n * sizeof(int32_t);
+    rt_ao_params_t d_params;
+    rt_ao_t d_out;
+    CopyBack back;
+    char* d_items = nullptr;
+    if (const int rc = stage_ao_host(c, *params, *out, n, 2 * vec_bytes + index_bytes, stream, d_params, d_out, back, d_items)) return rc;
+    RT_HIP(c, hipMemcpyAsync(d_items, point, vec_bytes, hipMemcpyHostToDevice, stream));
+    RT_HIP(c, hipMemcpyAsync(d_items + vec_bytes, normal, vec_bytes, hipMemcpyHostToDevice, stream));
+    if (index) RT_HIP(c, hipMemcpyAsync(d_items + 2 * vec_bytes, index, index_bytes, hipMemcpyHostToDevice, stream));
+    c->ao_frame = false;
+    if (const int rc = enqueue_ao(c, rt::GBufferShard{n, n, 1, 0, 1}, reinterpret_cast<const float*>(d_items),
+                                  reinterpret_cast<const float*>(d_items + vec_bytes),
+                                  index ? reinterpret_cast<const int32_t*>(d_items + 2 * vec_bytes) : nullptr, d_params, d_out, stream))
+        return rc;
+    return back.finish(c, stream);
+}
+
+int rt_get_ao_info(rt_context* c, rt_ao_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->ao.made) return fail(c, RT_ERR_STATE, "rt_get_ao_info: no ambient-occlusion pass has been made on this context");
+    RT_DEVICE(c);
+    rt::AoCounters ctr = {};
+    if (const int rc = read_counted(c, c->ao, &ctr, &info->ao_ms)) return rc;
+    float gbuffer = 0.f;
+    if (c->ao_frame) RT_HIP(c, hipEventElapsedTime(&gbuffer, c->ev_ao_gbuffer[0], c->ev_ao_gbuffer[1]));  // (before the kernel: it has ended)
+    info->n_items = c->ao_items;
+    info->n_live = ctr.n_live;
+    info->n_rays = ctr.q.n_rays;
+    info->n_grid = ctr.q.n_grid;
+    info->n_brute = ctr.q.n_brute;
+    info->object_tests = ctr.q.tests;
+    info->gbuffer_ms = (double)gbuffer;
     return RT_OK;
 }
 

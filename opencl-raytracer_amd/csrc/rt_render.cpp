@@ -599,4 +599,61 @@ int rt_get_gbuffer_info(rt_context* c, rt_gbuffer_info_t* info) {
     return RT_OK;
 }
 
+// ---- ambient-occlusion frames (hip_raytracer.h): the G-buffer pass into context-owned staging, then the AO kernel on the same stream ----
+// Every pointer of d_params / d_out is device memory; the refusals are made. c->shard.n_local > 0.
+static int enqueue_ao_frame(rt_context* c, const rt_ao_params_t& d_params, const rt_ao_t& d_out, hipStream_t stream) {
+    const Shard& sh = c->shard;
+    const size_t n = (size_t)sh.n_local;
+    for (hipEvent_t& e : c->ev_ao_gbuffer)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    if (const int rc = ensure_counted(c, c->ao)) return rc;
+    int rc = c->d_gb_index.grow(c, n * sizeof(int32_t));
+    if (rc == RT_OK) rc = c->d_gb_point.grow(c, n * 16);
+    if (rc == RT_OK) rc = c->d_gb_normal.grow(c, n * 16);
+    if (rc) return rc;
+    c->ao.made = false;  // until this pass is enqueued whole: rt_get_ao_info never pairs events of two passes
+    c->ao_frame = true;
+    const rt_gbuffer_t records{nullptr, static_cast<int32_t*>(c->d_gb_index.p), static_cast<float*>(c->d_gb_point.p),
+                               static_cast<float*>(c->d_gb_normal.p), nullptr};
+    RT_HIP(c, hipEventRecord(c->ev_ao_gbuffer[0], stream));
+    if ((rc = enqueue_gbuffer(c, records, stream))) return rc;
+    RT_HIP(c, hipEventRecord(c->ev_ao_gbuffer[1], stream));
+    const rt::GBufferShard shard{c->n_rays, sh.n_local, sh.tile_rays ? sh.tile_rays : 1, sh.rank, sh.world};
+    return enqueue_ao(c, shard, records.point, records.normal, records.index, d_params, d_out, stream);
+}
+
+// what both frame forms refuse, in this order; then an empty shard is RT_OK (`empty`) before the primary rays are asked for
+static int check_ao_frame(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* out, bool device, bool& empty) {
+    if (const int rc = check_ao(c, params, out, device)) return rc;
+    if (const int rc = refuse_ao_context(c)) return rc;
+    empty = c->shard.n_local == 0;
+    return empty ? RT_OK : refuse_no_primary_rays(c);
+}
+
+// NULL is the legacy default stream, as for rt_render_gbuffer_device
+int rt_render_ao_device(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* d_out, void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    bool empty = false;
+    if (const int rc = check_ao_frame(c, params, d_out, true, empty)) return rc;
+    if (empty) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_ao_frame(c, *params, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host twin: table and results staged in the patch buffer, on the context's stream; synchronous
+int rt_render_ao(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    bool empty = false;
+    if (const int rc = check_ao_frame(c, params, out, false, empty)) return rc;
+    if (empty) return RT_OK;
+    RT_DEVICE(c);
+    rt_ao_params_t d_params;
+    rt_ao_t d_out;
+    CopyBack back;
+    char* unused = nullptr;
+    if (const int rc = stage_ao_host(c, *params, *out, c->shard.n_local, 0, c->stream, d_params, d_out, back, unused)) return rc;
+    if (const int rc = enqueue_ao_frame(c, d_params, d_out, c->stream)) return rc;
+    return back.finish(c, c->stream);
+}
+
 }  // extern "C"

@@ -260,6 +260,11 @@ class ShardedHIPRaytracer:
         rank's pixels (samples, with supersample=s). The per-rank form: nothing is exchanged."""
         return self.rt.render_gbuffer(want, out)
 
+    def render_ao(self, dirs, samples: int, bias: float = 1e-3, want=("ao",), out=None):
+        """Ambient occlusion of THIS rank's tiles (HIPRaytracer.render_ao): rt.local_rays elements per member, in the order of the
+        rank's pixels. The sets are chosen by the GLOBAL work-item, so the ranks' parts are the unsharded pass's, item for item."""
+        return self.rt.render_ao(dirs, samples, bias, want, out)
+
     def render_local(self):
         """Asynchronous: this rank's tiles into its torch buffer, on torch's current stream."""
         self._render_into(self.gatherer.local, torch.cuda.current_stream(self.device).cuda_stream)

@@ -53,6 +53,7 @@ EXPORTS = [
     "rt_get_compact_info",
     "rt_get_block_range",
     "rt_render_gbuffer_device", "rt_render_gbuffer", "rt_get_gbuffer_info",
+    "rt_ao_device", "rt_ao", "rt_render_ao_device", "rt_render_ao", "rt_get_ao_info",
 ]
 
 
@@ -222,6 +223,30 @@ class RTGBufferInfo(ctypes.Structure):
 
 
 GBUFFER_FIELDS = {"t": _T, "index": _INDEX, "point": _VEC4, "normal": _VEC4, "albedo": _VEC4}
+
+
+class RTAOParams(ctypes.Structure):
+    """rt_ao_params_t: samples (1, 2, 4 ... 64), n_sets (1 .. 4096), bias, reserved (0) and the table of n_sets * samples float4."""
+    _fields_ = [("samples", ctypes.c_uint32), ("n_sets", ctypes.c_uint32), ("bias", ctypes.c_float), ("reserved", ctypes.c_uint32),
+                ("dirs", ctypes.c_void_p)]
+
+
+class RTAO(ctypes.Structure):
+    """rt_ao_t: two pointers, each may be NULL (not both)."""
+    _fields_ = [("unoccluded", ctypes.c_void_p), ("ao", ctypes.c_void_p)]
+
+
+class RTAOInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_items", ctypes.c_uint64), ("n_live", ctypes.c_uint64), ("n_rays", ctypes.c_uint64), ("n_grid", ctypes.c_uint64),
+        ("n_brute", ctypes.c_uint64), ("object_tests", ctypes.c_uint64), ("gbuffer_ms", ctypes.c_double), ("ao_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
+
+
+AO_FIELDS = {"unoccluded": ((), np.uint8, "uint8"), "ao": _T}
 
 _lib = None
 
@@ -423,6 +448,17 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_render_gbuffer.argtypes = [vp, ctypes.POINTER(RTGBuffer)]
         lib.rt_get_gbuffer_info.restype = i32
         lib.rt_get_gbuffer_info.argtypes = [vp, ctypes.POINTER(RTGBufferInfo)]
+    if hasattr(lib, "rt_render_ao_device"):  # (the same: a build from before ambient-occlusion frames)
+        lib.rt_ao_device.restype = i32
+        lib.rt_ao_device.argtypes = [vp, vp, vp, vp, u64, ctypes.POINTER(RTAOParams), ctypes.POINTER(RTAO), vp]
+        lib.rt_ao.restype = i32
+        lib.rt_ao.argtypes = [vp, vp, vp, vp, u64, ctypes.POINTER(RTAOParams), ctypes.POINTER(RTAO)]
+        lib.rt_render_ao_device.restype = i32
+        lib.rt_render_ao_device.argtypes = [vp, ctypes.POINTER(RTAOParams), ctypes.POINTER(RTAO), vp]
+        lib.rt_render_ao.restype = i32
+        lib.rt_render_ao.argtypes = [vp, ctypes.POINTER(RTAOParams), ctypes.POINTER(RTAO)]
+        lib.rt_get_ao_info.restype = i32
+        lib.rt_get_ao_info.argtypes = [vp, ctypes.POINTER(RTAOInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -655,6 +691,107 @@ def _render_gbuffer(lib, ctx, n: int, want, out, device: int):
     if n:
         _check_rc(lib, ctx, lib.rt_render_gbuffer(ctx, ctypes.byref(gb)))
     return res
+
+
+def _ao_table(dirs, samples: int, device):
+    """(keep-alive object, pointer, n_sets) of a direction table: `device` None - a host table from anything ao.table takes; else a
+    device tensor - a float32 (n_sets * samples, 4) tensor on that device as it is, anything else uploaded."""
+    from . import ao as AO
+    if _is_tensor(dirs) and device is not None:
+        import torch
+        if not dirs.is_cuda or dirs.dtype != torch.float32 or not dirs.is_contiguous() or dirs.dim() < 2 or dirs.shape[-1] != 4:
+            raise ValueError("a device direction table is float32, contiguous, on the GPU, with 4 columns")
+        if dirs.device.index not in (None, device.index):
+            raise ValueError(f"the direction table lives on device {dirs.device.index}, the context on device {device.index}")
+        rows = dirs.numel() // 4
+        if rows == 0 or rows % samples:
+            raise ValueError("dirs: a whole number of sets of `samples` directions, at least one")
+        return dirs, dirs.data_ptr(), rows // samples
+    host = AO.table(dirs.cpu().numpy() if _is_tensor(dirs) else dirs, samples)
+    if device is None:
+        return host, host.ctypes.data, len(host) // samples
+    import torch
+    dev = torch.from_numpy(host).to(device)
+    return dev, dev.data_ptr(), len(host) // samples
+
+
+def _render_ao(lib, ctx, n: int, dirs, samples: int, bias: float, want, out, device: int):
+    """HIPRaytracer.render_ao: numpy arrays through rt_render_ao, or - with `out` - torch tensors through rt_render_ao_device on torch's
+    current stream. n: the context's local work-items."""
+    from . import ao as AO
+    if samples not in AO.SAMPLES:
+        raise ValueError(f"samples is one of {AO.SAMPLES}")
+    want = _wanted(want, AO_FIELDS)
+    if out is not None:
+        import torch
+        res = _device_outputs(n, want, out, AO_FIELDS, lambda t: t.is_cuda and t.device.index in (None, device), "the context's device")
+        keep, ptr, n_sets = _ao_table(dirs, samples, res[want[-1]].device)
+        params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+        if n:
+            stream = _current_stream_of(res[want[-1]])
+            o = RTAO(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_render_ao_device(ctx, ctypes.byref(params), ctypes.byref(o), ctypes.c_void_p(stream) if stream else None))
+        return res
+    keep, ptr, n_sets = _ao_table(dirs, samples, None)
+    params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+    res, o = _host_outputs(n, want, AO_FIELDS, RTAO)
+    if n:
+        _check_rc(lib, ctx, lib.rt_render_ao(ctx, ctypes.byref(params), ctypes.byref(o)))
+    return res
+
+
+def _ao_pass(lib, ctx, point, normal, index, dirs, samples: int, bias: float, want, out, device: int):
+    """HIPRaytracer.ao_pass: rt_ao for numpy items, rt_ao_device on torch's current stream for device tensors."""
+    from . import ao as AO
+    if samples not in AO.SAMPLES:
+        raise ValueError(f"samples is one of {AO.SAMPLES}")
+    want = _wanted(want, AO_FIELDS)
+    if _is_tensor(point):
+        import torch
+
+        def vec4(t, name):
+            if not _is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() % 4 or t.device != point.device:
+                raise ValueError(f"{name}: a contiguous float32 tensor on the GPU with 4 elements per item, on the device of point")
+            return t
+        vec4(point, "point"), vec4(normal, "normal")
+        if point.device.index is not None and point.device.index != device:
+            raise ValueError(f"the items live on device {point.device.index}, the context on device {device}")
+        n = point.numel() // 4
+        if normal.numel() != 4 * n:
+            raise ValueError("point and normal have one float4 per item")
+        i_ptr = _device_mask(index, point, n)
+        res = _device_outputs(n, want, out, AO_FIELDS, lambda t: t.device == point.device, "the items' device", point.device)
+        keep, ptr, n_sets = _ao_table(dirs, samples, point.device)
+        params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+        if n:
+            stream = _current_stream_of(point)
+            o = RTAO(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_ao_device(ctx, ctypes.c_void_p(point.data_ptr()), ctypes.c_void_p(normal.data_ptr()), i_ptr, n,
+                                                 ctypes.byref(params), ctypes.byref(o), ctypes.c_void_p(stream) if stream else None))
+        return res
+    if out is not None:
+        raise ValueError("out= takes device tensors: numpy items return fresh arrays")
+    point = np.ascontiguousarray(np.asarray(point, dtype=np.float32).reshape(-1, 4))
+    normal = np.ascontiguousarray(np.asarray(normal, dtype=np.float32).reshape(-1, 4))
+    n = len(point)
+    if len(normal) != n:
+        raise ValueError("point and normal have one float4 per item")
+    if index is not None:
+        index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
+        if len(index) != n:
+            raise ValueError("index: one int32 entry per item")
+    keep, ptr, n_sets = _ao_table(dirs, samples, None)
+    params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+    res, o = _host_outputs(n, want, AO_FIELDS, RTAO)
+    if n:
+        _check_rc(lib, ctx, lib.rt_ao(ctx, _ptr(point), _ptr(normal), _ptr(index), n, ctypes.byref(params), ctypes.byref(o)))
+    return res
+
+
+def _ao_info(lib, ctx) -> dict:
+    info = RTAOInfo()
+    _check_rc(lib, ctx, lib.rt_get_ao_info(ctx, ctypes.byref(info)))
+    return info.as_dict()
 
 
 def _query_info(lib, ctx) -> dict:
@@ -1186,6 +1323,32 @@ class HIPRaytracer:
         self._check(self._lib.rt_get_gbuffer_info(self._ctx, ctypes.byref(info)))
         return info.as_dict()
 
+    # -- ambient-occlusion frames (hip_raytracer.h: K occlusion rays per work-item in one kernel; ao.py is the definition) -------------
+    def render_ao(self, dirs, samples: int, bias: float = 1e-3, want=("ao",), out=None):
+        """Ambient occlusion of every local work-item (rt_render_ao / rt_render_ao_device): the G-buffer pass, then `samples`
+        occlusion rays per work-item from its hit point along the directions of its set of `dirs` (n_sets * samples rows of 3 or 4
+        columns; a direction's LENGTH is the occlusion radius - ao.directions makes a table), mirrored to the normal's side and
+        started `bias` along the normal. A dict of the members named in `want`, local_rays elements each, in render_device's order:
+        "unoccluded" uint8[n], the rays that reached their end; "ao" float32[n] = unoccluded / samples. A miss reads samples / 1.0.
+        Returns numpy arrays; with `out` - a dict of contiguous torch tensors on the context's device - the pass is enqueued on
+        torch's current stream with no host synchronisation (a `dirs` tensor on the device is used where it lies). Per SAMPLE under
+        supersampling; refused on a context with triangles. ao.rays / ao.reduce are the definition, CPURaytracer.render_ao runs it
+        without a GPU."""
+        return _render_ao(self._lib, self._ctx, self.local_rays, dirs, int(samples), bias, want, out, self._device)
+
+    def ao_pass(self, point, normal, index, dirs, samples: int, bias: float = 1e-3, want=("ao",), out=None):
+        """The pass alone (rt_ao / rt_ao_device) on items of the caller's: `point` and `normal` float32 (n, 4) as render_gbuffer or
+        query_hits deliver them, `index` int32[n] or None (an item with a negative entry, or a point / normal that is not finite, is
+        dead: it traces nothing and reads samples / 1.0). numpy items: synchronous, numpy results; torch tensors on the context's
+        device: on torch's current stream, no host synchronisation, `out` may name tensors to write into. Item i takes set
+        hash(i) of the table; works on any kernel, also without primary rays."""
+        return _ao_pass(self._lib, self._ctx, point, normal, index, dirs, int(samples), bias, want, out, self._device)
+
+    def ao_info(self) -> dict:
+        """rt_get_ao_info: n_items, n_live, n_rays (= samples * n_live), n_grid, n_brute, object_tests, gbuffer_ms (0 for ao_pass) and
+        ao_ms of the last render_ao / ao_pass; waits for it."""
+        return _ao_info(self._lib, self._ctx)
+
     def _grid_width(self) -> int:
         """The width of the grid the rays in use were generated for: the camera's, or the last set_pose's (0: a plain ray buffer)."""
         st = self.stats()
@@ -1371,6 +1534,13 @@ class MultiHIPRaytracer:
 
     def query_info(self) -> dict:
         return _query_info(self._lib, self._shard0())
+
+    def ao_pass(self, point, normal, index, dirs, samples: int, bias: float = 1e-3, want=("ao",), out=None):
+        """HIPRaytracer.ao_pass through shard 0 (the frame form has no _multi twin: rt_multi_context(m, r) gives each shard's)."""
+        return _ao_pass(self._lib, self._shard0(), point, normal, index, dirs, int(samples), bias, want, out, self._device0)
+
+    def ao_info(self) -> dict:
+        return _ao_info(self._lib, self._shard0())
 
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()

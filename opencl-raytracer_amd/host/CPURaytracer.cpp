@@ -530,6 +530,42 @@ void CPURaytracer::RenderGBuffer(GBuffer& out) const {
     out.normal.swap(hits.normal);
 }
 
+void CPURaytracer::RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, AO& out) const {
+    const unsigned int K = samples;
+    if (K == 0 || K > 64 || (K & (K - 1))) throw std::invalid_argument("RenderAO: samples is one of 1, 2, 4, 8, 16, 32, 64");
+    if (dirs.empty() || dirs.size() % K || dirs.size() / K > 4096) throw std::invalid_argument("RenderAO: dirs holds 1 .. 4096 whole sets of `samples` directions");
+    if (!(bias >= 0.f) || !std::isfinite(bias)) throw std::invalid_argument("RenderAO: bias must be finite and not negative");
+    const uint32_t n_sets = (uint32_t)(dirs.size() / K);
+    GBuffer g;
+    RenderGBuffer(g);
+    const size_t n = g.t.size();
+    std::vector<Ray3D> rays;
+    std::vector<size_t> owner;   // the item of every traced ray
+    for (size_t i = 0; i < n; ++i) {
+        const rtm::vec4 &p = g.point[i], &nr = g.normal[i];
+        const bool live = g.index[i] >= 0 && std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && std::isfinite(nr.x) &&
+                          std::isfinite(nr.y) && std::isfinite(nr.z);
+        if (!live) continue;
+        const uint32_t h = (uint32_t)i * 0x9E3779B1u;
+        const uint32_t set = (h >> 16) % n_sets;
+        for (unsigned int k = 0; k < K; ++k) {
+            rtm::vec4 d = dirs[(size_t)set * K + k];
+            const float s = (d.x * nr.x + d.y * nr.y) + d.z * nr.z;   // (-ffp-contract=off: every product and sum rounded)
+            if (s < 0.f) { d.x = -d.x; d.y = -d.y; d.z = -d.z; }
+            rays.emplace_back(rtm::vec3(p.x + bias * nr.x, p.y + bias * nr.y, p.z + bias * nr.z), rtm::vec3(d.x, d.y, d.z));
+            owner.push_back(i);
+        }
+    }
+    std::vector<uint8_t> occluded;
+    QueryOccluded(rays, occluded);
+    out.unoccluded.assign(n, (uint8_t)K);
+    for (size_t r = 0; r < rays.size(); ++r)
+        if (occluded[r]) --out.unoccluded[owner[r]];
+    const float inv_k = 1.0f / (float)K;
+    out.ao.resize(n);
+    for (size_t i = 0; i < n; ++i) out.ao[i] = (float)out.unoccluded[i] * inv_k;
+}
+
 void CPURaytracer::QueryShade(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask, Shade& out) const {
     const size_t n = q.size();
     if (!mask.empty() && mask.size() != n) throw std::invalid_argument("QueryShade: the mask must be empty or have one entry per ray");

@@ -115,6 +115,18 @@ public:
     };
     void RenderGBuffer(GBuffer& out) const;
 
+    // Ambient-occlusion frames, the same option as HIPRaytracer's (hip_raytracer.h, "ambient-occlusion frames"), as the composition it
+    // is defined as: RenderGBuffer, then per live item (index >= 0, finite point and normal) `samples` rays - set (h >> 16) % n_sets
+    // with h = (uint32)i * 0x9E3779B1; d = dirs[set * samples + k], negated where (d.x n.x + d.y n.y) + d.z n.z < 0; start = p +
+    // (bias * n), float, product then sum - through QueryOccluded; unoccluded = samples - the occluded ones, ao = unoccluded *
+    // (1.0f / samples); a dead item reads samples and 1. std::invalid_argument for another `samples` than 1, 2, 4 ... 64, a table
+    // that is no 1 .. 4096 whole sets, a bias that is negative or not finite.
+    struct AO {
+        std::vector<uint8_t> unoccluded;
+        std::vector<float> ao;
+    };
+    void RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, AO& out) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

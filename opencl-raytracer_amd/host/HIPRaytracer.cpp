@@ -304,6 +304,36 @@ rt_gbuffer_info_t HIPRaytracer::GBufferInfo(unsigned int shard) {
     return info;
 }
 
+HIPRaytracer::AO HIPRaytracer::RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, unsigned int shard) {
+    static_assert(sizeof(rtm::vec4) == 16, "the ABI's records");
+    rt_context* c = multi ? rt_multi_context(multi, shard) : ctx;
+    if (!c) throw std::runtime_error("HIPRaytracer::RenderAO: no context");
+    if (samples == 0 || dirs.empty() || dirs.size() % samples) throw std::runtime_error("HIPRaytracer::RenderAO: dirs holds a whole number of sets of `samples` directions");
+    const size_t n = (size_t)rt_local_rays(c);
+    AO a;
+    a.unoccluded.assign(n, (uint8_t)samples);
+    a.ao.assign(n, 1.f);
+    rt_ao_params_t params;
+    params.samples = samples;
+    params.n_sets = (uint32_t)(dirs.size() / samples);
+    params.bias = bias;
+    params.reserved = 0;
+    params.dirs = dirs.data();
+    if (n == 0) return a;
+    rt_ao_t out;
+    out.unoccluded = a.unoccluded.data();
+    out.ao = a.ao.data();
+    if (rt_render_ao(c, &params, &out) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::RenderAO: ") + rt_last_error(c));
+    return a;
+}
+
+rt_ao_info_t HIPRaytracer::AOInfo(unsigned int shard) {
+    rt_ao_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, shard) : ctx;
+    if (!c || rt_get_ao_info(c, &info) != RT_OK) throw std::runtime_error(std::string("HIPRaytracer::AOInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

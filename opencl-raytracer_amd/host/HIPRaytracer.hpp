@@ -152,6 +152,19 @@ public:
     GBuffer RenderGBuffer(unsigned int shard = 0);
     rt_gbuffer_info_t GBufferInfo(unsigned int shard = 0);
 
+    // Ambient-occlusion frames (hip_raytracer.h, "ambient-occlusion frames"): `samples` (1, 2, 4 ... 64) occlusion rays per local
+    // work-item from its primary hit, along the directions of its set of `dirs` (n_sets * samples entries, w ignored; a direction's
+    // length is the occlusion radius) mirrored to the normal's side, started `bias` along the normal - the G-buffer pass and one
+    // kernel. unoccluded: the rays that reached their end; ao = unoccluded / samples; a miss reads samples and 1. One entry per
+    // work-item in the order Render() writes pixels; the frame is left alone. Synchronous (rt_render_ao); `shard` as RenderGBuffer's.
+    // Throws on a scene with triangles. AOInfo(): rt_get_ao_info of that shard's last pass.
+    struct AO {
+        std::vector<uint8_t> unoccluded;
+        std::vector<float> ao;
+    };
+    AO RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias = 1e-3f, unsigned int shard = 0);
+    rt_ao_info_t AOInfo(unsigned int shard = 0);
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

@@ -21,6 +21,11 @@
 //                       no GPU backend can be made, CPURaytracer::RenderGBuffer - the same records): <out-prefix>_normal.ppm, the
 //                       unit normal mapped as 0.5 n + 0.5, and <out-prefix>_depth.ppm, t divided by the largest finite t of the
 //                       frame; a miss is black in both. Bytes by the rule of ppm.format_p6 (floor(255 v), clamped)
+//   scene_tool ao      <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius]
+//                       ambient occlusion of the W x H picture as a grey binary PPM (HIPRaytracer::RenderAO; with `cpu`, or where no
+//                       GPU backend can be made, CPURaytracer::RenderAO - the same counts): K = 1, 2, 4 ... 64 rays per pixel of
+//                       length `radius` (default 1) from 16 sets of cosine-weighted directions made here from a fixed seed; a pixel
+//                       is floor(255 ao), a miss white
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -192,6 +197,62 @@ int main(int argc, char** argv) {
             PPMExporter::ExportP6(prefix + "_normal.ppm", (size_t)gw, (size_t)gh, nb.data(), 3);
             PPMExporter::ExportP6(prefix + "_depth.ppm", (size_t)gw, (size_t)gh, db.data(), 3);
             std::printf("gbuffer %zu hits of %zu, largest t %.9g, %s\n", hits, n, (double)t_max, backend_name);
+            return 0;
+        }
+        if (std::strcmp(argv[1], "ao") == 0) {
+            if (argc < 7) { std::fprintf(stderr, "usage: scene_tool ao <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius]\n"); return 1; }
+            const int aw = std::atoi(argv[3]), ah = std::atoi(argv[4]);
+            const unsigned K = (unsigned)std::atoi(argv[5]);
+            const float radius = argc > 8 ? (float)std::atof(argv[8]) : 1.0f;
+            if (aw <= 0 || ah <= 0 || K == 0 || K > 64 || (K & (K - 1)) || !(radius > 0.f)) {
+                std::fprintf(stderr, "ao: W > 0, H > 0, K one of 1, 2, 4, 8, 16, 32, 64, radius > 0\n");
+                return 1;
+            }
+            float afov = rtm::radians(60.f);
+            afov *= 0.5f;
+            const float az = -((ah / 2.0f) / tanf(afov));
+            std::vector<Ray3D> grid;
+            grid.reserve((size_t)aw * ah);
+            for (int jj = 0; jj < ah; ++jj)
+                for (int ii = 0; ii < aw; ++ii)
+                    grid.emplace_back(rtm::vec3(0, 0, 0), rtm::vec3((float)ii - aw / 2.0f, (float)(ah - jj) - ah / 2.0f, az));
+            // 16 sets of K cosine-weighted directions about +z (the pass mirrors each to the normal's side), from a fixed seed
+            std::vector<rtm::vec4> dirs;
+            uint32_t state = 0x2545F491u;
+            auto uniform = [&state]() { state ^= state << 13; state ^= state >> 17; state ^= state << 5; return (float)(state >> 8) * (1.0f / 16777216.0f); };
+            for (unsigned j = 0; j < 16 * K; ++j) {
+                const float u = uniform(), phi = 6.2831853f * uniform(), r = std::sqrt(u);
+                dirs.emplace_back(radius * r * std::cos(phi), radius * r * std::sin(phi), radius * std::sqrt(1.0f - u), 0.f);
+            }
+            const size_t n = grid.size();
+            std::vector<uint8_t> unoccluded;
+            std::vector<float> ao;
+            const char* backend_name = (argc > 7 && std::strcmp(argv[7], "cpu") == 0) ? "cpu" : "hip";
+            if (std::strcmp(backend_name, "hip") == 0) {
+                try {
+                    HIPRaytracer backend(objects, lights, grid, 0);
+                    HIPRaytracer::AO a = backend.RenderAO(dirs, K);
+                    unoccluded.swap(a.unoccluded); ao.swap(a.ao);
+                } catch (const std::exception& e) {  // (no GPU: the CPU backend's counts - said on stderr and in the last line)
+                    std::fprintf(stderr, "ao: %s; using the CPU backend\n", e.what());
+                    backend_name = "cpu";
+                }
+            }
+            if (std::strcmp(backend_name, "cpu") == 0) {
+                CPURaytracer backend(objects, lights, grid, 0);
+                CPURaytracer::AO a;
+                backend.RenderAO(dirs, K, 1e-3f, a);
+                unoccluded.swap(a.unoccluded); ao.swap(a.ao);
+            }
+            std::vector<uint8_t> grey(3 * n, 0);
+            size_t sum = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const float f = std::floor(ao[i] * 255.0f);
+                grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = (uint8_t)(f >= 0.0f ? (f >= 255.0f ? 255.0f : f) : 0.0f);
+                sum += unoccluded[i];
+            }
+            PPMExporter::ExportP6(argv[6], (size_t)aw, (size_t)ah, grey.data(), 3);
+            std::printf("ao %zu of %zu rays unoccluded, %s\n", sum, n * K, backend_name);
             return 0;
         }
         if (argc < 7) return 1;
