@@ -84,7 +84,10 @@ extern "C" {
  *      Later addition, same version: the block walk's occupied range - rt_block_range_t, rt_get_block_range. Additions only; detect
  *      by dlsym of rt_get_block_range.
  *      Later addition, same version: ambient-occlusion frames - rt_ao_params_t, rt_ao_t, rt_ao_info_t, rt_ao_device, rt_ao,
- *      rt_render_ao_device, rt_render_ao, rt_get_ao_info. Additions only; detect by dlsym of rt_render_ao_device. */
+ *      rt_render_ao_device, rt_render_ao, rt_get_ao_info. Additions only; detect by dlsym of rt_render_ao_device.
+ *      Later addition, same version: filtered ambient occlusion - rt_ao_filter_params_t, rt_ao_filtered_t, rt_ao_filter_info_t,
+ *      rt_ao_filter_device, rt_ao_filter, rt_render_ao_filtered_device, rt_render_ao_filtered, rt_get_ao_filter_info. Additions only;
+ *      detect by dlsym of rt_ao_filter_device. */
 #define RT_ABI_VERSION 3
 
 typedef struct rt_context rt_context;
@@ -1080,6 +1083,68 @@ int rt_ao(rt_context* ctx, const float* point, const float* normal, const int32_
 int rt_render_ao_device(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_t* d_out, void* hip_stream);  /* G-buffer pass + the pass */
 int rt_render_ao(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_t* out);
 int rt_get_ao_info(rt_context* ctx, rt_ao_info_t* info);                  /* RT_ERR_STATE before the first pass */
+
+/* ---- filtered ambient occlusion ----------------------------------------------------------------------------------------------------
+ * The AO pass picks an item's direction set by a hash of its work-item number: interleaved sampling, which trades banding for noise
+ * per item and expects a spatial filter to recombine the sets. This is that filter: an edge-aware box blur of the COUNTS over a
+ * (2r + 1)^2 window, stopped by the G-buffer's normals and planes, in ONE kernel (csrc/rt_ao_filter.hip: a 64 x 16 tile and its halo
+ * in LDS). ao.py: filter() is the executable definition; the kernel matches it bit for bit - no tolerance anywhere.
+ *
+ * Inputs: a row-major array of width x rows items, n = width * rows; item i sits at column i % width, row i / width. Per item
+ * unoccluded[i] (a uint8, as rt_ao_t delivers it), point[i] and normal[i] (float4) and, optionally, index[i] (int32; NULL: every item
+ * may be live). rt_ao_filter_params_t: radius r is 1 .. 4, normal_min any float, plane_max finite and >= 0, reserved 0; samples K is
+ * one of 1, 2, 4 ... 64.
+ *   live(i)         the AO pass's rule: index[i] >= 0 (where index is given) and point.xyz, normal.xyz all finite.
+ *   window of p     every q with |col_q - col_p| <= r and |row_q - row_p| <= r inside the array. Nothing wraps; nothing outside the
+ *                   array is read.
+ *   accepted(p, q)  for a live p and q != p: live(q), and c = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z with c >= normal_min,
+ *                   and d = P_q - P_p per component, e = (n_p.x * d.x + n_p.y * d.y) + n_p.z * d.z with fabsf(e) <= plane_max. All
+ *                   fp32, every product and sum rounded, nothing contracted, sums left to right, in EVERY arithmetic mode. A
+ *                   comparison with a NaN is false (inf - inf makes one). A live p always accepts itself, untested.
+ *   a live p        taps[p] = the accepted items, 1 .. (2r + 1)^2; sum[p] = the integer sum of their unoccluded bytes as they are
+ *                   (not clamped to K); ao[p] = (float)sum[p] / (float)(taps[p] * K), ONE correctly rounded IEEE division in every
+ *                   arithmetic mode.
+ *   a dead p        taps = 0, ao = 1.0f.
+ *   grey[p]         the byte the table of "8-bit frames" gives ao[p].
+ * The weights are 0 or 1 and the sums integers: the result does not depend on the order of summation.
+ *
+ * rt_ao_filtered_t: each member may be NULL, not all; ao 4-byte aligned, grey and taps of any alignment. Outputs must not overlap inputs.
+ * rt_ao_filter_device: the pass alone on the caller's device arrays, any width and rows, on a context of any kind - also one without
+ * primary rays or with triangles (it reads nothing of the scene). point and normal 16-byte aligned, index 4-byte aligned, unoccluded
+ * of any alignment. It touches only the caller's outputs and a counter block of its own, allocates nothing after the first call and
+ * is asynchronous (NULL is the legacy default stream). rt_ao_filter: its host twin, synchronous, staged through the context's
+ * grow-only patch buffer as rt_ao stages.
+ * rt_render_ao_filtered_device: the G-buffer pass and the AO kernel exactly as rt_render_ao_device runs them - the counts go to a
+ * context-owned grow-only buffer - then the filter, all on one stream; stream semantics are rt_render_gbuffer_device's, the frame is
+ * left alone as rt_render_ao_device leaves it, and rt_get_ao_info and rt_get_gbuffer_info afterwards describe the internal passes.
+ * The filter's width is the frame's SAMPLE-grid width - the pinhole camera's, or the pose's (the context remembers a pose's width and
+ * height) - and rows = rt_local_rays() / width: under supersampling it filters samples. rt_render_ao_filtered: the host twin.
+ * rt_get_ao_filter_info: the LAST pass of either kind; waits for it. accepted is the sum of taps over all items; gbuffer_ms and ao_ms
+ * are 0 for rt_ao_filter*.
+ * Refused, nothing touched - RT_ERR_INVALID_ARGUMENT: a NULL params or out struct, all outputs NULL, radius outside 1 .. 4, a
+ * plane_max that is negative or not finite, reserved != 0, another K, width * rows overflowing, a NULL input (unoccluded, point,
+ * normal) with n != 0, a misaligned device pointer, and the AO parameter errors as rt_render_ao_device reports them. RT_ERR_STATE, the
+ * frame forms only: a context with triangles (the AO pass's own refusal); a sharded context (world > 1: a tile's neighbours live on
+ * other shards); no primary rays; primary rays from a plain ray buffer (rt_set_rays*, RT_FLAG_NO_RAYGEN: it has no width);
+ * rt_get_ao_filter_info before the first pass. n == 0 returns RT_OK with nothing launched.
+ *
+ * NOT part of this call: sharded and _multi forms (they need a halo exchange); Gaussian or other non-binary weights; separable or
+ * a-trous passes; temporal accumulation; filtering colour frames; bent normals; fusing the filter into the AO kernel. */
+typedef struct rt_ao_filter_params_t { uint32_t radius; float normal_min, plane_max; uint32_t reserved; } rt_ao_filter_params_t;
+typedef struct rt_ao_filtered_t { float* ao; uint8_t* grey; uint8_t* taps; } rt_ao_filtered_t;   /* each may be NULL, not all */
+typedef struct rt_ao_filter_info_t {
+    uint64_t n_items, n_live, accepted;      /* items of the pass, the live ones, the sum of taps */
+    double   gbuffer_ms, ao_ms, filter_ms;   /* event pairs around the internal G-buffer pass, the AO kernel and the filter kernel */
+} rt_ao_filter_info_t;
+int rt_ao_filter_device(rt_context* ctx, const uint8_t* d_unoccluded, const float* d_point, const float* d_normal, const int32_t* d_index,
+                        uint64_t width, uint64_t rows, uint32_t samples, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* d_out,
+                        void* hip_stream);                                     /* the pass alone, asynchronous */
+int rt_ao_filter(rt_context* ctx, const uint8_t* unoccluded, const float* point, const float* normal, const int32_t* index, uint64_t width,
+                 uint64_t rows, uint32_t samples, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out);
+int rt_render_ao_filtered_device(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_filter_params_t* filter,
+                                 const rt_ao_filtered_t* d_out, void* hip_stream);   /* G-buffer pass + AO kernel + the filter */
+int rt_render_ao_filtered(rt_context* ctx, const rt_ao_params_t* params, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out);
+int rt_get_ao_filter_info(rt_context* ctx, rt_ao_filter_info_t* info);         /* RT_ERR_STATE before the first pass */
 
 void rt_destroy(rt_context* ctx);
 

@@ -5,7 +5,10 @@ reduce()  occlusion answers per ray -> the unoccluded count (uint8) and ao (floa
 directions()  a cosine-weighted direction table made with numpy - a convenience only, no part of exactness: the library takes any table
           and neither normalises nor scales a direction (its length is the occlusion radius).
 
-unoccluded = reduce(query_occluded(rays(...)), live, K) on the same context is what the GPU pass delivers, bit for bit."""
+filter()  the edge-aware box blur of the counts over a (2r + 1)^2 window ("filtered ambient occlusion"): taps, sum, ao and grey per item.
+
+unoccluded = reduce(query_occluded(rays(...)), live, K) on the same context is what the GPU pass delivers, bit for bit; so is filter()
+of rt_ao_filter* / rt_render_ao_filtered*."""
 from __future__ import annotations
 
 import numpy as np
@@ -14,6 +17,7 @@ F = np.float32
 SAMPLES = (1, 2, 4, 8, 16, 32, 64)
 MAX_SETS = 4096
 HASH = 0x9E3779B1
+RADII = (1, 2, 3, 4)
 
 
 def check(samples: int, n_sets: int, bias: float):
@@ -111,3 +115,67 @@ def directions(samples: int, n_sets: int, radius: float, seed: int = 0) -> np.nd
     d = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(np.maximum(0.0, 1.0 - u)), np.zeros_like(u)], axis=1) * float(radius)
     d[:, 3] = 0.0
     return d.astype(F)
+
+
+def check_filter(samples: int, radius: int, plane_max: float):
+    """What the library refuses of the filter's scalars (RT_ERR_INVALID_ARGUMENT there, ValueError here); normal_min is any float."""
+    if samples not in SAMPLES:
+        raise ValueError(f"samples is one of {SAMPLES}")
+    if radius not in RADII:
+        raise ValueError(f"radius is one of {RADII}")
+    if not (np.isfinite(F(plane_max)) and F(plane_max) >= 0):
+        raise ValueError("plane_max must be finite and not negative")
+
+
+def grey_of(ao) -> np.ndarray:
+    """The byte of the table of "8-bit frames" for every float32 value: p = v * 255.0f, f = floorf(p); a NaN or f < 0: 0; f >= 255: 255."""
+    with np.errstate(all="ignore"):
+        f = np.floor((np.asarray(ao, dtype=F) * F(255.0)).astype(F))
+        f = np.where(np.isnan(f) | (f < 0), F(0), np.where(f >= 255, F(255), f))
+    return f.astype(np.uint8)
+
+
+def filter(unoccluded, point, normal, index, width: int, samples: int, radius: int, normal_min: float, plane_max: float):
+    """{"ao": float32[n], "grey": uint8[n], "taps": uint8[n], "sum": uint32[n]} of a row-major array of `width` columns; n a multiple of
+    `width`. Item p is live as live_items() says. A live p accepts itself untested and every live q != p of its window (|dcol| <=
+    radius, |drow| <= radius, inside the array) with, all float32, every product and sum rounded and nothing contracted,
+        c = (n_p.x * n_q.x + n_p.y * n_q.y) + n_p.z * n_q.z >= normal_min   and
+        d = P_q - P_p,  e = (n_p.x * d.x + n_p.y * d.y) + n_p.z * d.z,  |e| <= plane_max            (a comparison with a NaN is false);
+    taps: the accepted items, sum: their `unoccluded` bytes added as integers (not clamped to `samples`),
+    ao = float32(sum) / float32(taps * samples), one correctly rounded division; grey = grey_of(ao). A dead p: taps 0, sum 0, ao 1, grey 255."""
+    check_filter(samples, radius, plane_max)
+    u = np.asarray(unoccluded).reshape(-1)
+    if u.dtype != np.uint8:
+        raise ValueError("unoccluded: uint8, one per item")
+    p, nr = np.asarray(point, dtype=F).reshape(-1, 4), np.asarray(normal, dtype=F).reshape(-1, 4)
+    n, width, r = len(u), int(width), int(radius)
+    if len(p) != n or len(nr) != n or (index is not None and np.asarray(index).size != n):
+        raise ValueError("unoccluded, point, normal and index have one entry per item")
+    if n == 0:
+        return {"ao": np.zeros(0, F), "grey": np.zeros(0, np.uint8), "taps": np.zeros(0, np.uint8), "sum": np.zeros(0, np.uint32)}
+    if width < 1 or n % width:
+        raise ValueError("width: at least 1, and the items are whole rows of it")
+    rows = n // width
+    live = live_items(p, nr, index).reshape(rows, width)
+    P, N, U = p[:, :3].reshape(rows, width, 3), nr[:, :3].reshape(rows, width, 3), u.reshape(rows, width).astype(np.uint32)
+    taps, total = live.astype(np.uint32), np.where(live, U, 0).astype(np.uint32)
+    nm, pm = F(normal_min), F(plane_max)
+    with np.errstate(all="ignore"):
+        for dy in range(-r, r + 1):
+            for dx in range(-r, r + 1):
+                if (dx == 0 and dy == 0) or abs(dy) >= rows or abs(dx) >= width:
+                    continue
+                pr, qr = slice(max(0, -dy), rows - max(0, dy)), slice(max(0, dy), rows - max(0, -dy))      # rows of p, rows of q = p + dy
+                pc, qc = slice(max(0, -dx), width - max(0, dx)), slice(max(0, dx), width - max(0, -dx))
+                Np, Nq, Pp, Pq = N[pr, pc], N[qr, qc], P[pr, pc], P[qr, qc]
+                c = ((Np[..., 0] * Nq[..., 0]).astype(F) + (Np[..., 1] * Nq[..., 1]).astype(F)).astype(F)
+                c = (c + (Np[..., 2] * Nq[..., 2]).astype(F)).astype(F)
+                d = (Pq - Pp).astype(F)
+                e = ((Np[..., 0] * d[..., 0]).astype(F) + (Np[..., 1] * d[..., 1]).astype(F)).astype(F)
+                e = (e + (Np[..., 2] * d[..., 2]).astype(F)).astype(F)
+                ok = live[pr, pc] & live[qr, qc] & (c >= nm) & (np.abs(e) <= pm)
+                taps[pr, pc] += ok
+                total[pr, pc] += np.where(ok, U[qr, qc], 0).astype(np.uint32)
+        ao = np.where(live, total.astype(F) / np.maximum(taps * np.uint32(samples), 1).astype(F), F(1.0)).astype(F)
+    ao = ao.reshape(-1)
+    return {"ao": ao, "grey": grey_of(ao), "taps": taps.reshape(-1).astype(np.uint8), "sum": total.reshape(-1)}

@@ -64,6 +64,9 @@ def load_library():
         if hasattr(lib, "cpu_rt_render_gbuffer"):
             lib.cpu_rt_render_gbuffer.restype = ctypes.c_int
             lib.cpu_rt_render_gbuffer.argtypes = [vp, u32, vp, u64, vp, vp, vp, vp, vp, ctypes.c_uint, vp, u32, u32, vp, u32, u32, vp, u32, u32]
+        if hasattr(lib, "cpu_rt_ao_filter"):
+            lib.cpu_rt_ao_filter.restype = ctypes.c_int
+            lib.cpu_rt_ao_filter.argtypes = [vp, vp, vp, vp, u64, u64, u32, u32, ctypes.c_float, ctypes.c_float, vp, vp, vp]
         _lib = lib
     return _lib
 
@@ -310,6 +313,50 @@ class CPURaytracer:
         HIPRaytracer.render_ao (unsharded, in the default arithmetic) that runs without a GPU."""
         g = self.render_gbuffer()
         return self.ao_pass(g["point"], g["normal"], g["index"], dirs, samples, bias)
+
+    # -- filtered ambient occlusion: CPURaytracer::FilterAO, plain loops in C++ - a second statement of ao.filter ----------------------------
+    def ao_filter(self, unoccluded, point, normal, index, width: int, samples: int, radius: int = 2, normal_min: float = 0.9,
+                  plane_max: float = None):
+        """{"ao": float32[n], "grey": uint8[n], "taps": uint8[n]} of a row-major array of `width` columns (ao.filter's inputs), through
+        the C++ loops of CPURaytracer::FilterAO. ValueError for what ao.check_filter refuses; plane_max has no default."""
+        from . import ao as AO
+        if plane_max is None:
+            raise TypeError("plane_max has no default: it is a length of the scene's")
+        AO.check_filter(int(samples), int(radius), plane_max)
+        u = np.asarray(unoccluded)
+        if u.dtype != np.uint8:
+            raise ValueError("unoccluded: uint8, one per item")
+        u = np.ascontiguousarray(u.reshape(-1))
+        p = np.ascontiguousarray(np.asarray(point, dtype=np.float32).reshape(-1, 4))
+        nr = np.ascontiguousarray(np.asarray(normal, dtype=np.float32).reshape(-1, 4))
+        n, width = len(u), int(width)
+        ix = None if index is None else np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
+        if len(p) != n or len(nr) != n or (ix is not None and len(ix) != n):
+            raise ValueError("unoccluded, point, normal and index have one entry per item")
+        if n and (width < 1 or n % width):
+            raise ValueError("width: at least 1, and the items are whole rows of it")
+        ao, grey, taps = np.ones(n, np.float32), np.full(n, 255, np.uint8), np.zeros(n, np.uint8)
+        if n:
+            def ptr(a):
+                return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+            rc = self._lib.cpu_rt_ao_filter(ptr(u), ptr(p), ptr(nr), ptr(ix), width, n // width, int(samples), int(radius), float(normal_min),
+                                            float(plane_max), ptr(ao), ptr(grey), ptr(taps))
+            if rc != 0:
+                raise ValueError("cpu_rt_ao_filter: unsupported arguments")
+        return {"ao": ao, "grey": grey, "taps": taps}
+
+    def render_ao_filtered(self, dirs, samples: int, bias: float = 1e-3, radius: int = 2, normal_min: float = 0.9, plane_max: float = None,
+                           width: int = None):
+        """render_gbuffer and render_ao, then ao_filter over rows of `width` work-items (None: the pose's width, else the sample_width
+        the object was made with - this object holds rays, not a camera). The definition of HIPRaytracer.render_ao_filtered
+        (in the default arithmetic) that runs without a GPU."""
+        if width is None:
+            width = self.pose[0] if getattr(self, "pose", None) else self.sample_width
+        if not width:
+            raise ValueError("render_ao_filtered: width - the rays of this object carry none")
+        g = self.render_gbuffer()
+        a = self.ao_pass(g["point"], g["normal"], g["index"], dirs, samples, bias)
+        return self.ao_filter(a["unoccluded"], g["point"], g["normal"], g["index"], width, samples, radius, normal_min, plane_max)
 
     def Render(self) -> np.ndarray:
         n = len(self.rays)

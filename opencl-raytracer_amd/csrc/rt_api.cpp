@@ -940,13 +940,14 @@ void rt_destroy(rt_context* c) {
     if (c->d_rays) (void)hipFree(c->d_rays);
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->h_scan) (void)hipHostFree(c->h_scan);
-    for (CountedSlot* s : {&c->query, &c->query_shade, &c->gb_records, &c->ao}) {
+    for (CountedSlot* s : {&c->query, &c->query_shade, &c->gb_records, &c->ao, &c->ao_filter}) {
         if (s->made) (void)hipEventSynchronize(s->ev[1]);  // (a device-form query or pass may still run on the caller's stream)
         if (s->d_counters) (void)hipFree(s->d_counters);
         for (hipEvent_t ev : s->ev) if (ev) (void)hipEventDestroy(ev);
     }
     for (hipEvent_t ev : c->ev_gb_trace) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_ao_gbuffer) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->ev_ao_filter_frame) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ev_xf) if (ev) (void)hipEventDestroy(ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (hipEvent_t ev : c->ev_pass) if (ev) (void)hipEventDestroy(ev);

@@ -21,6 +21,7 @@
 #include "rt_query.h"
 #include "rt_gbuffer.h"
 #include "rt_ao.h"
+#include "rt_ao_filter.h"
 #include "rt_compact.h"
 
 #include <hip/hip_runtime.h>
@@ -309,6 +310,15 @@ struct rt_context {
     hipEvent_t ev_ao_gbuffer[2] = {};
     uint64_t ao_items = 0;
     bool ao_frame = false;
+    // Filtered ambient occlusion (rt_ao_filter*, rt_render_ao_filtered*; rt_query_host.cpp, rt_render.cpp): the slot of the filter kernel
+    // (rt::AoFilterCounters), the items of the last pass and whether it was a frame form - then gbuffer_ms and ao_ms lie between the three
+    // events of ev_ao_filter_frame, this form's own: before the G-buffer pass, between it and the AO kernel, behind the AO kernel (the AO
+    // family's events are re-recorded by a later rt_render_ao*). d_ao_counts: the frame forms' counts, grow-only.
+    rt::host::CountedSlot ao_filter{sizeof(rt::AoFilterCounters) * rt::kAoFilterCounterSlots};
+    rt::host::Buffer d_ao_counts;
+    hipEvent_t ev_ao_filter_frame[3] = {};
+    uint64_t ao_filter_items = 0;
+    bool ao_filter_frame = false;
     // Posed cameras (rt_set_pose): the ray buffer in use was generated from a pose of this sample grid (0, 0: it was not). Nothing
     // but supersampling reads it - a posed frame renders as the buffer it is (pinhole stays false, width and height 0).
     uint32_t pose_w = 0, pose_h = 0;
@@ -545,6 +555,13 @@ int check_ao(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* out, bo
 int refuse_ao_context(rt_context* c);
 int enqueue_ao(rt_context* c, const rt::GBufferShard& shard, const float* d_point, const float* d_normal, const int32_t* d_index,
                const rt_ao_params_t& params, const rt_ao_t& d_out, hipStream_t stream);
+// Filtered ambient occlusion (rt_query_host.cpp; the frame forms are rt_render.cpp's). check_ao_filter: what every form refuses of the
+// filter's parameter and output structs and of K (`device`: the outputs are device pointers); enqueue_ao_filter: one pass over width x
+// rows items on `stream`, every pointer device memory, asynchronous.
+int check_ao_filter(rt_context* c, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out, uint32_t samples, bool device);
+int enqueue_ao_filter(rt_context* c, const uint8_t* d_unoccluded, const float* d_point, const float* d_normal, const int32_t* d_index,
+                      uint64_t width, uint64_t rows, uint32_t samples, const rt_ao_filter_params_t& filter, const rt_ao_filtered_t& d_out,
+                      hipStream_t stream);
 // The device copies of a host form's wanted outputs and their way back: select() hands out the device array of a wanted member (a
 // null host pointer: not wanted, null), finish() copies every selected array to its host array on `stream` and waits for the stream.
 struct CopyBack {
@@ -562,6 +579,10 @@ struct CopyBack {
 // `extra` bytes of the caller's own (16-byte aligned, at d_extra) behind one another in the patch buffer; d_params / d_out are the device forms' arguments.
 int stage_ao_host(rt_context* c, const rt_ao_params_t& params, const rt_ao_t& out, uint64_t n, size_t extra, hipStream_t stream,
                   rt_ao_params_t& d_params, rt_ao_t& d_out, CopyBack& back, char*& d_extra);
+// The wanted results of a host form of the filter, n items, selected in `back` at base + offset .. (ao_filter_output_bytes(n) bytes of the
+// patch buffer); returns the first byte behind them.
+size_t stage_ao_filter_outputs(char* base, size_t offset, const rt_ao_filtered_t& out, uint64_t n, rt_ao_filtered_t& d_out, CopyBack& back);
+size_t ao_filter_output_bytes(uint64_t n);
 // rt_visibility_host.cpp: the two refusals of rt_set_visibility; nothing is touched
 int check_set_visibility(rt_context* c, const void* visible, uint32_t first, uint32_t count);
 // rt_geometry.cpp: every refusal of rt_set_transforms, decided on the host over the whole range; nothing is touched

@@ -2,7 +2,8 @@
 // rt_query_closest / rt_query_occluded, rt_query_primary, the hit-record queries rt_query_hits_device / rt_query_hits /
 // rt_query_primary_hits, the shaded queries rt_query_shade_device / rt_query_shade / rt_query_primary_shade with their own
 // rt_get_query_shade_info, and rt_get_query_info; and the ambient-occlusion pass on items of the caller's, rt_ao_device / rt_ao with
-// rt_get_ao_info (its frame forms are rt_render.cpp's). A query reads the context's object records and grid as
+// rt_get_ao_info, and the filter of its counts, rt_ao_filter_device / rt_ao_filter with rt_get_ao_filter_info (the frame forms of both are
+// rt_render.cpp's). A query reads the context's object records and grid as
 // the setters have left them and writes the caller's outputs and the context's counter block - nothing of the frame: not its rays,
 // camera, pose, shard, supersampling factor, aux buffers or state buffers. The device forms enqueue a memset, two event records and one
 // kernel (rt_query.hip) and return; after the first call, which makes the counter block and the events, nothing is allocated.
@@ -393,6 +394,60 @@ int check_ao_items(rt_context* c, const float* point, const float* normal, const
 
 }  // namespace
 
+// ---- filtered ambient occlusion (hip_raytracer.h, "filtered ambient occlusion"; the frame forms are rt_render.cpp's) ------------------
+int check_ao_filter(rt_context* c, const rt_ao_filter_params_t* f, const rt_ao_filtered_t* o, uint32_t samples, bool device) {
+    if (!f) return fail(c, RT_ERR_INVALID_ARGUMENT, "the filter's parameter struct is NULL");
+    if (!o) return fail(c, RT_ERR_INVALID_ARGUMENT, "the output struct is NULL");
+    if (!o->ao && !o->grey && !o->taps) return fail(c, RT_ERR_INVALID_ARGUMENT, "all outputs are NULL");
+    if (f->radius < 1 || f->radius > 4) return fail(c, RT_ERR_INVALID_ARGUMENT, "radius is 1 .. 4");
+    if (!(f->plane_max >= 0.f) || !std::isfinite(f->plane_max)) return fail(c, RT_ERR_INVALID_ARGUMENT, "plane_max must be finite and not negative");
+    if (f->reserved != 0) return fail(c, RT_ERR_INVALID_ARGUMENT, "reserved must be 0");
+    if (samples == 0 || samples > 64 || (samples & (samples - 1u))) return fail(c, RT_ERR_INVALID_ARGUMENT, "samples is one of 1, 2, 4, 8, 16, 32, 64");
+    if (device && (reinterpret_cast<uintptr_t>(o->ao) & 3u)) return fail(c, RT_ERR_INVALID_ARGUMENT, "ao must be 4-byte aligned");
+    return RT_OK;
+}
+
+int enqueue_ao_filter(rt_context* c, const uint8_t* d_unoccluded, const float* d_point, const float* d_normal, const int32_t* d_index,
+                      uint64_t width, uint64_t rows, uint32_t samples, const rt_ao_filter_params_t& f, const rt_ao_filtered_t& d_out,
+                      hipStream_t stream) {
+    const int rc = enqueue_counted(c, c->ao_filter, stream, "ambient-occlusion filter launch", [&] {
+        const rt::AoFilterInputs in{d_unoccluded, reinterpret_cast<const float4*>(d_point), reinterpret_cast<const float4*>(d_normal), d_index,
+                                    width,        rows, samples, f.radius, f.normal_min, f.plane_max};
+        return rt::launch_ao_filter(in, rt::AoFilterOutputs{d_out.ao, d_out.grey, d_out.taps},
+                                    static_cast<rt::AoFilterCounters*>(c->ao_filter.d_counters), stream);
+    });
+    if (rc) return rc;
+    c->ao_filter_items = width * rows;
+    return RT_OK;
+}
+
+size_t ao_filter_output_bytes(uint64_t n) { return align16((size_t)n * sizeof(float)) + 2 * align16((size_t)n); }
+
+size_t stage_ao_filter_outputs(char* base, size_t offset, const rt_ao_filtered_t& out, uint64_t n, rt_ao_filtered_t& d_out, CopyBack& back) {
+    const size_t off_grey = offset + align16((size_t)n * sizeof(float)), off_taps = off_grey + align16((size_t)n);
+    d_out.ao = back.select<float>(out.ao, base + offset, (size_t)n * sizeof(float));
+    d_out.grey = back.select<uint8_t>(out.grey, base + off_grey, (size_t)n);
+    d_out.taps = back.select<uint8_t>(out.taps, base + off_taps, (size_t)n);
+    return off_taps + align16((size_t)n);
+}
+
+namespace {
+
+// what rt_ao_filter_device and rt_ao_filter refuse of (unoccluded, point, normal, index, width, rows); nothing is touched
+int check_ao_filter_items(rt_context* c, const uint8_t* unoccluded, const float* point, const float* normal, const int32_t* index, uint64_t width,
+                          uint64_t rows, bool device) {
+    if (width != 0 && rows > ((std::numeric_limits<size_t>::max)() / 64u) / width) return fail(c, RT_ERR_INVALID_ARGUMENT, "width * rows overflows");
+    if (width * rows != 0 && (!unoccluded || !point || !normal))
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "unoccluded, point or normal is NULL with a non-zero count");
+    if (!device) return RT_OK;
+    if ((reinterpret_cast<uintptr_t>(point) | reinterpret_cast<uintptr_t>(normal)) & 15u)
+        return fail(c, RT_ERR_INVALID_ARGUMENT, "point and normal must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(index) & 3u) return fail(c, RT_ERR_INVALID_ARGUMENT, "index must be 4-byte aligned");
+    return RT_OK;
+}
+
+}  // namespace
+
 int refuse_no_primary_rays(rt_context* c) {
     if (!c->pinhole && !c->have_rays)
         return fail(c, RT_ERR_STATE, "no primary rays: rt_create got rays == NULL and rt_set_camera was not called");
@@ -598,6 +653,72 @@ int rt_get_ao_info(rt_context* c, rt_ao_info_t* info) {
     info->n_brute = ctr.q.n_brute;
     info->object_tests = ctr.q.tests;
     info->gbuffer_ms = (double)gbuffer;
+    return RT_OK;
+}
+
+int rt_ao_filter_device(rt_context* c, const uint8_t* d_unoccluded, const float* d_point, const float* d_normal, const int32_t* d_index,
+                        uint64_t width, uint64_t rows, uint32_t samples, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* d_out,
+                        void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_ao_filter(c, filter, d_out, samples, true)) return rc;
+    if (const int rc = check_ao_filter_items(c, d_unoccluded, d_point, d_normal, d_index, width, rows, true)) return rc;
+    if (width * rows == 0) return RT_OK;
+    RT_DEVICE(c);
+    c->ao_filter_frame = false;
+    return enqueue_ao_filter(c, d_unoccluded, d_point, d_normal, d_index, width, rows, samples, *filter, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host twin: items and results staged in the patch buffer on the context's stream; synchronous
+int rt_ao_filter(rt_context* c, const uint8_t* unoccluded, const float* point, const float* normal, const int32_t* index, uint64_t width,
+                 uint64_t rows, uint32_t samples, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    if (const int rc = check_ao_filter(c, filter, out, samples, false)) return rc;
+    if (const int rc = check_ao_filter_items(c, unoccluded, point, normal, index, width, rows, false)) return rc;
+    const uint64_t n = width * rows;
+    if (n == 0) return RT_OK;
+    RT_DEVICE(c);
+    hipStream_t stream = c->stream;
+    const size_t vec_bytes = (size_t)n * 16u, index_bytes = (size_t)n * sizeof(int32_t);
+    const size_t off_normal = vec_bytes, off_index = 2 * vec_bytes, off_counts = off_index + align16(index_bytes), off_out = off_counts + align16((size_t)n);
+    if (const int rc = ensure_patch_stage(c, off_out + ao_filter_output_bytes(n))) return rc;
+    char* const base = static_cast<char*>(c->d_patch_stage.p);
+    rt_ao_filtered_t d_out;
+    CopyBack back;
+    stage_ao_filter_outputs(base, off_out, *out, n, d_out, back);
+    RT_HIP(c, hipMemcpyAsync(base, point, vec_bytes, hipMemcpyHostToDevice, stream));
+    RT_HIP(c, hipMemcpyAsync(base + off_normal, normal, vec_bytes, hipMemcpyHostToDevice, stream));
+    if (index) RT_HIP(c, hipMemcpyAsync(base + off_index, index, index_bytes, hipMemcpyHostToDevice, stream));
+    RT_HIP(c, hipMemcpyAsync(base + off_counts, unoccluded, (size_t)n, hipMemcpyHostToDevice, stream));
+    c->ao_filter_frame = false;
+    if (const int rc = enqueue_ao_filter(c, reinterpret_cast<const uint8_t*>(base + off_counts), reinterpret_cast<const float*>(base),
+                                         reinterpret_cast<const float*>(base + off_normal),
+                                         index ? reinterpret_cast<const int32_t*>(base + off_index) : nullptr, width, rows, samples, *filter, d_out,
+                                         stream))
+        return rc;
+    return back.finish(c, stream);
+}
+
+int rt_get_ao_filter_info(rt_context* c, rt_ao_filter_info_t* info) {
+    if (!c || !info) return RT_ERR_INVALID_ARGUMENT;
+    if (!c->ao_filter.made) return fail(c, RT_ERR_STATE, "rt_get_ao_filter_info: no filtered ambient-occlusion pass has been made on this context");
+    RT_DEVICE(c);
+    rt::AoFilterCounters slots[rt::kAoFilterCounterSlots] = {};
+    if (const int rc = read_counted(c, c->ao_filter, slots, &info->filter_ms)) return rc;
+    rt::AoFilterCounters ctr = {};
+    for (const rt::AoFilterCounters& s : slots) {
+        ctr.n_live += s.n_live;
+        ctr.accepted += s.accepted;
+    }
+    float gbuffer = 0.f, ao = 0.f;
+    if (c->ao_filter_frame) {  // (this form's own marks, recorded before the filter kernel on its stream: they have ended)
+        RT_HIP(c, hipEventElapsedTime(&gbuffer, c->ev_ao_filter_frame[0], c->ev_ao_filter_frame[1]));
+        RT_HIP(c, hipEventElapsedTime(&ao, c->ev_ao_filter_frame[1], c->ev_ao_filter_frame[2]));
+    }
+    info->n_items = c->ao_filter_items;
+    info->n_live = ctr.n_live;
+    info->accepted = ctr.accepted;
+    info->gbuffer_ms = (double)gbuffer;
+    info->ao_ms = (double)ao;
     return RT_OK;
 }
 

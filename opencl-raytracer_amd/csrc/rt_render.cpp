@@ -600,8 +600,9 @@ int rt_get_gbuffer_info(rt_context* c, rt_gbuffer_info_t* info) {
 }
 
 // ---- ambient-occlusion frames (hip_raytracer.h): the G-buffer pass into context-owned staging, then the AO kernel on the same stream ----
-// Every pointer of d_params / d_out is device memory; the refusals are made. c->shard.n_local > 0.
-static int enqueue_ao_frame(rt_context* c, const rt_ao_params_t& d_params, const rt_ao_t& d_out, hipStream_t stream) {
+// Every pointer of d_params / d_out is device memory; the refusals are made. c->shard.n_local > 0. `between`: an event of the caller's
+// recorded between the two passes (null: none).
+static int enqueue_ao_frame(rt_context* c, const rt_ao_params_t& d_params, const rt_ao_t& d_out, hipStream_t stream, hipEvent_t between = nullptr) {
     const Shard& sh = c->shard;
     const size_t n = (size_t)sh.n_local;
     for (hipEvent_t& e : c->ev_ao_gbuffer)
@@ -618,6 +619,7 @@ static int enqueue_ao_frame(rt_context* c, const rt_ao_params_t& d_params, const
     RT_HIP(c, hipEventRecord(c->ev_ao_gbuffer[0], stream));
     if ((rc = enqueue_gbuffer(c, records, stream))) return rc;
     RT_HIP(c, hipEventRecord(c->ev_ao_gbuffer[1], stream));
+    if (between) RT_HIP(c, hipEventRecord(between, stream));
     const rt::GBufferShard shard{c->n_rays, sh.n_local, sh.tile_rays ? sh.tile_rays : 1, sh.rank, sh.world};
     return enqueue_ao(c, shard, records.point, records.normal, records.index, d_params, d_out, stream);
 }
@@ -653,6 +655,76 @@ int rt_render_ao(rt_context* c, const rt_ao_params_t* params, const rt_ao_t* out
     char* unused = nullptr;
     if (const int rc = stage_ao_host(c, *params, *out, c->shard.n_local, 0, c->stream, d_params, d_out, back, unused)) return rc;
     if (const int rc = enqueue_ao_frame(c, d_params, d_out, c->stream)) return rc;
+    return back.finish(c, c->stream);
+}
+
+// ---- filtered ambient occlusion (hip_raytracer.h): rt_render_ao_device's two passes with the counts in d_ao_counts, then the filter ------
+// The staged index, point and normal, and the counts, are what the filter reads; width: the sample grid's. Refusals are made.
+static int enqueue_ao_filtered_frame(rt_context* c, const rt_ao_params_t& d_params, const rt_ao_filter_params_t& filter,
+                                     const rt_ao_filtered_t& d_out, hipStream_t stream) {
+    const uint64_t n = c->shard.n_local, width = sample_width(c);
+    if (const int rc = ensure_counted(c, c->ao_filter)) return rc;
+    for (hipEvent_t& e : c->ev_ao_filter_frame)
+        if (!e) RT_HIP(c, hipEventCreate(&e));
+    if (const int rc = c->d_ao_counts.grow(c, (size_t)n)) return rc;
+    c->ao_filter.made = false;  // until this pass is enqueued whole, as enqueue_ao_frame has it
+    c->ao_filter_frame = true;
+    uint8_t* const counts = static_cast<uint8_t*>(c->d_ao_counts.p);
+    // marks of this form's own around its two internal passes: a later rt_render_ao* re-records the AO family's events, not these
+    RT_HIP(c, hipEventRecord(c->ev_ao_filter_frame[0], stream));
+    if (const int rc = enqueue_ao_frame(c, d_params, rt_ao_t{counts, nullptr}, stream, c->ev_ao_filter_frame[1])) return rc;
+    RT_HIP(c, hipEventRecord(c->ev_ao_filter_frame[2], stream));
+    return enqueue_ao_filter(c, counts, static_cast<const float*>(c->d_gb_point.p), static_cast<const float*>(c->d_gb_normal.p),
+                             static_cast<const int32_t*>(c->d_gb_index.p), width, n / width, d_params.samples, filter, d_out, stream);
+}
+
+// what both frame forms refuse, in this order; then an empty frame is RT_OK (`empty`)
+static int check_ao_filtered_frame(rt_context* c, const rt_ao_params_t* params, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out,
+                                   bool device, bool& empty) {
+    if (!params) return fail(c, RT_ERR_INVALID_ARGUMENT, "the parameter struct is NULL");
+    if (const int rc = check_ao_filter(c, filter, out, params->samples, device)) return rc;
+    uint8_t counts_stand_in = 0;  // the AO pass's output is the context's own count buffer
+    const rt_ao_t counts{&counts_stand_in, nullptr};
+    if (const int rc = check_ao(c, params, &counts, device)) return rc;
+    if (const int rc = refuse_ao_context(c)) return rc;
+    if (c->shard.world > 1)
+        return fail(c, RT_ERR_STATE, "filtered ambient occlusion on a sharded context: a tile's neighbours live on other shards");
+    empty = c->shard.n_local == 0;
+    if (empty) return RT_OK;
+    if (const int rc = refuse_no_primary_rays(c)) return rc;
+    if (!has_sample_grid(c) || sample_width(c) == 0 || c->shard.n_local % sample_width(c))
+        return fail(c, RT_ERR_STATE, "filtered ambient occlusion needs a sample grid: the primary rays come from a plain ray buffer, which has no width");
+    return RT_OK;
+}
+
+int rt_render_ao_filtered_device(rt_context* c, const rt_ao_params_t* params, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* d_out,
+                                 void* hip_stream) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    bool empty = false;
+    if (const int rc = check_ao_filtered_frame(c, params, filter, d_out, true, empty)) return rc;
+    if (empty) return RT_OK;
+    RT_DEVICE(c);
+    return enqueue_ao_filtered_frame(c, *params, *filter, *d_out, static_cast<hipStream_t>(hip_stream));
+}
+
+// the host twin: table and results staged in the patch buffer, on the context's stream; synchronous
+int rt_render_ao_filtered(rt_context* c, const rt_ao_params_t* params, const rt_ao_filter_params_t* filter, const rt_ao_filtered_t* out) {
+    if (!c) return RT_ERR_INVALID_ARGUMENT;
+    bool empty = false;
+    if (const int rc = check_ao_filtered_frame(c, params, filter, out, false, empty)) return rc;
+    if (empty) return RT_OK;
+    RT_DEVICE(c);
+    const uint64_t n = c->shard.n_local;
+    const size_t dirs_bytes = (size_t)params->n_sets * params->samples * 16u;
+    if (const int rc = ensure_patch_stage(c, dirs_bytes + ao_filter_output_bytes(n))) return rc;
+    char* const base = static_cast<char*>(c->d_patch_stage.p);
+    RT_HIP(c, hipMemcpyAsync(base, params->dirs, dirs_bytes, hipMemcpyHostToDevice, c->stream));
+    rt_ao_params_t d_params = *params;
+    d_params.dirs = base;
+    rt_ao_filtered_t d_out;
+    CopyBack back;
+    stage_ao_filter_outputs(base, dirs_bytes, *out, n, d_out, back);
+    if (const int rc = enqueue_ao_filtered_frame(c, d_params, *filter, d_out, c->stream)) return rc;
     return back.finish(c, c->stream);
 }
 

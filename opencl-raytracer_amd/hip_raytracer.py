@@ -54,6 +54,7 @@ EXPORTS = [
     "rt_get_block_range",
     "rt_render_gbuffer_device", "rt_render_gbuffer", "rt_get_gbuffer_info",
     "rt_ao_device", "rt_ao", "rt_render_ao_device", "rt_render_ao", "rt_get_ao_info",
+    "rt_ao_filter_device", "rt_ao_filter", "rt_render_ao_filtered_device", "rt_render_ao_filtered", "rt_get_ao_filter_info",
 ]
 
 
@@ -247,6 +248,29 @@ class RTAOInfo(ctypes.Structure):
 
 
 AO_FIELDS = {"unoccluded": ((), np.uint8, "uint8"), "ao": _T}
+
+
+class RTAOFilterParams(ctypes.Structure):
+    """rt_ao_filter_params_t: radius (1 .. 4), normal_min, plane_max (finite, >= 0), reserved (0)."""
+    _fields_ = [("radius", ctypes.c_uint32), ("normal_min", ctypes.c_float), ("plane_max", ctypes.c_float), ("reserved", ctypes.c_uint32)]
+
+
+class RTAOFiltered(ctypes.Structure):
+    """rt_ao_filtered_t: three pointers, each may be NULL (not all)."""
+    _fields_ = [("ao", ctypes.c_void_p), ("grey", ctypes.c_void_p), ("taps", ctypes.c_void_p)]
+
+
+class RTAOFilterInfo(ctypes.Structure):
+    _fields_ = [
+        ("n_items", ctypes.c_uint64), ("n_live", ctypes.c_uint64), ("accepted", ctypes.c_uint64),
+        ("gbuffer_ms", ctypes.c_double), ("ao_ms", ctypes.c_double), ("filter_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {n: (float if t is ctypes.c_double else int)(getattr(self, n)) for n, t in self._fields_}
+
+
+AO_FILTER_FIELDS = {"ao": _T, "grey": ((), np.uint8, "uint8"), "taps": ((), np.uint8, "uint8")}
 
 _lib = None
 
@@ -459,6 +483,18 @@ def load_library(path: os.PathLike | None = None) -> ctypes.CDLL:
         lib.rt_render_ao.argtypes = [vp, ctypes.POINTER(RTAOParams), ctypes.POINTER(RTAO)]
         lib.rt_get_ao_info.restype = i32
         lib.rt_get_ao_info.argtypes = [vp, ctypes.POINTER(RTAOInfo)]
+    if hasattr(lib, "rt_ao_filter_device"):  # (the same: a build from before filtered ambient occlusion)
+        filt, filtered = ctypes.POINTER(RTAOFilterParams), ctypes.POINTER(RTAOFiltered)
+        lib.rt_ao_filter_device.restype = i32
+        lib.rt_ao_filter_device.argtypes = [vp, vp, vp, vp, vp, u64, u64, ctypes.c_uint32, filt, filtered, vp]
+        lib.rt_ao_filter.restype = i32
+        lib.rt_ao_filter.argtypes = [vp, vp, vp, vp, vp, u64, u64, ctypes.c_uint32, filt, filtered]
+        lib.rt_render_ao_filtered_device.restype = i32
+        lib.rt_render_ao_filtered_device.argtypes = [vp, ctypes.POINTER(RTAOParams), filt, filtered, vp]
+        lib.rt_render_ao_filtered.restype = i32
+        lib.rt_render_ao_filtered.argtypes = [vp, ctypes.POINTER(RTAOParams), filt, filtered]
+        lib.rt_get_ao_filter_info.restype = i32
+        lib.rt_get_ao_filter_info.argtypes = [vp, ctypes.POINTER(RTAOFilterInfo)]
     if path is None:
         _lib = lib
     return lib
@@ -791,6 +827,98 @@ def _ao_pass(lib, ctx, point, normal, index, dirs, samples: int, bias: float, wa
 def _ao_info(lib, ctx) -> dict:
     info = RTAOInfo()
     _check_rc(lib, ctx, lib.rt_get_ao_info(ctx, ctypes.byref(info)))
+    return info.as_dict()
+
+
+def _filter_params(samples: int, radius: int, normal_min: float, plane_max: float):
+    from . import ao as AO
+    if plane_max is None:
+        raise TypeError("plane_max has no default: it is a length of the scene's")
+    AO.check_filter(samples, radius, plane_max)
+    return RTAOFilterParams(int(radius), float(normal_min), float(plane_max), 0)
+
+
+def _ao_filter(lib, ctx, unoccluded, point, normal, index, width: int, samples: int, radius: int, normal_min: float, plane_max: float, want, out,
+               device: int):
+    """HIPRaytracer.ao_filter: rt_ao_filter for numpy items, rt_ao_filter_device on torch's current stream for device tensors."""
+    filt = _filter_params(samples, radius, normal_min, plane_max)
+    want = _wanted(want, AO_FILTER_FIELDS)
+    width = int(width)
+    if _is_tensor(point):
+        import torch
+
+        def vec4(t, name):
+            if not _is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() % 4 or t.device != point.device:
+                raise ValueError(f"{name}: a contiguous float32 tensor on the GPU with 4 elements per item, on the device of point")
+        vec4(point, "point"), vec4(normal, "normal")
+        if point.device.index is not None and point.device.index != device:
+            raise ValueError(f"the items live on device {point.device.index}, the context on device {device}")
+        n = point.numel() // 4
+        if normal.numel() != 4 * n:
+            raise ValueError("point and normal have one float4 per item")
+        if not _is_tensor(unoccluded) or unoccluded.device != point.device or unoccluded.dtype != torch.uint8 or not unoccluded.is_contiguous() or unoccluded.numel() != n:
+            raise ValueError("unoccluded: a contiguous uint8 tensor on the items' device, one entry per item")
+        if n and (width < 1 or n % width):
+            raise ValueError("width: at least 1, and the items are whole rows of it")
+        i_ptr = _device_mask(index, point, n)
+        res = _device_outputs(n, want, out, AO_FILTER_FIELDS, lambda t: t.device == point.device, "the items' device", point.device)
+        if n:
+            stream = _current_stream_of(point)
+            o = RTAOFiltered(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_ao_filter_device(ctx, ctypes.c_void_p(unoccluded.data_ptr()), ctypes.c_void_p(point.data_ptr()),
+                                                        ctypes.c_void_p(normal.data_ptr()), i_ptr, width, n // width, samples,
+                                                        ctypes.byref(filt), ctypes.byref(o), ctypes.c_void_p(stream) if stream else None))
+        return res
+    if out is not None:
+        raise ValueError("out= takes device tensors: numpy items return fresh arrays")
+    point = np.ascontiguousarray(np.asarray(point, dtype=np.float32).reshape(-1, 4))
+    normal = np.ascontiguousarray(np.asarray(normal, dtype=np.float32).reshape(-1, 4))
+    unoccluded = np.asarray(unoccluded)
+    if unoccluded.dtype != np.uint8:
+        raise ValueError("unoccluded: uint8, one per item")
+    unoccluded = np.ascontiguousarray(unoccluded.reshape(-1))
+    n = len(point)
+    if len(normal) != n or len(unoccluded) != n:
+        raise ValueError("unoccluded, point and normal have one entry per item")
+    if index is not None:
+        index = np.ascontiguousarray(np.asarray(index).reshape(-1), dtype=np.int32)
+        if len(index) != n:
+            raise ValueError("index: one int32 entry per item")
+    if n and (width < 1 or n % width):
+        raise ValueError("width: at least 1, and the items are whole rows of it")
+    res, o = _host_outputs(n, want, AO_FILTER_FIELDS, RTAOFiltered)
+    if n:
+        _check_rc(lib, ctx, lib.rt_ao_filter(ctx, _ptr(unoccluded), _ptr(point), _ptr(normal), _ptr(index), width, n // width, samples,
+                                             ctypes.byref(filt), ctypes.byref(o)))
+    return res
+
+
+def _render_ao_filtered(lib, ctx, n: int, dirs, samples: int, bias: float, radius: int, normal_min: float, plane_max: float, want, out, device: int):
+    """HIPRaytracer.render_ao_filtered: numpy arrays through rt_render_ao_filtered, or - with `out` - torch tensors through
+    rt_render_ao_filtered_device on torch's current stream. n: the context's local work-items."""
+    filt = _filter_params(samples, radius, normal_min, plane_max)
+    want = _wanted(want, AO_FILTER_FIELDS)
+    if out is not None:
+        res = _device_outputs(n, want, out, AO_FILTER_FIELDS, lambda t: t.is_cuda and t.device.index in (None, device), "the context's device")
+        keep, ptr, n_sets = _ao_table(dirs, samples, res[want[-1]].device)
+        params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+        if n:
+            stream = _current_stream_of(res[want[-1]])
+            o = RTAOFiltered(**{w: a.data_ptr() for w, a in res.items()})
+            _check_rc(lib, ctx, lib.rt_render_ao_filtered_device(ctx, ctypes.byref(params), ctypes.byref(filt), ctypes.byref(o),
+                                                                 ctypes.c_void_p(stream) if stream else None))
+        return res
+    keep, ptr, n_sets = _ao_table(dirs, samples, None)
+    params = RTAOParams(samples, n_sets, float(bias), 0, ptr)
+    res, o = _host_outputs(n, want, AO_FILTER_FIELDS, RTAOFiltered)
+    if n:
+        _check_rc(lib, ctx, lib.rt_render_ao_filtered(ctx, ctypes.byref(params), ctypes.byref(filt), ctypes.byref(o)))
+    return res
+
+
+def _ao_filter_info(lib, ctx) -> dict:
+    info = RTAOFilterInfo()
+    _check_rc(lib, ctx, lib.rt_get_ao_filter_info(ctx, ctypes.byref(info)))
     return info.as_dict()
 
 
@@ -1349,6 +1477,33 @@ class HIPRaytracer:
         ao_ms of the last render_ao / ao_pass; waits for it."""
         return _ao_info(self._lib, self._ctx)
 
+    # -- filtered ambient occlusion (hip_raytracer.h: an edge-aware box blur of the AO counts in one kernel; ao.filter is the definition) --
+    def ao_filter(self, unoccluded, point, normal, index, width: int, samples: int, radius: int = 2, normal_min: float = 0.9, plane_max: float = None,
+                  want=("ao",), out=None):
+        """The filter alone (rt_ao_filter / rt_ao_filter_device) on a row-major array of `width` columns: `unoccluded` uint8[n] as render_ao
+        delivers it, `point` and `normal` float32 (n, 4), `index` int32[n] or None. A live item averages the counts of the live items of
+        its (2 radius + 1)^2 window whose normal has a cosine >= normal_min with its own and that lie within plane_max of its tangent
+        plane; itself always. A dict of the members named in `want`: "ao" float32[n] = sum / (taps * samples), "grey" uint8[n] (the byte
+        of "8-bit frames"), "taps" uint8[n]. A dead item reads 1.0 / 255 / 0. numpy items: synchronous, numpy results; torch tensors on
+        the context's device: on torch's current stream, no host synchronisation, `out` may name tensors to write into. Works on any
+        context. `plane_max` has no default: it is a length of the scene's. ao.filter is the definition, bit for bit."""
+        return _ao_filter(self._lib, self._ctx, unoccluded, point, normal, index, width, int(samples), int(radius), normal_min, plane_max, want, out,
+                          self._device)
+
+    def render_ao_filtered(self, dirs, samples: int, bias: float = 1e-3, radius: int = 2, normal_min: float = 0.9, plane_max: float = None,
+                           want=("ao",), out=None):
+        """render_ao and ao_filter in one call (rt_render_ao_filtered / rt_render_ao_filtered_device): the G-buffer pass, the AO kernel
+        and the filter over the frame's sample grid - the camera's or the pose's width; per SAMPLE under supersampling - with nothing
+        copied back in between. Members and `out` as ao_filter's, local_rays elements each. Refused on a sharded context, on primary
+        rays from a plain ray buffer (it has no width) and on a context with triangles."""
+        return _render_ao_filtered(self._lib, self._ctx, self.local_rays, dirs, int(samples), bias, int(radius), normal_min, plane_max, want, out,
+                                   self._device)
+
+    def ao_filter_info(self) -> dict:
+        """rt_get_ao_filter_info: n_items, n_live, accepted (the sum of taps), gbuffer_ms and ao_ms (0 for ao_filter) and filter_ms of the
+        last render_ao_filtered / ao_filter; waits for it."""
+        return _ao_filter_info(self._lib, self._ctx)
+
     def _grid_width(self) -> int:
         """The width of the grid the rays in use were generated for: the camera's, or the last set_pose's (0: a plain ray buffer)."""
         st = self.stats()
@@ -1541,6 +1696,15 @@ class MultiHIPRaytracer:
 
     def ao_info(self) -> dict:
         return _ao_info(self._lib, self._shard0())
+
+    def ao_filter(self, unoccluded, point, normal, index, width: int, samples: int, radius: int = 2, normal_min: float = 0.9, plane_max: float = None,
+                  want=("ao",), out=None):
+        """HIPRaytracer.ao_filter through shard 0 (the frame form is refused on a sharded context: it would need a halo exchange)."""
+        return _ao_filter(self._lib, self._shard0(), unoccluded, point, normal, index, width, int(samples), int(radius), normal_min, plane_max, want,
+                          out, self._device0)
+
+    def ao_filter_info(self) -> dict:
+        return _ao_filter_info(self._lib, self._shard0())
 
     def Render(self) -> np.ndarray:
         out = ctypes.POINTER(ctypes.c_float)()

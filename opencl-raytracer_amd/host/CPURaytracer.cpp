@@ -566,6 +566,64 @@ void CPURaytracer::RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int sam
     for (size_t i = 0; i < n; ++i) out.ao[i] = (float)out.unoccluded[i] * inv_k;
 }
 
+void CPURaytracer::FilterAO(const std::vector<uint8_t>& unoccluded, const std::vector<rtm::vec4>& point, const std::vector<rtm::vec4>& normal,
+                            const std::vector<int32_t>& index, size_t width, unsigned int samples, unsigned int radius, float normal_min,
+                            float plane_max, FilteredAO& out) {
+    const unsigned int K = samples;
+    const size_t n = unoccluded.size();
+    if (K == 0 || K > 64 || (K & (K - 1))) throw std::invalid_argument("FilterAO: samples is one of 1, 2, 4, 8, 16, 32, 64");
+    if (radius < 1 || radius > 4) throw std::invalid_argument("FilterAO: radius is 1 .. 4");
+    if (!(plane_max >= 0.f) || !std::isfinite(plane_max)) throw std::invalid_argument("FilterAO: plane_max must be finite and not negative");
+    if (point.size() != n || normal.size() != n || (!index.empty() && index.size() != n))
+        throw std::invalid_argument("FilterAO: unoccluded, point, normal and index have one entry per item");
+    if (n != 0 && (width == 0 || n % width)) throw std::invalid_argument("FilterAO: the items are whole rows of `width`");
+    out.ao.assign(n, 1.f);
+    out.grey.assign(n, 255);
+    out.taps.assign(n, 0);
+    if (n == 0) return;
+    const long rows = (long)(n / width), cols = (long)width, r = (long)radius;
+    std::vector<uint8_t> live(n);
+    for (size_t i = 0; i < n; ++i) {
+        const rtm::vec4 &p = point[i], &nr = normal[i];
+        live[i] = (index.empty() || index[i] >= 0) && std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && std::isfinite(nr.x) &&
+                  std::isfinite(nr.y) && std::isfinite(nr.z);
+    }
+    for (long row = 0; row < rows; ++row)
+        for (long col = 0; col < cols; ++col) {
+            const size_t p = (size_t)row * width + (size_t)col;
+            if (!live[p]) continue;
+            const rtm::vec4 &pp = point[p], &np = normal[p];
+            uint32_t taps = 1, sum = unoccluded[p];   // itself, untested
+            for (long qr = std::max(0L, row - r); qr <= std::min(rows - 1, row + r); ++qr)
+                for (long qc = std::max(0L, col - r); qc <= std::min(cols - 1, col + r); ++qc) {
+                    const size_t q = (size_t)qr * width + (size_t)qc;
+                    if (q == p || !live[q]) continue;
+                    const rtm::vec4 &pq = point[q], &nq = normal[q];
+                    const float c = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;   // (-ffp-contract=off: every product and sum rounded)
+                    if (!(c >= normal_min)) continue;
+                    const float dx = pq.x - pp.x, dy = pq.y - pp.y, dz = pq.z - pp.z;
+                    const float e = (np.x * dx + np.y * dy) + np.z * dz;
+                    if (!(std::fabs(e) <= plane_max)) continue;
+                    ++taps;
+                    sum += unoccluded[q];
+                }
+            const float a = (float)sum / (float)(taps * K);
+            const float f = std::floor(a * 255.0f);
+            out.ao[p] = a;
+            out.grey[p] = !(f >= 0.f) ? 0 : (f >= 255.f ? 255 : (uint8_t)f);
+            out.taps[p] = (uint8_t)taps;
+        }
+}
+
+void CPURaytracer::RenderAOFiltered(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, size_t width, unsigned int radius,
+                                    float normal_min, float plane_max, FilteredAO& out) const {
+    GBuffer g;
+    RenderGBuffer(g);
+    AO a;
+    RenderAO(dirs, samples, bias, a);
+    FilterAO(a.unoccluded, g.point, g.normal, g.index, width, samples, radius, normal_min, plane_max, out);
+}
+
 void CPURaytracer::QueryShade(const std::vector<Ray3D>& q, const std::vector<int32_t>& mask, Shade& out) const {
     const size_t n = q.size();
     if (!mask.empty() && mask.size() != n) throw std::invalid_argument("QueryShade: the mask must be empty or have one entry per ray");

@@ -127,6 +127,24 @@ public:
     };
     void RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, AO& out) const;
 
+    // Filtered ambient occlusion (hip_raytracer.h, "filtered ambient occlusion"), a second statement of ao.py's filter() in plain loops:
+    // a row-major array of `width` columns (n = unoccluded.size() a multiple of it); index may be empty (every item may be live). A live
+    // item p (index >= 0, finite point and normal) accepts itself and every live q != p of its (2 radius + 1)^2 window inside the array
+    // with (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z >= normal_min and |(n_p.x d.x + n_p.y d.y) + n_p.z d.z| <= plane_max, d = P_q - P_p,
+    // float, product then sum; taps = the accepted items, ao = (float)sum of their counts / (float)(taps * samples), grey the byte of
+    // "8-bit frames"; a dead item reads 0, 1 and 255. std::invalid_argument for another `samples` than 1, 2, 4 ... 64, a radius outside
+    // 1 .. 4, a plane_max that is negative or not finite, arrays of different lengths or a width that does not divide them.
+    struct FilteredAO {
+        std::vector<float> ao;
+        std::vector<uint8_t> grey, taps;
+    };
+    static void FilterAO(const std::vector<uint8_t>& unoccluded, const std::vector<rtm::vec4>& point, const std::vector<rtm::vec4>& normal,
+                         const std::vector<int32_t>& index, size_t width, unsigned int samples, unsigned int radius, float normal_min,
+                         float plane_max, FilteredAO& out);
+    // RenderGBuffer and RenderAO, then FilterAO over rows of `width` work-items: what HIPRaytracer::RenderAOFiltered is defined as.
+    void RenderAOFiltered(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, size_t width, unsigned int radius,
+                          float normal_min, float plane_max, FilteredAO& out) const;
+
     uint64_t RaysTraced() const { return rays_traced; }   // primary + shadow + reflection rays of the last Render()
     uint64_t HitPixels() const { return hit_pixels; }
     unsigned int Threads() const { return n_threads; }

@@ -334,6 +334,60 @@ rt_ao_info_t HIPRaytracer::AOInfo(unsigned int shard) {
     return info;
 }
 
+HIPRaytracer::FilteredAO HIPRaytracer::FilterAO(const std::vector<uint8_t>& unoccluded, const std::vector<rtm::vec4>& point,
+                                                const std::vector<rtm::vec4>& normal, const std::vector<int32_t>& index, size_t width,
+                                                unsigned int samples, unsigned int radius, float normal_min, float plane_max) {
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c) throw std::runtime_error("HIPRaytracer::FilterAO: no context");
+    const size_t n = unoccluded.size();
+    if (point.size() != n || normal.size() != n || (!index.empty() && index.size() != n) || (n && (width == 0 || n % width)))
+        throw std::runtime_error("HIPRaytracer::FilterAO: one entry per item, whole rows of `width`");
+    FilteredAO f;
+    f.ao.assign(n, 1.f);
+    f.grey.assign(n, 255);
+    f.taps.assign(n, 0);
+    if (n == 0) return f;
+    const rt_ao_filter_params_t filter{radius, normal_min, plane_max, 0};
+    const rt_ao_filtered_t out{f.ao.data(), f.grey.data(), f.taps.data()};
+    if (rt_ao_filter(c, unoccluded.data(), &point[0].x, &normal[0].x, index.empty() ? nullptr : index.data(), width, n / width, samples, &filter,
+                     &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::FilterAO: ") + rt_last_error(c));
+    return f;
+}
+
+HIPRaytracer::FilteredAO HIPRaytracer::RenderAOFiltered(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, unsigned int radius,
+                                                        float normal_min, float plane_max) {
+    if (multi) throw std::runtime_error("HIPRaytracer::RenderAOFiltered: not on the several-GPU object (a tile's neighbours live on other shards)");
+    if (!ctx) throw std::runtime_error("HIPRaytracer::RenderAOFiltered: no context");
+    if (samples == 0 || dirs.empty() || dirs.size() % samples)
+        throw std::runtime_error("HIPRaytracer::RenderAOFiltered: dirs holds a whole number of sets of `samples` directions");
+    const size_t n = (size_t)rt_local_rays(ctx);
+    FilteredAO f;
+    f.ao.assign(n, 1.f);
+    f.grey.assign(n, 255);
+    f.taps.assign(n, 0);
+    rt_ao_params_t params;
+    params.samples = samples;
+    params.n_sets = (uint32_t)(dirs.size() / samples);
+    params.bias = bias;
+    params.reserved = 0;
+    params.dirs = dirs.data();
+    if (n == 0) return f;
+    const rt_ao_filter_params_t filter{radius, normal_min, plane_max, 0};
+    const rt_ao_filtered_t out{f.ao.data(), f.grey.data(), f.taps.data()};
+    if (rt_render_ao_filtered(ctx, &params, &filter, &out) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::RenderAOFiltered: ") + rt_last_error(ctx));
+    return f;
+}
+
+rt_ao_filter_info_t HIPRaytracer::AOFilterInfo() {
+    rt_ao_filter_info_t info;
+    rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;
+    if (!c || rt_get_ao_filter_info(c, &info) != RT_OK)
+        throw std::runtime_error(std::string("HIPRaytracer::AOFilterInfo: ") + (c ? rt_last_error(c) : "no context"));
+    return info;
+}
+
 rt_geometry_info_t HIPRaytracer::GeometryInfo() {
     rt_geometry_info_t info;
     rt_context* c = multi ? rt_multi_context(multi, 0) : ctx;

@@ -165,6 +165,24 @@ public:
     AO RenderAO(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias = 1e-3f, unsigned int shard = 0);
     rt_ao_info_t AOInfo(unsigned int shard = 0);
 
+    // Filtered ambient occlusion (hip_raytracer.h, "filtered ambient occlusion"): an edge-aware box blur of the AO counts over a
+    // (2 radius + 1)^2 window - a live item averages the live items of its window whose normal has a cosine >= normal_min with its own
+    // and that lie within plane_max of its tangent plane. ao = sum / (taps * samples), grey the byte of "8-bit frames", taps the
+    // accepted items; a dead item reads 1, 255 and 0. FilterAO: the pass alone on the caller's row-major array of `width` columns
+    // (rt_ao_filter; index may be empty; the several-GPU object runs it on its first shard). RenderAOFiltered: RenderAO's passes and the
+    // filter over the frame's sample grid with nothing copied back in between (rt_render_ao_filtered); it throws on the several-GPU
+    // object, on rays from a plain buffer (no width) and on a scene with triangles. AOFilterInfo(): rt_get_ao_filter_info.
+    struct FilteredAO {
+        std::vector<float> ao;
+        std::vector<uint8_t> grey, taps;
+    };
+    FilteredAO FilterAO(const std::vector<uint8_t>& unoccluded, const std::vector<rtm::vec4>& point, const std::vector<rtm::vec4>& normal,
+                        const std::vector<int32_t>& index, size_t width, unsigned int samples, unsigned int radius, float normal_min,
+                        float plane_max);
+    FilteredAO RenderAOFiltered(const std::vector<rtm::vec4>& dirs, unsigned int samples, float bias, unsigned int radius, float normal_min,
+                                float plane_max);
+    rt_ao_filter_info_t AOFilterInfo();
+
     rt_stats_t Stats();
     // rt_get_tiles_info: the screen tiles the next large-scene frame's primary round would use - the camera's (host-built) or, after
     // SetPose, the pose's (built on the GPU) - built now if the rays changed. The several-GPU object reports its first shard's.

@@ -374,6 +374,30 @@ int cpu_rt_render_gbuffer(const void* objs_, uint32_t n_objs, const void* rays_,
     return 0;
 }
 
+// CPURaytracer::FilterAO through the C entry: n = width * rows items; index may be NULL; ao, grey and taps may each be NULL. Needs no
+// scene. Returns 0, or -1 for what FilterAO throws on.
+int cpu_rt_ao_filter(const uint8_t* unoccluded, const float* point, const float* normal, const int32_t* index, uint64_t width, uint64_t rows,
+                     uint32_t samples, uint32_t radius, float normal_min, float plane_max, float* ao, uint8_t* grey, uint8_t* taps) {
+    const uint64_t n = width * rows;
+    if (n && (!unoccluded || !point || !normal)) return -1;
+    std::vector<rtm::vec4> p(n), nr(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        p[i] = rtm::vec4(point[4 * i], point[4 * i + 1], point[4 * i + 2], point[4 * i + 3]);
+        nr[i] = rtm::vec4(normal[4 * i], normal[4 * i + 1], normal[4 * i + 2], normal[4 * i + 3]);
+    }
+    CPURaytracer::FilteredAO f;
+    try {
+        CPURaytracer::FilterAO(std::vector<uint8_t>(unoccluded, unoccluded + n), p, nr, index ? std::vector<int32_t>(index, index + n) : std::vector<int32_t>(),
+                               (size_t)width, samples, radius, normal_min, plane_max, f);
+    } catch (const std::exception&) { return -1; }
+    if (n) {
+        if (ao) std::memcpy(ao, f.ao.data(), n * sizeof(float));
+        if (grey) std::memcpy(grey, f.grey.data(), n);
+        if (taps) std::memcpy(taps, f.taps.data(), n);
+    }
+    return 0;
+}
+
 // CPURaytracer::QueryShade through the C entry, on a backend made as cpu_rt_query's plus `lights_`, the colour `kernel` (1, 2) with
 // `max_bounces`, and SetMaterials(m_first, materials_[0 .. m_count)). `mask`: NULL or n_rays int32. rgba (n_rays x 4 floats), t and
 // index (n_rays each) may each be NULL; counts (or NULL) receives n_rays traced, rays_reference, hit_rays. Returns 0 or -1.

@@ -21,11 +21,13 @@
 //                       no GPU backend can be made, CPURaytracer::RenderGBuffer - the same records): <out-prefix>_normal.ppm, the
 //                       unit normal mapped as 0.5 n + 0.5, and <out-prefix>_depth.ppm, t divided by the largest finite t of the
 //                       frame; a miss is black in both. Bytes by the rule of ppm.format_p6 (floor(255 v), clamped)
-//   scene_tool ao      <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius]
+//   scene_tool ao      <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius] [--filter R,NORMAL_MIN,PLANE_MAX]
 //                       ambient occlusion of the W x H picture as a grey binary PPM (HIPRaytracer::RenderAO; with `cpu`, or where no
 //                       GPU backend can be made, CPURaytracer::RenderAO - the same counts): K = 1, 2, 4 ... 64 rays per pixel of
 //                       length `radius` (default 1) from 16 sets of cosine-weighted directions made here from a fixed seed; a pixel
-//                       is floor(255 ao), a miss white
+//                       is floor(255 ao), a miss white. With --filter (anywhere behind <out.ppm>) the picture is the FILTERED grey:
+//                       the edge-aware blur of the counts over a (2R + 1)^2 window (HIPRaytracer::RenderAOFiltered, or
+//                       CPURaytracer::RenderAOFiltered - the same bytes); without it the output is unchanged
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -200,7 +202,23 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (std::strcmp(argv[1], "ao") == 0) {
-            if (argc < 7) { std::fprintf(stderr, "usage: scene_tool ao <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius]\n"); return 1; }
+            // --filter R,NORMAL_MIN,PLANE_MAX is taken out of the arguments; the positional ones read as ever
+            bool filtered = false;
+            unsigned filter_radius = 0;
+            float filter_normal_min = 0.f, filter_plane_max = 0.f;
+            for (int a = 7; a < argc; ++a) {
+                if (std::strcmp(argv[a], "--filter") != 0) continue;
+                if (a + 1 >= argc || std::sscanf(argv[a + 1], "%u,%f,%f", &filter_radius, &filter_normal_min, &filter_plane_max) != 3 ||
+                    filter_radius < 1 || filter_radius > 4 || !(filter_plane_max >= 0.f) || !std::isfinite(filter_plane_max)) {
+                    std::fprintf(stderr, "ao: --filter R,NORMAL_MIN,PLANE_MAX with R 1 .. 4 and PLANE_MAX finite, >= 0\n");
+                    return 1;
+                }
+                filtered = true;
+                for (int b = a + 2; b < argc; ++b) argv[b - 2] = argv[b];
+                argc -= 2;
+                break;
+            }
+            if (argc < 7) { std::fprintf(stderr, "usage: scene_tool ao <scene.txt> <W> <H> <K> <out.ppm> [hip|cpu] [radius] [--filter R,NORMAL_MIN,PLANE_MAX]\n"); return 1; }
             const int aw = std::atoi(argv[3]), ah = std::atoi(argv[4]);
             const unsigned K = (unsigned)std::atoi(argv[5]);
             const float radius = argc > 8 ? (float)std::atof(argv[8]) : 1.0f;
@@ -227,12 +245,14 @@ int main(int argc, char** argv) {
             const size_t n = grid.size();
             std::vector<uint8_t> unoccluded;
             std::vector<float> ao;
+            std::vector<uint8_t> filtered_grey;   // --filter: the picture's bytes
             const char* backend_name = (argc > 7 && std::strcmp(argv[7], "cpu") == 0) ? "cpu" : "hip";
             if (std::strcmp(backend_name, "hip") == 0) {
                 try {
                     HIPRaytracer backend(objects, lights, grid, 0);
                     HIPRaytracer::AO a = backend.RenderAO(dirs, K);
                     unoccluded.swap(a.unoccluded); ao.swap(a.ao);
+                    if (filtered) filtered_grey = backend.RenderAOFiltered(dirs, K, 1e-3f, filter_radius, filter_normal_min, filter_plane_max).grey;
                 } catch (const std::exception& e) {  // (no GPU: the CPU backend's counts - said on stderr and in the last line)
                     std::fprintf(stderr, "ao: %s; using the CPU backend\n", e.what());
                     backend_name = "cpu";
@@ -243,12 +263,18 @@ int main(int argc, char** argv) {
                 CPURaytracer::AO a;
                 backend.RenderAO(dirs, K, 1e-3f, a);
                 unoccluded.swap(a.unoccluded); ao.swap(a.ao);
+                if (filtered) {
+                    CPURaytracer::FilteredAO f;
+                    backend.RenderAOFiltered(dirs, K, 1e-3f, (size_t)aw, filter_radius, filter_normal_min, filter_plane_max, f);
+                    filtered_grey.swap(f.grey);
+                }
             }
             std::vector<uint8_t> grey(3 * n, 0);
             size_t sum = 0;
             for (size_t i = 0; i < n; ++i) {
                 const float f = std::floor(ao[i] * 255.0f);
                 grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = (uint8_t)(f >= 0.0f ? (f >= 255.0f ? 255.0f : f) : 0.0f);
+                if (filtered) grey[3 * i] = grey[3 * i + 1] = grey[3 * i + 2] = filtered_grey[i];
                 sum += unoccluded[i];
             }
             PPMExporter::ExportP6(argv[6], (size_t)aw, (size_t)ah, grey.data(), 3);
